@@ -13,6 +13,11 @@ Every expected output below comes from the REFERENCE, not from this repository's
   the third-party call the reference makes at scripts/cli.py:66-73 (scipy version recorded
   in each file).
 * values: the literal NumPy statement np.sum(field[enc] * w, axis=1) (scripts/cli.py:100).
+* hex8_sweeps: SHA-256 digests of the reference's centroids, node ids and weights on four
+  random sweeps (tests/test_oracle_pinned.py regenerates the inputs and checks their digest).
+* newton_unit / newton_reference: the compiled reference's inverseCoordinateTransform (and
+  interpolateAtPoint) called one solve at a time; newton_reference keeps SHA-256 digests of
+  its 300,000 verdicts and final iterates (tests/test_newton_host.py::iterate_digests).
 
 Fixtures hold arrays only (inputs + expected outputs); no reference source text.
 """
@@ -137,6 +142,65 @@ def case_gather():
     save("gather.npz", **arrays)
 
 
+def case_sweeps():
+    # random sweeps over distortion and k that reach every branch of the locator; 3000-row outputs kept as digests of
+    # blocks of rows (tests/test_oracle_pinned.py::block_digests)
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_oracle_pinned as T
+
+    arrays = {key: [] for key in ("inputs", "centroid", "nfailed", "enc", "w")}
+    for seed, jitter, k in T.SWEEPS:
+        pa, ca, pb, cen, nn = T.sweep_inputs(seed, jitter, k, O.ref_centroid)
+        # the reference's own column reorder (scripts/cli.py:79-81), as in run_reference
+        conn = np.ascontiguousarray(ca[:, np.argsort([0, 3, 2, 1, 4, 5, 6, 7])])
+        enc, w, nfailed = O.ref_locate_hex8(nn, conn, pa, pb)
+        print(f"  sweep seed={seed} k={k}: nfailed={nfailed}")
+        arrays["inputs"].append(np.frombuffer(T.sha(pa, ca, pb, nn), np.uint8))
+        arrays["centroid"].append(np.frombuffer(T.sha(cen), np.uint8))
+        arrays["nfailed"].append(nfailed)
+        arrays["enc"].append([np.frombuffer(dg, np.uint8) for dg in T.block_digests(enc)])
+        arrays["w"].append([np.frombuffer(dg, np.uint8) for dg in T.block_digests(w)])
+    save("hex8_sweeps.npz", **{key: np.array(v) for key, v in arrays.items()})
+
+
+def _ref_newton(pnt, vtx):
+    R = O.reference_lib()
+    xi = np.zeros((len(pnt), 3))
+    ok = np.zeros(len(pnt), np.int8)
+    for i in range(len(pnt)):
+        ok[i] = R.inverseCoordinateTransform(pnt[i], vtx[i], xi[i]) != 0
+    return xi, ok
+
+
+def case_newton_unit():
+    # 400 solves around the elements of a distorted mesh, and the weights at every accepted xi
+    rng = np.random.default_rng(42)
+    pa, ca = synth.hex_mesh(4, seed=5, jitter=0.4)
+    conn = synth.reorder_hex8(ca)
+    vtx = np.empty((400, 8, 3))
+    pnt = np.empty((400, 3))
+    for i in range(400):
+        vtx[i] = pa[conn[rng.integers(0, len(conn))]]
+        pnt[i] = vtx[i].mean(0) + rng.normal(scale=0.3, size=3)
+    xi, ok = _ref_newton(pnt, vtx)
+    w = np.zeros((400, 8))
+    for i in np.flatnonzero(ok):
+        O.reference_lib().interpolateAtPoint(xi[i], w[i])
+    save("newton_unit.npz", pnt=pnt, vtx=vtx, ok=ok, xi=xi, w=w)
+
+
+def case_newton_reference():
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_newton_host as T
+
+    inputs, iterates = [], []
+    for _, (pnt, vtx) in T.reference_inputs():
+        xi, ok = _ref_newton(pnt, vtx)
+        inputs.append(np.frombuffer(T.input_digest(pnt, vtx), np.uint8))
+        iterates.append([np.frombuffer(d, np.uint8) for d in T.iterate_digests(xi, ok)])
+    save("newton_reference.npz", inputs=np.array(inputs), iterates=np.array(iterates))
+
+
 if __name__ == "__main__":
     if not O.have_reference():
         O.build(ref=True)
@@ -146,3 +210,6 @@ if __name__ == "__main__":
     case_structured_ties()
     case_knn()
     case_gather()
+    case_sweeps()
+    case_newton_unit()
+    case_newton_reference()

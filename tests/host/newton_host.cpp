@@ -76,9 +76,29 @@ int64_t nh_compare_start(int64_t n, const double *pnts, const double *vtxs, void
     return bad;
 }
 
-// n solves; staged != 0 runs this library's solve the way the pass kernel does (caps c1 -> c2 -> 50, every stage
-// continuing from the iterate the stage before stopped at).  Returns the number of solves whose verdict or final
-// iterate differs from other's; first_bad receives the index of the first one (or -1); converged the count.
+// one solve from xi = 0; staged != 0 runs it the way the pass kernel does (caps c1 -> c2 -> 50, every stage
+// continuing from the iterate the stage before stopped at)
+static int solve_staged(const double *p, const double *v, double *xi, int staged, int c1, int c2)
+{
+    if (!staged) return nh_newton(p, v, xi, 50, 0);
+    int ok = nh_newton(p, v, xi, c1, 0);
+    if (!ok) ok = nh_newton(p, v, xi, c2, c1);
+    if (!ok) ok = nh_newton(p, v, xi, 50, c2);
+    return ok;
+}
+
+// n solves as nh_compare runs them: verdicts and final iterates out (for digests stored under tests/golden/)
+void nh_solve(int64_t n, const double *pnts, const double *vtxs, int staged, int c1, int c2, double *xis, int8_t *oks)
+{
+    for (int64_t i = 0; i < n; ++i) {
+        double *xi = xis + i * 3;
+        xi[0] = xi[1] = xi[2] = 0.0;
+        oks[i] = (int8_t)solve_staged(pnts + i * 3, vtxs + i * 24, xi, staged, c1, c2);
+    }
+}
+
+// n solves by solve_staged.  Returns the number of solves whose verdict or final iterate differs from other's;
+// first_bad receives the index of the first one (or -1); converged the count.
 int64_t nh_compare(int64_t n, const double *pnts, const double *vtxs, void *other, int no_iters, int staged, int c1,
                    int c2, int64_t *first_bad, int64_t *converged)
 {
@@ -88,14 +108,7 @@ int64_t nh_compare(int64_t n, const double *pnts, const double *vtxs, void *othe
         const double *p = pnts + i * 3, *v = vtxs + i * 24;
         double xo[3] = {0, 0, 0}, xm[3] = {0, 0, 0};
         const int ok_o = no_iters ? ((other3_t)other)(p, v, xo) : ((other4_t)other)(p, v, xo, nullptr);
-        int ok_m;
-        if (staged) {
-            ok_m = nh_newton(p, v, xm, c1, 0);
-            if (!ok_m) ok_m = nh_newton(p, v, xm, c2, c1);
-            if (!ok_m) ok_m = nh_newton(p, v, xm, 50, c2);
-        } else {
-            ok_m = nh_newton(p, v, xm, 50, 0);
-        }
+        const int ok_m = solve_staged(p, v, xm, staged, c1, c2);
         conv += ok_m;
         if ((ok_o != 0) != (ok_m != 0) || !same_bits(xo, xm)) {
             if (*first_bad < 0) *first_bad = i;

@@ -1,11 +1,13 @@
 """The kernels' hex8 Newton solve (multimesh_amd/csrc/mm_newton_hex8.h) compiled for the HOST and compared, iterate
-for iterate, with the CPU oracle and the compiled reference (trilinearinterpolator.c:260-305).
+for iterate, with the CPU oracle and the compiled reference (trilinearinterpolator.c:260-305; its iterates are stored as
+digests in tests/golden/newton_reference.npz by tests/golden/make_golden.py).
 
 The header restates the reference's expressions with fewer fp64 instructions (Jacobian carried at 8x, first trip
 specialised at xi = 0, exact-product fused multiply-adds); the claim is bit equality of every final iterate and every
 verdict, also when a solve is stopped at a cap and continued, the way locate_pass_kernel's tiers do it.  The same
 header is what the GPU kernels compile, so this runs without a GPU; the -m gpu parity tests then check the kernels."""
 import ctypes as C
+import hashlib
 import os
 import subprocess
 
@@ -36,6 +38,9 @@ def host():
                              C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.nh_newton.restype = C.c_int
     L.nh_newton.argtypes = [f64p, f64p, f64p, C.c_int, C.c_int]
+    L.nh_solve.restype = None
+    L.nh_solve.argtypes = [C.c_int64, f64p, f64p, C.c_int, C.c_int, C.c_int, f64p,
+                           np.ctypeslib.ndpointer(dtype=np.int8, flags=["C_CONTIGUOUS"])]
     return L
 
 
@@ -47,6 +52,22 @@ def elements(rng, n, jitter, scale, offset, spread):
     pnt = vtx.mean(1) + rng.normal(scale=spread, size=(n, 3)) * stretch[:, 0] * (0.5 * scale)
     off = np.asarray(offset, float)
     return np.ascontiguousarray(pnt + off), np.ascontiguousarray(vtx + off)
+
+
+DIGEST_BLOCK = 1000
+
+
+def iterate_digests(xi, ok):
+    """SHA-256 of every block of DIGEST_BLOCK solves: verdicts (0 / 1) and final iterates, NaNs made one bit pattern (NaN
+    payloads are not part of the contract, as in nh_compare)."""
+    xi = np.where(np.isnan(xi), np.nan, xi)
+    ok = (np.asarray(ok) != 0).astype(np.int8)
+    return [hashlib.sha256(ok[a:a + DIGEST_BLOCK].tobytes() + xi[a:a + DIGEST_BLOCK].tobytes()).digest()
+            for a in range(0, len(ok), DIGEST_BLOCK)]
+
+
+def input_digest(pnt, vtx):
+    return hashlib.sha256(pnt.tobytes() + vtx.tobytes()).digest()
 
 
 def compare(L, fn, no_iters, pnt, vtx, staged, c1=6, c2=9):
@@ -86,15 +107,28 @@ def test_every_cap_pair_continues_to_the_same_iterate(host):
         assert bad == 0, (c1, c2, first)
 
 
-@pytest.mark.skipif(not os.path.exists(O.REF_SO), reason="compiled reference not built")
-def test_final_iterates_equal_the_compiled_reference(host):
-    R = O.reference_lib()
+REFERENCE_CASES = (0, 1, 2)
+REFERENCE_SOLVES = 100_000
+
+
+def reference_inputs():
+    """The solves the compiled reference's iterates are stored for (tests/golden/newton_reference.npz)."""
     rng = np.random.default_rng(5)
-    for case in (0, 1, 2):
+    for case in REFERENCE_CASES:
         jitter, scale, offset, spread = CASES[case]
-        pnt, vtx = elements(rng, 100_000, jitter, scale, offset, spread)
-        bad, first, _ = compare(host, R.inverseCoordinateTransform, 1, pnt, vtx, 1)
-        assert bad == 0, (case, first)
+        yield case, elements(rng, REFERENCE_SOLVES, jitter, scale, offset, spread)
+
+
+def test_final_iterates_equal_the_compiled_reference(host, golden):
+    # the reference's 300,000 verdicts and final iterates are stored as SHA-256 digests of blocks of 1000 solves (the
+    # iterates themselves are 7 MB): equal digests = every verdict and iterate bit-equal, NaN payloads aside
+    d = golden("newton_reference")
+    for i, (case, (pnt, vtx)) in enumerate(reference_inputs()):
+        assert input_digest(pnt, vtx) == d["inputs"][i].tobytes(), f"case {case}: not the inputs the fixture was made from"
+        xi, ok = np.zeros((len(pnt), 3)), np.zeros(len(pnt), np.int8)
+        host.nh_solve(len(pnt), pnt, vtx, 1, 6, 9, xi, ok)
+        bad = [b for b, dg in enumerate(iterate_digests(xi, ok)) if dg != d["iterates"][i, b].tobytes()]
+        assert not bad, (case, [b * DIGEST_BLOCK for b in bad[:5]])
 
 
 def test_the_gll_paths_corner_solve_equals_the_oracles(host):

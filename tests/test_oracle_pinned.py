@@ -2,10 +2,12 @@
 
 (1) against the committed golden fixtures, whose expected outputs were produced by the
     reference's own compiled C + scipy.cKDTree + NumPy (tests/golden/make_golden.py);
-(2) live against oracle/_ref/multi_mesh_ref.so when that build is present, on random sweeps
-    that reach every branch of the locator (accept, last-candidate fallback, failure).
+(2) against the outputs of oracle/_ref/multi_mesh_ref.so on random sweeps that reach every branch
+    of the locator (accept, last-candidate fallback, failure), stored as digests by the same script.
 All comparisons are bit-exact.
 """
+import hashlib
+
 import numpy as np
 import pytest
 
@@ -96,45 +98,54 @@ def test_empty_inputs():
     assert O.centroid(np.zeros((0, 8), np.int64), pa).shape == (0, 3)
 
 
-needs_ref = pytest.mark.skipif(not O.have_reference(), reason="oracle/_ref not built")
+SWEEPS = [(0, 0.2, 20), (1, 0.42, 2), (2, 0.45, 6), (3, 0.0, 8)]
+SWEEP_BLOCK = 500
 
 
-@needs_ref
-@pytest.mark.parametrize("seed,jitter,k", [(0, 0.2, 20), (1, 0.42, 2), (2, 0.45, 6), (3, 0.0, 8)])
-def test_oracle_vs_compiled_reference_live(seed, jitter, k):
+def sha(*arrays):
+    return hashlib.sha256(b"".join(np.ascontiguousarray(a).tobytes() for a in arrays)).digest()
+
+
+def block_digests(a):
+    """SHA-256 of every block of SWEEP_BLOCK rows (the sweeps' fixture holds these, not the 3000-row outputs)."""
+    return [sha(a[i:i + SWEEP_BLOCK]) for i in range(0, len(a), SWEEP_BLOCK)]
+
+
+def sweep_inputs(seed, jitter, k, centroid):
+    """synth.hex_mesh(9, seed, jitter), 3000 targets from default_rng(100 + seed) and, with `centroid` (a function of
+    connectivity and nodes), cKDTree's k nearest centroids: (nodes, connectivity, targets, centroids, nn)."""
     pa, ca = synth.hex_mesh(9, seed=seed, jitter=jitter)
-    rng = np.random.default_rng(100 + seed)
-    pb = rng.uniform(-0.1, 1.1, size=(3000, 3))
-    cen = O.centroid(ca, pa)
-    assert np.array_equal(cen, O.ref_centroid(ca, pa))
+    pb = np.random.default_rng(100 + seed).uniform(-0.1, 1.1, size=(3000, 3))
+    cen = centroid(ca, pa)
     nn, _ = O.knn_ckdtree(cen, pb, k)
-    conn = synth.reorder_hex8(ca)
-    enc, w, nf = O.locate_hex8(nn, conn, pa, pb)
-    enc_r, w_r, nf_r = O.ref_locate_hex8(nn, conn, pa, pb)
-    assert nf == nf_r
-    assert np.array_equal(enc, enc_r)
-    assert np.array_equal(w, w_r)
+    return pa, ca, pb, cen, nn
 
 
-@needs_ref
-def test_newton_and_weights_unit_level_vs_reference():
-    # unit-level goldens: the reference's helpers are individually callable
-    R = O.reference_lib()
+@pytest.mark.parametrize("seed,jitter,k", SWEEPS)
+def test_oracle_vs_compiled_reference_live(golden, seed, jitter, k):
+    # the compiled reference's centroids, node ids and weights on these inputs, as digests of blocks of rows
+    d = golden("hex8_sweeps")
+    i = SWEEPS.index((seed, jitter, k))
+    pa, ca, pb, cen, nn = sweep_inputs(seed, jitter, k, O.centroid)
+    assert sha(cen) == d["centroid"][i].tobytes()
+    assert sha(pa, ca, pb, nn) == d["inputs"][i].tobytes(), "not the inputs the fixture was made from"
+    enc, w, nf = O.locate_hex8(nn, synth.reorder_hex8(ca), pa, pb)
+    assert nf == int(d["nfailed"][i])
+    bad_enc = [b for b, dg in enumerate(block_digests(enc)) if dg != d["enc"][i, b].tobytes()]
+    bad_w = [b for b, dg in enumerate(block_digests(w)) if dg != d["w"][i, b].tobytes()]
+    assert not bad_enc and not bad_w, ([b * SWEEP_BLOCK for b in bad_enc], [b * SWEEP_BLOCK for b in bad_w])
+
+
+def test_newton_and_weights_unit_level_vs_reference(golden):
+    # unit-level goldens: the reference's helpers inverseCoordinateTransform / interpolateAtPoint on 400 solves
+    d = golden("newton_unit")
     L = O.lib()
-    rng = np.random.default_rng(42)
-    pa, ca = synth.hex_mesh(4, seed=5, jitter=0.4)
-    conn = synth.reorder_hex8(ca)
-    for _ in range(400):
-        e = rng.integers(0, len(conn))
-        vtx = np.ascontiguousarray(pa[conn[e]])
-        p = vtx.mean(0) + rng.normal(scale=0.3, size=3)
-        xi_r, xi_o = np.zeros(3), np.zeros(3)
-        ok_r = R.inverseCoordinateTransform(p, vtx, xi_r)
-        ok_o = L.mmo_hex8_newton(p, vtx, xi_o, None)
+    for p, vtx, ok_r, xi_r, w_r in zip(d["pnt"], d["vtx"], d["ok"], d["xi"], d["w"]):
+        xi_o = np.zeros(3)
+        ok_o = L.mmo_hex8_newton(np.ascontiguousarray(p), np.ascontiguousarray(vtx), xi_o, None)
         assert ok_r == ok_o
         assert np.array_equal(xi_r, xi_o, equal_nan=True)
         if ok_r:
-            w_r, w_o = np.zeros(8), np.zeros(8)
-            R.interpolateAtPoint(xi_r, w_r)
+            w_o = np.zeros(8)
             L.mmo_hex8_weights(xi_o, w_o)
             assert np.array_equal(w_r, w_o)

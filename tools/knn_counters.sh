@@ -8,7 +8,7 @@ O=gpurun_out/counters; rm -rf $O; mkdir -p $O
 OUT=${1:-$O/knn_counters.json}
 # MM_COUNTER_ARGS: another workload (e.g. "bench.py --workload cfg5 --steps 2 --warmup 1 --no-cpu-baseline" ->
 # profiles/*_gll_counters.json); MM_COUNTER_VALU_ONLY=1: only the instruction-count groups roofline_valu needs
-ARGS=${MM_COUNTER_ARGS:-"bench.py --steps 2 --warmup 1 --no-cpu-baseline"}
+ARGS=${MM_COUNTER_ARGS:-"bench.py --full --steps 2 --warmup 1 --no-cpu-baseline"}
 i=0
 for group in \
   "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_BUSY_CYCLES" \

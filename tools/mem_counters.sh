@@ -5,7 +5,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/memcounters; rm -rf $O; mkdir -p $O
 OUT=${1:-$O/mem_counters.json}
-ARGS=${MM_COUNTER_ARGS:-"bench.py --steps 2 --warmup 1 --no-cpu-baseline"}
+ARGS=${MM_COUNTER_ARGS:-"bench.py --full --steps 2 --warmup 1 --no-cpu-baseline"}
 i=0
 # (small groups: a block has few counter slots -- six TA counters in one pass abort rocprofv3 with "exceeds the
 # capabilities of the hardware" and leave it hanging; every pass runs under its own timeout)

@@ -18,7 +18,7 @@ extra = sys.argv[3:]
 
 def run(args):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--steps", "10", "--warmup", "3",
-                        "--no-cpu-baseline"] + args + extra, capture_output=True, text=True)
+                        "--no-cpu-baseline", "--full"] + args + extra, capture_output=True, text=True)
     if r.returncode != 0:
         raise SystemExit(f"bench.py {args} failed:\n{r.stderr[-2000:]}")
     return json.loads(r.stdout.strip().splitlines()[-1])

@@ -199,6 +199,32 @@ int mm_scatter_elements(mm_context *ctx, const double *values_d, int64_t nunique
                         const int64_t *inverse_d, const int64_t *elem_ids_d, int64_t nmasked, int64_t P,
                         int64_t nelem_out, double *out_d);
 
+/* Earth meshes onto the sphere of their 1-D model (reference components/interpolator.py:1085-1144, make_spherical of
+ * the drivers).  points_d f64[npoints][3]; rad_d = the z_node_1D values, f64[nrad].
+ * mm_map_to_sphere: out = ((p * r_ref) * rad) / |p| per component, |p| = sqrt((x*x + y*y) + z*z), for every point with
+ * |p| > 0; other points are copied unchanged.  Bit-identical to the reference's NumPy statements (r_ref = 6371000).
+ * first_d == NULL: the element-nodal layout, rad_d[i] belongs to point i (nrad == npoints).  Otherwise the node
+ * layout: point n takes rad_d[first_d[n]] (mm_first_occurrence); a point whose index is outside [0, nrad) is
+ * copied unchanged.  out_d may be points_d (in place) but must not overlap it otherwise. */
+int mm_map_to_sphere(mm_context *ctx, const double *points_d, int64_t npoints, const double *rad_d, int64_t nrad,
+                     const int64_t *first_d, double r_ref, double *out_d);
+
+/* np.unique(connectivity, return_index=True) as the node layout of map_to_sphere reads it: first_d int64[nnodes]
+ * receives, for every node n, the smallest flat index i with connectivity_d[i] == n, or -1 when no entry names n.
+ * connectivity_d int64[nentries] (the flattened [nelem][P] array).  Returns the number of unreferenced nodes
+ * (>= 0; the map is only valid when it is 0), MM_ERR_ARG when an entry lies outside [0, nnodes), or another
+ * negative MM_ERR_*.  Synchronises. */
+int64_t mm_first_occurrence(mm_context *ctx, const int64_t *connectivity_d, int64_t nentries, int64_t nnodes,
+                            int64_t *first_d);
+
+/* map_to_ellipse's radial ratio (reference interpolator.py:1093-1097): ratio_d[i] = (|p_i| / r_ref) / rad, with rad
+ * and first_d as in mm_map_to_sphere (a point without a valid radius index gets NaN). */
+int mm_sphere_ratio(mm_context *ctx, const double *points_d, int64_t npoints, const double *rad_d, int64_t nrad,
+                    const int64_t *first_d, double r_ref, double *ratio_d);
+
+/* out = factor_d[i] * p_i per component (reference interpolator.py:1121); out_d may be points_d. */
+int mm_scale_points(mm_context *ctx, const double *points_d, int64_t npoints, const double *factor_d, double *out_d);
+
 /* find_gll_coeffs as query_model / gll_2_gll drive it (reference components/interpolator.py:113, :777): the tree is built
  * over ALL GLL points and the neighbour list of point indices becomes a list of element indices by
  * np.floor(index / P) -- in place on the device (idx_d int64[n]). */

@@ -16,6 +16,8 @@ GLL paths (the reference's salvus.fem numerics restated): the arr
 file-level drivers under the reference's names -- :func:`query_model`, :func:`exodus_2_gll`,
 :func:`gll_2_exodus`, :func:`gll_2_gll`, :func:`gll_2_gll_layered_multi_two` -- reading and writing meshes
 through :mod:`multimesh_amd.io`.
+Earth meshes: :func:`map_to_sphere` and :func:`map_to_ellipse` (reference interpolator.py:1085-1144, in place), and
+``make_spherical`` of the drivers (mapped copies).
 """
 from __future__ import annotations
 
@@ -24,7 +26,7 @@ import time
 
 import numpy as np
 
-from .device import default_context
+from .device import DeviceArray, default_context
 from .helpers import check
 from .mesh import HexMesh
 
@@ -131,15 +133,15 @@ def interpolate_to_points(mesh, points, params_to_interp, make_spherical=False, 
                           nelem_to_search=25, context=None):
     """Maps values from a mesh to predefined points, xyz or geocentric latlondepth
     (reference api.py:320-350).  Returns f64[npoints, nparams]; points that are not found get zero
-    (reference interpolator.py:963-977)."""
-    if make_spherical:
-        raise NotImplementedError("map_to_sphere (reference interpolator.py:1085-1144) is Earth-specific "
-                                  "pre-processing outside the hot path (SURVEY.md §2 #15)")
+    (reference interpolator.py:963-977).  ``make_spherical``: the mesh's nodes are mapped onto the sphere of
+    its 1-D model first (its ``z_node_1D`` field, :func:`map_to_sphere`) -- a mapped copy: ``mesh`` is not
+    changed; the points are taken as they are, as in the reference (interpolator.py:945-946)."""
     if geocentric:
         points = latlondepth_to_xyz(points)
     ctx = context or default_context()
+    nodes = _sphere_mapped(mesh, ctx).numpy() if make_spherical else mesh.points
     points = np.ascontiguousarray(points, dtype=np.float64)
-    vals, nfailed = ctx.interpolate_hex8_host(mesh.points, mesh.connectivity, points,
+    vals, nfailed = ctx.interpolate_hex8_host(nodes, mesh.connectivity, points,
                                               mesh.fields_matrix(params_to_interp), nelem_to_search=nelem_to_search)
     if nfailed > 0:
         print(nfailed, "points could not find an enclosing element. These points will be set to zero. "
@@ -147,12 +149,21 @@ def interpolate_to_points(mesh, points, params_to_interp, make_spherical=False, 
     return vals
 
 
-def interpolate_to_mesh(old_mesh, new_mesh, params_to_interp=("VSV", "VSH", "VPV", "VPH"), context=None):
-    """Interpolate ``params_to_interp`` from old_mesh onto the nodes of new_mesh
-    (reference api.py:353-393, minus the Earth-specific sphere mapping).  Values that are not found
-    are given zero."""
+def interpolate_to_mesh(old_mesh, new_mesh, params_to_interp=("VSV", "VSH", "VPV", "VPH"), make_spherical=False,
+                        context=None):
+    """Interpolate ``params_to_interp`` from old_mesh onto the nodes of new_mesh (reference api.py:353-393).
+    Values that are not found are given zero.  The reference ALWAYS maps both meshes onto the sphere of their
+    1-D model first (their ``z_node_1D`` fields); here that is ``make_spherical=True``, and the default keeps
+    the coordinates as they are.  Either way the meshes' coordinates are not changed (the reference restores
+    them, :388-390); only the fields are attached to ``new_mesh``."""
     start = time.time()
-    vals = interpolate_to_points(old_mesh, new_mesh.points, list(params_to_interp), context=context)
+    if make_spherical:
+        ctx = context or default_context()
+        targets = _sphere_mapped(new_mesh, ctx).numpy()
+        source = HexMesh(_sphere_mapped(old_mesh, ctx).numpy(), old_mesh.connectivity, old_mesh.nodal_fields)
+        vals = interpolate_to_points(source, targets, list(params_to_interp), context=ctx)
+    else:
+        vals = interpolate_to_points(old_mesh, new_mesh.points, list(params_to_interp), context=context)
     for i, param in enumerate(params_to_interp):
         new_mesh.attach_field(param, vals[:, i])
     _report(start)
@@ -179,6 +190,126 @@ class GllMesh:
         return self.gll_points.mean(axis=1)
 
 
+R_EARTH = 6371000.0   # the radius map_to_sphere scales z_node_1D by (reference interpolator.py:1093, :1137)
+
+
+def _mesh_points(mesh):
+    return mesh.gll_points if isinstance(mesh, GllMesh) else mesh.points
+
+
+def _z_node_1d(mesh):
+    """The mesh's ``z_node_1D`` field: element-nodal (``element_nodal_fields``, or a Salvus file's ``MODEL/data``
+    read on demand) or nodal (``nodal_fields`` of a :class:`HexMesh`)."""
+    for attr in ("element_nodal_fields", "nodal_fields"):
+        fields = getattr(mesh, attr, None)
+        if fields is not None and "z_node_1D" in fields:
+            return np.ascontiguousarray(fields["z_node_1D"], dtype=np.float64)
+    if "z_node_1D" in getattr(mesh, "nodal_parameter_indices", ()):
+        return np.ascontiguousarray(mesh.get_element_nodal_field("z_node_1D"), dtype=np.float64)
+    raise ValueError("the mesh has no z_node_1D field (the radius of its 1-D model over 6371 km, which "
+                     "map_to_sphere scales every point to)")
+
+
+def _sphere_layout(mesh):
+    """(points, z_node_1D, connectivity or None) as :meth:`Context.map_to_sphere` takes them."""
+    pts = np.asarray(_mesh_points(mesh))
+    if pts.ndim not in (2, 3) or pts.shape[-1] != 3:
+        raise ValueError(f"map_to_sphere maps 3-D meshes only (points of shape {pts.shape})")
+    z = _z_node_1d(mesh)
+    if z.shape == pts.shape[:-1]:                  # element-nodal points, or a nodal field: one radius per point
+        return pts, z, None
+    connectivity = getattr(mesh, "connectivity", None)
+    if pts.ndim != 2 or connectivity is None or np.shape(connectivity) != z.shape:
+        raise ValueError(f"z_node_1D of shape {z.shape} fits neither the points {pts.shape} nor the connectivity")
+    return pts, z, connectivity
+
+
+def _sphere_mapped(mesh, ctx):
+    """The mesh's points mapped onto the sphere of its 1-D model, as a new device array (the mesh is untouched)."""
+    pts, z, connectivity = _sphere_layout(mesh)
+    return ctx.map_to_sphere(np.ascontiguousarray(pts, dtype=np.float64), z, connectivity=connectivity,
+                             r_ref=R_EARTH)
+
+
+def _set_points(mesh, mapped):
+    pts = _mesh_points(mesh)
+    if isinstance(pts, np.ndarray) and pts.dtype == np.float64 and pts.flags.writeable and pts.shape == mapped.shape:
+        pts[...] = mapped                          # in place, like the reference's x[r > 0] = ... on views
+    elif isinstance(mesh, GllMesh):
+        mesh.gll_points = mapped
+    else:
+        mesh.points = mapped
+
+
+def _map_read_meshes(original_mesh, new_mesh, context):
+    """make_spherical of the Salvus-file drivers: the coordinates both readers hold -- copies of the files'
+    ``MODEL/coordinates`` -- mapped onto the sphere; the files themselves are not written."""
+    ctx = context or default_context()
+    original_mesh.points = _sphere_mapped(original_mesh, ctx).numpy()
+    new_mesh.points = _sphere_mapped(new_mesh, ctx).numpy()
+
+
+def map_to_sphere(mesh, context=None):
+    """Maps an Earth mesh onto the sphere of its 1-D model, IN PLACE (reference interpolator.py:1125-1144):
+    every point p with |p| > 0 becomes ``((p * 6371000) * z_node_1D) / |p|``, bit-identical to the reference's
+    NumPy statements; points at the centre are left alone.  Runs on the device (:meth:`Context.map_to_sphere`).
+
+    ``mesh``: a :class:`GllMesh` or a Salvus mesh (element-nodal points [E, P, 3] and an element-nodal
+    ``z_node_1D``), a :class:`HexMesh` with a nodal ``z_node_1D`` field, or any object with ``points`` [N, 3],
+    ``connectivity`` [E, P] and an element-nodal ``z_node_1D`` in ``element_nodal_fields`` -- node n then takes
+    the value at its first occurrence in the flattened connectivity, as the reference's UnstructuredMesh branch
+    does (a node no element references raises ``ValueError``).  Raises ``ValueError`` without ``z_node_1D`` and
+    for 2-D meshes.  Returns the mesh."""
+    ctx = context or default_context()
+    _set_points(mesh, _sphere_mapped(mesh, ctx).numpy())
+    return mesh
+
+
+def _element_nodal_base(mesh, ctx):
+    """(gll_points [E, P, 3], z_node_1D [E, P], shape_order) of a base mesh for map_to_ellipse.  A node layout
+    gives every copy of a node the node's own value (first occurrence), as the reference's r_ratio[connectivity]."""
+    pts, z, connectivity = _sphere_layout(mesh)
+    if pts.ndim == 3:
+        return np.ascontiguousarray(pts, dtype=np.float64), z, int(mesh.shape_order)
+    if connectivity is not None:
+        z = z.reshape(-1)[ctx.first_occurrence(connectivity, pts.shape[0]).numpy()]
+    if isinstance(mesh, HexMesh):        # exodus hex8 -> the tensor order of an order-1 GLL element
+        conn, order = mesh.connectivity[:, [0, 1, 3, 2, 4, 5, 7, 6]], 1
+    else:                                # GLL nodes listed in tensor order (p = i + (n+1) j + (n+1)^2 k)
+        conn, order = np.asarray(mesh.connectivity), int(mesh.shape_order)
+    return np.ascontiguousarray(pts[conn], dtype=np.float64), np.ascontiguousarray(z[conn]), order
+
+
+def map_to_ellipse(base_mesh, mesh, nelem_to_search=25, tolerance=1.05, context=None):
+    """Stretches ``mesh`` (IN PLACE) to the ellipticity and topography of ``base_mesh`` (reference
+    interpolator.py:1085-1122, whose call to get_element_weights lacks its shape_order argument and cannot
+    run as written; this follows its evident intent):
+
+    1. the radial ratio ``(|p| / 6371000) / z_node_1D`` on the base's element-nodal points;
+    2. sphere-mapped copies of both meshes (:func:`map_to_sphere`'s arithmetic);
+    3. the ratio interpolated at the mapped points of ``mesh`` through the GLL path of the base
+       (:meth:`Context.interpolate_gll`: centroid kNN, ``tolerance``, no snapping);
+    4. if any point has no enclosing element, ``ValueError`` -- before anything is written;
+    5. ``mesh``'s points become ``ratio * (mapped point)``.
+
+    ``base_mesh`` is never modified.  It needs element-nodal GLL points (a :class:`GllMesh`, a Salvus mesh), a
+    :class:`HexMesh`, or ``points`` + ``connectivity`` in GLL tensor order + ``shape_order``.  Returns ``mesh``."""
+    ctx = context or default_context()
+    gp, z_en, order = _element_nodal_base(base_mesh, ctx)
+    gp_d = ctx.to_device(gp)
+    ratio = ctx.sphere_ratio(gp_d, z_en, r_ref=R_EARTH)
+    base_sphere = ctx.map_to_sphere(gp_d, z_en, r_ref=R_EARTH)
+    targets = _sphere_mapped(mesh, ctx)
+    flat = DeviceArray(ctx, targets.ptr, (targets.size // 3, 3), np.float64, owner=False, keepalive=targets)
+    values, missing = ctx.interpolate_gll(order, base_sphere, flat, ratio, nelem_to_search=nelem_to_search,
+                                          tolerance=tolerance)
+    if missing:
+        raise ValueError(f"{missing} points could not find an enclosing element.")
+    ctx.scale_points(targets, values, out=targets)
+    _set_points(mesh, targets.numpy())
+    return mesh
+
+
 def get_element_weights(gll_points, shape_order, centroid_tree, points, nelem_to_search=25, tolerance=1.05,
                         snap_to_nearest=False, context=None):
     """Enclosing element and interpolation coefficients of every point
@@ -203,13 +334,16 @@ def check_if_inside_element(gll_model, nearest_elements, points, shape_order, co
 
 
 def interpolate_gll_to_points(mesh: GllMesh, points, params_to_interp, nelem_to_search=25, tolerance=1.05,
-                              context=None):
+                              context=None, make_spherical=False):
     """The GLL form of ``interpolate_to_points`` (reference interpolator.py:931-977): centroid tree,
-    element weights, then ``np.sum(coeffs * field[elem], axis=1)`` per parameter -> f64[N, C]."""
+    element weights, then ``np.sum(coeffs * field[elem], axis=1)`` per parameter -> f64[N, C].
+    ``make_spherical``: the mesh's GLL points are mapped onto the sphere of its 1-D model first (:943-944), on
+    the device and as a copy (``mesh`` is not changed); the points are taken as they are."""
     ctx = context or default_context()
     points = np.ascontiguousarray(points, dtype=np.float64)
     fields = np.stack([mesh.element_nodal_fields[p] for p in params_to_interp])
-    vals, num_failed = ctx.interpolate_gll(mesh.shape_order, mesh.gll_points, points, fields,
+    gll_points = _sphere_mapped(mesh, ctx) if make_spherical else mesh.gll_points
+    vals, num_failed = ctx.interpolate_gll(mesh.shape_order, gll_points, points, fields,
                                            nelem_to_search=nelem_to_search, tolerance=tolerance)
     if num_failed > 0:
         print(num_failed, "points could not find an enclosing element. These points will be set to zero. "
@@ -648,15 +782,16 @@ def gll_2_gll_layered_multi_two(from_gll, to_gll, layers, nelem_to_search=30, pa
     """Layer by layer, GLL model to GLL model, through the fast Salvus-mesh reader (reference api.py:645-699,
     interpolator.py:980-1082): the ``layer`` elemental field of both meshes, :func:`interpolate_gll_to_gll_layered`,
     every parameter attached to ``to_gll``.  ``layers``: "all" or a list of layer numbers (the Earth presets
-    need mesh metadata); ``make_spherical`` is Earth-specific and refused."""
+    need mesh metadata).  ``make_spherical``: both meshes' coordinates are mapped onto the sphere of their 1-D
+    model (their ``z_node_1D`` fields) right after they are read (:1016-1026); the files' ``MODEL/coordinates``
+    are not changed."""
     from . import io as mio
 
-    if make_spherical:
-        raise NotImplementedError("map_to_sphere (reference interpolator.py:1085-1144) is Earth-specific "
-                                  "(out of scope, SURVEY.md §8)")
     start = time.time()
     original_mesh = mio.SalvusMesh(from_gll, fast_mode=False)
     new_mesh = mio.SalvusMesh(to_gll, fast_mode=False)
+    if make_spherical:
+        _map_read_meshes(original_mesh, new_mesh, context)
     if isinstance(parameters, str) and parameters == "all":
         parameters = list(original_mesh.element_nodal_fields.keys())
     parameters = mio.pick_parameters(parameters)
@@ -685,12 +820,12 @@ def _gll_2_gll_layered_bbox(from_gll, to_gll, layers, nelem_to_search, parameter
                             keep_existing, context):
     from . import io as mio
 
-    if make_spherical:
-        raise NotImplementedError("map_to_sphere (reference interpolator.py:1085-1144) is Earth-specific "
-                                  "(out of scope, SURVEY.md §8)")
     print("Initialization stage")
     original_mesh = mio.SalvusMesh(from_gll, fast_mode=False)
     new_mesh = mio.SalvusMesh(to_gll, fast_mode=False)
+    if make_spherical:
+        # (reference interpolator.py:326-339, :484-494: both meshes right after they are read)
+        _map_read_meshes(original_mesh, new_mesh, context)
     if isinstance(parameters, str) and parameters == "all":
         parameters = list(original_mesh.element_nodal_fields.keys())
     parameters = mio.pick_parameters(parameters)

@@ -465,6 +465,101 @@ class Context:
         return int(check(self.lib.mm_fluid_solid_fix(self.handle, v.ptr, prev.ptr, sol.ptr, nelem, ncomp, P, int(vs_index)),
                          "mm_fluid_solid_fix"))
 
+    # ---- Earth meshes onto their 1-D sphere (reference interpolator.py:1085-1144) ------------------------------
+    def _points3(self, points):
+        pts = self.asdevice(points, np.float64)
+        if len(pts.shape) < 2 or pts.shape[-1] != 3:
+            raise ValueError("points must be [..., 3] (3-D meshes only)")
+        return pts, pts.size // 3
+
+    def first_occurrence(self, connectivity, nnodes):
+        """``np.unique(connectivity, return_index=True)[1]`` as the node layout of ``map_to_sphere`` reads it:
+        int64[nnodes] with the smallest flat index of every node.  Raises ``ValueError`` when a node is not
+        referenced (the reference would fail there with an index error) or an entry lies outside [0, nnodes)."""
+        conn = self.asdevice(connectivity, np.int64)
+        first = self.empty((int(nnodes),), np.int64)
+        rc = self.lib.mm_first_occurrence(self.handle, conn.ptr, conn.size, int(nnodes), first.ptr)
+        if rc == -1:
+            raise ValueError(self.lib.mm_last_error().decode(errors="replace"))
+        unreferenced = check(rc, "mm_first_occurrence")
+        if unreferenced:
+            raise ValueError(f"{unreferenced} nodes are not referenced by the connectivity: z_node_1D has no value "
+                             "for them")
+        return first
+
+    def _radius_index(self, npoints, rad, connectivity, first):
+        """(rad DeviceArray, first DeviceArray or None) for ``npoints`` points."""
+        r = self.asdevice(rad, np.float64)
+        if connectivity is None and first is None:
+            if r.size != npoints:
+                raise ValueError("element-nodal layout: rad (z_node_1D) needs one value per point")
+            return r, None
+        if first is None:
+            conn = self.asdevice(connectivity, np.int64)
+            if conn.size != r.size:
+                raise ValueError("node layout: z_node_1D must be element-nodal, the shape of the connectivity")
+            first = self.first_occurrence(conn, npoints)
+        else:
+            first = self.asdevice(first, np.int64)
+            if first.size != npoints:
+                raise ValueError("first must hold one index per point")
+        return r, first
+
+    def map_to_sphere(self, points, rad, connectivity=None, out=None, r_ref=6371000.0, first=None):
+        """Every point rescaled radially onto the radius of its 1-D model, ``((p * r_ref) * rad) / |p|``
+        (reference interpolator.py:1125-1144); points at the centre are left alone.
+
+        Element-nodal layout: ``points`` f64[E, P, 3] (or [N, 3]) and ``rad`` (z_node_1D) f64[E, P] (or [N]).
+        Node layout: ``points`` f64[N, 3], ``rad`` f64[E, P] element-nodal and ``connectivity`` int64[E, P]: node
+        n takes the value of its first occurrence in the flattened connectivity (or pass ``first``, what
+        :meth:`first_occurrence` returned).  ``out``: None -> a new device array; ``out`` may be ``points``
+        itself for the in-place map (a DeviceArray, a device tensor, or a NumPy array, which then receives the
+        result).  Returns the mapped points (``out`` when given)."""
+        pts, n = self._points3(points)
+        r, first = self._radius_index(n, rad, connectivity, first)
+        host_out = out if isinstance(out, np.ndarray) else None
+        if host_out is not None:
+            if host_out.shape != pts.shape or host_out.dtype != np.float64 or not host_out.flags.c_contiguous:
+                raise ValueError("out must be a C-contiguous f64 array of the shape of points")
+            out = pts if host_out is points else None
+        if out is None:
+            out = self.empty(pts.shape, np.float64)
+        else:
+            out = self.asdevice(out, np.float64)
+            if out.size != pts.size:
+                raise ValueError("out must have the shape of points")
+        check(self.lib.mm_map_to_sphere(self.handle, pts.ptr, n, r.ptr, r.size, first.ptr if first else None,
+                                        float(r_ref), out.ptr), "mm_map_to_sphere")
+        if host_out is not None:      # a NumPy ``out`` (``points`` itself for the in-place map) receives the result
+            check(self.lib.mm_copy_d2h(self.handle, host_out.ctypes.data, out.ptr, host_out.nbytes), "mm_copy_d2h")
+            return host_out
+        return out
+
+    def sphere_ratio(self, points, rad, connectivity=None, r_ref=6371000.0, first=None):
+        """``(|p| / r_ref) / rad`` per point (reference interpolator.py:1093-1097), the radial stretch of an
+        elliptic mesh over its sphere; layouts as :meth:`map_to_sphere`.  Returns f64 of the points' leading shape."""
+        pts, n = self._points3(points)
+        r, first = self._radius_index(n, rad, connectivity, first)
+        out = self.empty(pts.shape[:-1], np.float64)
+        check(self.lib.mm_sphere_ratio(self.handle, pts.ptr, n, r.ptr, r.size, first.ptr if first else None,
+                                       float(r_ref), out.ptr), "mm_sphere_ratio")
+        return out
+
+    def scale_points(self, points, factor, out=None):
+        """``factor[i] * p_i`` (reference interpolator.py:1121); ``out`` may be ``points`` (in place)."""
+        pts, n = self._points3(points)
+        f = self.asdevice(factor, np.float64)
+        if f.size != n:
+            raise ValueError("factor needs one value per point")
+        if out is None:
+            out = self.empty(pts.shape, np.float64)
+        else:
+            out = self.asdevice(out, np.float64)
+            if out.size != pts.size:
+                raise ValueError("out must have the shape of points")
+        check(self.lib.mm_scale_points(self.handle, pts.ptr, n, f.ptr, out.ptr), "mm_scale_points")
+        return out
+
     # ---- A11 ----------------------------------------------------------------------------
     def unique_points(self, points, unique_out=None, inverse_out=None, ordered=True):
         """``np.unique(points, axis=0, return_inverse=True)`` (reference utils.py:484-488) on the

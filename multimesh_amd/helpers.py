@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = (
     "mm_scatter_elements", "mm_fluid_solid_fix", "mm_set_profiling", "mm_last_timings", "mm_set_lazy_lists", "mm_unique_points", "mm_locate_gll_bbox", "mm_interpolate_gll",
     "mm_set_fp_mode", "mm_get_fp_mode", "mm_last_locate_stats",
     "mm_source_create", "mm_source_destroy", "mm_interpolate_hex8_on", "mm_points_to_elements", "mm_unique_points_any_order",
+    "mm_map_to_sphere", "mm_first_occurrence", "mm_sphere_ratio", "mm_scale_points",
 )
 
 
@@ -147,6 +148,14 @@ def load_lib():
     lib.mm_source_destroy.argtypes = [vp, vp]
     lib.mm_interpolate_hex8_on.restype = C.c_int64
     lib.mm_interpolate_hex8_on.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp, vp]
+    lib.mm_map_to_sphere.restype = C.c_int
+    lib.mm_map_to_sphere.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_double, vp]
+    lib.mm_first_occurrence.restype = C.c_int64
+    lib.mm_first_occurrence.argtypes = [vp, vp, C.c_int64, C.c_int64, vp]
+    lib.mm_sphere_ratio.restype = C.c_int
+    lib.mm_sphere_ratio.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_double, vp]
+    lib.mm_scale_points.restype = C.c_int
+    lib.mm_scale_points.argtypes = [vp, vp, C.c_int64, vp, vp]
     lib.mm_set_fp_mode.restype = C.c_int
     lib.mm_set_fp_mode.argtypes = [vp, C.c_int]
     lib.mm_get_fp_mode.restype = C.c_int

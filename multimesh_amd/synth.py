@@ -175,3 +175,65 @@ CONFIGS = {
     "cfg4": dict(n_src=216, n_tgt=465, ncomp=1),   # 100M targets over 8 GPUs
     # cfg5 (order-4 GLL hexes, 43^3 source / 47^3 target elements) is served by gll_mesh(44, 4) / (48, 4)
 }
+
+
+R_EARTH = 6371000.0
+
+
+def earth_chunk(order=2, nlat=4, nlon=4, lat=(-8.0, 8.0), lon=(-8.0, 8.0), radii=(5_971_000.0, 6_171_000.0, R_EARTH),
+                nrad=(2, 2), fluid_layers=(), ellipticity=0.0, topography=0.0, taper_radius=6_071_000.0, topo_seed=0):
+    """An order-``order`` GLL chunk of a spherical shell, the element-nodal layout of a Salvus Earth mesh.
+
+    Elements form a (lat, lon, radius) grid: ``nlat`` x ``nlon`` over the ``lat`` / ``lon`` extents (degrees,
+    geocentric) and, between consecutive ``radii`` (m, ascending), ``nrad[l]`` radial elements of layer ``l + 1``
+    (layers are numbered outwards, the numbering the ``layer`` field of a Salvus mesh has).  Node index
+    p = i + (order+1) j + (order+1)^2 k with (i, j, k) along (lon, lat, radius).  Returns a dict with
+    ``points`` f64[E, P, 3], ``z_node_1D`` f64[E, P] = r / R_EARTH of the node's 1-D radius r (exactly the quotient,
+    also after the deformation), ``layer`` and ``fluid`` f64[E] (elemental; fluid = 1 for ``fluid_layers``).
+
+    Deformation, as a function of the undeformed node (so that copies of a node stay bit-identical):
+    ``p * (1 + e(r) (1/3 - cos^2 theta) + t(lat, lon) s(r))`` with theta the colatitude, e(r) = ellipticity * (r/R)^2,
+    t a seeded smooth pattern of amplitude ``topography`` (relative: 3e-4 is ~2 km) and s(r) the taper
+    ((r - taper_radius) / (R - taper_radius))^2 above ``taper_radius``, 0 below."""
+    g = (gll_nodes_1d(order) + 1.0) / 2.0                        # [0, 1]
+    m = order + 1
+
+    def axis(lo, hi, nel):
+        edges = np.linspace(lo, hi, nel + 1)
+        pts = (edges[:-1, None] + (edges[1:] - edges[:-1])[:, None] * g[None, :]).reshape(-1)
+        return np.ascontiguousarray(np.concatenate([pts.reshape(nel, m)[:, :-1].reshape(-1), edges[-1:]]))
+
+    lon_ax = axis(lon[0], lon[1], nlon)                           # global node coordinates along each axis
+    lat_ax = axis(lat[0], lat[1], nlat)
+    if len(radii) != len(nrad) + 1:
+        raise ValueError("radii needs one more entry than nrad")
+    r_parts, layer_of_rad = [], []
+    for li, ne in enumerate(nrad):
+        a = axis(radii[li], radii[li + 1], ne)
+        r_parts.append(a if li == 0 else a[1:])
+        layer_of_rad += [li + 1] * ne
+    r_ax = np.concatenate(r_parts)
+    nr = len(layer_of_rad)
+
+    # element (kr, jlat, ilon) -> global node indices along each axis
+    kr, jl, il = np.meshgrid(np.arange(nr), np.arange(nlat), np.arange(nlon), indexing="ij")
+    kr, jl, il = kr.reshape(-1), jl.reshape(-1), il.reshape(-1)
+    kk, jj, ii = np.meshgrid(np.arange(m), np.arange(m), np.arange(m), indexing="ij")   # p = i + m j + m^2 k
+    kk, jj, ii = kk.reshape(-1), jj.reshape(-1), ii.reshape(-1)
+    lon_d = lon_ax[il[:, None] * order + ii[None, :]]
+    lat_d = lat_ax[jl[:, None] * order + jj[None, :]]
+    r = r_ax[kr[:, None] * order + kk[None, :]]
+    colat = np.deg2rad(90.0 - lat_d)
+    phi = np.deg2rad(lon_d)
+    pts = np.stack([r * np.sin(colat) * np.cos(phi), r * np.sin(colat) * np.sin(phi), r * np.cos(colat)], axis=-1)
+    if ellipticity or topography:
+        e = ellipticity * (r / R_EARTH) ** 2
+        rng = np.random.default_rng(topo_seed)
+        kx, ky, ph1, ph2 = rng.uniform(0.5, 2.0), rng.uniform(0.5, 2.0), rng.uniform(0, 2 * np.pi), rng.uniform(0, 2 * np.pi)
+        t = topography * 0.5 * (np.sin(kx * np.deg2rad(lat_d) * 20 + ph1) + np.cos(ky * phi * 20 + ph2))
+        s = np.where(r > taper_radius, ((r - taper_radius) / (R_EARTH - taper_radius)) ** 2, 0.0)
+        pts = pts * (1.0 + e * (1.0 / 3.0 - np.cos(colat) ** 2) + t * s)[..., None]
+    layer = np.asarray(layer_of_rad, dtype=np.float64)[kr]
+    fluid = np.isin(layer, np.asarray(fluid_layers, dtype=np.float64)).astype(np.float64)
+    return {"points": np.ascontiguousarray(pts), "z_node_1D": np.ascontiguousarray(r / R_EARTH),
+            "layer": layer, "fluid": fluid}

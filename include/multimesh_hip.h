@@ -184,7 +184,8 @@ int64_t mm_unique_points(mm_context *ctx, const double *points_d, int64_t npoint
 
 /* The same collapse WITHOUT NumPy's order, for callers that only scatter values back through the inverse -- which is all
  * the reference ever does with get_unique_points (components/interpolator.py:823, :1079-1081): the unique rows come in the
- * order of their first occurrence (unique[inverse[i]] == points[i] as above, -0.0 stored as +0.0).  A hash table instead of
+ * order of their first occurrence (unique[inverse[i]] == points[i] as above, -0.0 stored as +0.0; a row with a NaN
+ * coordinate is a class of its own, as in np.unique(axis=0)).  A hash table instead of
  * a sort: 2-3x faster.  Returns the number of unique rows, or a negative MM_ERR_*. */
 int64_t mm_unique_points_any_order(mm_context *ctx, const double *points_d, int64_t npoints, int64_t dim,
                                    double *unique_d, int64_t *inverse_d);

@@ -220,7 +220,8 @@ MM_HD bool newton_hex8(const double px, const double py, const double pz, const 
 //     anything else -- a test inside its band, updates that do not shrink, no convergence inside the cap, a
 //     non-finite number, an element so ill-conditioned that delta > 1e-6 -- returns MM_FAST_UNSURE and the caller
 //     repeats the solve with newton_hex8 (locate_pass_kernel<..., FAST> hands such targets to the exact kernel).
-// With MM_FAST_ACCEPT xi is the reference's final iterate to within delta (same trip count).
+// With MM_FAST_ACCEPT xi is the reference's final iterate to within delta (same trip count), and delta is small enough
+// against the element's shortest edge for the weights' stated tolerance (fast_weights_within_bound).
 // =====================================================================================================================
 #define MM_FAST_REJECT 0
 #define MM_FAST_ACCEPT 1
@@ -311,6 +312,35 @@ MM_HD void fast_axis(const double (&c)[8], double q0, double r, double s, double
     res = __builtin_fma(-t, c[3], __builtin_fma(-s, D, __builtin_fma(-r, gr, q0)));
 }
 
+// An accept also hands out weights, which MM_FP_TOL promises within B = max(1e-12, 64 eps max|x| / h), h the shortest
+// edge (include/multimesh_hip.h).  delta follows the element's smallest HEIGHT (through |J^-1|), B its shortest edge: on
+// a thin element whose edges across the layer are slanted the two part ways, and without a check weights missed B by
+// 2x (tests/test_newton_host.py, sheared and warped slabs).  The cap is derived, not fitted:
+//   * the error model: on a certified accept |xi - xi_ref|_max <= delta / 128 (host tests assert it on every certified
+//     accept of every family; the largest measured is delta / 217, tangled elements, delta / 300 on thin slabs);
+//   * the weights' sensitivity: |dw_n / dxi_q| <= 0.125 (1 + |xi|)^2 <= 0.53 for max|xi| < 1.025, so over the three
+//     axes |w(xi) - w(xi_ref)| <= 1.58 |xi - xi_ref|_max; weights_hex8_fast adds < 4e-16 against the reference's
+//     polynomials;
+//   * so delta <= 64 B' gives weights within 1.58 x 64 / 128 B' + 4e-16 < 0.8 B' + 4e-16 <= B, where B' <= B is B
+//     with h from the three edges at corner 0 (an upper bound on the shortest edge) and max|x| from corner 0 and the
+//     point (a lower bound on the largest coordinate).
+// Regular elements have delta ~ 24 B (Earth scale) or less; what the cap turns away is slabs of aspect >= ~100.
+constexpr double kFastWcap = 64.0;
+
+MM_HD bool fast_weights_within_bound(const double px, const double py, const double pz, const double (&x)[8],
+                                     const double (&y)[8], const double (&z)[8], const double delta)
+{
+    if (delta <= kFastWcap * 1e-12) return true;
+    // corner 0's neighbours along r, s, t: corners 3, 1, 4
+    const double e3 = __builtin_fma(x[3] - x[0], x[3] - x[0], __builtin_fma(y[3] - y[0], y[3] - y[0], (z[3] - z[0]) * (z[3] - z[0])));
+    const double e1 = __builtin_fma(x[1] - x[0], x[1] - x[0], __builtin_fma(y[1] - y[0], y[1] - y[0], (z[1] - z[0]) * (z[1] - z[0])));
+    const double e4 = __builtin_fma(x[4] - x[0], x[4] - x[0], __builtin_fma(y[4] - y[0], y[4] - y[0], (z[4] - z[0]) * (z[4] - z[0])));
+    const double h2 = __builtin_fmin(__builtin_fmin(e3, e1), e4);
+    const double xm = __builtin_fmax(mm_max3abs(x[0], y[0], z[0]), mm_max3abs(px, py, pz));
+    const double b = (kFastWcap * 64.0 * kFastEps) * xm;
+    return delta * delta * h2 <= b * b;
+}
+
 // diag (nullable, host tests): {delta, the trip that found convergence, largest |u_i| / |u_i-1| seen}
 MM_HD int newton_hex8_fast(const double px, const double py, const double pz, const double (&x)[8],
                            const double (&y)[8], const double (&z)[8], double (&xi)[3], const int max_it,
@@ -360,6 +390,7 @@ MM_HD int newton_hex8_fast(const double px, const double py, const double pz, co
             if (diag) diag[1] = it;
             const double worst = mm_max3abs(r, s, t);
             verdict = worst < (1 + 0.025) - delta ? MM_FAST_ACCEPT : (worst > (1 + 0.025) + delta ? MM_FAST_REJECT : MM_FAST_UNSURE);
+            if (verdict == MM_FAST_ACCEPT && !fast_weights_within_bound(px, py, pz, x, y, z, delta)) verdict = MM_FAST_UNSURE;
             break;
         }
         // inside the band (or not a number); or no verdict inside the cap: the reference may run to 50

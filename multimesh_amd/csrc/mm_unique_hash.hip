@@ -10,7 +10,8 @@
 // one compare-and-swap, keeping the SMALLEST row index of its class), one pass that marks the class representatives,
 // a prefix sum, one pass that writes the unique rows and the inverse.  Deterministic: the representative of a class is
 // its smallest index whatever the order of the atomics, and the output order is ascending representative index.
-// -0.0 equals +0.0 as in NumPy (the row kept is the first one); NaN rows never merge.
+// -0.0 equals +0.0 as in NumPy (the row kept is the first one); a row with a NaN never merges, not even with a row of
+// the same bits (np.unique(axis=0) keeps every such row apart): it hashes by its own index and claims a slot of its own.
 #include "mm_common.h"
 
 int mm_exclusive_scan_int(mm_context *ctx, const int *counts, i64 n, int *start, int *tile_sums);
@@ -37,6 +38,11 @@ __device__ __forceinline__ u64 mix64(u64 h)
     return h;
 }
 
+__device__ __forceinline__ bool nan_bits(u64 b)
+{
+    return (b & 0x7fffffffffffffffull) > 0x7ff0000000000000ull;
+}
+
 template <int DIM>
 __device__ __forceinline__ void load_row(const double *__restrict__ pts, i64 i, u64 (&b)[3])
 {
@@ -54,7 +60,10 @@ __global__ __launch_bounds__(kBlock) void unique_insert_kernel(const double *__r
     if (i >= n) return;
     u64 b[3];
     load_row<DIM>(pts, i, b);
-    unsigned s = (unsigned)mix64(b[0] ^ mix64(b[1] ^ mix64(b[2] + 0x9e3779b97f4a7c15ull))) & mask;
+    const bool lone = nan_bits(b[0]) || nan_bits(b[1]) || nan_bits(b[2]);
+    u64 h = mix64(b[0] ^ mix64(b[1] ^ mix64(b[2] + 0x9e3779b97f4a7c15ull)));
+    if (lone) h = mix64(h ^ (u64)i);   // equal NaN rows would otherwise probe one chain
+    unsigned s = (unsigned)h & mask;
     for (;;) {
         int cur = __atomic_load_n(&table[s], __ATOMIC_RELAXED);
         if (cur < 0) {
@@ -64,7 +73,7 @@ __global__ __launch_bounds__(kBlock) void unique_insert_kernel(const double *__r
         }
         u64 c[3];
         load_row<DIM>(pts, (i64)cur, c);
-        if (c[0] == b[0] && c[1] == b[1] && c[2] == b[2]) {
+        if (!lone && c[0] == b[0] && c[1] == b[1] && c[2] == b[2]) {
             if ((int)i < cur) atomicMin(&table[s], (int)i);
             break;
         }

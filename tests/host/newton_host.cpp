@@ -177,4 +177,68 @@ double nh_fast_weights(int64_t n, const double *xis, void (*other)(const double 
     }
     return worst;
 }
+
+// MM_FP_TOL's stated contract for the weights (include/multimesh_hip.h, bench.py): for every solve newton_hex8_fast
+// (cap trips) certifies as an accept, weights_hex8_fast of its iterate against weights(the reference iterate of
+// newton = the oracle's mmo_hex8_newton) within bound = max(1e-12, 64 eps max|x| / h), max|x| the largest coordinate of
+// the element's corners and the point, h its shortest edge.  Returns the largest |w_fast - w_ref|_max / bound;
+// out[0] the number of certified accepts checked, out[1] the largest |w_fast - w_ref|, out[2] the bound where the
+// ratio peaked, out[3] the largest |xi_fast - xi_ref|_max / delta over the certified accepts.
+double nh_fast_weight_ratio(int64_t n, const double *pnts, const double *vtxs, void *newton,
+                            void (*weights)(const double *, double *), int cap, double *out)
+{
+    double worst = 0;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const double *p = pnts + i * 3, *v = vtxs + i * 24;
+        double x[8], y[8], z[8], xm[3] = {0, 0, 0}, diag[3];
+        for (int c = 0; c < 8; ++c) {
+            x[c] = v[c * 3 + 0];
+            y[c] = v[c * 3 + 1];
+            z[c] = v[c * 3 + 2];
+        }
+        if (newton_hex8_fast(p[0], p[1], p[2], x, y, z, xm, cap, diag) != MM_FAST_ACCEPT) continue;
+        double xo[3] = {0, 0, 0}, wm[8], wo[8];
+        ((other4_t)newton)(p, v, xo, nullptr);
+        for (int q = 0; q < 3; ++q) out[3] = __builtin_fmax(out[3], __builtin_fabs(xm[q] - xo[q]) / diag[0]);
+        weights_hex8_fast(xm, wm);
+        weights(xo, wo);
+        double xmax = mm_max3abs(p[0], p[1], p[2]), h = __builtin_inf();
+        for (int a = 0; a < 8; ++a) {
+            xmax = __builtin_fmax(xmax, mm_max3abs(x[a], y[a], z[a]));
+            for (int b = a + 1; b < 8; ++b) {
+                // an edge joins corners whose (R, S, T) signs differ in exactly one place
+                const int diff = (MM_R(a) != MM_R(b)) + (MM_S(a) != MM_S(b)) + (MM_T(a) != MM_T(b));
+                if (diff != 1) continue;
+                const double dx = x[a] - x[b], dy = y[a] - y[b], dz = z[a] - z[b];
+                h = __builtin_fmin(h, __builtin_sqrt(dx * dx + dy * dy + dz * dz));
+            }
+        }
+        const double bound = __builtin_fmax(1e-12, 64.0 * kFastEps * xmax / h);
+        double d = 0;
+        for (int q = 0; q < 8; ++q) d = __builtin_fmax(d, __builtin_fabs(wm[q] - wo[q]));
+        out[0] += 1;
+        out[1] = __builtin_fmax(out[1], d);
+        if (!(d / bound <= worst)) {
+            worst = d / bound;
+            out[2] = bound;
+        }
+    }
+    return worst;
+}
+
+// newton_hex8_fast's verdict (MM_FAST_ACCEPT / REJECT / UNSURE) of each of n solves
+void nh_fast_verdicts(int64_t n, const double *pnts, const double *vtxs, int cap, int8_t *verdicts)
+{
+    for (int64_t i = 0; i < n; ++i) {
+        const double *p = pnts + i * 3, *v = vtxs + i * 24;
+        double x[8], y[8], z[8], xm[3];
+        for (int c = 0; c < 8; ++c) {
+            x[c] = v[c * 3 + 0];
+            y[c] = v[c * 3 + 1];
+            z[c] = v[c * 3 + 2];
+        }
+        verdicts[i] = (int8_t)newton_hex8_fast(p[0], p[1], p[2], x, y, z, xm, cap);
+    }
+}
 }

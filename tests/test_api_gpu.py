@@ -269,6 +269,60 @@ def test_unique_points_edge_cases():
     ctx.close()
 
 
+def _rows_with_nan_zeros_and_infs(dim, seed):
+    """Rows from a small alphabet with NaN (also bit-identical and negative NaN), +-0.0 and +-inf, many of them repeated."""
+    rng = np.random.default_rng(seed)
+    neg_nan = -np.float64(np.nan)
+    alphabet = np.array([0.0, -0.0, 1.5, -2.0, np.inf, -np.inf, np.nan, neg_nan])
+    p = np.array([0.2, 0.2, 0.15, 0.15, 0.1, 0.1, 0.06, 0.04])
+    pts = rng.choice(alphabet, size=(40_000, dim), p=p)
+    pts[:4] = np.nan                                           # the same NaN bits in whole rows
+    pts[4:8] = alphabet[:4, None]                              # and rows with no NaN at all
+    return np.ascontiguousarray(pts[rng.permutation(len(pts))])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dim", [1, 2, 3])
+def test_unique_points_any_order_keeps_nan_rows_apart(dim):
+    # np.unique(axis=0) never merges a row that holds a NaN, not even with a row of the same bits: the order-free form must
+    # give every such row a class of its own (before the fix two bit-equal NaN rows landed on one hash slot and merged),
+    # -0.0 and +0.0 one class, +inf and -inf classes of their own
+    from multimesh_amd.device import Context
+    pts = _rows_with_nan_zeros_and_infs(dim, 40 + dim)
+    nan_rows = np.isnan(pts).any(axis=1)
+    assert nan_rows.sum() > 1000 and (~nan_rows).sum() > 1000
+    with Context(0) as ctx:
+        u, inv = ctx.unique_points(pts, ordered=False)
+        u, inv = u.numpy(), inv.numpy()
+        want_u, want_inv = _first_occurrence_form(pts)
+        assert u.shape == want_u.shape and np.array_equal(u, want_u, equal_nan=True) and np.array_equal(inv, want_inv)
+        assert np.array_equal(u[inv], pts, equal_nan=True) and not np.signbit(u[u == 0]).any()
+        assert len(np.unique(inv[nan_rows])) == nan_rows.sum()
+        u2, inv2 = ctx.unique_points(pts, ordered=False)
+        assert np.array_equal(u2.numpy(), u, equal_nan=True) and np.array_equal(inv2.numpy(), inv)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dim", [1, 2, 3])
+def test_unique_points_ordered_with_nan_rows_keeps_its_promise(dim):
+    # the ordered form documents NaN as unsupported ("ordered by bit pattern and never merge", csrc/mm_unique.hip): where a
+    # NaN row sorts relative to NumPy's order is not promised, so this asserts what is -- the rows without NaN are
+    # np.unique's rows of them, in its order, every NaN row is a class of its own, and the inverse rebuilds the input
+    from multimesh_amd.device import Context
+    pts = _rows_with_nan_zeros_and_infs(dim, 50 + dim)
+    nan_rows = np.isnan(pts).any(axis=1)
+    with Context(0) as ctx:
+        u, inv = ctx.unique_points(pts)
+        u, inv = u.numpy(), inv.numpy()
+    ref_u, ref_inv = np.unique(pts[~nan_rows], axis=0, return_inverse=True)
+    u_nan = np.isnan(u).any(axis=1)
+    assert len(u) == len(ref_u) + nan_rows.sum() and u_nan.sum() == nan_rows.sum()
+    assert np.array_equal(u[~u_nan], ref_u)
+    assert np.array_equal(u[inv], pts, equal_nan=True)
+    assert np.array_equal(np.cumsum(~u_nan)[inv[~nan_rows]] - 1, ref_inv.reshape(-1))
+    assert len(np.unique(inv[nan_rows])) == nan_rows.sum()
+
+
 @pytest.mark.gpu
 def test_gll_to_gll_on_arrays_reproduces_a_polynomial():
     # gll_2_gll's array core: unique targets, GLL locate + gather, scatter back with the inverse index

@@ -21,6 +21,7 @@
 #include <stdlib.h>
 
 #include <new>
+#include <type_traits>
 
 #include "mm_common.h"
 #include <cstring>
@@ -66,6 +67,22 @@ struct LaneWork {
     int2 *items;         // [max_items]
 };
 
+// Kernels are instantiated for a few list lengths k; a query runs the smallest instance that holds its k.
+template <int... Ks>
+struct KSet {};
+using kFastKs = KSet<1, 2, 4, 8, 16, 20, 25, 32>;       // the tiled kernels and the stragglers behind them
+using kListKs = KSet<8, 16, 20, 32, 40, MM_KNN_MAX_K>;  // a caller's list, and the long lists of every target
+using kTreeKs = KSet<1, 2, 4, 8, 16, 20>;               // the tree's windows and its ring search (k <= kLaneMaxK)
+
+// f(std::integral_constant<int, K>) for the smallest K of the set that is >= k (the last one for a larger k)
+template <int K0, int... Ks, typename F>
+void with_k(KSet<K0, Ks...>, int k, F &&f)
+{
+    if constexpr (sizeof...(Ks) == 0) f(std::integral_constant<int, K0>());
+    else if (k <= K0) f(std::integral_constant<int, K0>());
+    else with_k(KSet<Ks...>(), k, f);
+}
+
 template <int K, typename IDX>
 void launch_generic(mm_context *ctx, const mm_knn_index *ix, const GridParams &g, const double *pts, i64 npts,
                     int kout, IDX *idx, double *dist, const int *list, const int *list_count, int pstride = 0,
@@ -93,18 +110,14 @@ __global__ __launch_bounds__(kBlock) void list_all_kernel(int *__restrict__ list
 // target -- against 0.35 ms by lanes; the curves cross near 12 k targets).
 // Both kernels are launched; each returns at once when the length is on the other's side of the threshold.
 // K > 32: the scalar kernel only (a lane's private list must stay in registers).
-static int list_wave_max()
-{
-    static const int v = getenv("MM_KNN_LIST_WAVE_MAX") ? atoi(getenv("MM_KNN_LIST_WAVE_MAX")) : 8192;
-    return v;
-}
+constexpr int kListWaveMax = 8192;
 
 template <int K, typename IDX>
 void launch_list(mm_context *ctx, const mm_knn_index *ix, const LevelTable &lv, const double *pts, int pstride, i64 npts,
                  int kout, IDX *idx, double *dist, const int *list, const int *list_count, int keep_max)
 {
-    const int wave_max = K <= 32 ? list_wave_max() : -1;
-    if (K <= 32 && wave_max >= 0) {
+    const int wave_max = K <= 32 ? kListWaveMax : -1;
+    if (K <= 32) {
         const i64 cap = npts < wave_max ? npts : wave_max;
         const i64 grid = cap < 8192 ? (cap > 0 ? cap : 1) : 8192;
         hipLaunchKernelGGL((knn_list_wave_kernel<(K <= 32 ? K : 32), IDX>), dim3((unsigned)grid), dim3(kWave), 0,
@@ -159,12 +172,8 @@ void launch_fast(mm_context *ctx, const mm_knn_index *ix, const GridParams &g, c
                  int *fb_list, int *fb_count, int *down_list, int *down_count, bool record_stage,
                  unsigned *strip_list, int *strip_count, const LaneWork *lane)
 {
-#ifndef MM_KNN_CAP_EXTRA_SMALL   // tuning builds only
-#define MM_KNN_CAP_EXTRA_SMALL 8
-#endif
     // room for the candidates of buckets jb and jb+1 beyond the k-th (fewer for short lists)
-    constexpr int CAP = K + (K <= 8 ? MM_KNN_CAP_EXTRA_SMALL : 12);
-    static const int dbg_stop = getenv("MM_KNN_DBG_STOP") ? atoi(getenv("MM_KNN_DBG_STOP")) : 0;
+    constexpr int CAP = K + (K <= 8 ? 8 : 12);
     // 8 XCD slabs of ceil(columns/8) cell columns each (see the kernel's workgroup map)
     const i64 cols = (i64)ix->dims[0] * ix->dims[1];
     const i64 cell_grid = 8 * ((cols + 7) / 8) * ix->dims[2];
@@ -198,8 +207,6 @@ void launch_fast(mm_context *ctx, const mm_knn_index *ix, const GridParams &g, c
         // thousand strips of a thousand targets each) the strips are shared out, ~kSplitTargets each
         const i64 per_strip = npts / (cols * nstrips > 0 ? cols * nstrips : 1);
         i64 nsplit = (per_strip + kSplitTargets / 2) / kSplitTargets;
-        static const int force_split = getenv("MM_KNN_SPLIT") ? atoi(getenv("MM_KNN_SPLIT")) : 0;
-        if (force_split > 0) nsplit = force_split;
         nsplit = nsplit < 1 ? 1 : (nsplit > kMaxSplit ? kMaxSplit : nsplit);
         while (nsplit > 1 && strip_grid * nsplit > (i64)0x7fffffff) --nsplit;
         if (strip_list) {
@@ -211,23 +218,23 @@ void launch_fast(mm_context *ctx, const mm_knn_index *ix, const GridParams &g, c
             if (walkers > 16384) walkers = 16384;
             hipLaunchKernelGGL((knn_strip_kernel<K, CAP, IDX, 2>), dim3((unsigned)walkers), dim3(kWave), 0, ctx->stream, g,
                                ix->nsrc, ix->cell_start, ix->sorted_xyz, ix->ndim, kout, tstart, tsorted, idx, dist,
-                               fb_list, fb_count, dbg_stop, (int)nsplit, down_list, down_count, strip_list, strip_count);
+                               fb_list, fb_count, (int)nsplit, down_list, down_count, strip_list, strip_count);
         } else {
             strip_grid *= nsplit;
             if (down_list)
                 hipLaunchKernelGGL((knn_strip_kernel<K, CAP, IDX, 1>), dim3((unsigned)strip_grid), dim3(kWave), 0,
                                    ctx->stream, g, ix->nsrc, ix->cell_start, ix->sorted_xyz, ix->ndim, kout, tstart,
-                                   tsorted, idx, dist, fb_list, fb_count, dbg_stop, (int)nsplit, down_list, down_count,
+                                   tsorted, idx, dist, fb_list, fb_count, (int)nsplit, down_list, down_count,
                                    (const unsigned *)nullptr, (const int *)nullptr);
             else
                 hipLaunchKernelGGL((knn_strip_kernel<K, CAP, IDX, 0>), dim3((unsigned)strip_grid), dim3(kWave), 0,
                                    ctx->stream, g, ix->nsrc, ix->cell_start, ix->sorted_xyz, ix->ndim, kout, tstart,
-                                   tsorted, idx, dist, fb_list, fb_count, dbg_stop, (int)nsplit, (int *)nullptr,
+                                   tsorted, idx, dist, fb_list, fb_count, (int)nsplit, (int *)nullptr,
                                    (int *)nullptr, (const unsigned *)nullptr, (const int *)nullptr);
         }
     } else {
         hipLaunchKernelGGL((knn_cell_kernel<K, CAP, IDX>), dim3((unsigned)cell_grid), dim3(kWave), 0, ctx->stream, g,
-                           ix->nsrc, ix->cell_start, ix->sorted_xyz, pts, ix->ndim, kout, tstart, tsorted, idx, dist, fb_list, fb_count, dbg_stop);
+                           ix->nsrc, ix->cell_start, ix->sorted_xyz, pts, ix->ndim, kout, tstart, tsorted, idx, dist, fb_list, fb_count);
     }
     if (record_stage) mm_stage_end(ctx, MM_STAGE_KNN_CELL);
 }
@@ -248,6 +255,20 @@ GridParams params_of(const mm_knn_index *ix)
     g.ihy = ix->inv_h[1];
     g.ihz = ix->inv_h[2];
     return g;
+}
+
+// The grids of ix and its denser levels, at most max_levels of them.
+LevelTable level_table_of(const mm_knn_index *ix, int max_levels)
+{
+    LevelTable lv;
+    lv.n = 0;
+    for (const mm_knn_index *l = ix; l && lv.n < max_levels; l = l->fine) {
+        lv.g[lv.n] = params_of(l);
+        lv.cell_start[lv.n] = l->cell_start;
+        lv.sorted_xyz[lv.n] = l->sorted_xyz;
+        ++lv.n;
+    }
+    return lv;
 }
 
 void free_tree(mm_knn_tree *tr)
@@ -560,17 +581,11 @@ int mm_knn_build_impl(mm_context *ctx, const double *src_d, i64 nsrc, i64 ndim, 
         for (int q = 0; q < 6; ++q) box[q] = h_box[q];
     }
     // grid resolution: ~per_cell sources per cell over the axes that have extent
-    // (MM_KNN_PER_CELL overrides the default, for tuning experiments only)
     double per_cell = kDefaultPerCell;
-    if (const char *env = getenv("MM_KNN_PER_CELL")) {
-        const double v = atof(env);
-        if (v >= 0.25 && v <= 4096.0) per_cell = v;
-    }
     int max_levels = kMaxLevels;
     if (const char *env = getenv("MM_KNN_LEVELS")) max_levels = atoi(env) < 1 ? 1 : (atoi(env) > kMaxLevels ? kMaxLevels : atoi(env));
     int extra = 0;
     mm_knn_index *head = nullptr;
-    static const double sparse_limit = getenv("MM_KNN_SPARSE_SHARE") ? atof(getenv("MM_KNN_SPARSE_SHARE")) : kSparseShare;
     int rc = MM_OK;
     double per_cell_level0 = per_cell;
     for (int scale = 1;; scale *= 2) {
@@ -579,7 +594,7 @@ int mm_knn_build_impl(mm_context *ctx, const double *src_d, i64 nsrc, i64 ndim, 
         rc = build_level(ctx, src_d, nsrc, (int)ndim, box, per_cell, use_context_buffers, 0, max_levels > 1 ? &extra : nullptr,
                          &head, &sparse, /*stat_dirty=*/scale > 1 || nsrc == 0);
         if (rc != MM_OK) return rc;
-        if (scale >= 4 || !(sparse > sparse_limit)) break;
+        if (scale >= 4 || !(sparse > kSparseShare)) break;
         free_index(head);   // a large sparse region: cells of twice the volume
         head = nullptr;
         per_cell *= 2.0;
@@ -657,9 +672,8 @@ bool mm_knn_guess_confirmed(mm_context *ctx)
     if (memcmp(h_box, ctx->grid_guess.box, 6 * sizeof(double)) != 0) return false;
     if (ctx->grid_guess.stat_shift < 0) return true;   // (a mesh too small for the statistic: the ordinary build skips it too)
     double sparse_count = 0.0;
-    static const double sparse_limit = getenv("MM_KNN_SPARSE_SHARE") ? atof(getenv("MM_KNN_SPARSE_SHARE")) : kSparseShare;
     const int extra = stat_verdict(ctx, ctx->grid_guess.nsrc, ctx->grid_guess.stat_shift, &sparse_count);
-    return extra == 0 && !(sparse_count / (double)ctx->grid_guess.nsrc > sparse_limit);
+    return extra == 0 && !(sparse_count / (double)ctx->grid_guess.nsrc > kSparseShare);
 }
 
 
@@ -781,30 +795,19 @@ static void tree_ring(mm_context *ctx, const mm_knn_index *ix, const double *pts
     i64 grid = (npts + kBlock - 1) / kBlock;
     if (grid > 4096) grid = 4096;
     if (grid < 1) grid = 1;
-    LevelTable lv;
-    lv.n = 1;
-    lv.g[0] = params_of(ix);
-    lv.cell_start[0] = ix->cell_start;
-    lv.sorted_xyz[0] = ix->sorted_xyz;
+    const LevelTable lv = level_table_of(ix, 1);
     const i64 wgrid = npts < 8192 ? (npts > 0 ? npts : 1) : 8192;
-#define MM_TREE_RING(KK)                                                                                                           \
-    do {                                                                                                                           \
-        hipLaunchKernelGGL((knn_list_wave_kernel<KK, IDX>), dim3((unsigned)wgrid), dim3(kWave), 0, ctx->stream, lv, ix->nsrc, pts, \
-                           ix->ndim, pstride, kout, idx_d, dist_d, list, list_count, kListKeepMax, kTreeWaveListMax,               \
-                           (const int *)nullptr);                                                                                  \
-        if (npts > kTreeWaveListMax)                                                                                               \
-            hipLaunchKernelGGL((tree_ring_kernel<KK, IDX>), dim3((unsigned)grid), dim3(kBlock), 0, ctx->stream,                    \
-                               tree_params_of(tr), (const u64 *)tr->keys, (const int *)tr->coarse,                                 \
-                               (const unsigned char *)tr->level, (const double *)tr->xyz, (int)ix->nsrc, pts, ix->ndim, pstride,   \
-                               kout, idx_d, dist_d, list, list_count, kTreeWaveListMax);                                           \
-    } while (0)
-    if (kout <= 1) MM_TREE_RING(1);
-    else if (kout <= 2) MM_TREE_RING(2);
-    else if (kout <= 4) MM_TREE_RING(4);
-    else if (kout <= 8) MM_TREE_RING(8);
-    else if (kout <= 16) MM_TREE_RING(16);
-    else MM_TREE_RING(20);
-#undef MM_TREE_RING
+    with_k(kTreeKs{}, kout, [&](auto KK) {
+        constexpr int K = decltype(KK)::value;
+        hipLaunchKernelGGL((knn_list_wave_kernel<K, IDX>), dim3((unsigned)wgrid), dim3(kWave), 0, ctx->stream, lv, ix->nsrc, pts,
+                           ix->ndim, pstride, kout, idx_d, dist_d, list, list_count, kListKeepMax, kTreeWaveListMax,
+                           (const int *)nullptr);
+        if (npts > kTreeWaveListMax)
+            hipLaunchKernelGGL((tree_ring_kernel<K, IDX>), dim3((unsigned)grid), dim3(kBlock), 0, ctx->stream, tree_params_of(tr),
+                               (const u64 *)tr->keys, (const int *)tr->coarse, (const unsigned char *)tr->level,
+                               (const double *)tr->xyz, (int)ix->nsrc, pts, ix->ndim, pstride, kout, idx_d, dist_d, list,
+                               list_count, kTreeWaveListMax);
+    });
 }
 
 // lists shorter than this go straight to the ring search (sparse targets fill no 64-lane rounds)
@@ -833,8 +836,7 @@ static int tree_query(mm_context *ctx, const mm_knn_index *ix, const double *pts
         return MM_OK;
     }
     const size_t n_sz = (size_t)n;
-    static const bool unsorted_rows = getenv("MM_KNN_UNSORTED_ROWS") != nullptr;
-    const bool sorted_rows = !list && tsorted_out != nullptr && !unsorted_rows;
+    const bool sorted_rows = !list && tsorted_out != nullptr;
     const int scan_tiles = (int)((n + 1 + kScanTile - 1) / kScanTile);
     const size_t need = 2 * mm_round256(n_sz * sizeof(u64)) + 2 * mm_round256(n_sz * sizeof(unsigned)) + mm_radix_sort_scratch(n) +
                         2 * mm_round256((n_sz + 1) * sizeof(int)) + mm_round256((size_t)scan_tiles * sizeof(int)) +
@@ -882,18 +884,13 @@ static int tree_query(mm_context *ctx, const mm_knn_index *ix, const double *pts
     const unsigned *tvals = in_a ? val_a : val_b;
     u64 *node = in_a ? key_b : key_a;   // (the sort's other buffer is free now)
     hipLaunchKernelGGL(tree_records_kernel, dim3(gn), dim3(kBlock), 0, ctx->stream, pts_d, ix->ndim, pstride, tvals, n, list_count, tsorted);
-    // (MM_TREE_CELL_MIN / MM_TREE_TILE_MAX: tuning experiments only)
-    static const int env_cell_min = getenv("MM_TREE_CELL_MIN") ? atoi(getenv("MM_TREE_CELL_MIN")) : 0;
-    static const int env_tile_max = getenv("MM_TREE_TILE_MAX") ? atoi(getenv("MM_TREE_TILE_MAX")) : 0;
-    static const int env_cell_min2 = getenv("MM_TREE_CELL_MIN2") ? atoi(getenv("MM_TREE_CELL_MIN2")) : 0;
-    static const int env_tile_max2 = getenv("MM_TREE_TILE_MAX2") ? atoi(getenv("MM_TREE_TILE_MAX2")) : 0;
-    int cell_min = env_cell_min > 0 ? (kout <= 8 ? env_cell_min : (env_cell_min * 5 + 1) / 2) : tree_cell_min(kout);
-    int tile_max = env_tile_max > 0 ? env_tile_max : kTreeTileMax;
+    int cell_min = tree_cell_min(kout);
+    int tile_max = kTreeTileMax;
     if (second_pass) {
         // what the first windows could not serve -- too full for the tile, or a k-th neighbour beyond the margin --: margins
         // of ~1.8 local spacings instead of ~1.3 (cells of 3 x the sources), laid out for 70 % of the tile
-        cell_min = env_cell_min2 > 0 ? env_cell_min2 : (kout <= 8 ? 3 * cell_min : (3 * cell_min) / 2);
-        tile_max = env_tile_max2 > 0 ? env_tile_max2 : (7 * tile_max) / 10;
+        cell_min = kout <= 8 ? 3 * cell_min : (3 * cell_min) / 2;
+        tile_max = (7 * tile_max) / 10;
     }
     hipLaunchKernelGGL(tree_target_node_kernel, dim3(gn), dim3(kBlock), 0, ctx->stream, tkeys, n, list_count, tr->keys,
                        (int)ix->nsrc, tr->coarse, tr->level, cell_min, tile_max, node);
@@ -916,24 +913,17 @@ static int tree_query(mm_context *ctx, const mm_knn_index *ix, const double *pts
         const unsigned wgs = (unsigned)(8 * (nitems / 8 + 1));
         const GridParams g = params_of(ix);
         // thin layers per cell layer and half-width of a target's first window (a tree window has at most 6 cell layers:
-        // 6 T <= kLaneThinMax).  MM_TREE_T / MM_TREE_W: tuning experiments only.
-        static const int env_t = getenv("MM_TREE_T") ? atoi(getenv("MM_TREE_T")) : 0;
-        static const int env_w = getenv("MM_TREE_W") ? atoi(getenv("MM_TREE_W")) : 0;
-        const int T = env_t >= 1 && 6 * env_t <= kLaneThinMax ? env_t : kLaneThin;
-        const int W8 = env_w >= 1 && env_w <= T ? env_w : (T == kLaneThin ? kLaneWin : T);
+        // 6 kLaneThin <= kLaneThinMax)
+        static_assert(6 * kLaneThin <= kLaneThinMax, "a tree window's thin layers fit the prefix sum");
         if (!list) mm_stage_begin(ctx, MM_STAGE_KNN_CELL);
-#define MM_TREE_LANE(KK)                                                                                                          \
-    hipLaunchKernelGGL((knn_lane_kernel<KK, IDX, true>), dim3(wgs), dim3(kWave), 0, ctx->stream, g, ix->nsrc, (const int *)nullptr, \
-                       (const double *)tr->xyz, ix->ndim, kout, (const int *)nullptr, (const double *)tsorted, idx_d, dist_d,      \
-                       fb_list, fb_count, (const int2 *)nullptr, 0, 1, kWave * kLaneRounds, sorted_rows ? 1 : 0, down_list,        \
-                       down_list ? fb_count + 3 : (int *)nullptr, T, KK <= 8 ? W8 : T, ta)
-        if (kout <= 1) MM_TREE_LANE(1);
-        else if (kout <= 2) MM_TREE_LANE(2);
-        else if (kout <= 4) MM_TREE_LANE(4);
-        else if (kout <= 8) MM_TREE_LANE(8);
-        else if (kout <= 16) MM_TREE_LANE(16);
-        else MM_TREE_LANE(20);
-#undef MM_TREE_LANE
+        with_k(kTreeKs{}, kout, [&](auto KK) {
+            constexpr int K = decltype(KK)::value;
+            hipLaunchKernelGGL((knn_lane_kernel<K, IDX, true>), dim3(wgs), dim3(kWave), 0, ctx->stream, g, ix->nsrc,
+                               (const int *)nullptr, (const double *)tr->xyz, ix->ndim, kout, (const int *)nullptr,
+                               (const double *)tsorted, idx_d, dist_d, fb_list, fb_count, (const int2 *)nullptr, 0, 1,
+                               kWave * kLaneRounds, sorted_rows ? 1 : 0, down_list, down_list ? fb_count + 3 : (int *)nullptr,
+                               kLaneThin, K <= 8 ? kLaneWin : kLaneThin, ta);
+        });
         if (!list) mm_stage_end(ctx, MM_STAGE_KNN_CELL);
     }
     MM_HIP_CHECK(hipGetLastError());
@@ -980,7 +970,6 @@ static int knn_query_typed(mm_context *ctx, const mm_knn_index *ix, const double
     if (tsorted_out) *tsorted_out = nullptr;
     if (npts == 0 || k == 0) return MM_OK;
     MM_REQUIRE(npts < (i64)0x7fffffff, "too many targets for one query");
-    const GridParams g = params_of(ix);
     const int kout = (int)k;
     // a graded cloud with the adaptive index (lists the lane kernel can hold; a list only when its length is known here)
     if (ix->tree && k <= kLaneMaxK && (!list0 || list0_len >= 0) && !getenv("MM_KNN_FORCE_LIST"))
@@ -988,29 +977,16 @@ static int knn_query_typed(mm_context *ctx, const mm_knn_index *ix, const double
     if (k > 32) {
         // long lists: generic ring-expansion kernel for every target (in the grid that suits it, when
         // the cloud has density levels)
-        if (ix->fine) {
-            LevelTable lv;
-            lv.n = 0;
-            for (const mm_knn_index *l = ix; l && lv.n < kMaxLevels; l = l->fine) {
-                lv.g[lv.n] = params_of(l);
-                lv.cell_start[lv.n] = l->cell_start;
-                lv.sorted_xyz[lv.n] = l->sorted_xyz;
-                ++lv.n;
-            }
-            const dim3 grid((unsigned)((npts + kBlock - 1) / kBlock)), block(kBlock);
-            if (k <= 40)
-                hipLaunchKernelGGL((knn_query_levels_kernel<40, IDX>), grid, block, 0, ctx->stream, lv, ix->nsrc, pts_d,
-                                   ix->ndim, kout, idx_d, dist_d, (const int *)nullptr, (const int *)nullptr,
-                                   kListKeepMax, npts, -1);
+        const LevelTable lv = level_table_of(ix, kMaxLevels);
+        with_k(kListKs{}, kout, [&](auto KK) {
+            constexpr int K = decltype(KK)::value;
+            if (ix->fine)
+                hipLaunchKernelGGL((knn_query_levels_kernel<K, IDX>), dim3((unsigned)((npts + kBlock - 1) / kBlock)),
+                                   dim3(kBlock), 0, ctx->stream, lv, ix->nsrc, pts_d, ix->ndim, kout, idx_d, dist_d,
+                                   (const int *)nullptr, (const int *)nullptr, kListKeepMax, npts, -1);
             else
-                hipLaunchKernelGGL((knn_query_levels_kernel<MM_KNN_MAX_K, IDX>), grid, block, 0, ctx->stream, lv, ix->nsrc,
-                                   pts_d, ix->ndim, kout, idx_d, dist_d, (const int *)nullptr, (const int *)nullptr,
-                                   kListKeepMax, npts, -1);
-        } else if (k <= 40) {
-            launch_generic<40, IDX>(ctx, ix, g, pts_d, npts, kout, idx_d, dist_d, nullptr, nullptr);
-        } else {
-            launch_generic<MM_KNN_MAX_K, IDX>(ctx, ix, g, pts_d, npts, kout, idx_d, dist_d, nullptr, nullptr);
-        }
+                launch_generic<K, IDX>(ctx, ix, params_of(ix), pts_d, npts, kout, idx_d, dist_d, nullptr, nullptr);
+        });
         MM_HIP_CHECK(hipGetLastError());
         return MM_OK;
     }
@@ -1050,23 +1026,21 @@ static int knn_query_typed(mm_context *ctx, const mm_knn_index *ix, const double
     }
     // with density levels: level 0 only (every target starts there; strips too full for the tile are passed
     // down), and only for the short lists the lane kernel is best at
-    static const bool lane_level0 = !(getenv("MM_KNN_LANE_LEVEL0") && atoi(getenv("MM_KNN_LANE_LEVEL0")) == 0);
-    if (!force_kernel && lane_level0 && ix->fine && ix->dims[2] >= 6 && k <= 8 && npts >= 2 * ix->ncells) use_lane = true;
+    if (!force_kernel && ix->fine && ix->dims[2] >= 6 && k <= 8 && npts >= 2 * ix->ncells) use_lane = true;
     if (force_kernel) use_lane = strcmp(force_kernel, "lane") == 0 && !ix->fine && ix->dims[2] >= 2 && k <= kLaneMaxK;
     // MM_KNN_FORCE_LIST: every target through the list-mode kernel (tests of that kernel only)
-    // (MM_KNN_FORCE_LIST here and MM_KNN_LEVELS / MM_KNN_PER_CELL in the build are read per call on purpose: tests switch them
-    // inside one process; every other knob is read once)
+    // (MM_KNN_FORCE_LIST here and MM_KNN_LEVELS in the build are read per call on purpose: tests switch them inside one
+    // process; every other knob is read once)
     const bool force_list = getenv("MM_KNN_FORCE_LIST") != nullptr;
     if (force_list || list0) use_lane = lane_probe = false;
-    static const bool unsorted_rows = getenv("MM_KNN_UNSORTED_ROWS") != nullptr;
-    bool sorted_rows = use_lane && !ix->fine && tsorted_out != nullptr && !unsorted_rows;
+    bool sorted_rows = use_lane && !ix->fine && tsorted_out != nullptr;
     lane_work.sorted_rows = sorted_rows ? 1 : 0;
     if (use_lane) {
         static const int force_z = getenv("MM_KNN_LANE_Z") ? atoi(getenv("MM_KNN_LANE_Z")) : 0;
         lane_work.Z = force_z >= 1 && force_z <= kLaneZMax ? force_z : kLaneZ;
         if (lane_work.Z > ix->dims[2]) lane_work.Z = ix->dims[2];
         // thin layers: (Z + 2) T of them must fit the 64 lanes of the prefix sum; the window never reaches past one
-        // cell layer (W <= T).  MM_KNN_LANE_T / MM_KNN_LANE_W: tuning experiments only.
+        // cell layer (W <= T).  MM_KNN_LANE_Z / _T / _W: tests of the thin-layer variants.
         static const int force_t = getenv("MM_KNN_LANE_T") ? atoi(getenv("MM_KNN_LANE_T")) : 0;
         static const int force_w = getenv("MM_KNN_LANE_W") ? atoi(getenv("MM_KNN_LANE_W")) : 0;
         lane_work.T = force_t >= 1 ? force_t : kLaneThin;
@@ -1164,18 +1138,11 @@ static int knn_query_typed(mm_context *ctx, const mm_knn_index *ix, const double
             lane_work.sorted_rows = sorted_rows ? 1 : 0;
             if (sorted_rows) *tsorted_out = tsorted;
         }
-#define MM_FAST(KK)                                                                                                  \
-    launch_fast<KK, IDX>(ctx, l, gl, pts_d, npts, kout, start, tsorted, idx_d, dist_d, fb_list, fb_count, down_list, \
-                         down_count, level == 0, strip_list, strip_count, use_lane && level == 0 ? &lane_work : nullptr)
-        if (k <= 1) MM_FAST(1);
-        else if (k <= 2) MM_FAST(2);
-        else if (k <= 4) MM_FAST(4);
-        else if (k <= 8) MM_FAST(8);
-        else if (k <= 16) MM_FAST(16);
-        else if (k <= 20) MM_FAST(20);
-        else if (k <= 25) MM_FAST(25);
-        else MM_FAST(32);
-#undef MM_FAST
+        with_k(kFastKs{}, kout, [&](auto KK) {
+            launch_fast<decltype(KK)::value, IDX>(ctx, l, gl, pts_d, npts, kout, start, tsorted, idx_d, dist_d, fb_list, fb_count,
+                                                  down_list, down_count, level == 0, strip_list, strip_count,
+                                                  use_lane && level == 0 ? &lane_work : nullptr);
+        });
         MM_HIP_CHECK(hipGetLastError());
         static const bool dbg_query = getenv("MM_KNN_DEBUG") != nullptr;
         if (dbg_query) {
@@ -1190,26 +1157,11 @@ static int knn_query_typed(mm_context *ctx, const mm_knn_index *ix, const double
         list_count = down_count;
     }
     // what no level could place: the generic kernel, once, every target in the grid that suits its home cell
-    LevelTable lv;
-    lv.n = 0;
-    for (const mm_knn_index *l = ix; l && lv.n < kMaxLevels; l = l->fine) {
-        lv.g[lv.n] = params_of(l);
-        lv.cell_start[lv.n] = l->cell_start;
-        lv.sorted_xyz[lv.n] = l->sorted_xyz;
-        ++lv.n;
-    }
-#define MM_GENERIC(KK)                                                                                               \
-    launch_list<KK, IDX>(ctx, ix, lv, sorted_rows ? *tsorted_out : pts_d, sorted_rows ? kRec : ix->ndim, npts, kout,  \
-                         idx_d, dist_d, fb_list, fb_count, kListKeepMax)
-    if (k <= 1) MM_GENERIC(1);
-    else if (k <= 2) MM_GENERIC(2);
-    else if (k <= 4) MM_GENERIC(4);
-    else if (k <= 8) MM_GENERIC(8);
-    else if (k <= 16) MM_GENERIC(16);
-    else if (k <= 20) MM_GENERIC(20);
-    else if (k <= 25) MM_GENERIC(25);
-    else MM_GENERIC(32);
-#undef MM_GENERIC
+    const LevelTable lv = level_table_of(ix, kMaxLevels);
+    with_k(kFastKs{}, kout, [&](auto KK) {
+        launch_list<decltype(KK)::value, IDX>(ctx, ix, lv, sorted_rows ? *tsorted_out : pts_d, sorted_rows ? kRec : ix->ndim, npts,
+                                              kout, idx_d, dist_d, fb_list, fb_count, kListKeepMax);
+    });
     MM_HIP_CHECK(hipGetLastError());
     return MM_OK;
 }
@@ -1226,24 +1178,11 @@ int mm_knn_query_list_impl(mm_context *ctx, const mm_knn_index *ix, const double
     // anything in the context's scratch pool across this call: the cascade carves it anew.)
     if ((list_len_hint >= kLongListMin || (ix->tree && list_len_hint >= 0)) && k <= 32)
         return knn_query_typed<int>(ctx, ix, pts_d, npts, k, idx_d, nullptr, nullptr, list, list_count, list_len_hint);
-    LevelTable lv;
-    lv.n = 0;
-    for (const mm_knn_index *l = ix; l && lv.n < kMaxLevels; l = l->fine) {
-        lv.g[lv.n] = params_of(l);
-        lv.cell_start[lv.n] = l->cell_start;
-        lv.sorted_xyz[lv.n] = l->sorted_xyz;
-        ++lv.n;
-    }
-#define MM_LIST(KK)                                                                                                  \
-    launch_list<KK, int>(ctx, ix, lv, pts_d, ix->ndim, npts, kout, idx_d, (double *)nullptr, list, list_count,       \
-                         kListKeepMax)
-    if (k <= 8) MM_LIST(8);
-    else if (k <= 16) MM_LIST(16);
-    else if (k <= 20) MM_LIST(20);
-    else if (k <= 32) MM_LIST(32);
-    else if (k <= 40) MM_LIST(40);
-    else MM_LIST(MM_KNN_MAX_K);
-#undef MM_LIST
+    const LevelTable lv = level_table_of(ix, kMaxLevels);
+    with_k(kListKs{}, kout, [&](auto KK) {
+        launch_list<decltype(KK)::value, int>(ctx, ix, lv, pts_d, ix->ndim, npts, kout, idx_d, (double *)nullptr, list, list_count,
+                                              kListKeepMax);
+    });
     MM_HIP_CHECK(hipGetLastError());
     return MM_OK;
 }

@@ -43,8 +43,7 @@ __global__ __launch_bounds__(kWave, 4) void knn_cell_kernel(GridParams g, i64 ns
                                                             const double *__restrict__ tsorted,
                                                             IDX *__restrict__ idx_out,
                                                             double *__restrict__ dist_out,
-                                                            int *__restrict__ fb_list, int *__restrict__ fb_count,
-                                                            int dbg_stop)
+                                                            int *__restrict__ fb_list, int *__restrict__ fb_count)
 {
     static_assert(CAP <= 64, "rank mask is 64 bits");
     __shared__ float4 tile[kTileCap + 1];                       // +1: far-away sentinel entry
@@ -92,7 +91,6 @@ __global__ __launch_bounds__(kWave, 4) void knn_cell_kernel(GridParams g, i64 ns
     }
     const int tn = t1 - t0;
     if (tn == 0) return;
-    if (dbg_stop == 6) return;
     int total = 0;
     bool runs_fit = true;
 #pragma unroll
@@ -126,7 +124,6 @@ __global__ __launch_bounds__(kWave, 4) void knn_cell_kernel(GridParams g, i64 ns
         scale = (float)kHistBuckets / (2.2f * r2);
     }
     const bool cell_ok = runs_fit && total >= kout && total <= kTileCap && scale > 0.f && scale < INFINITY;
-    if (dbg_stop == 7) { if (total == 12345 && scale == 1.f) fb_list[0] = 1; return; }
     if (!cell_ok) {
         // the whole cell goes to the generic kernel
         for (int q = lane; q < tn; q += kWave)
@@ -184,7 +181,6 @@ __global__ __launch_bounds__(kWave, 4) void knn_cell_kernel(GridParams g, i64 ns
         }
     }
     if (lane == 0) tile[total] = make_float4(1e30f, 1e30f, 1e30f, 0.f);  // slots past the end read this
-    if (dbg_stop == 1) return;  // diagnostic builds only (MM_KNN_DBG_STOP): time the phases
 
     for (int r0 = 0; r0 < tn; r0 += tpw) {
         const int tt = r0 + tg;
@@ -237,7 +233,6 @@ __global__ __launch_bounds__(kWave, 4) void knn_cell_kernel(GridParams g, i64 ns
             s_pk[m][lane] = packed;
         }
         wave_sync();
-        if (dbg_stop == 2 || (dbg_stop >= 20 && dbg_stop <= 23)) return;
 
         // ---- jb = first bucket whose running count reaches k: each lane sums its share of the
         // buckets, a group prefix sum locates the lane whose share crosses k
@@ -267,7 +262,6 @@ __global__ __launch_bounds__(kWave, 4) void knn_cell_kernel(GridParams g, i64 ns
             const double D2 = D * (1.0 + 4.0 * kU) + E;
             if (!(D2 * D2 * (1.0 + 8.0 * kU) < e2)) hand_over = true;
         }
-        if (dbg_stop == 3) { if (jb == 77) fb_list[0] = jb; return; }
 
         // ---- P2: candidates in buckets <= jb+1 go to the target's list.  Each lane marks its
         // qualifying slots in a bit mask; a group prefix sum of the counts gives the list offsets.
@@ -293,7 +287,6 @@ __global__ __launch_bounds__(kWave, 4) void knn_cell_kernel(GridParams g, i64 ns
         }
         if (sl == 0) s_cnt[tg] = n;
         wave_sync();
-        if (dbg_stop == 4) return;
         if (n > CAP) hand_over = true;
         // widest list in this round (uniform loop bounds below)
         int nmax = 0;
@@ -328,7 +321,6 @@ __global__ __launch_bounds__(kWave, 4) void knn_cell_kernel(GridParams g, i64 ns
             }
         }
         wave_sync();
-        if (dbg_stop == 5) return;
 
         // ---- P3: rank by exact d2: list entries are read four at a time (broadcast within the
         // group) and compared against the owned ones
@@ -346,7 +338,6 @@ __global__ __launch_bounds__(kWave, 4) void knn_cell_kernel(GridParams g, i64 ns
                 }
             }
         }
-        if (dbg_stop == 8) return;
         // distinct distances <=> the ranks are a permutation of 0..n-1
         const unsigned long long full = n >= 64 ? ~0ull : ((1ull << n) - 1ull);
 #pragma unroll
@@ -370,7 +361,6 @@ __global__ __launch_bounds__(kWave, 4) void knn_cell_kernel(GridParams g, i64 ns
             }
             wave_sync();
         }
-        if (dbg_stop == 9) return;
         // sorted order back into the list (every lane has finished reading it)
 #pragma unroll
         for (int o = 0; o < MAXE; ++o) {
@@ -381,7 +371,6 @@ __global__ __launch_bounds__(kWave, 4) void knn_cell_kernel(GridParams g, i64 ns
             }
         }
         wave_sync();
-        if (dbg_stop == 10) return;
         if (valid && !hand_over) {
             // the group's lanes write the target's row side by side (coalesced 8-byte stores)
             IDX *row = idx_out + i * kout;
@@ -407,7 +396,6 @@ __global__ __launch_bounds__(kWave, 4) void knn_cell_kernel(GridParams g, i64 ns
             if (sizeof(IDX) == 4 && (kout & 3) == 0 && drow)
                 for (int e = sl; e < kout; e += S) drow[e] = sqrt(s_bd[e][tg]);
         }
-        if (dbg_stop == 11) return;
         if (valid && sl == 0) {
             if (!hand_over) {
                 // could a nearer source sit outside the 3x3x3 block?
@@ -439,18 +427,11 @@ __global__ __launch_bounds__(kWave, 4) void knn_cell_kernel(GridParams g, i64 ns
 //            lanes per target) so that a round for one or two left-over targets is short.
 // Everything inside a round (P1 histogram, jb, P2 list, exact fp64, P3 rank sort, error bound) is the
 // cell kernel's, see there; only the fp32 rounding bound E uses the strip's extent in z.
-#ifndef MM_STRIP_Z          // tuning builds only (make EXTRA="-DMM_STRIP_Z=4 -DMM_STRIP_CAP=496")
-#define MM_STRIP_Z 2
-#define MM_STRIP_CAP 352   // 36 cells x ~8 expected = 288, + 3 sigma
-#endif
-constexpr int kStripZ = MM_STRIP_Z;
+constexpr int kStripZ = 2;
 constexpr int kStripLayers = kStripZ + 2;
 typedef float v2f __attribute__((ext_vector_type(2)));
-constexpr int kStripTileCap = MM_STRIP_CAP;
-#ifndef MM_STRIP_GROUPS
-#define MM_STRIP_GROUPS 8
-#endif
-constexpr int kStripGroups = MM_STRIP_GROUPS;            // targets per round at the narrowest split
+constexpr int kStripTileCap = 352;   // 36 cells x ~8 expected = 288, + 3 sigma
+constexpr int kStripGroups = 8;      // targets per round at the narrowest split
 constexpr int kStripSlots = kTileCap / (kWave / kStripGroups);   // window entries per lane at the narrowest split
 static_assert(kStripLayers * 9 <= kWave, "one lane stages one tile cell");
 
@@ -466,7 +447,7 @@ __global__ __launch_bounds__(kWave, 4) void knn_strip_kernel(GridParams g, i64 n
                                                              IDX *__restrict__ idx_out,
                                                              double *__restrict__ dist_out,
                                                              int *__restrict__ fb_list, int *__restrict__ fb_count,
-                                                             int dbg_stop, int nsplit, int *__restrict__ down_list,
+                                                             int nsplit, int *__restrict__ down_list,
                                                              int *__restrict__ down_count,
                                                              const unsigned *__restrict__ strip_list,
                                                              const int *__restrict__ strip_count)
@@ -474,12 +455,9 @@ __global__ __launch_bounds__(kWave, 4) void knn_strip_kernel(GridParams g, i64 n
     static_assert(CAP <= 64, "rank mask is 64 bits");
     constexpr bool WALK = MODE == 2;
     if (MODE == 0) down_list = nullptr;
-#ifndef MM_STRIP_NB_SMALL   // tuning builds only
-#define MM_STRIP_NB_SMALL 32
-#endif
     // histogram buckets: short lists need less resolution (the two buckets collected beyond the k-th
     // distance hold ~1.5 k / buckets * 2.2 candidates each)
-    constexpr int kNB = K <= 8 ? MM_STRIP_NB_SMALL : kHistBuckets;
+    constexpr int kNB = K <= 8 ? 32 : kHistBuckets;
     // log2 of the lanes per target: the widest split (at most one lane per histogram bucket) whose
     // round still covers `left` targets, at least kWave / kStripGroups lanes
     constexpr int kLgMax = kNB >= kWave ? 6 : (kNB >= 32 ? 5 : 4);
@@ -524,7 +502,6 @@ __global__ __launch_bounds__(kWave, 4) void knn_strip_kernel(GridParams g, i64 n
     __shared__ int s_layer[kStripLayers + 1];
 
     const int lane = threadIdx.x;
-    if (dbg_stop == 100) return;   // diagnostic: what dispatching the grid alone costs
     // XCD-aware strip -> workgroup map (see knn_cell_kernel): XCD x owns a slab of columns
     const int ncols = g.nx * g.ny;
     const int cols_per_xcd = (ncols + 7) / 8;
@@ -673,7 +650,6 @@ __global__ __launch_bounds__(kWave, 4) void knn_strip_kernel(GridParams g, i64 n
         MM_NEXT_STRIP
     }
     wave_sync();  // tile and layer table staged
-    if (dbg_stop == 1) return;  // diagnostic builds only (MM_KNN_DBG_STOP): time the phases
 
     // widest window of the strip's cells (uniform loop bounds), block volume per layer
     int maxwin = 0;
@@ -791,7 +767,6 @@ __global__ __launch_bounds__(kWave, 4) void knn_strip_kernel(GridParams g, i64 n
             s_pk[m][lane] = packed;
         }
         wave_sync();
-        if (dbg_stop == 2) return;
 
         // ---- jb = first bucket whose running count reaches k
         {
@@ -824,7 +799,6 @@ __global__ __launch_bounds__(kWave, 4) void knn_strip_kernel(GridParams g, i64 n
             const double D2 = D * (1.0 + 4.0 * kU) + E;
             if (!(D2 * D2 * (1.0 + 8.0 * kU) < e2)) hand_over = true;
         }
-        if (dbg_stop == 3) { if (jb == 77) fb_list[0] = jb; return; }
 
         // ---- P2: candidates in buckets <= jb+1 go to the target's list
         // (four bucket numbers per word, each < 64: adding 126 - jb sets a byte's top bit exactly when
@@ -851,7 +825,6 @@ __global__ __launch_bounds__(kWave, 4) void knn_strip_kernel(GridParams g, i64 n
         }
         if (sl == 0) s_cnt[tg] = n;
         wave_sync();
-        if (dbg_stop == 4) return;
         if (n > CAP) hand_over = true;
         int nmax = 0;
         for (int q = 0; q < tpw; ++q) nmax = max(nmax, min(s_cnt[q], CAP));
@@ -885,7 +858,6 @@ __global__ __launch_bounds__(kWave, 4) void knn_strip_kernel(GridParams g, i64 n
             }
         }
         wave_sync();
-        if (dbg_stop == 5) return;
 
         // ---- P3: rank by exact d2
         for (int j0 = 0; j0 < nmax; j0 += U) {
@@ -925,7 +897,6 @@ __global__ __launch_bounds__(kWave, 4) void knn_strip_kernel(GridParams g, i64 n
             }
             wave_sync();
         }
-        if (dbg_stop == 6) return;
         // sorted order back into the list (every lane has finished reading it)
 #pragma unroll
         for (int o = 0; o < MAXE; ++o) {
@@ -958,7 +929,6 @@ __global__ __launch_bounds__(kWave, 4) void knn_strip_kernel(GridParams g, i64 n
             if (sizeof(IDX) == 4 && (kout & 3) == 0 && drow)
                 for (int e = sl; e < kout; e += S) drow[e] = sqrt(s_bd[tg][e]);
         }
-        if (dbg_stop == 7) return;
         if (valid && sl == 0) {
             if (!hand_over) {
                 // could a nearer source sit outside the target's 3x3x3 block?
@@ -996,7 +966,6 @@ __global__ __launch_bounds__(kWave, 4) void knn_strip_kernel(GridParams g, i64 n
             }
         }
         wave_sync();  // before the next round clears the counters
-        if (dbg_stop == 8) return;
     }
     if (!WALK) break;
     }

@@ -87,37 +87,18 @@ __device__ __forceinline__ void lagrange_1d(const double (&g)[ORDER + 1], double
 }
 
 // The node loads of the unrolled sum-factorised loops are kept from being hoisted to the top (all (order+1)^3 x 3
-// values live at once: spills) by a compiler fence every MM_GLL_FENCE_EVERY rows of nodes (cfg5's locate stage, ms:
-// every row 5.04, every 2nd 4.92, every 3rd / 5th 5.06 / 5.03, none: 470 registers spilled).
-#ifndef MM_GLL_FENCE_EVERY
-#define MM_GLL_FENCE_EVERY 2
-#endif
-#define MM_GLL_ROW_FENCE(row) do { if ((row) % MM_GLL_FENCE_EVERY == 0) asm volatile("" ::: "memory"); } while (0)
-// ... and the running sums pinned there as well (round 4): a memory fence keeps the LOADS of a row behind it but not
-// their consumption -- the scheduler still parks every loaded value in a register and folds them in at the end.
-template <int N>
-__device__ __forceinline__ void gll_pin(double (&v)[N])
-{
-#pragma unroll
-    for (int q = 0; q < N; ++q) asm volatile("" : "+v"(v[q])::"memory");
-}
+// values live at once: spills) by a compiler fence every kGllFenceEvery rows of nodes (cfg5's locate stage, ms:
+// every row 5.04, every 2nd 4.92, every 3rd / 5th 5.06 / 5.03, none: 470 registers spilled).  Pinning the running sums
+// there as well (round 4) serialised the walking passes' node loads: 0.46 -> 1.0 ms a pass.
+constexpr int kGllFenceEvery = 2;
+#define MM_GLL_ROW_FENCE(row) do { if ((row) % kGllFenceEvery == 0) asm volatile("" ::: "memory"); } while (0)
 // Waves per SIMD the register allocator must leave room for in the GLL locate kernels.  1: it takes what the kernel
 // needs -- at order 4 in 3-D 256 VGPRs + ~90 AGPRs, one wave per SIMD, nothing in scratch memory -- and the lower orders
 // still run 2 to 5 waves (95 - 211 VGPRs).  Asking for 3 (168 VGPRs, rounds 1 - 2) left 340 registers of the order-4
 // kernels in scratch: cfg5's locate stage 6.2 ms at 3, 5.5 at 2 (150 spilled), 5.1 at 1.
-#ifndef MM_GLL_WAVES
-#define MM_GLL_WAVES 1
-#endif
-#ifndef MM_GLL_PIN_SUMS   // 1: the partial sums of the MAP are pinned at every row of nodes as well (see gll_pin).  Measured at
-#define MM_GLL_PIN_SUMS 0 //    cfg5's shape and left off: it serialises the walking passes' node loads (0.46 -> 1.0 ms a pass)
-#endif
-#ifndef MM_GLL_VALUES_WAVES   // waves per SIMD gll_values_kernel is compiled for
-#define MM_GLL_VALUES_WAVES 2
-#endif
-#ifndef MM_GLL_GUESS_TRIPS   // (tuning builds only: the oracle's start runs 8)
-#define MM_GLL_GUESS_TRIPS 8
-#endif
-constexpr int kGllGuessTrips = MM_GLL_GUESS_TRIPS;   // hex8 trips of the corner solve that starts a 3-D inverse transform
+constexpr int kGllWaves = 1;
+constexpr int kGllValuesWaves = 2;   // waves per SIMD gll_values_kernel is compiled for
+constexpr int kGllGuessTrips = 8;    // hex8 trips of the corner solve that starts a 3-D inverse transform (as the oracle's)
 constexpr double kGllGuessMax = 3.0;    // a start beyond this (or NaN) is not used
 
 template <int ORDER, int DIM>
@@ -151,11 +132,7 @@ struct Gll {
                 cz[c] = ctrl[3 * node + 2];
             }
             double q[3];
-#ifdef MM_GLL_OLD_START   // timing experiment only (the oracle follows newton_hex8_start)
-            (void)newton_hex8<true>(pnt[0], pnt[1], pnt[DIM - 1], cx, cy, cz, q, kGllGuessTrips);
-#else
             newton_hex8_start(pnt[0], pnt[1], pnt[DIM - 1], cx, cy, cz, q, kGllGuessTrips);
-#endif
             if (fabs(q[0]) <= kGllGuessMax && fabs(q[1]) <= kGllGuessMax && fabs(q[2]) <= kGllGuessMax) {
                 xi[0] = q[0];
                 xi[1] = q[1];
@@ -188,12 +165,6 @@ struct Gll {
                         // keep the scheduler from hoisting all (order+1)^3 node loads to the top of
                         // the unrolled loop: one row of nodes at a time
                         MM_GLL_ROW_FENCE(j);
-                        if (MM_GLL_PIN_SUMS) {
-                            gll_pin(b00);
-                            gll_pin(b01);
-                            gll_pin(b10);
-                            gll_pin(x);
-                        }
                         double a0[3] = {0.0, 0.0, 0.0}, a1[3] = {0.0, 0.0, 0.0};
 #pragma unroll
                         for (int i = 0; i < n; ++i) {
@@ -415,7 +386,7 @@ __device__ __forceinline__ void gll_emit(const GllEmit &em, i64 i, i64 e, const 
 // element with zero coefficients like NumPy's field[-1] * 0).  One lane per target; neighbouring targets lie in the same
 // or neighbouring elements, so a wave's loads of a field row fall on a few lines.
 template <int ORDER, int DIM>
-__global__ __launch_bounds__(256, MM_GLL_VALUES_WAVES) void gll_values_kernel(i64 npoints, const int *__restrict__ elem,
+__global__ __launch_bounds__(256, kGllValuesWaves) void gll_values_kernel(i64 npoints, const int *__restrict__ elem,
                                                          const double *__restrict__ xi_all,
                                                          const double *__restrict__ fields, i64 nelem, int ncomp,
                                                          double *__restrict__ out)
@@ -452,7 +423,7 @@ constexpr int kGllWalkFrom = 1; // passes that advance one candidate before the 
                                 // values formed in a kernel of their own the one-candidate passes 1 and 2 cost more than they save: 3.12 -> 2.92 ms)
 
 template <int ORDER, int DIM, typename IDX, bool DEFER = false>
-__global__ __launch_bounds__(64, MM_GLL_WAVES) void locate_gll_pass_kernel(i64 k, int kavail, i64 npoints,
+__global__ __launch_bounds__(64, kGllWaves) void locate_gll_pass_kernel(i64 k, int kavail, i64 npoints,
                                                              const IDX *__restrict__ nn,
                                                              const double *__restrict__ gll_points, i64 nelem,
                                                              const double *__restrict__ points, double tolerance,
@@ -589,7 +560,7 @@ __global__ __launch_bounds__(64, MM_GLL_WAVES) void locate_gll_pass_kernel(i64 k
 // wave with more distinct elements (thinly populated elements) takes further turns of the stage/solve
 // loop.  Same arithmetic, same results as locate_gll_pass_kernel with q_in == null.
 template <int ORDER, int DIM, typename IDX, bool DEFER = false>
-__global__ __launch_bounds__(64, MM_GLL_WAVES) void locate_gll_first_pass_kernel(
+__global__ __launch_bounds__(64, kGllWaves) void locate_gll_first_pass_kernel(
     i64 k, int kavail, i64 npoints, const IDX *__restrict__ nn, const double *__restrict__ gll_points, i64 nelem,
     const double *__restrict__ points, double tolerance, int snap_to_nearest, GllEmit em,
     unsigned long long *__restrict__ nmissing, const int *__restrict__ order,
@@ -820,7 +791,6 @@ int launch_locate(mm_context *ctx, i64 k, int kavail, i64 npoints, const IDX *nn
     // chip (17 such passes: 2.9 of cfg5's 8.6 ms), so from there a lane walks its list to the end.  With lazy
     // lists the walk ends at the short list's end, the open targets' full lists are fetched once, and one
     // more walking pass finishes them.
-    static const int walk_from = getenv("MM_GLL_WALK_FROM") ? atoi(getenv("MM_GLL_WALK_FROM")) : kGllWalkFrom;
     i64 jdone = 0;        // candidates every open target is past
     bool full = false;    // the passes read the full lists (lazy only)
     for (int c = 0; c == 0 || jdone < k; ++c) {
@@ -837,7 +807,7 @@ int launch_locate(mm_context *ctx, i64 k, int kavail, i64 npoints, const IDX *nn
             full = true;
         }
         const i64 avail = full ? k : (i64)kavail;
-        const int walk = c >= walk_from ? 1 : 0;
+        const int walk = c >= kGllWalkFrom ? 1 : 0;
         if (c == 0 && k > 0 && nelem > 0) {
             hipLaunchKernelGGL((locate_gll_first_pass_kernel<ORDER, DIM, IDX, DEFER>), dim3((unsigned)grid), dim3(64), 0,
                                ctx->stream, k, kavail, npoints, nn, gll, nelem, pts, tol, snap, em, nmiss, order, q_out,
@@ -889,7 +859,7 @@ __global__ __launch_bounds__(256) void gll_box_kernel(i64 nelem, const double *_
 // One lane per target, candidates in order (lock-step: this variant is the completeness path, the
 // tolerance/snap variant above is the tuned one).
 template <int ORDER, int DIM>
-__global__ __launch_bounds__(64, MM_GLL_WAVES) void locate_gll_v1_kernel(i64 k, i64 npoints, const i64 *__restrict__ nn,
+__global__ __launch_bounds__(64, kGllWaves) void locate_gll_v1_kernel(i64 k, i64 npoints, const i64 *__restrict__ nn,
                                                               const double *__restrict__ gll_points, i64 nelem,
                                                               const double *__restrict__ boxes,
                                                               const double *__restrict__ points,
@@ -1200,8 +1170,7 @@ extern "C" int64_t mm_interpolate_gll(mm_context *ctx, int order, int dim, const
         GllEmit em = {(i64 *)elem_out_d, coeffs_out_d, ncomp > 0 ? fields_d : nullptr, ncomp > 0 ? out_d : nullptr,
                       (int)ncomp};
         // values without the operator: the locate kernels leave {element, xi}, the sums are formed afterwards
-        static const bool defer_on = !(getenv("MM_GLL_DEFER") && atoi(getenv("MM_GLL_DEFER")) == 0);
-        const bool defer = defer_on && em.out && !em.coeffs;
+        const bool defer = em.out && !em.coeffs;
         if (defer) {
             rc = mm_buffer_get(ctx, MM_BUF_W, (size_t)npoints * dim * sizeof(double), (void **)&em.xi_defer);
             if (rc == MM_OK) rc = mm_buffer_get(ctx, MM_BUF_ENC, (size_t)npoints * sizeof(int), (void **)&em.elem_defer);

@@ -347,12 +347,6 @@ __global__ __launch_bounds__(256) void locate_hex8_group_kernel(i64 k, i64 npoin
     }
 }
 
-#ifndef MM_PASS_ITERS   // tuning builds only
-#define MM_PASS_ITERS 6
-#endif
-#ifndef MM_MID_ITERS
-#define MM_MID_ITERS 9
-#endif
 // Newton caps of the three tiers of solves (loop trips; a solve that converges after n updates needs
 // n + 1 trips, the last one only evaluates the residual).  Measured on the metric meshes with the
 // reference's arithmetic: 99.99 % of the ACCEPTED solves take 3 or 4 updates, rejected candidates
@@ -360,8 +354,8 @@ __global__ __launch_bounds__(256) void locate_hex8_group_kernel(i64 k, i64 npoin
 // its full 50).  A wave runs in lock step, so every round costs the trips of its slowest lane:
 // with one cap of 10 for everybody 42 % of the rounds ran to 10 for the sake of one lane (6.5 trips
 // per round on average against 5 for the mean solve).
-constexpr int kPassIters = MM_PASS_ITERS;   // ordinary solves: fresh targets and retries
-constexpr int kMidIters = MM_MID_ITERS;     // solves that outlast kPassIters, in each other's company
+constexpr int kPassIters = 6;   // ordinary solves: fresh targets and retries
+constexpr int kMidIters = 9;    // solves that outlast kPassIters, in each other's company
 constexpr int kRefIters = 50;               // the reference's own cap (trilinearinterpolator.c:264)
 
 
@@ -382,26 +376,12 @@ constexpr int kRefIters = 50;               // the reference's own cap (trilinea
 // the reference's cap rejects the candidate, as in the reference.
 constexpr int kPassBlock = 256;
 constexpr int kGroupListMax = 1 << 16;   // reference-order lists up to this long: one candidate per lane (u^2.2 graded mesh, ~0.5 M on the list: loop 2.9 ms, groups 3.8; u^1.5, 30 k: 1.0 -> 0.1)
-#ifndef MM_PASS_WAVES   // tuning builds only: minimum waves per SIMD the register allocator must leave room for
-#define MM_PASS_WAVES 2
-#endif
-#ifndef MM_PASS_PREFETCH   // 1: a fresh batch's targets, first candidates and their connectivity rows are requested a
-#define MM_PASS_PREFETCH 0  //    round ahead (measured: no faster -- the pass is bound by its L1 misses in flight, not by the chain)
-#endif
-#ifndef MM_DRAIN_SLOW_FIRST   // at the end of a wave's input: slow tiers' leftovers before the ordinary drain rounds
-#define MM_DRAIN_SLOW_FIRST 0
-#endif
-#ifndef MM_DRAIN_G8           // drain rounds with at most this many targets try 8 candidates per target at once (0: never)
-#define MM_DRAIN_G8 0
-#endif
-#ifndef MM_FAST_WAVES   // ... for the MM_FP_TOL instances
-#define MM_FAST_WAVES 2
-#endif
+constexpr int kPassWaves = 2;   // minimum waves per SIMD the register allocator must leave room for (MM_FP_TOL instances too)
 // LDS entries per wave and queue.  A full queue (>= 64 waiting) is served before anything is added to it, the
 // slowest tier first: tiers 1 and 2 only grow in rounds of the tier below, which run while they hold fewer
 // than 64 (< 128 after the round); tier 0 grows in every round -- 63 + 64 from its own rounds, then one
 // round each of tiers 1 and 2 before it is served again: < 256.
-// Batches of one plane per panel of the walk order (see the kernel; MM_LOCATE_PANEL overrides, 0 = in order).  -1: as many
+// Batches of one plane per panel of the walk order (see the kernel; 0 = in order).  -1: as many
 // as the XCD has waves in the launch -- wave w then takes column w of a panel in plane after plane: its consecutive
 // batches are neighbours ACROSS planes (the same strip of cells, one plane on), which share a layer of elements, and the
 // front of all waves is one plane's slice of the panel.  Measured on the metric meshes (locate pass, ms): in order 1.536,
@@ -461,7 +441,7 @@ __device__ unsigned long long g_loc_stamps[kLocStampSlots * 8];
 // rounds of 50-trip stragglers and the candidates behind them, one after the other with nothing to overlap them.  Inside
 // the one launch they ride along.)  unsure_count (nullable): solves repeated, one atomic per wave at its end.
 template <bool EXODUS, typename IDX, bool SORTED, typename NID, bool FAST = false>
-__global__ __launch_bounds__(kPassBlock, FAST ? MM_FAST_WAVES : MM_PASS_WAVES) void locate_pass_kernel(i64 k, i64 npoints,
+__global__ __launch_bounds__(kPassBlock, kPassWaves) void locate_pass_kernel(i64 k, i64 npoints,
                                                                  const IDX *__restrict__ nn,
                                                                  const i64 *__restrict__ conn, i64 nelem,
                                                                  Emit em,
@@ -549,43 +529,6 @@ __global__ __launch_bounds__(kPassBlock, FAST ? MM_FAST_WAVES : MM_PASS_WAVES) v
         }
     };
     advance();
-    // A ROUND AHEAD (MM_PASS_PREFETCH): a fresh batch needs its targets' records, their first candidates, those elements'
-    // connectivity rows and then the corner coordinates -- four dependent round trips before the first multiplication,
-    // and with the cheap MM_FP_TOL solve the pass waits for memory 70 % of its wave-cycles.  The batch a wave will
-    // take next is known as soon as it takes one, so its records and first candidates are requested then (stage a) and
-    // the connectivity rows at the end of that round (stage b: the candidates have arrived by then); they land while
-    // the wave works on other rounds and wait in 17 registers: a fresh round starts at the corner coordinates.
-    const bool pf_on = MM_PASS_PREFETCH && !in_list;
-    double pf_p[4] = {0., 0., 0., 0.};
-    int pf_elem = -1;
-    NID pf_id[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    bool need_b = false;   // (wave-uniform)
-    auto prefetch_a = [&]() {
-        const i64 q = next + lane;
-        if (q < total) {   // (next == total: no batch left, nothing is requested)
-            if (SORTED) {
-                const double2 *r2 = reinterpret_cast<const double2 *>(pts + q * 4);
-                const double2 xy = r2[0], zw = r2[1];
-                pf_p[0] = xy.x;
-                pf_p[1] = xy.y;
-                pf_p[2] = zw.x;
-                pf_p[3] = zw.y;
-            } else {
-                pf_p[0] = pts[q * 3 + 0];
-                pf_p[1] = pts[q * 3 + 1];
-                pf_p[2] = pts[q * 3 + 2];
-            }
-            pf_elem = j0 < k ? (int)nn[q * k + j0] : -1;
-        }
-    };
-    auto prefetch_b = [&]() {
-        const i64 q = next + lane;
-        if (q < total && pf_elem >= 0 && !(nelem > 0 && (i64)pf_elem >= nelem)) load_ids<EXODUS>(conn, (i64)pf_elem, pf_id);
-    };
-    if (pf_on) {
-        prefetch_a();
-        prefetch_b();
-    }
 #ifdef MM_LOCATE_STAMPS
     unsigned long long stamp_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long stamp_last = __builtin_amdgcn_s_memtime();
@@ -601,10 +544,6 @@ __global__ __launch_bounds__(kPassBlock, FAST ? MM_FAST_WAVES : MM_PASS_WAVES) v
         double xi_in[3] = {0., 0., 0.};   // tiers 1 and 2: the iterate the solve stopped at under the tier below's cap
         int tier = 0;          // whose cap this round's solves run under
         int lgG = 0;           // log2 of the lanes per target (only the drain rounds work ahead)
-        bool fresh = false;    // this round's targets and first candidates wait in the prefetch registers
-        double cur_p[4] = {0., 0., 0., 0.};
-        int cur_elem = -1;
-        NID cur_id[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         if (held2 >= 64 || held1 >= 64 || held0 >= 64) {
             int from;
             if (held2 >= 64) {
@@ -633,27 +572,11 @@ __global__ __launch_bounds__(kPassBlock, FAST ? MM_FAST_WAVES : MM_PASS_WAVES) v
             if (active) {
                 i = in_list ? (i64)in_list[q] : q;
             }
-            if (pf_on) {
-                fresh = true;
-#pragma unroll
-                for (int a = 0; a < 4; ++a) cur_p[a] = pf_p[a];
-                cur_elem = pf_elem;
-#pragma unroll
-                for (int n = 0; n < 8; ++n) cur_id[n] = pf_id[n];
-            }
             advance();
-            if (pf_on) {
-                prefetch_a();
-                need_b = true;
-            }
-#ifdef MM_EXP_NODRAIN   // timing experiment only (results are wrong): how long the drain at the end of the pass takes
-        } else if (true) {
-            break;
-#endif
-        } else if ((held1 > 0 || held2 > 0) && (MM_DRAIN_SLOW_FIRST || held0 == 0)) {
+        } else if ((held1 > 0 || held2 > 0) && held0 == 0) {
             // input exhausted: the slow solves that are left, one lane each -- the slowest tier first, so that what they
             // reject joins the drain rounds below instead of starting another chain of rounds behind them
-            tier = MM_DRAIN_SLOW_FIRST ? (held2 > 0 ? 2 : 1) : (held1 > 0 ? 1 : 2);
+            tier = held1 > 0 ? 1 : 2;
             active = lane < (tier == 1 ? held1 : held2);
             if (active) {
                 const int2 e = (tier == 1 ? my_q1 : my_q2)[lane];
@@ -669,10 +592,10 @@ __global__ __launch_bounds__(kPassBlock, FAST ? MM_FAST_WAVES : MM_PASS_WAVES) v
         } else if (held0 > 0) {
             // ... then what is left of the ordinary retries, with partly filled waves (63 -> ~22 -> ~8 -> ...: a
             // handful of short rounds at the very end of the pass instead of another pass).  The idle
-            // lanes work ahead: with at most 32 (16, 8) targets left, 2 (4, 8) lanes per target try its
-            // next 2 (4, 8) candidates at once, which shortens the chain of rounds a hard target needs;
+            // lanes work ahead: with at most 32 (16) targets left, 2 (4) lanes per target try its
+            // next 2 (4) candidates at once, which shortens the chain of rounds a hard target needs;
             // the group then acts on the first candidate, in order, that is not a plain rejection.
-            lgG = held0 <= MM_DRAIN_G8 ? 3 : (held0 <= 16 ? 2 : (held0 <= 32 ? 1 : 0));
+            lgG = held0 <= 16 ? 2 : (held0 <= 32 ? 1 : 0);
             const int entry = lane >> lgG;
             active = entry < held0;
             if (active) {
@@ -698,12 +621,7 @@ __global__ __launch_bounds__(kPassBlock, FAST ? MM_FAST_WAVES : MM_PASS_WAVES) v
         i64 tid = i;   // the target's own index
         if (active) {
             double px, py, pz;
-            if (fresh) {
-                px = cur_p[0];
-                py = cur_p[1];
-                pz = cur_p[2];
-                if (SORTED) tid = (i64)(int)__double_as_longlong(cur_p[3]);
-            } else if (SORTED) {
+            if (SORTED) {
                 const double2 *r2 = reinterpret_cast<const double2 *>(pts + i * 4);
                 const double2 xy = r2[0], zw = r2[1];
                 px = xy.x;
@@ -723,17 +641,11 @@ __global__ __launch_bounds__(kPassBlock, FAST ? MM_FAST_WAVES : MM_PASS_WAVES) v
             // that works ahead looks at its one candidate only: outside the box = rejected)
             bool have = false;
             for (; j < k; ++j) {
-                const bool from_pf = fresh && j == j0;
-                const i64 elem = from_pf ? (i64)cur_elem : (i64)nn[i * k + j];
+                const i64 elem = (i64)nn[i * k + j];
                 const bool valid_elem = !(nelem > 0 && (unsigned long long)elem >= (unsigned long long)nelem);
                 bool outside = true;
                 if (valid_elem) {
-                    if (from_pf) {
-#pragma unroll
-                        for (int n = 0; n < 8; ++n) c.id[n] = cur_id[n];
-                    } else {
-                        load_ids<EXODUS>(conn, elem, c.id);
-                    }
+                    load_ids<EXODUS>(conn, elem, c.id);
                     load_xyz(nodes, c);
                     double xlo = c.x[0], xhi = c.x[0], ylo = c.y[0], yhi = c.y[0];
 #pragma unroll
@@ -747,18 +659,6 @@ __global__ __launch_bounds__(kPassBlock, FAST ? MM_FAST_WAVES : MM_PASS_WAVES) v
                     const double my = 0.05 * (yhi - ylo) + 1e-7 * fmax(xhi - xlo, yhi - ylo);
                     // NaN corners or point: comparisons are false -> treated as "inside" (never skipped)
                     outside = px < xlo - mx || px > xhi + mx || py < ylo - my || py > yhi + my;
-#ifdef MM_EXP_ZBOX   // experiment only (NOT the reference's semantics: it never tests the z residual)
-                    {
-                        double zlo = c.z[0], zhi = c.z[0];
-#pragma unroll
-                        for (int n = 1; n < 8; ++n) {
-                            zlo = fmin(zlo, c.z[n]);
-                            zhi = fmax(zhi, c.z[n]);
-                        }
-                        const double mz = (0.01 * MM_EXP_ZBOX) * (zhi - zlo);
-                        outside = outside || pz < zlo - mz || pz > zhi + mz;
-                    }
-#endif
                 }
                 MM_LCOUNT(4, outside && valid_elem);   // candidates dropped by the box test (their rows and corners were loaded)
                 if (!outside) {
@@ -859,10 +759,6 @@ __global__ __launch_bounds__(kPassBlock, FAST ? MM_FAST_WAVES : MM_PASS_WAVES) v
             else held2 += __popcll(svote);
         }
         wave_fence();
-        if (need_b) {
-            prefetch_b();
-            need_b = false;
-        }
         MM_LSTAMP(6);   // queue appends
     }
     if (FAST && unsure_count && lane == 0 && unsure > 0) atomicAdd(unsure_count, unsure);
@@ -948,15 +844,7 @@ static int launch_locate_typed(mm_context *ctx, i64 k, i64 npoints, const IDX *n
     const typename PassFn<IDX>::type first_fn = fast ? pass_kernel_for<IDX, true>(conn_is_exodus != 0, tsorted != nullptr, nid32)
                                                      : pass_kernel_for<IDX, false>(conn_is_exodus != 0, tsorted != nullptr, nid32);
     const i64 resident = resident_workgroups(ctx, first_fn);
-    i64 grid = resident < full_grid ? resident : full_grid;
-    {
-        // (tuning: MM_LOCATE_BATCHES_PER_WAVE = fewest fresh batches a wave should get before the grid is cut down)
-        static const i64 min_batches = getenv("MM_LOCATE_BATCHES_PER_WAVE") ? atoll(getenv("MM_LOCATE_BATCHES_PER_WAVE")) : 0;
-        if (min_batches > 0) {
-            const i64 want = ((npoints + 63) / 64 + min_batches * (kPassBlock / 64) - 1) / (min_batches * (kPassBlock / 64));
-            if (want < grid) grid = want < 8 ? 8 : want;
-        }
-    }
+    const i64 grid = resident < full_grid ? resident : full_grid;
     // ONE launch over all targets.  Persistent waves: exactly as many workgroups as the device keeps
     // resident, so that every wave lives for the whole pass and its private queues see a long stream
     // of targets.
@@ -964,11 +852,9 @@ static int launch_locate_typed(mm_context *ctx, i64 k, i64 npoints, const IDX *n
     {
         dim3 g_((unsigned)grid), b_(block);
         // (walk order of the sorted targets: see the kernel; the kNN grid's x dimension comes with the lazy lists)
-        static const int panel_env = getenv("MM_LOCATE_PANEL") ? atoi(getenv("MM_LOCATE_PANEL")) : kPassPanel;
         const int planes = (tsorted && lazy && lazy->index && !lazy->index->graded()) ? lazy->index->dims[0] : 0;
-        const int panel = panel_env;   // (0: in order, < 0: the kernel's default)
         hipLaunchKernelGGL(first_fn, g_, b_, 0, ctx->stream, k, npoints, nn, conn, nelem, em, nodes, tsorted ? tsorted : pts,
-                           slow, slow_count, (const int *)nullptr, (const int *)nullptr, 0, planes, panel, unsure_count,
+                           slow, slow_count, (const int *)nullptr, (const int *)nullptr, 0, planes, kPassPanel, unsure_count,
                            (const int *)ctx->abort_flags);
     }
     mm_stage_end(ctx, MM_STAGE_LOCATE_PASS0);
@@ -1015,16 +901,15 @@ static int launch_locate_typed(mm_context *ctx, i64 k, i64 npoints, const IDX *n
         if (sgrid < 256) sgrid = full_grid < 256 ? full_grid : 256;
         dim3 g((unsigned)sgrid), b(block);
         // Two launches, one of which returns at once: lists up to kGroupListMax take one candidate per lane (a target's
-        // critical path is ONE solve), longer ones the loop (see locate_hex8_group_kernel).  MM_LOCATE_GROUP=0: the loop only.
-        static const int group_max = getenv("MM_LOCATE_GROUP") && atoi(getenv("MM_LOCATE_GROUP")) == 0 ? -1 : kGroupListMax;
-        if (group_max >= 0 && k_slow <= 64) {
+        // critical path is ONE solve), longer ones the loop (see locate_hex8_group_kernel).
+        if (k_slow <= 64) {
             i64 ggrid = (npoints * (k_slow <= 32 ? 32 : 64) + 255) / 256;
             if (ggrid > 8192) ggrid = 8192;
             if (ggrid < 1) ggrid = 1;
             dim3 gg((unsigned)ggrid);
 #define MM_GROUP(EX, GG)                                                                                                   \
     hipLaunchKernelGGL((locate_hex8_group_kernel<EX, IDX, GG>), gg, b, 0, ctx->stream, k_slow, npoints, nn_slow, conn, nelem, em, \
-                       nodes, pts, (unsigned long long *)d_nfailed, slow, slow_count, zero_failed, group_max,                \
+                       nodes, pts, (unsigned long long *)d_nfailed, slow, slow_count, zero_failed, kGroupListMax,                \
                        (const int *)ctx->abort_flags)
             if (conn_is_exodus) {
                 if (k_slow <= 32) MM_GROUP(true, 32);
@@ -1035,7 +920,7 @@ static int launch_locate_typed(mm_context *ctx, i64 k, i64 npoints, const IDX *n
             }
 #undef MM_GROUP
         }
-        const int loop_min = group_max >= 0 && k_slow <= 64 ? group_max : -1;
+        const int loop_min = k_slow <= 64 ? kGroupListMax : -1;
         if (conn_is_exodus)
             hipLaunchKernelGGL((locate_hex8_kernel<true, IDX>), g, b, 0, ctx->stream, k_slow, npoints, nn_slow, conn,
                                nelem, em, nodes, pts, (unsigned long long *)d_nfailed, slow, slow_count, zero_failed,

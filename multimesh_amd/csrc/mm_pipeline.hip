@@ -120,9 +120,8 @@ static int64_t interpolate_hex8_impl(mm_context *ctx, const double *nodes_d, int
     // acceptance, and the operator rows are only materialised when the caller asks for them (both
     // pointers).  Many components: 8 gathers per component inside the register-heavy locate kernel
     // cost more than writing the rows and streaming them through the gather kernel.
-    static const int64_t fuse_max = getenv("MM_FUSE_GATHER_MAXC") ? atoll(getenv("MM_FUSE_GATHER_MAXC")) : kFuseGatherMaxComp;
     const bool want_values = out_d && ncomp > 0;
-    const bool fuse_gather = want_values && ncomp <= fuse_max;
+    const bool fuse_gather = want_values && ncomp <= kFuseGatherMaxComp;
     if (!(enc && w)) {
         enc = nullptr;
         w = nullptr;
@@ -144,10 +143,10 @@ static int64_t interpolate_hex8_impl(mm_context *ctx, const double *nodes_d, int
     // guess runs the call again the ordinary way (twice wrong: no more guessing in this context).  MM_GRID_GUESS=0
     // switches it off.
     static const bool guess_on = !(getenv("MM_GRID_GUESS") && atoi(getenv("MM_GRID_GUESS")) == 0);
-    // (MM_KNN_PER_CELL / MM_KNN_LEVELS are read per call by the ordinary build -- tests switch them inside one process --
-    // and a guessed build would ignore them)
+    // (MM_KNN_LEVELS is read per call by the ordinary build -- tests switch it inside one process -- and a guessed build
+    // would ignore it)
     guessed = guess_on && ctx->grid_guess.valid && ctx->grid_guess.nsrc == nelem && ctx->grid_guess.misses < 2 &&
-              !getenv("MM_KNN_PER_CELL") && !getenv("MM_KNN_LEVELS") && !resident;
+              !getenv("MM_KNN_LEVELS") && !resident;
 again:
     ctx->abort_flags = nullptr;
     if (resident) {

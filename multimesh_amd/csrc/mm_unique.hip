@@ -424,62 +424,59 @@ extern "C" int64_t mm_unique_points(mm_context *ctx, const double *points_d, int
         return MM_OK;
     };
     // fast path: one sort by x, then the runs of equal x: short ones in place, long ones as a sub-sort
-    static const bool force_general = getenv("MM_UNIQUE_GENERAL") != nullptr;   // (tests: the dim-sorts path on any input)
-    bool general = force_general;
-    if (!general) {
-        hipLaunchKernelGGL(iota_kernel, grid, block, 0, ctx->stream, ord_a, n);
-        hipLaunchKernelGGL(key_kernel, grid, block, 0, ctx->stream, points_d, n, (int)dim, 0, ord_a, key_a);
-        static_assert(kKeyLowBits % 16 == 0, "an even number of 8-bit passes");
-        // (1-D: nothing follows that could order the rest of x -- all 64 bits)
-        if ((rc = radix_sort(key_a, key_b, ord_a, ord_b, n, dim > 1 ? kKeyLowBits : 0)) != MM_OK) return rc;
-        if (dim > 1) {
-            MM_HIP_CHECK(hipMemsetAsync(long_runs, 0, sizeof(int), ctx->stream));
-            hipLaunchKernelGGL(run_fixup_kernel, grid, block, 0, ctx->stream, key_a, n, points_d, (int)dim, ord_a, long_runs);
-            int nlong = 0;
-            MM_HIP_CHECK(hipMemcpyAsync(&nlong, long_runs, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    bool general = false;
+    hipLaunchKernelGGL(iota_kernel, grid, block, 0, ctx->stream, ord_a, n);
+    hipLaunchKernelGGL(key_kernel, grid, block, 0, ctx->stream, points_d, n, (int)dim, 0, ord_a, key_a);
+    static_assert(kKeyLowBits % 16 == 0, "an even number of 8-bit passes");
+    // (1-D: nothing follows that could order the rest of x -- all 64 bits)
+    if ((rc = radix_sort(key_a, key_b, ord_a, ord_b, n, dim > 1 ? kKeyLowBits : 0)) != MM_OK) return rc;
+    if (dim > 1) {
+        MM_HIP_CHECK(hipMemsetAsync(long_runs, 0, sizeof(int), ctx->stream));
+        hipLaunchKernelGGL(run_fixup_kernel, grid, block, 0, ctx->stream, key_a, n, points_d, (int)dim, ord_a, long_runs);
+        int nlong = 0;
+        MM_HIP_CHECK(hipMemcpyAsync(&nlong, long_runs, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        if (nlong > kMaxLongRuns) {
+            general = true;
+        } else if (nlong > 0) {
+            // lengths by bisection on the device, the layout of the sub-array on the host (a few runs)
+            int *d_start = long_runs + 1, *d_len = long_runs + 1 + kMaxLongRuns, *d_table = long_runs + 1 + 2 * kMaxLongRuns;
+            hipLaunchKernelGGL(run_length_kernel, dim3((unsigned)((nlong + kBlock - 1) / kBlock)), block, 0, ctx->stream, key_a,
+                               n, d_start, nlong, d_len);
+            std::vector<int> h(2 * (size_t)kMaxLongRuns);
+            MM_HIP_CHECK(hipMemcpyAsync(h.data(), d_start, sizeof(int) * (size_t)nlong, hipMemcpyDeviceToHost, ctx->stream));
+            MM_HIP_CHECK(hipMemcpyAsync(h.data() + kMaxLongRuns, d_len, sizeof(int) * (size_t)nlong, hipMemcpyDeviceToHost,
+                                        ctx->stream));
             MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-            if (nlong > kMaxLongRuns) {
-                general = true;
-            } else if (nlong > 0) {
-                // lengths by bisection on the device, the layout of the sub-array on the host (a few runs)
-                int *d_start = long_runs + 1, *d_len = long_runs + 1 + kMaxLongRuns, *d_table = long_runs + 1 + 2 * kMaxLongRuns;
-                hipLaunchKernelGGL(run_length_kernel, dim3((unsigned)((nlong + kBlock - 1) / kBlock)), block, 0, ctx->stream, key_a,
-                                   n, d_start, nlong, d_len);
-                std::vector<int> h(2 * (size_t)kMaxLongRuns);
-                MM_HIP_CHECK(hipMemcpyAsync(h.data(), d_start, sizeof(int) * (size_t)nlong, hipMemcpyDeviceToHost, ctx->stream));
-                MM_HIP_CHECK(hipMemcpyAsync(h.data() + kMaxLongRuns, d_len, sizeof(int) * (size_t)nlong, hipMemcpyDeviceToHost,
+            std::vector<int> by_start((size_t)nlong);
+            for (int r = 0; r < nlong; ++r) by_start[(size_t)r] = r;
+            std::sort(by_start.begin(), by_start.end(), [&](int a, int b) { return h[(size_t)a] < h[(size_t)b]; });
+            std::vector<int> table(3 * (size_t)nlong);
+            i64 m = 0;
+            int longest = 0;
+            for (int q = 0; q < nlong; ++q) {
+                const int r = by_start[(size_t)q], len = h[(size_t)kMaxLongRuns + r];
+                table[3 * (size_t)q] = h[(size_t)r];
+                table[3 * (size_t)q + 1] = (int)m;
+                table[3 * (size_t)q + 2] = len;
+                m += len;
+                longest = len > longest ? len : longest;
+            }
+            if (m > n / 4) {
+                general = true;   // a structured cloud: most rows sit in long runs
+            } else {
+                MM_HIP_CHECK(hipMemcpyAsync(d_table, table.data(), sizeof(int) * 3 * (size_t)nlong, hipMemcpyHostToDevice,
                                             ctx->stream));
-                MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-                std::vector<int> by_start((size_t)nlong);
-                for (int r = 0; r < nlong; ++r) by_start[(size_t)r] = r;
-                std::sort(by_start.begin(), by_start.end(), [&](int a, int b) { return h[(size_t)a] < h[(size_t)b]; });
-                std::vector<int> table(3 * (size_t)nlong);
-                i64 m = 0;
-                int longest = 0;
-                for (int q = 0; q < nlong; ++q) {
-                    const int r = by_start[(size_t)q], len = h[(size_t)kMaxLongRuns + r];
-                    table[3 * (size_t)q] = h[(size_t)r];
-                    table[3 * (size_t)q + 1] = (int)m;
-                    table[3 * (size_t)q + 2] = len;
-                    m += len;
-                    longest = len > longest ? len : longest;
-                }
-                if (m > n / 4) {
-                    general = true;   // a structured cloud: most rows sit in long runs
-                } else {
-                    MM_HIP_CHECK(hipMemcpyAsync(d_table, table.data(), sizeof(int) * 3 * (size_t)nlong, hipMemcpyHostToDevice,
-                                                ctx->stream));
-                    // the runs' rows side by side in x order -> sorted by (x, y, z, index) -> back to the runs' places: both
-                    // orders are x-major, so sub-array position o_r + t IS place start_r + t of the result
-                    int gx = (longest + kBlock - 1) / kBlock;
-                    if (gx > 1024) gx = 1024;
-                    hipLaunchKernelGGL(run_copy_kernel, dim3((unsigned)gx, (unsigned)nlong), block, 0, ctx->stream, d_table, nlong,
-                                       ord_a, sub_a, 1);
-                    if ((rc = sort_rows(key_b, key_b + m, sub_a, sub_b, m)) != MM_OK) return rc;
-                    hipLaunchKernelGGL(run_copy_kernel, dim3((unsigned)gx, (unsigned)nlong), block, 0, ctx->stream, d_table, nlong,
-                                       ord_a, sub_a, 0);
-                    MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // (the host table goes out of scope)
-                }
+                // the runs' rows side by side in x order -> sorted by (x, y, z, index) -> back to the runs' places: both
+                // orders are x-major, so sub-array position o_r + t IS place start_r + t of the result
+                int gx = (longest + kBlock - 1) / kBlock;
+                if (gx > 1024) gx = 1024;
+                hipLaunchKernelGGL(run_copy_kernel, dim3((unsigned)gx, (unsigned)nlong), block, 0, ctx->stream, d_table, nlong,
+                                   ord_a, sub_a, 1);
+                if ((rc = sort_rows(key_b, key_b + m, sub_a, sub_b, m)) != MM_OK) return rc;
+                hipLaunchKernelGGL(run_copy_kernel, dim3((unsigned)gx, (unsigned)nlong), block, 0, ctx->stream, d_table, nlong,
+                                   ord_a, sub_a, 0);
+                MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // (the host table goes out of scope)
             }
         }
     }

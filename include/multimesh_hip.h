@@ -297,9 +297,20 @@ int mm_set_lazy_lists(mm_context *ctx, int on);
 #define MM_FP_TOL 1
 int mm_set_fp_mode(mm_context *ctx, int mode);
 int mm_get_fp_mode(mm_context *ctx);
-/* out4 = {solves of the last hex8 locate stage that MM_FP_TOL repeated in the reference's arithmetic, targets that went
- * through the reference-order kernel, targets of a long on-demand list's second pass, 0}.  Synchronises. */
+/* out4 = {solves of the last hex8 locate stage that MM_FP_TOL repeated in the reference's arithmetic, targets the first
+ * pass left over (they go to the reference-order kernel, or with a long on-demand list to its second pass), targets that
+ * second pass left over for the reference-order kernel, 0}.  Synchronises. */
 int mm_last_locate_stats(mm_context *ctx, long long *out4);
+/* The kNN kernels the last call launched, as a mask of MM_KNN_RAN_* (tests: which branch of the dispatcher ran).  A
+ * list-mode launch is a pair of kernels, one wave or one lane per target, and the list's length picks the one that works. */
+#define MM_KNN_RAN_LANE 1      /* knn_lane_kernel */
+#define MM_KNN_RAN_STRIP 2     /* knn_strip_kernel */
+#define MM_KNN_RAN_CELL 4      /* knn_cell_kernel */
+#define MM_KNN_RAN_LIST 8      /* list mode: the stragglers, a forced list, a caller's list */
+#define MM_KNN_RAN_GENERIC 16  /* k > 32: knn_query_kernel over one grid */
+#define MM_KNN_RAN_LEVELS 32   /* k > 32: knn_query_levels_kernel over density levels */
+#define MM_KNN_RAN_TREE 64     /* the density-adaptive tree */
+int mm_last_knn_kernels(mm_context *ctx, int *mask);
 
 /* Stage timers (hipEvents on the context's stream).  With profiling on, every kernel
  * launched by the calls above is bracketed by events; mm_last_timings fills ms[stage] for

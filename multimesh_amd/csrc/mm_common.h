@@ -116,6 +116,7 @@ struct mm_context {
         i64 npts = 0, ncells = 0;
         bool dense = false;
     } lane_hint;
+    int knn_kernels = 0;   // MM_KNN_RAN_* bits of the kNN kernels launched since the last mm_stage_reset (mm_last_knn_kernels)
     int *abort_flags = nullptr;   // non-null during a call over a guessed grid: d_counters + kMmAbortSlot (mm_aborted)
     hipStream_t copy_stream = nullptr;   // host-array entry points: uploads run beside the kernels (created on first use)
     hipEvent_t ev_copy[3] = {nullptr, nullptr, nullptr};

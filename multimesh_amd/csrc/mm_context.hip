@@ -419,8 +419,17 @@ extern "C" int mm_last_locate_stats(mm_context *ctx, long long *out4)
     return MM_OK;
 }
 
+extern "C" int mm_last_knn_kernels(mm_context *ctx, int *mask)
+{
+    MM_REQUIRE(ctx != nullptr && mask != nullptr, "null argument");
+    *mask = ctx->knn_kernels;
+    return MM_OK;
+}
+
+// (every public entry point starts here: the kNN kernel record is per call as well)
 void mm_stage_reset(mm_context *ctx)
 {
+    ctx->knn_kernels = 0;
     for (int s = 0; s < MM_STAGE_COUNT; ++s) ctx->ev_used[s] = false;
 }
 

@@ -117,6 +117,7 @@ void launch_list(mm_context *ctx, const mm_knn_index *ix, const LevelTable &lv, 
                  int kout, IDX *idx, double *dist, const int *list, const int *list_count, int keep_max)
 {
     const int wave_max = K <= 32 ? kListWaveMax : -1;
+    ctx->knn_kernels |= MM_KNN_RAN_LIST;
     if (K <= 32) {
         const i64 cap = npts < wave_max ? npts : wave_max;
         const i64 grid = cap < 8192 ? (cap > 0 ? cap : 1) : 8192;
@@ -190,6 +191,7 @@ void launch_fast(mm_context *ctx, const mm_knn_index *ix, const GridParams &g, c
         hipLaunchKernelGGL(lane_items_offsets_kernel, dim3(1), dim3(kBlock), 0, ctx->stream, lane->tile_sums, ntiles);
         hipLaunchKernelGGL(lane_items_place_kernel, dim3(ntiles), dim3(kBlock), 0, ctx->stream, g, tstart, lane->Z, per_item,
                            lane->nstrips_total, lane->tile_sums, ntiles, lane->items);
+        ctx->knn_kernels |= MM_KNN_RAN_LANE;
         const i64 wgs = lane->max_items;   // one workgroup per slot (a multiple of 8; < 2^31: npts and the strip count are)
         if (record_stage) mm_stage_begin(ctx, MM_STAGE_KNN_CELL);
         hipLaunchKernelGGL((knn_lane_kernel<KL, IDX>), dim3((unsigned)wgs), dim3(kWave), 0, ctx->stream, g, ix->nsrc,
@@ -200,6 +202,7 @@ void launch_fast(mm_context *ctx, const mm_knn_index *ix, const GridParams &g, c
         return;
     }
     if (record_stage) mm_stage_begin(ctx, MM_STAGE_KNN_CELL);
+    ctx->knn_kernels |= use_strip ? MM_KNN_RAN_STRIP : MM_KNN_RAN_CELL;
     if (use_strip) {
         const i64 nstrips = (ix->dims[2] + kStripZ - 1) / kStripZ;
         i64 strip_grid = 8 * ((cols + 7) / 8) * nstrips;
@@ -830,6 +833,7 @@ static int tree_query(mm_context *ctx, const mm_knn_index *ix, const double *pts
     const mm_knn_tree *tr = ix->tree;
     const i64 n = list ? list_len : npts;
     if (n <= 0) return MM_OK;
+    ctx->knn_kernels |= MM_KNN_RAN_TREE;
     if (list && n < kTreeRingListMax) {
         tree_ring<IDX>(ctx, ix, pts_d, pstride, n, kout, idx_d, dist_d, list, list_count);
         MM_HIP_CHECK(hipGetLastError());
@@ -978,6 +982,7 @@ static int knn_query_typed(mm_context *ctx, const mm_knn_index *ix, const double
         // long lists: generic ring-expansion kernel for every target (in the grid that suits it, when
         // the cloud has density levels)
         const LevelTable lv = level_table_of(ix, kMaxLevels);
+        ctx->knn_kernels |= ix->fine ? MM_KNN_RAN_LEVELS : MM_KNN_RAN_GENERIC;
         with_k(kListKs{}, kout, [&](auto KK) {
             constexpr int K = decltype(KK)::value;
             if (ix->fine)

@@ -16,6 +16,9 @@ import numpy as np
 
 from .helpers import MM_FP_EXACT, MM_FP_TOL, MM_KNN_MAX_K, STAGES, MultiMeshHipError, check, load_lib
 
+# MM_KNN_RAN_* in bit order
+KNN_KERNELS = ("lane", "strip", "cell", "list", "generic", "levels", "tree")
+
 _NP2ITEM = {np.dtype(np.float64): 8, np.dtype(np.int64): 8, np.dtype(np.int32): 4, np.dtype(np.uint8): 1}
 
 
@@ -213,11 +216,18 @@ class Context:
         return "tol" if check(self.lib.mm_get_fp_mode(self.handle), "mm_get_fp_mode") == MM_FP_TOL else "exact"
 
     def last_locate_stats(self):
-        """Of the last hex8 locate stage: solves MM_FP_TOL repeated in the reference's arithmetic, targets that went
-        through the reference-order kernel, targets of a long on-demand list's second pass (synchronises)."""
+        """Of the last hex8 locate stage: solves MM_FP_TOL repeated in the reference's arithmetic, targets the first pass
+        left over (for the reference-order kernel, or a long on-demand list's second pass), targets that second pass left
+        over for the reference-order kernel (synchronises)."""
         buf = (C.c_longlong * 4)()
         check(self.lib.mm_last_locate_stats(self.handle, buf), "mm_last_locate_stats")
         return {"redone_exact": int(buf[0]), "reference_order": int(buf[1]), "second_pass": int(buf[2])}
+
+    def last_knn_kernels(self):
+        """Names of the kNN kernels the last call launched: a subset of KNN_KERNELS (include/multimesh_hip.h)."""
+        m = C.c_int()
+        check(self.lib.mm_last_knn_kernels(self.handle, C.byref(m)), "mm_last_knn_kernels")
+        return {name for bit, name in enumerate(KNN_KERNELS) if m.value >> bit & 1}
 
     def last_timings(self):
         """Per-stage milliseconds of the last call (hipEvents on this context's stream)."""

@@ -39,7 +39,7 @@ EXPORTED_SYMBOLS = (
     "mm_centroid", "mm_knn_build", "mm_knn_query", "mm_knn_destroy",
     "mm_locate_hex8", "mm_gather", "mm_interpolate_hex8", "mm_interpolate_hex8_host", "mm_locate_gll", "mm_gather_elem",
     "mm_scatter_elements", "mm_fluid_solid_fix", "mm_set_profiling", "mm_last_timings", "mm_set_lazy_lists", "mm_unique_points", "mm_locate_gll_bbox", "mm_interpolate_gll",
-    "mm_set_fp_mode", "mm_get_fp_mode", "mm_last_locate_stats",
+    "mm_set_fp_mode", "mm_get_fp_mode", "mm_last_locate_stats", "mm_last_knn_kernels",
     "mm_source_create", "mm_source_destroy", "mm_interpolate_hex8_on", "mm_points_to_elements", "mm_unique_points_any_order",
     "mm_map_to_sphere", "mm_first_occurrence", "mm_sphere_ratio", "mm_scale_points",
 )
@@ -162,6 +162,8 @@ def load_lib():
     lib.mm_get_fp_mode.argtypes = [vp]
     lib.mm_last_locate_stats.restype = C.c_int
     lib.mm_last_locate_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
+    lib.mm_last_knn_kernels.restype = C.c_int
+    lib.mm_last_knn_kernels.argtypes = [vp, C.POINTER(C.c_int)]
     lib.mm_set_profiling.restype = C.c_int
     lib.mm_set_profiling.argtypes = [vp, C.c_int]
     lib.mm_last_timings.restype = C.c_int

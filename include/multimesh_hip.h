@@ -172,6 +172,32 @@ int64_t mm_interpolate_gll(mm_context *ctx, int order, int dim, const double *gl
                            int64_t nelem_to_search, double tolerance, int snap_to_nearest, double *out_d,
                            int64_t *elem_out_d, double *coeffs_out_d);
 
+/* A 3-D GLL model sampled on latitude x longitude x depth columns: extract_regular_grid (reference api.py:600-642,
+ * components/interpolator.py:1600-1646), the depth slice of plot_depth_slice (plotter.py:89-102, :159-187) and the
+ * radius x path section of plot_cross_section (plotter.py:360-391).  The targets are generated on the device:
+ *   lat_d f64[nlat][2] = {sin colat, cos colat}, lon_d f64[nlon][2] = {cos lon, sin lon}, radius_d f64[ndepth]
+ *   (6371000 - depth), all computed on the host as latlondepth_to_xyz computes them (reference utils.py:526-542);
+ *   column h: latitude h / nlon and longitude h % nlon (paired == 0, ncol = nlat * nlon), or latitude h and
+ *   longitude h (paired == 1, a path, nlat == nlon = ncol);
+ *   target (d, h) = {(r_d * sin_colat) * cos_lon, (r_d * sin_colat) * sin_lon, r_d * cos_colat} in that order, no
+ *   fused multiply-add: bit for bit latlondepth_to_xyz of the row (lat, lon, depth).
+ * Every target is then served as mm_interpolate_gll (dim 3, snap_to_nearest 0) serves the same point -- same
+ * element, same acceptance, same value -- except that a target without an element gets fill_value.
+ *   gll_points_d f64[nelem][P][3], fields_d f64[ncomp][nelem][P], out_d f64[ncomp][ndepth][ncol] (component-major, in
+ *   grid order), points_out_d (nullable) f64[ndepth][ncol][3] receives the generated targets.
+ * The centroid tree is built once per call; the targets go through in chunks of chunk_points consecutive flat indices
+ * d * ncol + h (0: automatic, MM_SAMPLE_CHUNK_BYTES / the per-target bytes 4 min(k, 8) + 4 k (k > 8) + 28 + 24 (no
+ * points_out_d) + MM_SAMPLE_STAGE_BYTES; never more than MM_SAMPLE_CHUNK_MAX).  Results do not depend on the chunk size.
+ * Returns the number of targets without an element, or a negative MM_ERR_*. */
+#define MM_SAMPLE_CHUNK_BYTES ((int64_t)1 << 34) /* per-target scratch of one automatic chunk (16 GiB) */
+#define MM_SAMPLE_STAGE_BYTES 96                 /* the kNN and locate stages' own per-target arrays, counted flat */
+#define MM_SAMPLE_CHUNK_MAX ((int64_t)0x7fffff00) /* int32 target indices of the locate stage */
+int64_t mm_sample_columns_gll(mm_context *ctx, int order, const double *gll_points_d, int64_t nelem,
+                              const double *fields_d, int64_t ncomp, const double *lat_d, int64_t nlat,
+                              const double *lon_d, int64_t nlon, int paired, const double *radius_d, int64_t ndepth,
+                              int64_t nelem_to_search, double tolerance, double fill_value, int64_t chunk_points,
+                              double *out_d, double *points_out_d);
+
 /* Unique points and the index array that rebuilds the input: np.unique(points, axis=0,
  * return_inverse=True) of reference utils.py:484-488 (get_unique_points, the pre-step of the GLL
  * target flows; scatter-back at components/interpolator.py:823).  points_d f64[npoints][dim];

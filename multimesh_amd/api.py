@@ -18,6 +18,8 @@ file-level drivers under the reference's names -- :func:`query_model`, :func:`ex
 through :mod:`multimesh_amd.io`.
 Earth meshes: :func:`map_to_sphere` and :func:`map_to_ellipse` (reference interpolator.py:1085-1144, in place), and
 ``make_spherical`` of the drivers (mapped copies).
+Regular grids: :func:`extract_regular_grid` (reference api.py:600-642), :func:`extract_depth_slice` and
+:func:`extract_cross_section` (what plot_depth_slice / plot_cross_section sample), targets generated on the device.
 """
 from __future__ import annotations
 
@@ -861,3 +863,219 @@ def gll_2_gll_layered_multi(from_gll, to_gll, layers="nocore", nelem_to_search=2
     _gll_2_gll_layered_bbox(from_gll, to_gll, layers, nelem_to_search, parameters, stored_array, make_spherical,
                             keep_existing=True, context=context)
     _report(start)
+
+
+# ---------------------------------------------------------------------------------------------------
+# Sampling on latitude x longitude x depth columns: extract_regular_grid (reference api.py:600-642,
+# interpolator.py:1600-1646), the depth slice plot_depth_slice samples (plotter.py:89-110, :159-187) and the
+# radius x path section of plot_cross_section (plotter.py:360-391).  The targets are generated on the device
+# (Context.sample_columns_gll); the host only computes the 1-D factors below.  Plotting is not part of this.
+DIMS = ("depth", "latitude", "longitude")
+UNITS = {"depth": "m", "latitude": "deg", "longitude": "deg"}
+
+
+def _extent(extent, name):
+    """``np.linspace(min, max, num)`` of an extent ``(min, max, num)``, as the reference forms its axes."""
+    try:
+        lo, hi, num = extent
+        lo, hi = float(lo), float(hi)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be (min, max, num), got {extent!r}") from None
+    if not (np.isfinite(lo) and np.isfinite(hi)):
+        raise ValueError(f"{name}: the bounds must be finite, got {extent!r}")
+    if isinstance(num, (bool, np.bool_)) or not float(num).is_integer() or int(num) < 1:
+        raise ValueError(f"{name}: num must be an integer >= 1, got {num!r}")
+    return np.linspace(lo, hi, int(num))
+
+
+def column_tables(lat, lon, depth):
+    """``(lat_table f64[nlat, 2], lon_table f64[nlon, 2], radius f64[D])`` as :meth:`Context.sample_columns_gll`
+    reads them: (sin colat, cos colat), (cos lon, sin lon) and 6371000 - depth, computed with the expressions of
+    :func:`latlondepth_to_xyz` on columns of [n, 3] arrays like its own (so that NumPy runs the same loops).  The
+    device forms ``((r * sin colat) * cos lon, (r * sin colat) * sin lon, r * cos colat)`` from them: that
+    function's rows bit for bit."""
+    def rows(values, col):
+        a = np.zeros((len(values), 3))
+        a[:, col] = np.asarray(values, dtype=np.float64)
+        return a
+
+    la, lo, de = rows(lat, 0), rows(lon, 1), rows(depth, 2)
+    colat = np.deg2rad(90.0 - la[:, 0])
+    lonr = np.deg2rad(lo[:, 1])
+    lat_table = np.ascontiguousarray(np.stack([np.sin(colat), np.cos(colat)], axis=1))
+    lon_table = np.ascontiguousarray(np.stack([np.cos(lonr), np.sin(lonr)], axis=1))
+    return lat_table, lon_table, np.ascontiguousarray(6371000.0 - de[:, 2])
+
+
+def _gll_model(mesh, parameters, make_spherical, ctx):
+    """(gll_points f64[E, P, 3] (host or device), shape_order, fields f64[C, E, P]) of a :class:`GllMesh` or of a Salvus
+    model (a file, or an h5py-like object read through :func:`multimesh_amd.io.load_hdf5_params_to_memory`, whose
+    parameters are picked by name from ``DIMENSION_LABELS``).  ``make_spherical`` maps a copy onto the mesh's 1-D sphere."""
+    from . import io as mio
+
+    parameters = mio.pick_parameters(parameters)
+    if not isinstance(mesh, GllMesh):
+        points, data, names = mio.load_hdf5_params_to_memory(mesh)
+        missing = [p for p in parameters if p not in names]
+        if missing:
+            raise ValueError(f"parameters {missing} are not in the model (it holds {names})")
+        P = points.shape[1]
+        order = int(round(P ** (1.0 / 3.0))) - 1
+        if points.ndim != 3 or points.shape[2] != 3 or (order + 1) ** 3 != P:
+            raise ValueError(f"MODEL/coordinates must be [nelem, (order+1)^3, 3], got {points.shape}")
+        wanted = set(parameters) | ({"z_node_1D"} if make_spherical and "z_node_1D" in names else set())
+        mesh = GllMesh(points, order, {p: data[:, names.index(p), :] for p in wanted})
+    fields = np.stack([np.asarray(mesh.element_nodal_fields[p], dtype=np.float64) for p in parameters])
+    gll_points = _sphere_mapped(mesh, ctx) if make_spherical else mesh.gll_points
+    return gll_points, mesh.shape_order, fields
+
+
+def _sample(mesh, parameters, lat, lon, depth, paired, make_spherical, nelem_to_search, tolerance, fill_value,
+            chunk_points, context):
+    """values f64[C, D, H] (host) and the number of targets without an element."""
+    ctx = context or default_context()
+    gll_points, order, fields = _gll_model(mesh, parameters, make_spherical, ctx)
+    lat_t, lon_t, radius = column_tables(lat, lon, depth)
+    values, nmissing = ctx.sample_columns_gll(order, gll_points, fields, lat_t, lon_t, radius, paired=paired,
+                                              nelem_to_search=nelem_to_search, tolerance=tolerance,
+                                              fill_value=fill_value, chunk_points=chunk_points)
+    return values.numpy(), nmissing
+
+
+class RegularGrid:
+    """What reference ``extract_regular_grid`` returns as an xarray Dataset (``utils.create_xarray_dataset``,
+    utils.py:619-646), without xarray: ``coords`` depth (m), latitude and longitude (deg); ``data_vars`` one f64
+    array per parameter with dims (depth, latitude, longitude); ``attrs`` {"radius_in_meters": 6371000.0};
+    ``nmissing`` targets outside the mesh, which hold ``fill_value``.  ``grid[name]`` returns a variable or a
+    coordinate."""
+
+    dims = DIMS
+
+    def __init__(self, depth, latitude, longitude, data_vars, nmissing=0, fill_value=np.nan):
+        self.coords = {"depth": np.asarray(depth, dtype=np.float64), "latitude": np.asarray(latitude, dtype=np.float64),
+                       "longitude": np.asarray(longitude, dtype=np.float64)}
+        shape = tuple(len(self.coords[d]) for d in DIMS)
+        self.data_vars = {}
+        for name, v in data_vars.items():
+            v = np.asarray(v, dtype=np.float64)
+            if v.shape != shape:
+                raise ValueError(f"{name}: shape {v.shape}, the grid is {shape}")
+            self.data_vars[name] = v
+        self.attrs = {"radius_in_meters": 6371000.0}
+        self.nmissing = int(nmissing)
+        self.fill_value = float(fill_value)
+
+    def __getitem__(self, name):
+        return self.data_vars[name] if name in self.data_vars else self.coords[name]
+
+    def to_netcdf(self, path):
+        """Classic netCDF with 64-bit offsets (``scipy.io.netcdf_file(version=2)``): dimensions and coordinate
+        variables depth / latitude / longitude with their ``units``, the global ``radius_in_meters``, one f64 variable
+        per parameter over (depth, latitude, longitude) with ``_FillValue`` = the fill value (NaN stays NaN).  A
+        variable the format cannot hold (4 GiB - 4 bytes at most) raises ``ValueError`` before anything is written."""
+        from scipy.io import netcdf_file
+
+        limit = 2 ** 32 - 4
+        for name, v in list(self.coords.items()) + list(self.data_vars.items()):
+            if v.nbytes > limit:
+                raise ValueError(f"variable {name!r} needs {v.nbytes} bytes; the 64-bit-offset netCDF format holds "
+                                 f"at most {limit} per variable: write a smaller grid (or fewer depths) per file")
+        clash = set(self.data_vars) & set(DIMS)
+        if clash:
+            raise ValueError(f"parameter names {sorted(clash)} clash with the coordinates")
+        with netcdf_file(path, "w", version=2) as f:
+            f.radius_in_meters = self.attrs["radius_in_meters"]
+            for d in DIMS:
+                f.createDimension(d, len(self.coords[d]))
+                c = f.createVariable(d, "d", (d,))
+                c[:] = self.coords[d]
+                c.units = UNITS[d]
+            for name, v in self.data_vars.items():
+                var = f.createVariable(name, "d", DIMS)
+                var._FillValue = self.fill_value
+                var[:] = v
+
+    def __repr__(self):
+        shape = ", ".join(f"{d}: {len(self.coords[d])}" for d in DIMS)
+        return f"<RegularGrid ({shape}) {list(self.data_vars)} nmissing={self.nmissing}>"
+
+
+def extract_regular_grid(mesh, parameters, lat_extent, lon_extent, depth_extent, save_to_netcdf=False, netcdf_path=None,
+                         *, make_spherical=False, nelem_to_search=25, tolerance=1.05, fill_value=np.nan,
+                         chunk_points=None, context=None):
+    """A GLL model on a regular latitude x longitude x depth grid (reference api.py:600-642, interpolator.py:1600-1646).
+
+    ``mesh``: a :class:`GllMesh`, a Salvus model file, or an h5py-like object (parameters picked by name from
+    ``MODEL/data``'s ``DIMENSION_LABELS``).  Extents are ``(min, max, num)`` through ``np.linspace``; latitudes are
+    geocentric degrees and depths metres below 6371 km (:func:`latlondepth_to_xyz`).  Every grid point is
+    interpolated as :meth:`Context.interpolate_gll` interpolates it (centroid kNN over ``nelem_to_search``,
+    acceptance at ``tolerance``); points outside the mesh hold ``fill_value``.  The points are generated on the
+    device in chunks (``chunk_points``; None: a fixed scratch budget).  ``make_spherical`` samples a copy of the mesh
+    mapped onto its 1-D sphere (:func:`map_to_sphere`); the caller's arrays are not changed.
+
+    Returns a :class:`RegularGrid` (the reference returns an xarray Dataset; xarray is not used here), or, with
+    ``save_to_netcdf``, writes it to ``netcdf_path`` (:meth:`RegularGrid.to_netcdf`) and returns None."""
+    lat = _extent(lat_extent, "lat_extent")
+    lon = _extent(lon_extent, "lon_extent")
+    depth = _extent(depth_extent, "depth_extent")
+    if save_to_netcdf and netcdf_path is None:
+        raise ValueError("save_to_netcdf needs a netcdf_path")
+    from . import io as mio
+
+    parameters = mio.pick_parameters(parameters)
+    values, nmissing = _sample(mesh, parameters, lat, lon, depth, False, make_spherical, nelem_to_search, tolerance,
+                               fill_value, chunk_points, context)
+    shape = (len(depth), len(lat), len(lon))
+    grid = RegularGrid(depth, lat, lon, {p: values[c].reshape(shape) for c, p in enumerate(parameters)}, nmissing,
+                       fill_value)
+    if save_to_netcdf:
+        grid.to_netcdf(netcdf_path)
+        return None
+    return grid
+
+
+def extract_depth_slice(mesh, depth_in_km, num, lat_extent=(-90.0, 90.0), lon_extent=(-180.0, 180.0), parameter="VSV",
+                        diff_percentage=False, *, make_spherical=False, nelem_to_search=25, tolerance=1.05,
+                        fill_value=np.nan, chunk_points=None, context=None):
+    """The ``num x num`` array reference ``plot_depth_slice`` plots (plotter.py:89-110): ``parameter`` at
+    ``depth_in_km`` on ``np.linspace`` latitudes and longitudes, in the reference's layout -- the points of
+    ``_create_depthslice`` (``np.meshgrid(lat, lon)``, raveled) reshaped to (num, num), i.e. ``[longitude, latitude]``.
+    ``diff_percentage``: ``(v - mean) / mean * 100`` with the mean over the points inside the mesh, and all zeros
+    when the largest deviation is below 0.1 % (a 1-D model), as the reference does.  Points outside the mesh hold
+    ``fill_value``."""
+    lat = _extent((lat_extent[0], lat_extent[1], num), "lat_extent")
+    lon = _extent((lon_extent[0], lon_extent[1], num), "lon_extent")
+    depth = np.array([depth_in_km * 1000.0])
+    values, _ = _sample(mesh, [parameter], lat, lon, depth, False, make_spherical, nelem_to_search, tolerance, np.nan,
+                        chunk_points, context)
+    vals = np.ascontiguousarray(values[0, 0].reshape(len(lat), len(lon)).T)   # [lat, lon] -> the reference's [lon, lat]
+    found = ~np.isnan(vals)
+    if diff_percentage and found.any():
+        mean = np.mean(vals[found])
+        vals = (vals - mean) / mean * 100.0
+        if np.max(np.abs(vals[found])) < 0.1:   # (reference plotter.py:108-109)
+            vals[found] = 0.0
+    vals[~found] = fill_value
+    return vals
+
+
+def extract_cross_section(mesh, parameters, lats, lons, depths, make_spherical=True, *, nelem_to_search=25,
+                          tolerance=1.05, fill_value=np.nan, chunk_points=None, context=None):
+    """A radius x path section, what reference ``plot_cross_section`` samples (plotter.py:360-391):
+    values f64[C, ndepth, npath] at the points (``lats[h]``, ``lons[h]``, ``depths[d]``) -> :func:`latlondepth_to_xyz`.
+
+    The reference builds its path as a WGS84 geodesic between two points (``greatcircle_points`` through
+    geographiclib) and converts it to geocentric latitudes; that library is not used here, so the caller passes the
+    path itself: ``lats`` (geocentric degrees) and ``lons`` of equal length, and ``depths`` in metres.
+    ``make_spherical`` (default True, as plotter.py:385-390) samples a copy of the mesh mapped onto its 1-D sphere.
+    Points outside the mesh hold ``fill_value``; the reference's per-radius percentage is plotting and not done."""
+    lats = np.atleast_1d(np.asarray(lats, dtype=np.float64))
+    lons = np.atleast_1d(np.asarray(lons, dtype=np.float64))
+    depths = np.atleast_1d(np.asarray(depths, dtype=np.float64))
+    if lats.ndim != 1 or lons.ndim != 1 or depths.ndim != 1 or len(lats) != len(lons):
+        raise ValueError("lats and lons must be 1-D of the same length, depths 1-D")
+    if not (np.isfinite(lats).all() and np.isfinite(lons).all() and np.isfinite(depths).all()):
+        raise ValueError("the path and the depths must be finite")
+    values, _ = _sample(mesh, parameters, lats, lons, depths, True, make_spherical, nelem_to_search, tolerance,
+                        fill_value, chunk_points, context)
+    return values

@@ -78,7 +78,8 @@ enum mm_buffer_slot {
     MM_BUF_TREE_COARSE,
     MM_BUF_TREE_DOWN,                     //   ... targets of a query whose first window overflowed the tile (second pass)
     MM_BUF_LEVELS,                        // density levels of the kNN grid: {cell_start, sorted_xyz} per level
-    MM_BUF_COUNT = MM_BUF_LEVELS + 2 * 8
+    MM_BUF_SAMPLE_POINTS = MM_BUF_LEVELS + 2 * 8,   // mm_sample_columns_gll: the chunk's generated targets
+    MM_BUF_COUNT
 };
 
 struct mm_context {

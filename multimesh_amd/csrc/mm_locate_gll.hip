@@ -1213,6 +1213,168 @@ extern "C" int64_t mm_interpolate_gll(mm_context *ctx, int order, int dim, const
     return result;
 }
 
+// ---- mm_sample_columns_gll: a model sampled on latitude x longitude x depth columns --------------------------------
+// Target t = d * ncol + h of a chunk [t0, t0 + n): radius d, column h -- latitude h / nlon and longitude h % nlon on a
+// grid, latitude h and longitude h of a path (paired).  The host gives the trig tables; the point is formed with the
+// operations of latlondepth_to_xyz (reference utils.py:526-542) in its order, x = (r * sin colat) * cos lon, ... (no
+// fused multiply-add: -ffp-contract=off), so that it is that function's row bit for bit.
+__global__ __launch_bounds__(256) void sample_points_kernel(i64 t0, i64 n, i64 ncol, i64 nlon, int paired,
+                                                            const double *__restrict__ lat,
+                                                            const double *__restrict__ lon,
+                                                            const double *__restrict__ radius, double *__restrict__ pts)
+{
+    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const i64 t = t0 + i;
+    const i64 d = t / ncol, h = t - d * ncol;
+    const i64 a = paired ? h : h / nlon;
+    const i64 b = paired ? h : h - a * nlon;
+    const double r = radius[d];
+    const double rs = r * lat[2 * a];
+    pts[3 * i + 0] = rs * lon[2 * b];
+    pts[3 * i + 1] = rs * lon[2 * b + 1];
+    pts[3 * i + 2] = r * lat[2 * a + 1];
+}
+
+// gll_values_kernel for the sampled columns: the same weighted sums (NumPy's row-sum order), written component-major
+// out[c * stride + i] (out starts at the chunk's first target), and fill for a target without an element instead of
+// NumPy's +-0 of field[-1] * 0.
+template <int ORDER>
+__global__ __launch_bounds__(256, kGllValuesWaves) void gll_column_values_kernel(i64 npoints, const int *__restrict__ elem,
+                                                                 const double *__restrict__ xi_all,
+                                                                 const double *__restrict__ fields, i64 nelem,
+                                                                 int ncomp, double fill, i64 stride,
+                                                                 double *__restrict__ out)
+{
+    using G = Gll<ORDER, 3>;
+    constexpr int P = G::P;
+    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npoints) return;
+    const int e = elem[i];
+    if (e < 0) {
+        for (int c = 0; c < ncomp; ++c) out[(i64)c * stride + i] = fill;
+        return;
+    }
+    double g[G::n];
+    gll_nodes<ORDER>(g);
+    double l[3][G::n], dl[3][G::n];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) lagrange_1d<ORDER>(g, xi_all[i * 3 + d], l[d], dl[d]);
+    for (int c = 0; c < ncomp; ++c)
+        out[(i64)c * stride + i] = G::template weighted_sum<true>(l, false, fields + ((i64)c * nelem + e) * P);
+}
+
+// Targets per chunk a call takes when the caller leaves it open (see MM_SAMPLE_CHUNK_BYTES in the header).
+static i64 sample_chunk_auto(i64 k, int kavail, bool lazy, bool points_out)
+{
+    const i64 per = 4 * (i64)kavail + (lazy ? 4 * k : 0) + 3 * 8 + 4 + (points_out ? 0 : 3 * 8) + MM_SAMPLE_STAGE_BYTES;
+    const i64 c = MM_SAMPLE_CHUNK_BYTES / per;
+    return c < 1 ? 1 : c;
+}
+
+// One centroid tree for the whole call, then chunk after chunk: targets generated into the chunk's point buffer (or
+// straight into points_out), the k nearest centroids, the acceptance loop of interpolator.py:1181-1233 with deferred
+// values (locate_gll_run, as mm_interpolate_gll without operator outputs), the sums into the chunk's slice of out.
+// Every target's result depends on its point alone, so the chunking cannot change it.
+extern "C" int64_t mm_sample_columns_gll(mm_context *ctx, int order, const double *gll_points_d, int64_t nelem,
+                                         const double *fields_d, int64_t ncomp, const double *lat_d, int64_t nlat,
+                                         const double *lon_d, int64_t nlon, int paired, const double *radius_d,
+                                         int64_t ndepth, int64_t k, double tolerance, double fill_value,
+                                         int64_t chunk_points, double *out_d, double *points_out_d)
+{
+    MM_REQUIRE(ctx != nullptr, "ctx is null");
+    MM_REQUIRE(order == 1 || order == 2 || order == 4, "order must be 1, 2 or 4");
+    MM_REQUIRE(k >= 1 && k <= MM_KNN_MAX_K, "nelem_to_search must be in 1..MM_KNN_MAX_K");
+    MM_REQUIRE(nelem >= 1 && nelem < (int64_t)0x7ffffff0, "nelem must be in 1..0x7ffffff0");
+    MM_REQUIRE(ncomp >= 0 && ncomp < (1 << 20), "bad ncomp");
+    MM_REQUIRE(nlat >= 0 && nlon >= 0 && ndepth >= 0 && chunk_points >= 0, "negative size");
+    MM_REQUIRE(nlat < ((int64_t)1 << 31) && nlon < ((int64_t)1 << 31), "too many latitudes / longitudes");
+    MM_REQUIRE(paired == 0 || paired == 1, "paired must be 0 or 1");
+    MM_REQUIRE(!paired || nlat == nlon, "a path pairs latitude h with longitude h: nlat must equal nlon");
+    const i64 ncol = paired ? nlat : nlat * nlon;
+    MM_REQUIRE(ncol == 0 || ndepth <= INT64_MAX / 8 / ncol / (ncomp > 3 ? ncomp : 3), "too many targets");
+    const i64 total = ncol * ndepth;
+    MM_REQUIRE(total == 0 || (gll_points_d && lat_d && lon_d && radius_d), "null array");
+    MM_REQUIRE(total == 0 || ncomp == 0 || (fields_d && out_d), "null array");
+    MM_HIP_CHECK(hipSetDevice(ctx->device));
+    mm_stage_reset(ctx);
+    if (total == 0) return 0;
+    constexpr int P_of[5] = {0, 8, 27, 0, 125};
+    const int P = P_of[order];
+
+    double *cen = nullptr;
+    int rc = mm_buffer_get(ctx, MM_BUF_CENTROID, (size_t)nelem * 3 * sizeof(double), (void **)&cen);
+    if (rc != MM_OK) return rc;
+    hipLaunchKernelGGL((centroid_nodal_kernel<3>), dim3((unsigned)((nelem + 255) / 256)), dim3(256), 0, ctx->stream,
+                       (i64)nelem, P, gll_points_d, cen);
+    mm_knn_index *ix = nullptr;
+    rc = mm_knn_build_impl(ctx, cen, nelem, 3, &ix, /*use_context_buffers=*/true, nullptr, 0);
+    if (rc != MM_OK) return rc;
+
+    const bool lazy_on = ctx->lazy_lists && k > kGllLazyK;
+    const int kavail = lazy_on ? kGllLazyK : (int)k;
+    i64 chunk = chunk_points > 0 ? chunk_points : sample_chunk_auto(k, kavail, lazy_on, points_out_d != nullptr);
+    if (chunk > MM_SAMPLE_CHUNK_MAX) chunk = MM_SAMPLE_CHUNK_MAX;   // the locate stage's int32 target indices
+    if (chunk > total) chunk = total;
+    int *nn = nullptr, *nn_full = nullptr, *elem = nullptr;
+    double *xi = nullptr, *pts_buf = nullptr;
+    rc = mm_buffer_get(ctx, MM_BUF_NN, (size_t)chunk * kavail * sizeof(int), (void **)&nn);
+    if (rc == MM_OK && lazy_on) rc = mm_buffer_get(ctx, MM_BUF_NN_FULL, (size_t)chunk * k * sizeof(int), (void **)&nn_full);
+    if (rc == MM_OK) rc = mm_buffer_get(ctx, MM_BUF_W, (size_t)chunk * 3 * sizeof(double), (void **)&xi);
+    if (rc == MM_OK) rc = mm_buffer_get(ctx, MM_BUF_ENC, (size_t)chunk * sizeof(int), (void **)&elem);
+    if (rc == MM_OK && !points_out_d)
+        rc = mm_buffer_get(ctx, MM_BUF_SAMPLE_POINTS, (size_t)chunk * 3 * sizeof(double), (void **)&pts_buf);
+    if (rc == MM_OK) {
+        hipError_t e = hipMemsetAsync(ctx->d_counters, 0, sizeof(i64), ctx->stream);
+        if (e != hipSuccess) {
+            mm_set_error(MM_ERR_HIP, "memset: %s", hipGetErrorString(e));
+            rc = MM_ERR_HIP;
+        }
+    }
+    GllEmit em = {nullptr, nullptr, nullptr, nullptr, 0};
+    em.xi_defer = xi;
+    em.elem_defer = elem;
+    const GllLazy lz = {ix, nn_full};
+    for (i64 t0 = 0; rc == MM_OK && t0 < total; t0 += chunk) {
+        const i64 n = total - t0 < chunk ? total - t0 : chunk;
+        double *pts = points_out_d ? points_out_d + 3 * t0 : pts_buf;
+        const dim3 g((unsigned)((n + 255) / 256)), b(256);
+        hipLaunchKernelGGL(sample_points_kernel, g, b, 0, ctx->stream, t0, n, ncol, (i64)nlon, paired, lat_d, lon_d,
+                           radius_d, pts);
+        rc = mm_knn_query_impl(ctx, ix, pts, n, kavail, nn, nullptr, /*idx_is_int32=*/true);
+        if (rc == MM_OK)
+            rc = locate_gll_run<int>(ctx, order, 3, k, kavail, n, nn, gll_points_d, nelem, pts, tolerance, 0, em,
+                                     lazy_on ? &lz : nullptr);
+        if (rc == MM_OK && ncomp > 0) {
+#define MM_GLL_COLUMNS(O)                                                                                             \
+    if (order == O)                                                                                                   \
+        hipLaunchKernelGGL((gll_column_values_kernel<O>), g, b, 0, ctx->stream, n, (const int *)elem, (const double *)xi, \
+                           fields_d, (i64)nelem, (int)ncomp, fill_value, total, out_d + t0);
+            MM_GLL_COLUMNS(1) MM_GLL_COLUMNS(2) MM_GLL_COLUMNS(4)
+#undef MM_GLL_COLUMNS
+        }
+        if (rc == MM_OK && hipGetLastError() != hipSuccess) {
+            mm_set_error(MM_ERR_HIP, "mm_sample_columns_gll: kernel launch failed");
+            rc = MM_ERR_HIP;
+        }
+    }
+    int64_t result = rc;
+    if (rc == MM_OK) {
+        hipError_t e = hipMemcpyAsync(ctx->h_counters, ctx->d_counters, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) {
+            mm_set_error(MM_ERR_HIP, "mm_sample_columns_gll: %s", hipGetErrorString(e));
+            result = MM_ERR_HIP;
+        } else {
+            result = ctx->h_counters[0];
+        }
+    } else {
+        (void)hipStreamSynchronize(ctx->stream);
+    }
+    mm_knn_destroy(nullptr, ix);   // borrowed arrays stay in the context cache
+    return result;
+}
+
 extern "C" int mm_gather_elem(mm_context *ctx, const double *fields_d, int64_t nelem, int64_t ncomp,
                               const int64_t *elem_d, const double *coeffs_d, int64_t npoints, int64_t P,
                               double *out_d, int out_point_major)

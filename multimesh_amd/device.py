@@ -380,6 +380,53 @@ class Context:
             return out, elem, coeffs, int(miss)
         return out, int(miss)
 
+    def sample_columns_gll(self, shape_order, gll_points, element_nodal_fields, lat_table, lon_table, radius,
+                           paired=False, nelem_to_search=25, tolerance=1.05, fill_value=np.nan, chunk_points=None,
+                           want_points=False, out=None):
+        """A 3-D GLL model sampled on latitude x longitude x radius columns, the targets generated on the device
+        (``mm_sample_columns_gll``).  ``lat_table`` f64[nlat, 2] = (sin colat, cos colat), ``lon_table`` f64[nlon, 2]
+        = (cos lon, sin lon), ``radius`` f64[D]; columns are the nlat x nlon grid (latitude outer) or, with
+        ``paired``, the path of latitude h with longitude h.  Every target's value is what :meth:`interpolate_gll`
+        gives for the same point; targets without an element hold ``fill_value``.  ``chunk_points``: targets per
+        chunk (None: the library's byte budget).
+        Returns (values f64[C, D, H], nmissing) or, with ``want_points``, (values, nmissing, points f64[D, H, 3])."""
+        gp = self.asdevice(gll_points, np.float64)
+        f = self.asdevice(element_nodal_fields, np.float64)
+        if len(f.shape) == 2:
+            f = DeviceArray(self, f.ptr, (1,) + f.shape, f.dtype, owner=False, keepalive=f)
+        lat = self.asdevice(lat_table, np.float64)
+        lon = self.asdevice(lon_table, np.float64)
+        rad = self.asdevice(radius, np.float64)
+        if len(gp.shape) != 3 or gp.shape[2] != 3 or gp.shape[1] != (shape_order + 1) ** 3:
+            raise ValueError("gll_points must be [nelem, (order+1)^3, 3]")
+        nelem, P, _ = gp.shape
+        if f.shape[1:] != (nelem, P):
+            raise ValueError("element_nodal_fields must be [C, nelem, P]")
+        if len(lat.shape) != 2 or lat.shape[1] != 2 or len(lon.shape) != 2 or lon.shape[1] != 2 or len(rad.shape) != 1:
+            raise ValueError("lat_table and lon_table must be [n, 2], radius [D]")
+        nlat, nlon, nd = lat.shape[0], lon.shape[0], rad.shape[0]
+        if paired and nlat != nlon:
+            raise ValueError("a path pairs latitude h with longitude h: lat_table and lon_table need the same length")
+        if chunk_points is not None and int(chunk_points) < 1:
+            raise ValueError("chunk_points must be >= 1 (or None)")
+        ncol = nlat if paired else nlat * nlon
+        ncomp = f.shape[0]
+        if out is None:
+            out = self.empty((ncomp, nd, ncol), np.float64)
+        else:
+            out = self.asdevice(out, np.float64)
+            if tuple(out.shape) != (ncomp, nd, ncol):
+                raise ValueError("out must be [C, D, H]")
+        pts = self.empty((nd, ncol, 3), np.float64) if want_points else None
+        miss = check(self.lib.mm_sample_columns_gll(self.handle, int(shape_order), gp.ptr, nelem, f.ptr, ncomp, lat.ptr,
+                                                    nlat, lon.ptr, nlon, 1 if paired else 0, rad.ptr, nd,
+                                                    int(nelem_to_search), float(tolerance), float(fill_value),
+                                                    int(chunk_points or 0), out.ptr, pts.ptr if pts else None),
+                     "mm_sample_columns_gll")
+        if want_points:
+            return out, int(miss), pts
+        return out, int(miss)
+
     def interpolate_hex8(self, nodes, connectivity, points, fields, nelem_to_search=20, want_operator=False,
                          out=None):
         """The whole hot path of reference scripts/cli.py:62-100 on resident arrays.

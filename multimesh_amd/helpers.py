@@ -28,6 +28,8 @@ MM_OK = 0
 MM_KNN_MAX_K = 64
 MM_FP_EXACT = 0
 MM_FP_TOL = 1
+MM_SAMPLE_CHUNK_BYTES = 1 << 34   # include/multimesh_hip.h: per-target scratch of one automatic chunk of mm_sample_columns_gll
+MM_SAMPLE_STAGE_BYTES = 96
 STAGES = ("centroid", "knn_build", "knn_query", "locate", "gather", "knn_cell", "locate_pass0")
 
 #: every symbol include/multimesh_hip.h declares (tests check the library exports all of them)
@@ -41,7 +43,7 @@ EXPORTED_SYMBOLS = (
     "mm_scatter_elements", "mm_fluid_solid_fix", "mm_set_profiling", "mm_last_timings", "mm_set_lazy_lists", "mm_unique_points", "mm_locate_gll_bbox", "mm_interpolate_gll",
     "mm_set_fp_mode", "mm_get_fp_mode", "mm_last_locate_stats", "mm_last_knn_kernels",
     "mm_source_create", "mm_source_destroy", "mm_interpolate_hex8_on", "mm_points_to_elements", "mm_unique_points_any_order",
-    "mm_map_to_sphere", "mm_first_occurrence", "mm_sphere_ratio", "mm_scale_points",
+    "mm_map_to_sphere", "mm_first_occurrence", "mm_sphere_ratio", "mm_scale_points", "mm_sample_columns_gll",
 )
 
 
@@ -132,6 +134,9 @@ def load_lib():
     lib.mm_interpolate_gll.restype = C.c_int64
     lib.mm_interpolate_gll.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, C.c_int64,
                                        C.c_double, C.c_int, vp, vp, vp]
+    lib.mm_sample_columns_gll.restype = C.c_int64
+    lib.mm_sample_columns_gll.argtypes = [vp, C.c_int, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, C.c_int,
+                                          vp, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int64, vp, vp]
     lib.mm_locate_gll_bbox.restype = C.c_int64
     lib.mm_locate_gll_bbox.argtypes = [vp, C.c_int, C.c_int, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp, vp, vp]
     lib.mm_unique_points.restype = C.c_int64

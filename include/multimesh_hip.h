@@ -198,6 +198,41 @@ int64_t mm_sample_columns_gll(mm_context *ctx, int order, const double *gll_poin
                               int64_t nelem_to_search, double tolerance, double fill_value, int64_t chunk_points,
                               double *out_d, double *points_out_d);
 
+/* The TRANSPOSE of an interpolation operator: what comes back from the targets to the sources (a gradient on the event
+ * mesh -> the inversion mesh, so that <P m, g> = <m, P^T g>; P^T 1 = the coverage map).  Deterministic: the result is bit for
+ * bit np.add.at on zeros, i.e. the sequential loop, on every run (no float atomics, no reordering).
+ *   node form (the hex8 operator of mm_interpolate_hex8 / mm_locate_hex8, any ids int64[N][P], w f64[N][P]):
+ *     out[c][j] = (((+0.0 + t1) + t2) + ...), every t = w[n][p] * v[n][c] rounded as a product on its own (no fused
+ *     multiply-add), over all (n, p) with ids[n][p] == j in ascending flat index n * P + p.  Every row takes part, the all-zero
+ *     rows of failed targets included (as in NumPy); a destination nobody names is +0.0.
+ *     = np.add.at(out[c], ids, w * v[:, c, None]).
+ *   element form (the GLL operator of mm_interpolate_gll / mm_locate_gll: elem int64[N], coeffs f64[N][P]):
+ *     out[c][e][p] = the same sequential sum from +0.0 of coeffs[n][p] * v[n][c] over the n with elem[n] == e, ascending n;
+ *     rows with elem[n] == -1 are skipped (mm_gather_elem gives 0 for them).
+ * create groups the contributions by destination ONCE (a stable sort; it synchronises); apply then runs for any number of
+ * value sets -- the operator / gather split in the other direction.
+ *   create: every id must lie in [0, nsrc) (element form: [-1, nelem)), else MM_ERR_ARG (one reduction over the ids, as in
+ *     mm_first_occurrence).  P <= 128.  npoints * P (element form: npoints) must stay below 2^31 -- the sort carries the flat
+ *     index as a 32-bit payload and counts with 32-bit signed offsets -- else MM_ERR_UNSUPPORTED, decided from the sizes alone
+ *     before anything is allocated.  npoints == 0 is valid.
+ *     The node-form handle OWNS what it sorted: the weights in destination order (8 B), the target index of each (4 B) and
+ *     the row offsets (4 B per destination): 12 B per contribution, 0.97 GB + 0.04 GB for 10,077,696 hex8 targets onto as
+ *     many nodes; ids_d / w_d are not needed after create.  While it runs, create also holds the sort's two key and payload
+ *     buffers (24 B per contribution), freed before it returns.
+ *     The element-form handle owns only the target permutation (4 B per target) and the offsets (4 B per element); it
+ *     BORROWS coeffs_d, which must stay alive and unchanged until mm_transpose_destroy (as mm_source borrows its mesh).
+ *   apply: values_d f64[N][C] when values_point_major (what mm_gather returns by default), else f64[C][N];
+ *     out_d f64[C][nsrc] (the layout mm_gather reads fields in) or f64[C][nelem][P] (the layout mm_gather_elem reads);
+ *     every element of out_d is written.  ncomp == 0 is valid.  Timed as MM_STAGE_GATHER. */
+typedef struct mm_transpose mm_transpose;
+int mm_transpose_create_nodes(mm_context *ctx, const int64_t *ids_d, const double *w_d, int64_t npoints, int64_t P,
+                              int64_t nsrc, mm_transpose **out);
+int mm_transpose_create_elem(mm_context *ctx, const int64_t *elem_d, const double *coeffs_d, int64_t npoints, int64_t P,
+                             int64_t nelem, mm_transpose **out);
+int mm_transpose_apply(mm_context *ctx, const mm_transpose *op, const double *values_d, int64_t ncomp,
+                       int values_point_major, double *out_d);
+void mm_transpose_destroy(mm_context *ctx, mm_transpose *op);
+
 /* Unique points and the index array that rebuilds the input: np.unique(points, axis=0,
  * return_inverse=True) of reference utils.py:484-488 (get_unique_points, the pre-step of the GLL
  * target flows; scatter-back at components/interpolator.py:823).  points_d f64[npoints][dim];

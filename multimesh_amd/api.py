@@ -71,6 +71,30 @@ def apply_operator(mesh_a: HexMesh, enclosing_elem_node_indices, weights, params
     return ctx.gather(mesh_a.fields_matrix(params), enclosing_elem_node_indices, weights).numpy()
 
 
+def apply_operator_transpose(mesh_a: HexMesh, enclosing_elem_node_indices, weights, values, context=None):
+    """The transpose of :func:`apply_operator`: values f64[N, C] (or [N]) on the targets -> f64[C, npoint] on mesh A's
+    nodes, the layout of ``fields_matrix``.  ``np.add.at(out[c], enc, weights * values[:, c, None])`` bit for bit, the
+    same on every run; ``enc`` / ``weights`` as :func:`interpolate_operator` or :func:`load_stored_operator` return them."""
+    ctx = context or default_context()
+    op = ctx.transpose_nodes(np.ascontiguousarray(enclosing_elem_node_indices, dtype=np.int64), weights, mesh_a.npoint)
+    try:
+        return op.apply(values).numpy()
+    finally:
+        op.free()
+
+
+def apply_gll_operator_transpose(elements, coeffs, values, nelem, context=None):
+    """The transpose of ``np.sum(coeffs * field[elements], axis=1)``: values f64[N, C] (or [N]) on the targets ->
+    f64[C, nelem, P] on the source elements' nodes; targets without an element (-1) contribute nothing.  ``elements`` /
+    ``coeffs`` as :func:`get_element_weights` or :func:`load_stored_operator` return them."""
+    ctx = context or default_context()
+    op = ctx.transpose_elem(np.ascontiguousarray(elements, dtype=np.int64), coeffs, nelem)
+    try:
+        return op.apply(values).numpy()
+    finally:
+        op.free()
+
+
 def load_stored_operator(stored_array):
     """The reference's operator cache (interpolator.py:724-740): ``elements.npy`` + ``coeffs.npy`` in
     the ``stored_array`` directory.  Returns ``(elements, coeffs)`` or ``None`` when not (fully) there.

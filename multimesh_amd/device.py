@@ -142,6 +142,50 @@ class Source:
             pass
 
 
+class TransposedOperator:
+    """The transpose of an interpolation operator, grouped by destination once (mm_transpose_create_nodes / _elem) and
+    applied to any number of value sets: bit for bit ``np.add.at`` on zeros (include/multimesh_hip.h)."""
+
+    def __init__(self, ctx, handle, npoints, out_shape, keepalive):
+        self.ctx, self.handle, self.npoints = ctx, handle, int(npoints)
+        self.out_shape = tuple(int(s) for s in out_shape)   # one component: (nsrc,) or (nelem, P)
+        self._keepalive = keepalive                         # (the element form's coeffs are borrowed by the library)
+
+    def apply(self, values, point_major=True, out=None):
+        """values f64[N, C] (point_major; [N] = one component) or f64[C, N] -> f64[C, nsrc] / f64[C, nelem, P]."""
+        ctx = self.ctx
+        if not self.handle:
+            raise ValueError("the operator has been freed")
+        v = ctx.asdevice(values, np.float64)
+        if len(v.shape) == 1:
+            v = DeviceArray(ctx, v.ptr, (v.shape[0], 1) if point_major else (1, v.shape[0]), v.dtype, owner=False, keepalive=v)
+        if len(v.shape) != 2 or v.shape[0 if point_major else 1] != self.npoints:
+            raise ValueError("values must be [N, C] (point_major) or [C, N]")
+        ncomp = v.shape[1 if point_major else 0]
+        shape = (ncomp,) + self.out_shape
+        if out is None:
+            out = ctx.empty(shape, np.float64)
+        else:
+            out = ctx.asdevice(out, np.float64)
+            if out.shape != shape:
+                raise ValueError(f"out must be {shape}")
+        check(ctx.lib.mm_transpose_apply(ctx.handle, self.handle, v.ptr, ncomp, 1 if point_major else 0, out.ptr),
+              "mm_transpose_apply")
+        return out
+
+    def free(self):
+        if self.handle and self.ctx.handle:
+            self.ctx.lib.mm_transpose_destroy(self.ctx.handle, self.handle)
+        self.handle = None
+        self._keepalive = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Context:
     """One GPU + one HIP stream.  ``stream`` is a raw hipStream_t value (e.g.
     ``torch.cuda.current_stream().cuda_stream``); None = the device's default stream."""
@@ -346,6 +390,33 @@ class Context:
         check(self.lib.mm_gather_elem(self.handle, f.ptr, nelem, ncomp, el.ptr, co.ptr, n, P, out.ptr,
                                       1 if point_major else 0), "mm_gather_elem")
         return out
+
+    # ---- the transposes of gather / gather_elem ------------------------------------------------
+    def transpose_nodes(self, ids, weights, nsrc):
+        """Group the operator (ids int64[N, P], weights f64[N, P]) by source node: a :class:`TransposedOperator` whose
+        ``apply(values)`` is ``np.add.at(out[c], ids, weights * values[:, c, None])`` -> f64[C, nsrc]."""
+        idv = self.asdevice(ids, np.int64)
+        w = self.asdevice(weights, np.float64)
+        if idv.shape != w.shape or len(idv.shape) != 2:
+            raise ValueError("ids and weights must both be [N, P]")
+        n, p = idv.shape
+        h = C.c_void_p()
+        check(self.lib.mm_transpose_create_nodes(self.handle, idv.ptr, w.ptr, n, p, int(nsrc), C.byref(h)),
+              "mm_transpose_create_nodes")
+        return TransposedOperator(self, h.value, n, (int(nsrc),), None)   # (the handle owns its sorted copy)
+
+    def transpose_elem(self, elem, coeffs, nelem):
+        """Group the GLL operator (elem int64[N], coeffs f64[N, P]) by source element: ``apply(values)`` ->
+        f64[C, nelem, P], the sequential sums of ``coeffs[n] * values[n, c]`` per element; rows with elem -1 are skipped."""
+        el = self.asdevice(elem, np.int64)
+        co = self.asdevice(coeffs, np.float64)
+        if len(el.shape) != 1 or len(co.shape) != 2 or co.shape[0] != el.shape[0]:
+            raise ValueError("elem must be [N] and coeffs [N, P]")
+        n, p = co.shape
+        h = C.c_void_p()
+        check(self.lib.mm_transpose_create_elem(self.handle, el.ptr, co.ptr, n, p, int(nelem), C.byref(h)),
+              "mm_transpose_create_elem")
+        return TransposedOperator(self, h.value, n, (int(nelem), p), co)
 
     # ---- fused ---------------------------------------------------------------------------
     def interpolate_gll(self, shape_order, gll_points, points, element_nodal_fields, nelem_to_search=20,
@@ -663,4 +734,4 @@ def default_context(device=0):
     return _default[device]
 
 
-__all__ = ["Context", "DeviceArray", "KnnIndex", "default_context", "MultiMeshHipError"]
+__all__ = ["Context", "DeviceArray", "KnnIndex", "TransposedOperator", "default_context", "MultiMeshHipError"]

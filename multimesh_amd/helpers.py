@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = (
     "mm_set_fp_mode", "mm_get_fp_mode", "mm_last_locate_stats", "mm_last_knn_kernels",
     "mm_source_create", "mm_source_destroy", "mm_interpolate_hex8_on", "mm_points_to_elements", "mm_unique_points_any_order",
     "mm_map_to_sphere", "mm_first_occurrence", "mm_sphere_ratio", "mm_scale_points", "mm_sample_columns_gll",
+    "mm_transpose_create_nodes", "mm_transpose_create_elem", "mm_transpose_apply", "mm_transpose_destroy",
 )
 
 
@@ -161,6 +162,14 @@ def load_lib():
     lib.mm_sphere_ratio.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_double, vp]
     lib.mm_scale_points.restype = C.c_int
     lib.mm_scale_points.argtypes = [vp, vp, C.c_int64, vp, vp]
+    lib.mm_transpose_create_nodes.restype = C.c_int
+    lib.mm_transpose_create_nodes.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.POINTER(vp)]
+    lib.mm_transpose_create_elem.restype = C.c_int
+    lib.mm_transpose_create_elem.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.POINTER(vp)]
+    lib.mm_transpose_apply.restype = C.c_int
+    lib.mm_transpose_apply.argtypes = [vp, vp, vp, C.c_int64, C.c_int, vp]
+    lib.mm_transpose_destroy.restype = None
+    lib.mm_transpose_destroy.argtypes = [vp, vp]
     lib.mm_set_fp_mode.restype = C.c_int
     lib.mm_set_fp_mode.argtypes = [vp, C.c_int]
     lib.mm_get_fp_mode.restype = C.c_int

@@ -1,0 +1,144 @@
+"""CPU side of the operator transpose (mm_transpose_*): the NumPy statement in tests/transpose_cases.py IS the sequential
+loop of the definition, it agrees with scipy.sparse to the bound the term count gives, every ordering case of the GPU
+tests depends on the order of its rows' terms, and the library exports what the header declares."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import transpose_cases as T
+from multimesh_amd import helpers
+
+SYMBOLS = ("mm_transpose_create_nodes", "mm_transpose_create_elem", "mm_transpose_apply", "mm_transpose_destroy")
+EPS = 2.0 ** -52
+
+
+def _small_nodes(P, seed):
+    rng = np.random.default_rng(seed)
+    n, nsrc = 60, 17
+    ids = rng.integers(0, nsrc - 3, size=(n, P))          # three nodes nobody names
+    ids[rng.random(n) < 0.1] = 0                           # failed targets: all-zero rows (node 0, weight 0)
+    w = T.wide(rng, (n, P))
+    w[(ids == 0).all(axis=1)] = 0.0
+    return ids, w, T.wide(rng, (n, 3)), nsrc
+
+
+def _small_elem(P, seed):
+    rng = np.random.default_rng(seed)
+    n, nelem = 80, 9
+    elem = rng.integers(-1, nelem - 2, size=n)
+    return elem, T.wide(rng, (n, P)), T.wide(rng, (n, 3)), nelem
+
+
+@pytest.mark.parametrize("P", [1, 4, 8, 27])
+def test_add_at_is_the_flat_order_loop_nodes(P):
+    ids, w, v, nsrc = _small_nodes(P, 100 + P)
+    ref = T.transpose_nodes(ids, w, v, nsrc)
+    assert T.same_bits(ref, T.transpose_nodes_loop(ids, w, v, nsrc))
+    assert not np.signbit(ref[:, nsrc - 3:]).any() and not ref[:, nsrc - 3:].any()     # unnamed: +0.0
+
+
+@pytest.mark.parametrize("P", [4, 9, 27])
+def test_add_at_is_the_flat_order_loop_elem(P):
+    elem, co, v, nelem = _small_elem(P, 200 + P)
+    assert (elem == -1).any()
+    ref = T.transpose_elem(elem, co, v, nelem)
+    assert T.same_bits(ref, T.transpose_elem_loop(elem, co, v, nelem))
+    assert not np.signbit(ref[:, nelem - 2:]).any() and not ref[:, nelem - 2:].any()
+
+
+def _row_bound(rows, terms, nrows):
+    """n * 2^-52 * sum|t| per row: n terms added one after the other, each add with a relative error of at most 2^-53
+    on a partial sum that never exceeds sum|t| (the sparse product adds the same rounded products in another order, so
+    the two results are within twice the one-sided bound (n - 1) * 2^-53 * sum|t|)."""
+    count = np.bincount(rows, minlength=nrows)
+    mass = np.bincount(rows, weights=np.abs(terms), minlength=nrows)
+    return count * EPS * mass
+
+
+def test_agrees_with_scipy_sparse_nodes():
+    sp = pytest.importorskip("scipy.sparse")
+    for name in ("P8", "P27", "skewed"):
+        ids, w, nsrc = T.node_case(name)
+        n = len(ids)
+        v = T.case_values(name, n, 2)
+        A = sp.csr_matrix((w.ravel(), ids.ravel(), np.arange(0, ids.size + 1, ids.shape[1])), shape=(n, nsrc))
+        ref = T.transpose_nodes(ids, w, v, nsrc)
+        for c in range(2):
+            got = A.T @ v[:, c]
+            bound = _row_bound(ids.ravel(), (w * v[:, c, None]).ravel(), nsrc)
+            assert (np.abs(got - ref[c]) <= bound).all(), name
+
+
+def test_agrees_with_scipy_sparse_elem():
+    sp = pytest.importorskip("scipy.sparse")
+    elem, co, nelem = T.elem_case("P9")
+    n, P = co.shape
+    v = T.case_values("P9", n, 1)
+    found = np.flatnonzero(elem >= 0)
+    cols = (elem[found, None] * P + np.arange(P)[None, :]).ravel()
+    A = sp.csr_matrix((co[found].ravel(), cols, np.arange(0, cols.size + 1, P)), shape=(len(found), nelem * P))
+    got = (A.T @ v[found, 0]).reshape(nelem, P)
+    bound = _row_bound(cols, (co[found] * v[found, 0, None]).ravel(), nelem * P).reshape(nelem, P)
+    assert (np.abs(got - T.transpose_elem(elem, co, v, nelem)[0]) <= bound).all()
+
+
+@pytest.mark.parametrize("name", T.NODE_CASES)
+def test_node_cases_depend_on_the_order(name):
+    ids, w, nsrc = T.node_case(name)
+    v = T.case_values(name, len(ids), 1)
+    assert not T.same_bits(T.transpose_nodes(ids, w, v, nsrc), T.transpose_nodes_reversed(ids, w, v, nsrc))
+
+
+@pytest.mark.parametrize("name", T.ELEM_CASES)
+def test_elem_cases_depend_on_the_order(name):
+    elem, co, nelem = T.elem_case(name)
+    v = T.case_values(name, len(elem), 1)
+    assert not T.same_bits(T.transpose_elem(elem, co, v, nelem), T.transpose_elem_reversed(elem, co, v, nelem))
+
+
+@pytest.mark.parametrize("name", ["hex8_small", "hex8_hard_k20", "hex8_hard_k1"])
+def test_fixture_operators_depend_on_the_order(golden, name):
+    enc, w, nsrc = T.golden_operator(golden, name)
+    if name != "hex8_small":
+        assert (~w.any(axis=1)).any(), "the hard fixtures have failed, all-zero rows"
+    v = T.case_values(name, len(enc), 1)
+    assert not T.same_bits(T.transpose_nodes(enc, w, v, nsrc), T.transpose_nodes_reversed(enc, w, v, nsrc))
+
+
+def test_straddle_cases_hold_every_bin_edge():
+    for name in ("straddle_unsorted", "straddle_sorted", "straddle_reverse_sorted"):
+        ids, _, nsrc = T.node_case(name)
+        assert sorted(np.bincount(ids.ravel(), minlength=nsrc)) == sorted(T.STRADDLE_LENGTHS)
+    ids_s = T.node_case("straddle_sorted")[0].ravel()
+    ids_r = T.node_case("straddle_reverse_sorted")[0].ravel()
+    assert (np.diff(ids_s) >= 0).all() and (np.diff(ids_r) <= 0).all()
+    assert (np.diff(T.node_case("straddle_unsorted")[0].ravel()) < 0).any()
+    assert {T.LONG_ROW - 1, T.LONG_ROW, T.LONG_ROW + 1} <= set(T.STRADDLE_LENGTHS)
+    elem, _, nelem = T.elem_case("elem_straddle")
+    lengths = set(np.bincount(elem[elem >= 0], minlength=nelem))
+    assert all({g - 1, g, g + 1} <= lengths for g in T.ELEM_GROUPS) and (elem == -1).any()
+
+
+def test_library_exports_the_transpose_symbols():
+    import os
+    import re
+
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "multimesh_hip.h")).read()
+    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    lib = helpers.load_lib()
+    for name in SYMBOLS:
+        assert re.search(r"\b%s\s*\(" % name, header), f"{name} is not declared in the header"
+        assert name in helpers.EXPORTED_SYMBOLS
+        assert hasattr(lib, name), f"{name} missing from {lib._filename}"
+        assert getattr(lib, name).argtypes is not None, f"helpers.load_lib does not declare {name}"
+    assert lib.mm_transpose_apply.restype is C.c_int and lib.mm_transpose_destroy.restype is None
+
+
+def test_argument_validation_needs_no_gpu():
+    lib = helpers.load_lib()
+    h = C.c_void_p()
+    assert lib.mm_transpose_create_nodes(None, None, None, 0, 8, 0, C.byref(h)) == -1      # null ctx: MM_ERR_ARG
+    assert lib.mm_transpose_create_elem(None, None, None, 0, 8, 0, C.byref(h)) == -1
+    assert lib.mm_transpose_apply(None, None, None, 1, 1, None) == -1
+    lib.mm_transpose_destroy(None, None)                                                   # a null handle is a no-op

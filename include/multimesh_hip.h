@@ -233,6 +233,37 @@ int mm_transpose_apply(mm_context *ctx, const mm_transpose *op, const double *va
                        int values_point_major, double *out_d);
 void mm_transpose_destroy(mm_context *ctx, mm_transpose *op);
 
+/* The diagonal GLL MASS MATRIX of an element-nodal mesh, M[e][p] = w_p |det J_e(xi_p)|: the inner product of a
+ * spectral-element mesh is a^T M b, so that a density (a sensitivity kernel K with d chi = int K dm dV) goes from mesh to
+ * mesh as M_c K_c = P^T (M_f K_f), and int f dV = sum M f.  The reference has no counterpart (its mass matrix lives in Salvus).
+ *   gll_points_d f64[nelem][P][dim], P = (order+1)^dim, order 1, 2 or 4, dim 2 or 3, node p = i + m j + m^2 k with
+ *   m = order + 1 (the layout mm_locate_gll takes); deriv_d f64[m][m] with D[i][a] = l_a'(g_i) and weights_d f64[m], the GLL
+ *   rule's tables, made on the host (as the sine and cosine tables of mm_sample_columns_gll: the device then does only + and
+ *   *, and the result is stated bit for bit).  mass_d f64[nelem][P]; det_d f64[nelem][P] or NULL, the signed determinant.
+ * Every product is rounded on its own (no fused multiply-add), every sum starts from its first term and adds in ascending a:
+ *   J[0][c] = sum_a D[i][a] * X[a,j,k][c]    J[1][c] = sum_a D[j][a] * X[i,a,k][c]    J[2][c] = sum_a D[k][a] * X[i,j,a][c]
+ *   det3 = (J00*(J11*J22 - J12*J21) - J01*(J10*J22 - J12*J20)) + J02*(J10*J21 - J11*J20)          det2 = J00*J11 - J01*J10
+ *   mass = ((w_k * w_j) * w_i) * |det3|                                                    (2-D: (w_j * w_i) * |det2|)
+ * Returns the number of nodes whose determinant is not > 0 (zero, negative, NaN): positive for an inverted or collapsed
+ * element, every node for a left-handed mesh; or a negative MM_ERR_* (order, dim or a null table: MM_ERR_ARG, nothing is
+ * written).  nelem == 0 is valid.  Synchronises. */
+int64_t mm_gll_mass(mm_context *ctx, int order, int dim, const double *gll_points_d, int64_t nelem, const double *deriv_d,
+                    const double *weights_d, double *mass_d, double *det_d);
+
+/* The volume integral of ncomp fields, out_d[c] = sum_i mass_d[i] * fields_d[c][i] over n values (fields_d f64[ncomp][n];
+ * NULL with ncomp == 1: the sum of mass_d, the volume).  out_d f64[ncomp] on the device.  Deterministic: no float atomics, and
+ * the order of the sum is fixed by this definition, not by a launch shape.  With t[i] = mass[i] * field[i], a product rounded
+ * on its own (t[i] = mass[i] without fields), padded with +0.0 to whole chunks of 4096 values:
+ *   in a chunk, lane l of 256 adds t[l], t[l + 256], ... t[l + 3840] in that order, from the first;
+ *   the 256 lane sums are halved eight times, s[l] = s[l] + s[l + h] for h = 128, 64, ... 1; s[0] is the chunk's sum;
+ *   the chunk sums are summed by the same rule (as t, without fields) until one value is left.  n == 0 gives +0.0.
+ * Not synchronising (the result is on the device). */
+int mm_weighted_sum(mm_context *ctx, const double *mass_d, const double *fields_d, int64_t n, int64_t ncomp, double *out_d);
+
+/* out_d[c][i] = num_d[c][i] / den_d[i] for ncomp rows of n values: the last step of the mass-weighted adjoint,
+ * K_c = (P^T (M_f K_f)) / M_c.  IEEE division: a zero den_d[i] gives inf or NaN.  out_d may be num_d. */
+int mm_divide_rows(mm_context *ctx, const double *num_d, const double *den_d, int64_t n, int64_t ncomp, double *out_d);
+
 /* Unique points and the index array that rebuilds the input: np.unique(points, axis=0,
  * return_inverse=True) of reference utils.py:484-488 (get_unique_points, the pre-step of the GLL
  * target flows; scatter-back at components/interpolator.py:823).  points_d f64[npoints][dim];

@@ -1,0 +1,268 @@
+// A13 -- the diagonal GLL mass matrix of an element-nodal mesh, the volume integrals it gives, and the elementwise
+// quotient the mass-weighted adjoint ends in.  The inner product of two nodal fields of a spectral-element mesh is
+// a^T M b with M[e][p] = w_p |det J_e(xi_p)|; the transposes of mm_transpose.hip are adjoint in the plain dot product.
+//
+//   mm_gll_mass      : mass[e][p] = ((w_k * w_j) * w_i) * |det J|, det J from the tensor-line sums of the header
+//   mm_weighted_sum  : out[c] = sum_i mass[i] * field[c][i] in the fixed order of the header (chunks of 4096, 256 lanes)
+//   mm_divide_rows   : out[c][i] = num[c][i] / den[i]
+//
+// Bit parity with the NumPy statement (tests/mass_cases.py): the derivative matrix and the weights come from the host, so
+// the device does only + and *, every product rounded on its own (-ffp-contract=off), every sum from its first term in
+// ascending a.
+//
+// mm_gll_mass is a streaming kernel: 24 B read and 8 B written per node, ~110 flops.  A 256-thread block takes a TILE of
+// 256 / P whole elements (2 at P = 125, 9 at P = 27, 32 at P = 8), which are contiguous in memory: their coordinates go
+// into LDS by coalesced 8-byte loads (three per thread), then lane t of the block is node t of the tile and reads its
+// 3 m neighbours along the three tensor lines from LDS.  A lane is the same node (i, j, k) of every tile its block
+// takes, so its three rows of D and its weight product live in registers for the whole kernel (read once from a copy of
+// the tables in LDS).  Blocks stride over the tiles; the next tile's loads are issued before the current one is computed.
+#include "mm_common.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kWave = 64;
+constexpr i64 kMaxBlocks = 2048;   // 256 CUs x 8 resident blocks; blocks stride over the rest
+constexpr int kChunk = 4096;       // mm_weighted_sum: values per chunk (fixed by the definition, not a launch shape)
+
+constexpr int ipow(int b, int e) { return e == 0 ? 1 : b * ipow(b, e - 1); }
+
+template <int ORDER, int DIM>
+__global__ __launch_bounds__(kThreads) void gll_mass_kernel(const double *__restrict__ gp, i64 nelem,
+                                                            const double *__restrict__ deriv,
+                                                            const double *__restrict__ weights,
+                                                            double *__restrict__ mass, double *__restrict__ det_out,
+                                                            unsigned long long *__restrict__ nbad)
+{
+    constexpr int M = ORDER + 1;
+    constexpr int P = ipow(M, DIM);
+    constexpr int TILE = kThreads / P;            // elements per block and step
+    constexpr int TILE_DOUBLES = TILE * P * DIM;  // <= 768
+    constexpr int LOADS = (TILE_DOUBLES + kThreads - 1) / kThreads;
+    __shared__ double xs[TILE_DOUBLES];
+    __shared__ double tab[M * M + M];
+
+    const int tid = threadIdx.x;
+    if (tid < M * M) tab[tid] = deriv[tid];
+    else if (tid < M * M + M) tab[tid] = weights[tid - M * M];
+    __syncthreads();
+
+    // this lane's node of the tile
+    const bool node_lane = tid < TILE * P;
+    const int el = node_lane ? tid / P : 0;
+    const int p = node_lane ? tid - el * P : 0;
+    const int i = p % M, j = (p / M) % M, k = DIM == 3 ? p / (M * M) : 0;
+    double di[M], dj[M], dk[M];
+#pragma unroll
+    for (int a = 0; a < M; ++a) {
+        di[a] = tab[i * M + a];
+        dj[a] = tab[j * M + a];
+        dk[a] = tab[k * M + a];
+    }
+    const double wprod = DIM == 3 ? (tab[M * M + k] * tab[M * M + j]) * tab[M * M + i] : tab[M * M + j] * tab[M * M + i];
+    // LDS offsets (in doubles) of the first node of this lane's three tensor lines, and the lines' strides
+    const int base = el * P * DIM;
+    const int line_i = base + (p - i) * DIM;
+    const int line_j = base + (p - j * M) * DIM;
+    const int line_k = base + (p - k * M * M) * DIM;
+
+    const i64 ntiles = (nelem + TILE - 1) / TILE;
+    unsigned bad = 0;
+    double stage[LOADS];
+    i64 tile = blockIdx.x;
+    // valid doubles of a tile: the last one may hold fewer elements
+    auto tile_doubles = [&](i64 t) -> int {
+        const i64 left = nelem - t * TILE;
+        return (int)(left < TILE ? left : TILE) * P * DIM;
+    };
+    auto fetch = [&](i64 t) {
+        const int nd = tile_doubles(t);
+        const double *src = gp + t * (i64)TILE_DOUBLES;
+#pragma unroll
+        for (int r = 0; r < LOADS; ++r) {
+            const int idx = r * kThreads + tid;
+            stage[r] = idx < nd ? src[idx] : 0.0;
+        }
+    };
+    if (tile < ntiles) fetch(tile);
+    for (; tile < ntiles; tile += gridDim.x) {
+        __syncthreads();   // (the previous step's reads of xs are done)
+#pragma unroll
+        for (int r = 0; r < LOADS; ++r) {
+            const int idx = r * kThreads + tid;
+            if (idx < TILE_DOUBLES) xs[idx] = stage[r];
+        }
+        __syncthreads();
+        const int nd = tile_doubles(tile);
+        if (tile + gridDim.x < ntiles) fetch(tile + gridDim.x);
+        if (node_lane && base < nd) {
+            double J[3][3];
+#pragma unroll
+            for (int c = 0; c < DIM; ++c) {
+                J[0][c] = di[0] * xs[line_i + c];
+                J[1][c] = dj[0] * xs[line_j + c];
+                if constexpr (DIM == 3) J[2][c] = dk[0] * xs[line_k + c];
+            }
+#pragma unroll
+            for (int a = 1; a < M; ++a) {
+#pragma unroll
+                for (int c = 0; c < DIM; ++c) {
+                    J[0][c] = J[0][c] + di[a] * xs[line_i + a * DIM + c];
+                    J[1][c] = J[1][c] + dj[a] * xs[line_j + a * M * DIM + c];
+                    if constexpr (DIM == 3) J[2][c] = J[2][c] + dk[a] * xs[line_k + a * M * M * DIM + c];
+                }
+            }
+            double det;
+            if constexpr (DIM == 3) {
+                det = (J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) - J[0][1] * (J[1][0] * J[2][2] - J[1][2] * J[2][0])) +
+                      J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
+            } else {
+                det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
+            }
+            const i64 node = tile * (i64)(TILE * P) + tid;
+            mass[node] = wprod * fabs(det);
+            if (det_out) det_out[node] = det;
+            if (!(det > 0.0)) ++bad;
+        }
+    }
+    // integer counts: the order of the atomics does not reach the result
+    unsigned total = bad;
+#pragma unroll
+    for (int off = kWave / 2; off >= 1; off >>= 1) total += __shfl_down(total, off);
+    if ((tid & (kWave - 1)) == 0 && total != 0) atomicAdd(nbad, (unsigned long long)total);
+}
+
+template <int ORDER, int DIM>
+void launch_mass(mm_context *ctx, const double *gp, i64 nelem, const double *deriv, const double *weights, double *mass,
+                 double *det, unsigned long long *nbad)
+{
+    constexpr int TILE = kThreads / ipow(ORDER + 1, DIM);
+    const i64 ntiles = (nelem + TILE - 1) / TILE;
+    hipLaunchKernelGGL((gll_mass_kernel<ORDER, DIM>), dim3((unsigned)(ntiles < kMaxBlocks ? ntiles : kMaxBlocks)),
+                       dim3(kThreads), 0, ctx->stream, gp, nelem, deriv, weights, mass, det, nbad);
+}
+
+// ---- the weighted sum.  One block per chunk of kChunk values and component: lane l adds its 16 terms l, l + 256, ... in
+// that order, then the 256 lane sums are halved eight times (s[l] + s[l + h], h = 128 .. 1).  a: the weights (component
+// stride sa, 0 for a shared mass); f: the fields (nullable; component stride n).  partial[c * nchunks + chunk].
+__global__ __launch_bounds__(kThreads) void weighted_sum_kernel(const double *__restrict__ a, i64 sa,
+                                                                const double *__restrict__ f, i64 n,
+                                                                double *__restrict__ partial)
+{
+    __shared__ double s[kThreads];
+    const int tid = threadIdx.x;
+    const i64 c = blockIdx.y;
+    const i64 first = (i64)blockIdx.x * kChunk;
+    const double *ac = a + c * sa;
+    const double *fc = f ? f + c * n : nullptr;
+    double acc = 0.0;
+#pragma unroll
+    for (int r = 0; r < kChunk / kThreads; ++r) {
+        const i64 idx = first + r * kThreads + tid;
+        double t = 0.0;   // (the padding of the last chunk)
+        if (idx < n) t = fc ? ac[idx] * fc[idx] : ac[idx];
+        acc = r == 0 ? t : acc + t;
+    }
+    s[tid] = acc;
+    __syncthreads();
+#pragma unroll
+    for (int h = kThreads / 2; h >= 1; h >>= 1) {
+        if (tid < h) s[tid] = s[tid] + s[tid + h];
+        __syncthreads();
+    }
+    if (tid == 0) partial[c * gridDim.x + blockIdx.x] = s[0];
+}
+
+__global__ __launch_bounds__(kThreads) void divide_rows_kernel(const double *num, const double *__restrict__ den, i64 n,
+                                                               i64 ncomp, double *out)
+{
+    // (out may be num: each thread reads its value before writing it)
+    const i64 stride = (i64)gridDim.x * blockDim.x;
+    for (i64 idx = (i64)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += stride) {
+        const double d = den[idx];
+        for (i64 c = 0; c < ncomp; ++c) out[c * n + idx] = num[c * n + idx] / d;
+    }
+}
+
+i64 chunks_of(i64 n) { return n <= kChunk ? 1 : (n + kChunk - 1) / kChunk; }
+
+}  // namespace
+
+extern "C" int64_t mm_gll_mass(mm_context *ctx, int order, int dim, const double *gll_points_d, int64_t nelem,
+                               const double *deriv_d, const double *weights_d, double *mass_d, double *det_d)
+{
+    MM_REQUIRE(ctx != nullptr, "ctx is null");
+    MM_REQUIRE(order == 1 || order == 2 || order == 4, "order must be 1, 2 or 4");
+    MM_REQUIRE(dim == 2 || dim == 3, "dim must be 2 or 3");
+    MM_REQUIRE(nelem >= 0 && nelem < ((i64)1 << 48), "nelem out of range");
+    MM_REQUIRE(deriv_d != nullptr && weights_d != nullptr, "null table");
+    if (nelem == 0) return 0;
+    MM_REQUIRE(gll_points_d != nullptr && mass_d != nullptr, "null array");
+    MM_HIP_CHECK(hipSetDevice(ctx->device));
+    unsigned long long *nbad = (unsigned long long *)(ctx->d_counters + 2);
+    MM_HIP_CHECK(hipMemsetAsync(nbad, 0, sizeof(i64), ctx->stream));
+#define MM_MASS_CASE(O, D)                                                                              \
+    if (order == O && dim == D) launch_mass<O, D>(ctx, gll_points_d, nelem, deriv_d, weights_d, mass_d, det_d, nbad)
+    MM_MASS_CASE(1, 2);
+    MM_MASS_CASE(2, 2);
+    MM_MASS_CASE(4, 2);
+    MM_MASS_CASE(1, 3);
+    MM_MASS_CASE(2, 3);
+    MM_MASS_CASE(4, 3);
+#undef MM_MASS_CASE
+    MM_HIP_CHECK(hipGetLastError());
+    MM_HIP_CHECK(hipMemcpyAsync(ctx->h_counters + 2, nbad, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
+    MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return ctx->h_counters[2];
+}
+
+extern "C" int mm_weighted_sum(mm_context *ctx, const double *mass_d, const double *fields_d, int64_t n, int64_t ncomp,
+                               double *out_d)
+{
+    MM_REQUIRE(ctx != nullptr, "ctx is null");
+    MM_REQUIRE(n >= 0 && n < ((i64)1 << 42), "n out of range");
+    MM_REQUIRE(ncomp >= 0 && ncomp < 65536, "ncomp out of range");
+    MM_REQUIRE(fields_d != nullptr || ncomp <= 1, "without fields there is one sum");
+    if (ncomp == 0) return MM_OK;
+    MM_REQUIRE(out_d != nullptr && (mass_d != nullptr || n == 0), "null array");
+    MM_HIP_CHECK(hipSetDevice(ctx->device));
+    // the partial sums of every level but the last: level 0 has chunks_of(n) per component, level 1 chunks_of(that) ...
+    i64 level_n = chunks_of(n);
+    size_t need = 0;
+    for (i64 m = level_n; m > 1; m = chunks_of(m)) need += mm_round256((size_t)(m * ncomp) * sizeof(double));
+    if (need) {
+        const int rc = mm_scratch_begin(ctx, need);
+        if (rc != MM_OK) return rc;
+    }
+    const double *a = mass_d, *f = fields_d;
+    i64 sa = 0, count = n;
+    for (;;) {
+        const i64 nchunks = chunks_of(count);
+        double *dst = nchunks == 1 ? out_d : (double *)mm_scratch_take(ctx, (size_t)(nchunks * ncomp) * sizeof(double));
+        hipLaunchKernelGGL(weighted_sum_kernel, dim3((unsigned)nchunks, (unsigned)ncomp), dim3(kThreads), 0, ctx->stream, a,
+                           sa, f, count, dst);
+        if (nchunks == 1) break;
+        a = dst;          // the next level sums the chunk sums: no fields, one row per component
+        f = nullptr;
+        sa = nchunks;
+        count = nchunks;
+    }
+    MM_HIP_CHECK(hipGetLastError());
+    return MM_OK;
+}
+
+extern "C" int mm_divide_rows(mm_context *ctx, const double *num_d, const double *den_d, int64_t n, int64_t ncomp,
+                              double *out_d)
+{
+    MM_REQUIRE(ctx != nullptr, "ctx is null");
+    MM_REQUIRE(n >= 0 && ncomp >= 0, "negative size");
+    MM_REQUIRE(n < ((i64)1 << 48) && ncomp < (1 << 20), "size out of range");
+    if (n == 0 || ncomp == 0) return MM_OK;
+    MM_REQUIRE(num_d && den_d && out_d, "null array");
+    MM_HIP_CHECK(hipSetDevice(ctx->device));
+    const i64 blocks = (n + kThreads - 1) / kThreads;
+    hipLaunchKernelGGL(divide_rows_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(kThreads), 0, ctx->stream,
+                       num_d, den_d, n, ncomp, out_d);
+    MM_HIP_CHECK(hipGetLastError());
+    return MM_OK;
+}

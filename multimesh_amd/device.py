@@ -418,6 +418,58 @@ class Context:
               "mm_transpose_create_elem")
         return TransposedOperator(self, h.value, n, (int(nelem), p), co)
 
+    # ---- the GLL mass matrix and what it weights ----------------------------------------------
+    def gll_mass(self, shape_order, gll_points, want_det=False):
+        """The diagonal GLL mass matrix ``w_p |det J_e(xi_p)|`` of gll_points f64[E, (order+1)^dim, dim], orders 1, 2, 4
+        (``mm_gll_mass``: bit for bit the NumPy statement of include/multimesh_hip.h).  Returns (mass f64[E, P], n_bad)
+        or, with ``want_det``, (mass, n_bad, det f64[E, P]); ``n_bad`` counts the nodes whose determinant is not > 0."""
+        from .synth import gll_derivative_matrix, gll_weights_1d   # (ValueError for an order without tables)
+
+        deriv, weights = gll_derivative_matrix(shape_order), gll_weights_1d(shape_order)
+        gp = self.asdevice(gll_points, np.float64)
+        if len(gp.shape) != 3 or gp.shape[2] not in (2, 3) or gp.shape[1] != (shape_order + 1) ** gp.shape[2]:
+            raise ValueError("gll_points must be [nelem, (order+1)^dim, dim] with dim 2 or 3")
+        nelem, P, dim = gp.shape
+        mass = self.empty((nelem, P), np.float64)
+        det = self.empty((nelem, P), np.float64) if want_det else None
+        d_d, w_d = self.to_device(deriv), self.to_device(weights)
+        n_bad = check(self.lib.mm_gll_mass(self.handle, int(shape_order), dim, gp.ptr, nelem, d_d.ptr, w_d.ptr, mass.ptr,
+                                           det.ptr if det else None), "mm_gll_mass")
+        return (mass, int(n_bad), det) if want_det else (mass, int(n_bad))
+
+    def weighted_sum(self, mass, fields=None):
+        """``sum_i mass[i] * fields[c][i]`` -> f64[C] (NumPy), the volume integral of every field; ``fields=None``:
+        f64[1], the sum of ``mass``.  mass f64[E, P] (any shape), fields f64[C, E, P] or the shape of ``mass`` (one
+        field).  Deterministic, in the fixed order ``mm_weighted_sum`` states."""
+        m = self.asdevice(mass, np.float64)
+        ncomp, f = 1, None
+        if fields is not None:
+            f = self.asdevice(fields, np.float64)
+            if f.shape == m.shape:
+                ncomp = 1
+            elif f.shape[1:] == m.shape:
+                ncomp = f.shape[0]
+            else:
+                raise ValueError("fields must be [C, ...] over the shape of mass, or the shape of mass")
+        out = self.empty((ncomp,), np.float64)
+        check(self.lib.mm_weighted_sum(self.handle, m.ptr, f.ptr if f else None, m.size, ncomp, out.ptr), "mm_weighted_sum")
+        return out.numpy()
+
+    def divide_rows(self, num, den, out=None):
+        """``num[c] / den`` for num f64[C, ...] over den's shape (or the shape of den); ``out`` may be ``num``."""
+        a = self.asdevice(num, np.float64)
+        d = self.asdevice(den, np.float64)
+        if a.shape != d.shape and a.shape[1:] != d.shape:
+            raise ValueError("num must be [C, ...] over the shape of den, or the shape of den")
+        if out is None:
+            out = self.empty(a.shape, np.float64)
+        else:
+            out = self.asdevice(out, np.float64)
+            if out.shape != a.shape:
+                raise ValueError("out must have the shape of num")
+        check(self.lib.mm_divide_rows(self.handle, a.ptr, d.ptr, d.size, a.size // max(d.size, 1), out.ptr), "mm_divide_rows")
+        return out
+
     # ---- fused ---------------------------------------------------------------------------
     def interpolate_gll(self, shape_order, gll_points, points, element_nodal_fields, nelem_to_search=20,
                         tolerance=1.05, snap_to_nearest=False, want_operator=False, out=None):

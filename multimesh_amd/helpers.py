@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = (
     "mm_source_create", "mm_source_destroy", "mm_interpolate_hex8_on", "mm_points_to_elements", "mm_unique_points_any_order",
     "mm_map_to_sphere", "mm_first_occurrence", "mm_sphere_ratio", "mm_scale_points", "mm_sample_columns_gll",
     "mm_transpose_create_nodes", "mm_transpose_create_elem", "mm_transpose_apply", "mm_transpose_destroy",
+    "mm_gll_mass", "mm_weighted_sum", "mm_divide_rows",
 )
 
 
@@ -170,6 +171,12 @@ def load_lib():
     lib.mm_transpose_apply.argtypes = [vp, vp, vp, C.c_int64, C.c_int, vp]
     lib.mm_transpose_destroy.restype = None
     lib.mm_transpose_destroy.argtypes = [vp, vp]
+    lib.mm_gll_mass.restype = C.c_int64
+    lib.mm_gll_mass.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int64, vp, vp, vp, vp]
+    lib.mm_weighted_sum.restype = C.c_int
+    lib.mm_weighted_sum.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, vp]
+    lib.mm_divide_rows.restype = C.c_int
+    lib.mm_divide_rows.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, vp]
     lib.mm_set_fp_mode.restype = C.c_int
     lib.mm_set_fp_mode.argtypes = [vp, C.c_int]
     lib.mm_get_fp_mode.restype = C.c_int

@@ -13,6 +13,8 @@ column permutation the reference applies before calling the locator
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 
 # exodus hex8 corner offsets (di, dj, dk), nodes 0..7
@@ -115,6 +117,34 @@ def gll_nodes_1d(order: int) -> np.ndarray:
         a = np.sqrt(3.0 / 7.0)
         return np.array([-1.0, -a, 0.0, a, 1.0])
     raise ValueError("order must be 1, 2 or 4")
+
+
+def gll_weights_1d(order: int) -> np.ndarray:
+    """The weights of the GLL rule on :func:`gll_nodes_1d`, 2 / (N (N + 1) L_N(g)^2) as the rationals they are."""
+    if order == 1:
+        return np.array([1.0, 1.0])
+    if order == 2:
+        return np.array([1.0 / 3.0, 4.0 / 3.0, 1.0 / 3.0])
+    if order == 4:
+        return np.array([1.0 / 10.0, 49.0 / 90.0, 32.0 / 45.0, 49.0 / 90.0, 1.0 / 10.0])
+    raise ValueError("order must be 1, 2 or 4")
+
+
+def gll_derivative_matrix(order: int) -> np.ndarray:
+    """D[i][a] = l_a'(g_i), the derivative at GLL node i of the Lagrange polynomial of node a: off the diagonal
+    (L_N(g_i) / L_N(g_a)) / (g_i - g_a) with the Legendre polynomial L_N written out; the diagonal is minus the
+    (exactly rounded) sum of the rest of its row, so that D differentiates constants to zero."""
+    g = gll_nodes_1d(order)
+    legendre = {1: lambda x: x, 2: lambda x: (3.0 * x * x - 1.0) / 2.0,
+                4: lambda x: (35.0 * x ** 4 - 30.0 * x * x + 3.0) / 8.0}[order](g)
+    m = order + 1
+    D = np.zeros((m, m))
+    for i in range(m):
+        for a in range(m):
+            if a != i:
+                D[i, a] = (legendre[i] / legendre[a]) / (g[i] - g[a])
+        D[i, i] = 0.0 - math.fsum(D[i, a] for a in range(m) if a != i)
+    return D
 
 
 def gll_mesh(n: int, order: int, seed: int = 1, jitter: float = 0.2, dim: int = 3):

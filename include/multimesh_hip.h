@@ -264,6 +264,68 @@ int mm_weighted_sum(mm_context *ctx, const double *mass_d, const double *fields_
  * K_c = (P^T (M_f K_f)) / M_c.  IEEE division: a zero den_d[i] gives inf or NaN.  out_d may be num_d. */
 int mm_divide_rows(mm_context *ctx, const double *num_d, const double *den_d, int64_t n, int64_t ncomp, double *out_d);
 
+/* The STIFFNESS OPERATOR of an element-nodal GLL mesh, applied matrix-free: y[c][e][.] = K_e u[c][e][.] with
+ *   K_e[p][q] = sum_n mass_n (G_n grad phi_p(xi_n)) . kappa_n (G_n grad phi_q(xi_n)),   G_n = J_e(xi_n)^-1, mass_n = w_n |det J|,
+ * the weak form of -div(kappa grad u) with natural boundaries, element by element and NOT assembled: u^T y summed over the
+ * mesh is the roughness int grad u . kappa grad u dV, and M + tau A^T K A (A = the gather from unique nodes) is the matrix of
+ * a backward-Euler diffusion step.  kappa = kappa_h (1 - r r^T) + kappa_r r r^T with r = x / |x| the unit radius at the node
+ * when `anisotropic` (3-D only), else kappa_h.  Each kappa is its scalar argument times an optional element-nodal array
+ * f64[nelem][P] (NULL = 1).  The reference has no counterpart.
+ *   gll_points_d, order, dim, deriv_d, weights_d, the node numbering p = i + m j + m^2 k: as mm_gll_mass.
+ *   u_d, y_d f64[ncomp][nelem][P], two different arrays.
+ * Every product is rounded on its own, every sum starts from its first term and adds in ascending a.  At node (i, j, k):
+ *   J, det3 / det2                      : as mm_gll_mass, from the coordinates
+ *   rdet = 1 / det                      : the one division
+ *   G[0][0] = (J11*J22 - J12*J21)*rdet   G[0][1] = (J02*J21 - J01*J22)*rdet   G[0][2] = (J01*J12 - J02*J11)*rdet
+ *   G[1][0] = (J12*J20 - J10*J22)*rdet   G[1][1] = (J00*J22 - J02*J20)*rdet   G[1][2] = (J02*J10 - J00*J12)*rdet
+ *   G[2][0] = (J10*J21 - J11*J20)*rdet   G[2][1] = (J01*J20 - J00*J21)*rdet   G[2][2] = (J00*J11 - J01*J10)*rdet
+ *     (2-D: G[0][0] = J11*rdet, G[0][1] = (-J01)*rdet, G[1][0] = (-J10)*rdet, G[1][1] = J00*rdet)
+ *   mass = ((w_k * w_j) * w_i) * |det|  (2-D: (w_j * w_i) * |det|)
+ *   kh = kappa_h * kappa_h_d[n] (kappa_h without the array), kr likewise
+ *   g[0] = sum_a D[i][a] * u[a,j,k]     g[1] = sum_a D[j][a] * u[i,a,k]     g[2] = sum_a D[k][a] * u[i,j,a]
+ *   gr[c] = (G[c][0]*g[0] + G[c][1]*g[1]) + G[c][2]*g[2]                                    (2-D: the first two terms)
+ *   isotropic:   F[c] = (mass * kh) * gr[c]
+ *   anisotropic: rn = sqrt((x*x + y*y) + z*z),  rh[c] = x[c] / rn (0 where rn == 0),  s = (rh[0]*gr[0] + rh[1]*gr[1]) + rh[2]*gr[2],
+ *                F[c] = mass * (kh * gr[c] + ((kr - kh) * s) * rh[c])
+ *   f[d] = (G[0][d]*F[0] + G[1][d]*F[1]) + G[2][d]*F[2]                                     (2-D: the first two terms)
+ *   y = (sum_a D[a][i] * f[0][a,j,k] + sum_a D[a][j] * f[1][i,a,k]) + sum_a D[a][k] * f[2][i,j,a]
+ * Returns MM_OK or a negative MM_ERR_*; MM_ERR_ARG (nothing is written) for an order or dim without tables, a null table or
+ * array, anisotropic with dim 2, kappa_r_d without anisotropic, u_d == y_d.  nelem == 0 and ncomp == 0 are valid.  Not
+ * synchronising. */
+int mm_gll_diffusion_apply(mm_context *ctx, int order, int dim, const double *gll_points_d, int64_t nelem,
+                           const double *deriv_d, const double *weights_d, const double *u_d, int64_t ncomp, double kappa_h,
+                           const double *kappa_h_d, int anisotropic, double kappa_r, const double *kappa_r_d, double *y_d);
+
+/* The streaming kernels of a preconditioned conjugate-gradient loop over ncomp independent systems of n unknowns each
+ * (vectors f64[ncomp][n]), whose scalars never leave the device.  state_d f64[ncomp][8] holds, per system, the slots below:
+ * the dots are written into MM_PCG_RZ, MM_PCG_PAP and MM_PCG_BB by mm_weighted_sum (one call per system with ncomp = 1).
+ *   mm_pcg_combine:   out[c][i] = mass[i] * p[c][i] + tau * kp[c][i]; kp_d NULL: mass[i] * p[c][i]; mass_d NULL: tau * kp[c][i].
+ *   mm_pcg_scalars:   MM_PCG_PHASE_START: every system active, RZ_OLD = ALPHA = BETA = 0.
+ *                     MM_PCG_PHASE_BETA (after RZ = r^T z): an active system with sqrt(RZ) <= rtol * sqrt(BB) becomes inactive
+ *                       for good; BETA = RZ / RZ_OLD (0 in the first iteration and for inactive systems); RZ_OLD = RZ.
+ *                     MM_PCG_PHASE_ALPHA (after PAP = p^T A p): ALPHA = RZ_OLD / PAP (0 for inactive systems).
+ *                     *nactive_d (nullable) = the number of active systems: the one number the host reads per iteration.
+ *   mm_pcg_direction: p[c] = z[c] + BETA[c] * p[c] for active systems; the others are not touched.
+ *   mm_pcg_advance:   x[c] = x[c] + ALPHA[c] * p[c] and r[c] = r[c] - ALPHA[c] * ap[c] for active systems.
+ * MM_ERR_ARG (nothing is written) for a null ctx or array, a negative size, an unknown phase or a negative rtol.  Not
+ * synchronising. */
+#define MM_PCG_RZ 0
+#define MM_PCG_RZ_OLD 1
+#define MM_PCG_PAP 2
+#define MM_PCG_BB 3
+#define MM_PCG_ALPHA 4
+#define MM_PCG_BETA 5
+#define MM_PCG_ACTIVE 6
+#define MM_PCG_PHASE_START 0
+#define MM_PCG_PHASE_BETA 1
+#define MM_PCG_PHASE_ALPHA 2
+int mm_pcg_combine(mm_context *ctx, const double *mass_d, const double *p_d, double tau, const double *kp_d, int64_t n,
+                   int64_t ncomp, double *out_d);
+int mm_pcg_scalars(mm_context *ctx, double *state_d, int64_t ncomp, int phase, double rtol, int64_t *nactive_d);
+int mm_pcg_direction(mm_context *ctx, const double *state_d, const double *z_d, int64_t n, int64_t ncomp, double *p_d);
+int mm_pcg_advance(mm_context *ctx, const double *state_d, const double *p_d, const double *ap_d, int64_t n, int64_t ncomp,
+                   double *x_d, double *r_d);
+
 /* Unique points and the index array that rebuilds the input: np.unique(points, axis=0,
  * return_inverse=True) of reference utils.py:484-488 (get_unique_points, the pre-step of the GLL
  * target flows; scatter-back at components/interpolator.py:823).  points_d f64[npoints][dim];

@@ -22,7 +22,8 @@ Regular grids: :func:`extract_regular_grid` (reference api.py:600-642), :func:`e
 :func:`extract_cross_section` (what plot_depth_slice / plot_cross_section sample), targets generated on the device.
 Beyond the reference: the operator transposes, and the GLL mass matrix with what it weights -- :func:`gll_mass_matrix`,
 :func:`hex8_mass_matrix`, :func:`integrate`, :func:`assemble_gll`, :func:`apply_gll_operator_adjoint`,
-:func:`apply_operator_adjoint`.
+:func:`apply_operator_adjoint`; and the stiffness operator with the smoothing it gives -- :func:`gll_stiffness_apply`,
+:func:`gll_roughness`, :func:`smooth_gll`.
 """
 from __future__ import annotations
 
@@ -605,6 +606,143 @@ def apply_operator_adjoint(mesh_a: HexMesh, enclosing_elem_node_indices, weights
     finally:
         op.free()
     return ctx.divide_rows(rhs, _hex8_mass(mesh_a, ctx), out=rhs).numpy()
+
+
+# ---- diffusion: the stiffness operator of a GLL mesh and the smoothing it gives (include/multimesh_hip.h,
+# mm_gll_diffusion_apply).  The reference has no counterpart: its smoothing lives in Salvus.
+def _element_fields(mesh, params, shape):
+    """f64[C, E, P] from names of element-nodal fields or an array [C, E, P] / [E, P]."""
+    if isinstance(params, str):
+        params = [params]
+    if isinstance(params, (list, tuple)) and all(isinstance(p, str) for p in params):
+        if not params:
+            return np.zeros((0,) + tuple(shape))
+        fields = np.stack([np.asarray(mesh.element_nodal_fields[p], dtype=np.float64) for p in params])
+    else:
+        fields = np.asarray(params, dtype=np.float64)
+        if fields.ndim == 2:
+            fields = fields[None]
+    if fields.ndim != 3 or fields.shape[1:] != tuple(shape):
+        raise ValueError(f"params must name element-nodal fields or be an array [C, E, P] / [E, P] over {tuple(shape)}")
+    return np.ascontiguousarray(fields)
+
+
+def _sigma_lengths(sigma, shape, dim):
+    """sigma -> (lateral, radial or None), each a float or f64[E, P]: validated, nothing squared yet."""
+    def one(x, name):
+        x = np.asarray(x, dtype=np.float64)
+        if x.ndim != 0 and x.shape != tuple(shape):
+            raise ValueError(f"{name} must be a number or an element-nodal array {tuple(shape)}, not of shape {x.shape}")
+        if np.isnan(x).any() or np.isinf(x).any() or (x < 0).any():
+            raise ValueError(f"{name} must be finite and >= 0")
+        return float(x) if x.ndim == 0 else np.ascontiguousarray(x)
+
+    if isinstance(sigma, (tuple, list)):
+        if len(sigma) != 2:
+            raise ValueError("sigma must be a length, an element-nodal array, or a pair (lateral, radial) of either")
+        if dim != 3:
+            raise ValueError("a (lateral, radial) pair needs a 3-D mesh: in 2-D there is no radial direction to split off")
+        return one(sigma[0], "sigma[0]"), one(sigma[1], "sigma[1]")
+    return one(sigma, "sigma"), None
+
+
+def _all_zero(lengths):
+    return all(x is None or not np.any(x) for x in lengths)
+
+
+def _diffusion(ctx, pts, order, lengths):
+    lat, rad = lengths
+    return ctx.diffusion(order, pts, lat * lat, None if rad is None else rad * rad)
+
+
+def gll_stiffness_apply(mesh, values, sigma=None, context=None):
+    """``K_e u`` per element (not assembled) of a :class:`GllMesh` or a Salvus mesh -> f64[C, E, P]: the weak Laplacian
+    ``K_e[p][q] = int grad phi_p . kappa grad phi_q dV`` by GLL quadrature, applied matrix-free (``mm_gll_diffusion_apply``,
+    bit for bit the statement of include/multimesh_hip.h).  ``values``: names of element-nodal fields or an array
+    [C, E, P] / [E, P].  ``sigma``: None for kappa = 1, else as :func:`smooth_gll` takes it (kappa = sigma^2)."""
+    ctx = context or default_context()
+    pts, order = _gll_points_order(mesh)
+    synth.gll_derivative_matrix(order)                                            # (ValueError for an order without tables)
+    u = _element_fields(mesh, values, pts.shape[:2])
+    lengths = (1.0, None) if sigma is None else _sigma_lengths(sigma, pts.shape[:2], pts.shape[2])
+    op = _diffusion(ctx, pts, order, lengths)
+    try:
+        return op.apply(u).numpy()
+    finally:
+        op.free()
+
+
+def gll_roughness(mesh, params, sigma=None, context=None):
+    """``u^T K u = int grad u . kappa grad u dV`` for every parameter -> f64[C], the roughness a regularisation term
+    penalises; summed on the device in the fixed order of ``mm_weighted_sum``.  Arguments as :func:`gll_stiffness_apply`."""
+    ctx = context or default_context()
+    pts, order = _gll_points_order(mesh)
+    synth.gll_derivative_matrix(order)
+    u = _element_fields(mesh, params, pts.shape[:2])
+    lengths = (1.0, None) if sigma is None else _sigma_lengths(sigma, pts.shape[:2], pts.shape[2])
+    op = _diffusion(ctx, pts, order, lengths)
+    try:
+        return op.roughness(u)
+    finally:
+        op.free()
+
+
+def smooth_gll(mesh, params, sigma, steps=4, rtol=1e-10, max_iter=2000, layers=None, layer_ids=None, context=None):
+    """Element-nodal fields of a :class:`GllMesh` or a Salvus mesh smoothed by diffusion on the device -> f64[C, E, P].
+
+    Smoothing with a Gaussian of standard deviation ``sigma`` is diffusion to the time ``sigma^2 / 2``; it is taken in
+    ``steps`` backward-Euler steps ``(M + tau K) u_new = M u_old`` with ``tau = 1 / (2 steps)``, ``M`` the assembled GLL
+    mass (:func:`gll_mass_matrix`) and ``K`` the assembled stiffness operator with ``kappa = sigma^2``
+    (:func:`gll_stiffness_apply`), under natural boundary conditions: constants are kept and ``sum(M u)`` is conserved.
+    A mode of eigenvalue ``lam`` is scaled by ``(1 + sigma^2 lam / (2 steps))^-steps``, which tends to the Gaussian's
+    ``exp(-sigma^2 lam / 2)`` as ``steps`` grows: more steps, a truer Gaussian, at proportionally more work.
+
+    ``sigma``: a length in the mesh's units -- a number, an element-nodal array [E, P], or a pair ``(lateral, radial)`` of
+    either for a 3-D Earth mesh (``(L, 0)`` smooths along the spherical shells only).  ``params``: names of element-nodal
+    fields, or an array [C, E, P] / [E, P].  Copies of a shared node that differ are first reduced to their mass-weighted
+    mean (which keeps ``sum(M u)``); the copies of a node in the result hold identical bits.  Every step is solved by
+    conjugate gradients preconditioned with ``M``, all components together, each stopped when
+    ``sqrt(r^T M^-1 r) <= rtol * ||u_old||_M``, which bounds its error by ``||u - u*||_M <= rtol ||u_old||_M``; a step that
+    needs more than ``max_iter`` iterations raises ``RuntimeError``.  ``sigma = 0`` returns the node-averaged input.
+
+    ``layers`` (anything :func:`assess_layers` takes; ``layer_ids`` etc. default as in :func:`integrate`): each selected
+    layer's elements are smoothed as a mesh of their own -- nothing diffuses across a layer boundary -- and all other
+    elements are returned unchanged."""
+    ctx = context or default_context()
+    pts, order = _gll_points_order(mesh)
+    synth.gll_derivative_matrix(order)                                            # (ValueError for an order without tables)
+    fields = _element_fields(mesh, params, pts.shape[:2])
+    lengths = _sigma_lengths(sigma, pts.shape[:2], pts.shape[2])
+    if int(steps) < 1 or int(max_iter) < 1 or not 0.0 < float(rtol) < 1.0:
+        raise ValueError("need steps >= 1, max_iter >= 1 and 0 < rtol < 1")
+
+    def run(sub_pts, sub_fields, sub_lengths):
+        op = _diffusion(ctx, sub_pts, order, sub_lengths)
+        try:
+            return op.smooth(sub_fields, steps=0 if _all_zero(sub_lengths) else int(steps), rtol=rtol,
+                             max_iter=max_iter).numpy()
+        finally:
+            op.free()
+
+    if layers is None:
+        return run(pts, fields, lengths)
+    elemental = getattr(mesh, "elemental_fields", {})
+    if layer_ids is None:
+        if "layer" not in elemental:
+            raise ValueError("layers= needs layer_ids (the mesh has no `layer` elemental field)")
+        layer_ids = elemental["layer"]
+    moho_idx = _layer_metadata(mesh)["moho_idx"] if hasattr(mesh, "global_strings") else None
+    picked = assess_layers(layer_ids, layers, fluid=elemental.get("fluid"), moho_idx=moho_idx)
+    ids = np.asarray(layer_ids).astype(int)
+    if ids.shape != (pts.shape[0],):
+        raise ValueError("layer_ids must hold one layer number per element")
+    out = fields.copy()
+    for layer in picked:
+        mask = ids == layer
+        if mask.any():
+            sub = tuple(x if x is None or np.ndim(x) == 0 else np.ascontiguousarray(x[mask]) for x in lengths)
+            out[:, mask] = run(np.ascontiguousarray(pts[mask]), np.ascontiguousarray(fields[:, mask]), sub)
+    return out
 
 
 def assess_layers(layer_ids, layers, fluid=None, moho_idx=None):

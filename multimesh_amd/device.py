@@ -14,6 +14,7 @@ import ctypes as C
 
 import numpy as np
 
+from . import helpers as H
 from .helpers import MM_FP_EXACT, MM_FP_TOL, MM_KNN_MAX_K, STAGES, MultiMeshHipError, check, load_lib
 
 # MM_KNN_RAN_* in bit order
@@ -178,6 +179,189 @@ class TransposedOperator:
             self.ctx.lib.mm_transpose_destroy(self.ctx.handle, self.handle)
         self.handle = None
         self._keepalive = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class Diffusion:
+    """The stiffness operator ``K`` of an element-nodal GLL mesh with its diffusivity (``mm_gll_diffusion_apply``), and the
+    backward-Euler diffusion steps ``(M + tau K) u_new = M u_old`` on the assembled space that smooth a field with it.
+    What depends on the mesh alone -- the tables, the scatter-sum over shared nodes, the inverse index, the assembled mass
+    -- is built once (the assembly on the first :meth:`smooth`) and reused over steps, components and calls."""
+
+    def __init__(self, ctx, order, gll_points, kappa_h, kappa_r, tables):
+        self.ctx, self.order = ctx, int(order)
+        self.gp = gll_points                                    # device f64[E, P, dim]
+        self.nelem, self.P, self.dim = gll_points.shape
+        self.kappa_h, self.kappa_r = kappa_h, kappa_r           # (scalar, device array or None); kappa_r None: isotropic
+        self._deriv, self._weights = tables
+        self._asm = None
+        self.last_iterations = []                               # of the last smooth(): [steps][C] PCG iterations
+
+    # ---- K u ------------------------------------------------------------------------------
+    def _apply(self, u_ptr, ncomp, y_ptr):
+        kh_s, kh_a = self.kappa_h
+        kr_s, kr_a = self.kappa_r if self.kappa_r is not None else (0.0, None)
+        check(self.ctx.lib.mm_gll_diffusion_apply(self.ctx.handle, self.order, self.dim, self.gp.ptr, self.nelem,
+                                                  self._deriv.ptr, self._weights.ptr, u_ptr, ncomp, float(kh_s),
+                                                  kh_a.ptr if kh_a else None, 1 if self.kappa_r is not None else 0,
+                                                  float(kr_s), kr_a.ptr if kr_a else None, y_ptr),
+              "mm_gll_diffusion_apply")
+
+    def _fields(self, values):
+        v = self.ctx.asdevice(values, np.float64)
+        if v.shape == (self.nelem, self.P):
+            v = DeviceArray(self.ctx, v.ptr, (1,) + v.shape, v.dtype, owner=False, keepalive=v)
+        if len(v.shape) != 3 or v.shape[1:] != (self.nelem, self.P):
+            raise ValueError("values must be [C, E, P] (or [E, P]) over gll_points [E, P, dim]")
+        return v
+
+    def apply(self, u, out=None):
+        """``K_e u`` per element, not assembled: u f64[C, E, P] (or [E, P]) -> f64[C, E, P]."""
+        if self.gp is None:
+            raise ValueError("the operator has been freed")
+        v = self._fields(u)
+        if out is None:
+            out = self.ctx.empty(v.shape, np.float64)
+        else:
+            out = self.ctx.asdevice(out, np.float64)
+            if out.shape != v.shape or out.ptr == v.ptr:
+                raise ValueError("out must be another array of the shape of u")
+        self._apply(v.ptr, v.shape[0], out.ptr)
+        return out
+
+    def roughness(self, u):
+        """``u^T K u`` = ``int grad u . kappa grad u dV`` per component -> f64[C] (NumPy), in the fixed order of
+        ``mm_weighted_sum`` with ``u`` in the mass slot."""
+        ctx = self.ctx
+        v = self._fields(u)
+        y = self.apply(v)
+        n, ncomp = self.nelem * self.P, v.shape[0]
+        out = ctx.empty((ncomp,), np.float64)
+        for c in range(ncomp):
+            check(ctx.lib.mm_weighted_sum(ctx.handle, v.ptr + 8 * c * n, y.ptr + 8 * c * n, n, 1, out.ptr + 8 * c),
+                  "mm_weighted_sum")
+        return out.numpy()
+
+    # ---- the assembled space ------------------------------------------------------------------
+    def _assembly(self):
+        if self._asm is None:
+            ctx = self.ctx
+            n = self.nelem * self.P
+            flat = DeviceArray(ctx, self.gp.ptr, (n, self.dim), np.float64, owner=False, keepalive=self.gp)
+            uniq, inv = ctx.unique_points(flat, ordered=False)
+            nu = uniq.shape[0]
+            inverse = DeviceArray(ctx, inv.ptr, (n, 1), np.int64, owner=False, keepalive=inv)
+            ones = ctx.to_device(np.ones((n, 1)))
+            op = ctx.transpose_nodes(inverse, ones, nu)
+            elem_mass, _ = ctx.gll_mass(self.order, self.gp)
+            mass = op.apply(DeviceArray(ctx, elem_mass.ptr, (1, n), np.float64, owner=False, keepalive=elem_mass),
+                            point_major=False)                  # [1, U]: the assembled mass
+            self._asm = dict(op=op, inverse=inverse, ones=ones, elem_mass=elem_mass, mass=mass, n=n, nu=nu)
+        return self._asm
+
+    def _gather(self, x, ncomp, out):
+        """unique nodes [C, U] -> every copy [C, N]"""
+        a, ctx = self._asm, self.ctx
+        check(ctx.lib.mm_gather(ctx.handle, x.ptr, a["nu"], ncomp, a["inverse"].ptr, a["ones"].ptr, a["n"], 1, out.ptr, 0),
+              "mm_gather")
+
+    def _combine(self, mass, p, tau, kp, n, ncomp, out):
+        ctx = self.ctx
+        check(ctx.lib.mm_pcg_combine(ctx.handle, mass.ptr if mass else None, p.ptr if p else None, float(tau),
+                                     kp.ptr if kp else None, n, ncomp, out.ptr), "mm_pcg_combine")
+
+    def _dots(self, a, b, n, ncomp, state, slot):
+        ctx = self.ctx
+        for c in range(ncomp):
+            check(ctx.lib.mm_weighted_sum(ctx.handle, a.ptr + 8 * c * n, b.ptr + 8 * c * n, n, 1,
+                                          state.ptr + 8 * (c * H.MM_PCG_STATE + slot)), "mm_weighted_sum")
+
+    def smooth(self, values, steps=4, rtol=1e-10, max_iter=2000):
+        """``steps`` backward-Euler steps of ``tau = 1 / (2 steps)`` each: ``(M + tau K) u_new = M u_old`` on the unique
+        nodes, by conjugate gradients preconditioned with ``M`` and stopped, per component, when
+        ``sqrt(r^T M^-1 r) <= rtol * sqrt(b^T M^-1 b)``; so ``||u - u*||_M <= rtol ||u_old||_M`` per step.  values
+        f64[C, E, P] (or [E, P]); copies of a shared node that differ are first reduced to their mass-weighted mean.
+        Returns f64[C, E, P] on the device, copies of a node bit-identical.  ``steps=0`` returns the node-averaged input.
+        Raises ``RuntimeError`` when a step needs more than ``max_iter`` iterations.  ``last_iterations[step][c]``: the
+        iterations every component took."""
+        if self.gp is None:
+            raise ValueError("the operator has been freed")
+        steps, max_iter, rtol = int(steps), int(max_iter), float(rtol)
+        if steps < 0 or max_iter < 1 or not 0.0 < rtol < 1.0:
+            raise ValueError("need steps >= 0, max_iter >= 1 and 0 < rtol < 1")
+        ctx, lib = self.ctx, self.ctx.lib
+        v = self._fields(values)
+        ncomp = v.shape[0]
+        a = self._assembly()
+        n, nu, op, mass = a["n"], a["nu"], a["op"], a["mass"]
+        ve = ctx.empty((ncomp, n), np.float64)                  # element-nodal work array
+        ye = ctx.empty((ncomp, n), np.float64)
+        self._combine(a["elem_mass"], v, 0.0, None, n, ncomp, ve)
+        x = op.apply(ve, point_major=False)                     # [C, U]
+        check(lib.mm_divide_rows(ctx.handle, x.ptr, mass.ptr, nu, ncomp, x.ptr), "mm_divide_rows")
+        self.last_iterations = []
+        if steps and ncomp and n:
+            tau = 1.0 / (2.0 * steps)
+            r, z, ap, kp = (ctx.empty((ncomp, nu), np.float64) for _ in range(4))
+            p = ctx.zeros((ncomp, nu), np.float64)
+            state = ctx.zeros((ncomp, H.MM_PCG_STATE), np.float64)
+            nactive = ctx.zeros((1,), np.int64)
+
+            def stiffness(src):                                 # kp = A^T K_e A src
+                self._gather(src, ncomp, ve)
+                self._apply(ve.ptr, ncomp, ye.ptr)
+                op.apply(ye, point_major=False, out=kp)
+
+            for _ in range(steps):
+                check(lib.mm_pcg_scalars(ctx.handle, state.ptr, ncomp, H.MM_PCG_PHASE_START, rtol, None), "mm_pcg_scalars")
+                self._combine(mass, x, 0.0, None, nu, ncomp, ap)            # b = M u_old
+                self._dots(ap, x, nu, ncomp, state, H.MM_PCG_BB)            # b^T M^-1 b = ||u_old||_M^2
+                stiffness(x)
+                self._combine(None, None, -tau, kp, nu, ncomp, r)           # r = b - (M + tau K) u_old
+                done_at = [None] * ncomp
+                left = ncomp
+                for it in range(max_iter + 1):
+                    check(lib.mm_divide_rows(ctx.handle, r.ptr, mass.ptr, nu, ncomp, z.ptr), "mm_divide_rows")
+                    self._dots(r, z, nu, ncomp, state, H.MM_PCG_RZ)
+                    check(lib.mm_pcg_scalars(ctx.handle, state.ptr, ncomp, H.MM_PCG_PHASE_BETA, rtol, nactive.ptr),
+                          "mm_pcg_scalars")
+                    now = int(nactive.numpy()[0])                           # the one number read back per iteration
+                    if now != left:
+                        active = state.numpy()[:, H.MM_PCG_ACTIVE]
+                        for c in range(ncomp):
+                            if done_at[c] is None and active[c] == 0.0:
+                                done_at[c] = it
+                        left = now
+                    if now == 0:
+                        break
+                    if it == max_iter:
+                        raise RuntimeError(f"smooth: {now} of {ncomp} components did not reach rtol = {rtol} within "
+                                           f"{max_iter} iterations of a diffusion step")
+                    check(lib.mm_pcg_direction(ctx.handle, state.ptr, z.ptr, nu, ncomp, p.ptr), "mm_pcg_direction")
+                    stiffness(p)
+                    self._combine(mass, p, tau, kp, nu, ncomp, ap)
+                    self._dots(p, ap, nu, ncomp, state, H.MM_PCG_PAP)
+                    check(lib.mm_pcg_scalars(ctx.handle, state.ptr, ncomp, H.MM_PCG_PHASE_ALPHA, rtol, None),
+                          "mm_pcg_scalars")
+                    check(lib.mm_pcg_advance(ctx.handle, state.ptr, p.ptr, ap.ptr, nu, ncomp, x.ptr, r.ptr), "mm_pcg_advance")
+                self.last_iterations.append(done_at)
+        out = ctx.empty((ncomp, self.nelem, self.P), np.float64)
+        if n and ncomp:
+            self._gather(x, ncomp, out)
+        ctx.synchronize()                                       # (the work arrays are released when this returns)
+        return out
+
+    def free(self):
+        if self._asm is not None:
+            self._asm["op"].free()
+        self._asm = None
+        self.gp = None
+        self.kappa_h, self.kappa_r = (1.0, None), None
 
     def __del__(self):
         try:
@@ -469,6 +653,40 @@ class Context:
                 raise ValueError("out must have the shape of num")
         check(self.lib.mm_divide_rows(self.handle, a.ptr, d.ptr, d.size, a.size // max(d.size, 1), out.ptr), "mm_divide_rows")
         return out
+
+    # ---- diffusion: the stiffness operator and the smoothing it gives -------------------------------
+    def diffusion(self, shape_order, gll_points, kappa_h=1.0, kappa_r=None):
+        """A :class:`Diffusion` over gll_points f64[E, (order+1)^dim, dim], orders 1, 2, 4: ``apply(u)`` is the bare
+        ``K u``, ``smooth(values, ...)`` the diffusion steps.  ``kappa_h`` / ``kappa_r``: the lateral and the radial
+        diffusivity, each a number or an element-nodal array f64[E, P]; ``kappa_r=None``: isotropic (``kappa_h`` in every
+        direction; the only choice in 2-D).  A scalar is passed to the kernel as a scalar, never made an array."""
+        from .synth import gll_derivative_matrix, gll_weights_1d   # (ValueError for an order without tables)
+
+        deriv, weights = gll_derivative_matrix(shape_order), gll_weights_1d(shape_order)
+        gp = self.asdevice(gll_points, np.float64)
+        if len(gp.shape) != 3 or gp.shape[2] not in (2, 3) or gp.shape[1] != (shape_order + 1) ** gp.shape[2]:
+            raise ValueError("gll_points must be [nelem, (order+1)^dim, dim] with dim 2 or 3")
+        if kappa_r is not None and gp.shape[2] != 3:
+            raise ValueError("a radial diffusivity needs a 3-D mesh")
+
+        def kappa(k, name):
+            if isinstance(k, (DeviceArray,)) or (hasattr(k, "data_ptr") and hasattr(k, "shape")):
+                arr = self.asdevice(k, np.float64)
+                if arr.shape != gp.shape[:2]:
+                    raise ValueError(f"{name} must be a number or an array [E, P]")
+                return 1.0, arr
+            k = np.asarray(k, dtype=np.float64)
+            if not np.isfinite(k).all() or (k < 0).any():
+                raise ValueError(f"{name} must be finite and >= 0")
+            if k.ndim == 0:
+                return float(k), None
+            if k.shape != gp.shape[:2]:
+                raise ValueError(f"{name} must be a number or an array [E, P]")
+            return 1.0, self.to_device(k)
+
+        return Diffusion(self, shape_order, gp, kappa(kappa_h, "kappa_h"),
+                         None if kappa_r is None else kappa(kappa_r, "kappa_r"),
+                         (self.to_device(deriv), self.to_device(weights)))
 
     # ---- fused ---------------------------------------------------------------------------
     def interpolate_gll(self, shape_order, gll_points, points, element_nodal_fields, nelem_to_search=20,
@@ -786,4 +1004,4 @@ def default_context(device=0):
     return _default[device]
 
 
-__all__ = ["Context", "DeviceArray", "KnnIndex", "TransposedOperator", "default_context", "MultiMeshHipError"]
+__all__ = ["Context", "DeviceArray", "Diffusion", "KnnIndex", "TransposedOperator", "default_context", "MultiMeshHipError"]

@@ -30,6 +30,10 @@ MM_FP_EXACT = 0
 MM_FP_TOL = 1
 MM_SAMPLE_CHUNK_BYTES = 1 << 34   # include/multimesh_hip.h: per-target scratch of one automatic chunk of mm_sample_columns_gll
 MM_SAMPLE_STAGE_BYTES = 96
+# include/multimesh_hip.h: slots of the PCG state block (8 doubles per system) and the phases of mm_pcg_scalars
+MM_PCG_STATE = 8
+MM_PCG_RZ, MM_PCG_RZ_OLD, MM_PCG_PAP, MM_PCG_BB, MM_PCG_ALPHA, MM_PCG_BETA, MM_PCG_ACTIVE = range(7)
+MM_PCG_PHASE_START, MM_PCG_PHASE_BETA, MM_PCG_PHASE_ALPHA = range(3)
 STAGES = ("centroid", "knn_build", "knn_query", "locate", "gather", "knn_cell", "locate_pass0")
 
 #: every symbol include/multimesh_hip.h declares (tests check the library exports all of them)
@@ -46,6 +50,7 @@ EXPORTED_SYMBOLS = (
     "mm_map_to_sphere", "mm_first_occurrence", "mm_sphere_ratio", "mm_scale_points", "mm_sample_columns_gll",
     "mm_transpose_create_nodes", "mm_transpose_create_elem", "mm_transpose_apply", "mm_transpose_destroy",
     "mm_gll_mass", "mm_weighted_sum", "mm_divide_rows",
+    "mm_gll_diffusion_apply", "mm_pcg_combine", "mm_pcg_scalars", "mm_pcg_direction", "mm_pcg_advance",
 )
 
 
@@ -177,6 +182,17 @@ def load_lib():
     lib.mm_weighted_sum.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, vp]
     lib.mm_divide_rows.restype = C.c_int
     lib.mm_divide_rows.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, vp]
+    lib.mm_gll_diffusion_apply.restype = C.c_int
+    lib.mm_gll_diffusion_apply.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int64, vp, vp, vp, C.c_int64, C.c_double, vp, C.c_int,
+                                           C.c_double, vp, vp]
+    lib.mm_pcg_combine.restype = C.c_int
+    lib.mm_pcg_combine.argtypes = [vp, vp, vp, C.c_double, vp, C.c_int64, C.c_int64, vp]
+    lib.mm_pcg_scalars.restype = C.c_int
+    lib.mm_pcg_scalars.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_double, vp]
+    lib.mm_pcg_direction.restype = C.c_int
+    lib.mm_pcg_direction.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, vp]
+    lib.mm_pcg_advance.restype = C.c_int
+    lib.mm_pcg_advance.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, vp, vp]
     lib.mm_set_fp_mode.restype = C.c_int
     lib.mm_set_fp_mode.argtypes = [vp, C.c_int]
     lib.mm_get_fp_mode.restype = C.c_int

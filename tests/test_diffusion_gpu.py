@@ -1,0 +1,399 @@
+"""The GLL stiffness operator and the diffusion smoothing on the GPU.  mm_gll_diffusion_apply is compared BIT for bit with
+its NumPy statement (tests/diffusion_cases.py); api.smooth_gll is compared with a sparse direct solve of the statement's
+matrices within the bound its stopping rule gives:
+
+  CG on (M + tau K) u = M u_old, preconditioned with M, stops at sqrt(r^T M^-1 r) <= rtol * ||u_old||_M.  K >= 0, so
+  M + tau K >= M and ||u - u*||_M <= ||r||_(M^-1) <= rtol ||u_old||_M.  A step maps an earlier error through
+  (M + tau K)^-1 M, whose M-norm is <= 1, and ||u_old||_M <= ||f||_M at every step: after `steps` steps
+  ||u - u*||_M <= steps * rtol * ||f||_M.
+
+A 256-thread block of the kernel takes a tile of 256 // P whole elements (mass_cases.tile_elems): the element counts
+below include one below, exactly and one above a tile, and counts that leave a broken last tile."""
+import math
+
+import numpy as np
+import pytest
+
+import diffusion_cases as DC
+import mass_cases as M
+import transpose_cases as T
+from multimesh_amd import api, helpers, synth
+from multimesh_amd.api import GllMesh
+from multimesh_amd.device import Context
+
+pytestmark = pytest.mark.gpu
+
+EPS = M.EPS
+MM_ERR_ARG = -1
+SHAPES = [(1, 2), (2, 2), (4, 2), (1, 3), (2, 3), (4, 3)]
+MODES = ("iso", "arrays", "aniso", "aniso_arrays")
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    with Context(0) as c:
+        yield c
+
+
+def _tables(order):
+    _, w, D = api.gll_quadrature(order)
+    return w, D
+
+
+def _kappas(rng, mode, shape):
+    """Keyword arguments of diffusion_cases.apply for a mode."""
+    if mode == "iso":
+        return dict(kh=0.7)
+    if mode == "arrays":
+        return dict(kh=1.3, kh_array=rng.uniform(0.5, 2.0, size=shape))
+    if mode == "aniso":
+        return dict(kh=2.0, kr=0.5)
+    return dict(kh=1.1, kh_array=rng.uniform(0.5, 2.0, size=shape), kr=0.9, kr_array=rng.uniform(0.0, 2.0, size=shape))
+
+
+def _raw_apply(ctx, gp, order, u, kh=1.0, kh_array=None, kr=None, kr_array=None):
+    """Straight at the ABI: scalars stay scalars, arrays are optional."""
+    w, D = _tables(order)
+    E, P, dim = gp.shape
+    ncomp = u.shape[0]
+    gp_d, u_d, w_d, D_d = ctx.to_device(gp), ctx.to_device(u), ctx.to_device(w), ctx.to_device(D)
+    kh_d = ctx.to_device(kh_array) if kh_array is not None else None
+    kr_d = ctx.to_device(kr_array) if kr_array is not None else None
+    y = ctx.empty((ncomp, E, P), np.float64)
+    rc = ctx.lib.mm_gll_diffusion_apply(ctx.handle, order, dim, gp_d.ptr, E, D_d.ptr, w_d.ptr, u_d.ptr, ncomp, float(kh),
+                                        kh_d.ptr if kh_d else None, 0 if kr is None else 1, 0.0 if kr is None else float(kr),
+                                        kr_d.ptr if kr_d else None, y.ptr)
+    assert rc == 0, helpers.load_lib().mm_last_error()
+    return y.numpy()
+
+
+def _check_apply(ctx, gp, order, ncomp, mode, seed, what):
+    rng = np.random.default_rng(seed)
+    kappa = _kappas(rng, mode, gp.shape[:2])
+    u = T.wide(rng, (ncomp,) + gp.shape[:2])
+    w, D = _tables(order)
+    ref = DC.apply(gp, order, w, D, u, **kappa)
+    got = _raw_apply(ctx, gp, order, u, **kappa)
+    assert got.shape == ref.shape
+    assert M.same_bits(got, ref), (what, mode, ncomp, int((got != ref).sum()), got.size)
+
+
+# ---------------------------------------------------------------------------------------------- mm_gll_diffusion_apply
+@pytest.mark.parametrize("ncomp", [1, 3])
+@pytest.mark.parametrize("order,dim", SHAPES)
+def test_apply_bit_for_bit_on_gll_meshes(ctx, order, dim, ncomp):
+    gp = synth.gll_mesh(9 if dim == 3 else 30, order, seed=3, dim=dim)
+    for mode in MODES if dim == 3 else MODES[:2]:
+        _check_apply(ctx, gp, order, ncomp, mode, order * 100 + dim * 10 + ncomp, (order, dim))
+
+
+@pytest.mark.parametrize("order,dim", SHAPES)
+def test_apply_element_counts_around_a_tile(ctx, order, dim):
+    tile = M.tile_elems(order, dim)
+    gp = synth.gll_mesh(13 if dim == 3 else 48, order, seed=5, dim=dim)        # 1728 / 2209 elements
+    for nelem in (0, 1, tile - 1, tile, tile + 1, 3 * tile + max(tile // 2, 1), len(gp)):
+        if 0 <= nelem <= len(gp):
+            sub = np.ascontiguousarray(gp[:nelem])
+            _check_apply(ctx, sub, order, 2, "arrays", nelem, (order, dim, nelem))
+            if dim == 3:
+                _check_apply(ctx, sub, order, 1, "aniso", nelem, (order, dim, nelem))
+
+
+@pytest.mark.parametrize("order", [1, 2, 4])
+def test_apply_at_earth_scale(ctx, order):
+    chunk = synth.earth_chunk(order, nlat=5, nlon=6, ellipticity=3.3e-3, topography=3e-4)
+    for mode in MODES:
+        for ncomp in (1, 3):
+            _check_apply(ctx, chunk["points"], order, ncomp, mode, order, ("earth", order))
+
+
+def test_apply_through_the_context_and_the_api(ctx):
+    gp = synth.gll_mesh(6, 4, seed=3)
+    w, D = _tables(4)
+    rng = np.random.default_rng(4)
+    u = T.wide(rng, (2,) + gp.shape[:2])
+    sig_l, sig_r = rng.uniform(0.5, 2.0, size=gp.shape[:2]), 0.25
+    ref = DC.apply(gp, 4, w, D, u, kh=1.0, kh_array=sig_l * sig_l, kr=sig_r * sig_r)
+    op = ctx.diffusion(4, gp, kappa_h=sig_l * sig_l, kappa_r=sig_r * sig_r)
+    assert M.same_bits(op.apply(u).numpy(), ref)
+    assert M.same_bits(op.apply(u[0]).numpy(), ref[:1])                           # [E, P]: one field
+    op.free()
+    with pytest.raises(ValueError):
+        op.apply(u)
+    mesh = GllMesh(gp, 4, {"a": u[0], "b": u[1]})
+    assert M.same_bits(api.gll_stiffness_apply(mesh, ["a", "b"], sigma=(sig_l, sig_r), context=ctx), ref)
+    plain = DC.apply(gp, 4, w, D, u)
+    assert M.same_bits(api.gll_stiffness_apply(mesh, u, context=ctx), plain)
+    rough = api.gll_roughness(mesh, ["a", "b"], context=ctx)
+    assert M.same_bits(rough, np.array([M.weighted_sum(u[c], plain[c][None])[0] for c in range(2)]))
+    # the roughness of a linear field is the energy of its gradient (tests/test_diffusion.py)
+    a = np.array([1.5, -2.0, 3.0])
+    lin = gp @ a
+    mass = api.gll_mass_matrix(mesh, context=ctx)
+    got = api.gll_roughness(mesh, lin, context=ctx)[0]
+    assert abs(got - float(a @ a) * math.fsum(mass.ravel())) <= M.term_bound(lin * DC.apply(gp, 4, w, D, lin)[0])
+
+
+# ---------------------------------------------------------------------------------------------- smooth_gll
+def _cube(n, order):
+    gp = DC.welded(synth.gll_mesh(n, order, seed=3))
+    assert DC.unique_nodes(gp)[0] == (order * (n - 1) + 1) ** 3
+    return gp
+
+
+def _fields(gp, seed):
+    rng = np.random.default_rng(seed)
+    nu, inv = DC.unique_nodes(gp)
+    noisy = np.cos(np.pi * gp[..., 0]) * np.cos(2.0 * np.pi * gp[..., 1]) + 0.3 * rng.normal(size=nu)[inv].reshape(gp.shape[:2])
+    return np.stack([noisy, np.full(gp.shape[:2], 3.25), gp[..., 2] ** 2 - 0.1 * rng.normal(size=nu)[inv].reshape(gp.shape[:2])])
+
+
+def _per_node(values, inv, nu):
+    """Element-nodal [E, P] -> unique nodes [U]; asserts that the copies of every node hold identical bits."""
+    flat = np.ascontiguousarray(values).reshape(-1)
+    out = np.empty(nu)
+    out[inv] = flat
+    assert M.same_bits(out[inv], flat), "copies of a shared node differ"
+    return out
+
+
+def _check_against_direct(got, gp, order, f, steps, rtol, what, **kappa):
+    w, D = _tables(order)
+    star, u0, Mu, inv = DC.smooth_direct(gp, order, w, D, f, steps, **kappa)
+    me = M.mass(gp, order, w, D)[0].reshape(-1)
+    for c in range(f.shape[0]):
+        u = _per_node(got[c], inv, len(Mu))
+        d = u - star[c]
+        fnorm = DC.m_norm(Mu, u0[c])
+        bound = steps * rtol * fnorm
+        err2 = math.fsum(Mu * d * d)
+        print(f"{what} component {c}: ||u - u*||_M = {math.sqrt(err2):.3e}, bound {bound:.3e}")
+        assert err2 <= bound * bound + M.term_bound(Mu * d * d), (what, c)
+        # the integral: Cauchy-Schwarz on the same bound, plus the rounding of forming the two sums
+        total, before = math.fsum(Mu * u), math.fsum(me * f[c].reshape(-1))
+        slack = M.term_bound(Mu * u) + M.term_bound(me * f[c].reshape(-1))
+        assert abs(total - before) <= math.sqrt(math.fsum(Mu)) * bound + slack, (what, c)
+    return star, u0, Mu, inv
+
+
+@pytest.mark.parametrize("order,width", [(2, 1.0), (2, 2.0), (4, 1.0), (4, 2.0)])
+def test_smooth_against_the_direct_solve(ctx, order, width):
+    n, steps, rtol = 5, 4, 1e-10
+    gp = _cube(n, order)
+    f = _fields(gp, order)
+    sigma = width / (n - 1)
+    mesh = GllMesh(gp, order)
+    got = api.smooth_gll(mesh, f, sigma, steps=steps, rtol=rtol, context=ctx)
+    assert got.shape == f.shape
+    _, _, Mu, inv = _check_against_direct(got, gp, order, f, steps, rtol, f"order {order} sigma {width} h", kh=sigma * sigma)
+    # constants come back unchanged within that bound
+    const = _per_node(got[1], inv, len(Mu)) - 3.25
+    assert DC.m_norm(Mu, const) <= steps * rtol * DC.m_norm(Mu, np.full(len(Mu), 3.25))
+    # the same bits on a second call and from a second context
+    assert M.same_bits(api.smooth_gll(mesh, f, sigma, steps=steps, rtol=rtol, context=ctx), got)
+    with Context(0) as other:
+        assert M.same_bits(api.smooth_gll(mesh, f, sigma, steps=steps, rtol=rtol, context=other), got)
+    # the components advance together but each on its own: one of them alone gives the same bits
+    assert M.same_bits(api.smooth_gll(mesh, f[2], sigma, steps=steps, rtol=rtol, context=ctx)[0], got[2])
+
+
+def test_smooth_reports_iterations_and_reuses_the_mesh(ctx):
+    gp = _cube(5, 2)
+    f = _fields(gp, 9)
+    op = ctx.diffusion(2, gp, kappa_h=0.25 ** 2)
+    first = op.smooth(f, steps=3).numpy()
+    its = op.last_iterations
+    assert len(its) == 3 and all(len(step) == 3 for step in its)
+    assert all(step[1] == 0 for step in its), "a constant has no residual: no iteration"
+    assert all(1 <= step[c] <= 500 for step in its for c in (0, 2))
+    print("iterations per step and component:", its)
+    assert M.same_bits(op.smooth(f, steps=3).numpy(), first)                      # the assembly is reused
+    # steps = 0: the node-averaged input, a quotient of two sums of at most 8 copies each
+    assert (np.abs(op.smooth(f, steps=0).numpy() - f) <= 32 * EPS * np.abs(f).max()).all()
+    op.free()
+
+
+def test_copies_that_differ_are_averaged_by_mass(ctx):
+    gp = _cube(4, 2)
+    rng = np.random.default_rng(3)
+    f = rng.normal(size=(1,) + gp.shape[:2])                                      # copies of a node disagree
+    w, D = _tables(2)
+    got = api.smooth_gll(GllMesh(gp, 2), f, 0.0, context=ctx)                     # sigma = 0: no solve
+    _, u0, Mu, inv = DC.smooth_direct(gp, 2, w, D, f, 0)
+    u = _per_node(got[0], inv, len(Mu))
+    # a quotient of two sums of at most 8 copies each
+    assert (np.abs(u - u0[0]) <= 32 * EPS * np.abs(f).max()).all()
+    steps, rtol = 2, 1e-10
+    got = api.smooth_gll(GllMesh(gp, 2), f, 0.2, steps=steps, rtol=rtol, context=ctx)
+    _check_against_direct(got, gp, 2, f, steps, rtol, "differing copies", kh=0.2 ** 2)
+
+
+def test_smooth_with_sigma_arrays_in_2d(ctx):
+    gp = DC.welded(synth.gll_mesh(9, 4, seed=3, dim=2))
+    assert DC.unique_nodes(gp)[0] == 33 ** 2
+    rng = np.random.default_rng(6)
+    nu, inv = DC.unique_nodes(gp)
+    f = (np.cos(np.pi * gp[..., 0]) + 0.2 * rng.normal(size=nu)[inv].reshape(gp.shape[:2]))[None]
+    sigma = (0.1 + 0.2 * gp[..., 1])                                              # grows across the square
+    steps, rtol = 3, 1e-9
+    got = api.smooth_gll(GllMesh(gp, 4, {"f": f[0]}), ["f"], sigma, steps=steps, rtol=rtol, context=ctx)
+    _check_against_direct(got, gp, 4, f, steps, rtol, "2-D sigma array", kh=1.0, kh_array=sigma * sigma)
+
+
+# ---------------------------------------------------------------------------------------------- anisotropy and layers
+def _chunk():
+    chunk = synth.earth_chunk(2, nlat=3, nlon=3)
+    gp = chunk["points"]
+    rng = np.random.default_rng(12)
+    nu, inv = DC.unique_nodes(gp)
+    assert nu == 7 * 7 * 9                                                        # copies of a node are bit-identical
+    r = np.linalg.norm(gp, axis=-1)
+    f = (np.cos((r - 5_971_000.0) / 400_000.0 * np.pi) + 0.3 * rng.normal(size=nu)[inv].reshape(gp.shape[:2]))[None]
+    return chunk, gp, f
+
+
+def test_lateral_smoothing_on_an_earth_chunk(ctx):
+    chunk, gp, f = _chunk()
+    mesh = GllMesh(gp, 2)
+    L, steps, rtol = 300_000.0, 2, 1e-10
+    lateral = api.smooth_gll(mesh, f, (L, 0.0), steps=steps, rtol=rtol, context=ctx)
+    arrays = api.smooth_gll(mesh, f, (np.full(gp.shape[:2], L), np.zeros(gp.shape[:2])), steps=steps, rtol=rtol, context=ctx)
+    assert M.same_bits(lateral, arrays)
+    iso = api.smooth_gll(mesh, f, L, steps=steps, rtol=rtol, context=ctx)
+    assert not M.same_bits(lateral, iso)
+    _check_against_direct(lateral, gp, 2, f, steps, rtol, "lateral", kh=L * L, kr=0.0)
+    _check_against_direct(iso, gp, 2, f, steps, rtol, "isotropic", kh=L * L)
+
+
+def test_layers_are_smoothed_by_themselves(ctx):
+    chunk, gp, f = _chunk()
+    mesh = GllMesh(gp, 2)
+    L, steps = 200_000.0, 2
+    got = api.smooth_gll(mesh, f, L, steps=steps, layers=[2], layer_ids=chunk["layer"], context=ctx)
+    lower, upper = chunk["layer"] == 1, chunk["layer"] == 2
+    assert lower.any() and upper.any()
+    assert M.same_bits(got[:, lower], f[:, lower])
+    alone = api.smooth_gll(GllMesh(np.ascontiguousarray(gp[upper]), 2), np.ascontiguousarray(f[:, upper]), L, steps=steps,
+                           context=ctx)
+    assert M.same_bits(got[:, upper], alone)
+    whole = api.smooth_gll(mesh, f, L, steps=steps, context=ctx)
+    assert not M.same_bits(whole[:, upper], alone)                                # nothing crossed the boundary above
+    both = api.smooth_gll(mesh, f, L, steps=steps, layers="all", layer_ids=chunk["layer"], context=ctx)
+    assert M.same_bits(both[:, upper], alone) and not M.same_bits(both[:, lower], f[:, lower])
+    with pytest.raises(ValueError):
+        api.smooth_gll(mesh, f, L, layers=[2], context=ctx)                       # no layer_ids anywhere
+
+
+# ---------------------------------------------------------------------------------------------- error paths
+def test_error_paths(ctx):
+    lib = helpers.load_lib()
+    gp = synth.gll_mesh(4, 2, seed=3)
+    gp2 = synth.gll_mesh(5, 2, seed=3, dim=2)
+    mesh = GllMesh(gp, 2, {"f": np.cos(gp[..., 0])})
+    for sigma in (-1.0, float("nan"), np.ones(5), (1.0, -2.0)):
+        with pytest.raises(ValueError):
+            api.smooth_gll(mesh, ["f"], sigma, context=ctx)
+    with pytest.raises(ValueError):
+        api.smooth_gll(GllMesh(gp2, 2), np.ones(gp2.shape[:2]), (1.0, 0.5), context=ctx)
+    with pytest.raises(ValueError):
+        api.smooth_gll(GllMesh(np.zeros((2, 64, 3)), 3), np.ones((2, 64)), 1.0, context=ctx)
+    with pytest.raises(ValueError):
+        ctx.diffusion(2, gp2, kappa_h=1.0, kappa_r=1.0)
+    with pytest.raises(ValueError):
+        ctx.diffusion(2, gp, kappa_h=-1.0)
+    with pytest.raises(RuntimeError):
+        api.smooth_gll(mesh, ["f"], 0.5, max_iter=1, context=ctx)                 # not a half-smoothed field
+    # straight at the ABI: nothing is written
+    E, P, _ = gp.shape
+    sentinel = np.full((1, E, P), -7.0)
+    y = ctx.to_device(sentinel)
+    u = ctx.to_device(np.ones((1, E, P)))
+    gp_d, gp2_d = ctx.to_device(gp), ctx.to_device(gp2)
+    w, D = _tables(2)
+    w_d, D_d = ctx.to_device(w), ctx.to_device(D)
+    kr_d = ctx.to_device(np.ones((E, P)))
+    h, fn = ctx.handle, lib.mm_gll_diffusion_apply
+    cases = {
+        "order": fn(h, 3, 3, gp_d.ptr, E, D_d.ptr, w_d.ptr, u.ptr, 1, 1.0, None, 0, 0.0, None, y.ptr),
+        "dim 1": fn(h, 2, 1, gp_d.ptr, E, D_d.ptr, w_d.ptr, u.ptr, 1, 1.0, None, 0, 0.0, None, y.ptr),
+        "dim 4": fn(h, 2, 4, gp_d.ptr, E, D_d.ptr, w_d.ptr, u.ptr, 1, 1.0, None, 0, 0.0, None, y.ptr),
+        "null D": fn(h, 2, 3, gp_d.ptr, E, None, w_d.ptr, u.ptr, 1, 1.0, None, 0, 0.0, None, y.ptr),
+        "null w": fn(h, 2, 3, gp_d.ptr, E, D_d.ptr, None, u.ptr, 1, 1.0, None, 0, 0.0, None, y.ptr),
+        "null points": fn(h, 2, 3, None, E, D_d.ptr, w_d.ptr, u.ptr, 1, 1.0, None, 0, 0.0, None, y.ptr),
+        "null u": fn(h, 2, 3, gp_d.ptr, E, D_d.ptr, w_d.ptr, None, 1, 1.0, None, 0, 0.0, None, y.ptr),
+        "in place": fn(h, 2, 3, gp_d.ptr, E, D_d.ptr, w_d.ptr, y.ptr, 1, 1.0, None, 0, 0.0, None, y.ptr),
+        "nelem": fn(h, 2, 3, gp_d.ptr, -1, D_d.ptr, w_d.ptr, u.ptr, 1, 1.0, None, 0, 0.0, None, y.ptr),
+        "ncomp": fn(h, 2, 3, gp_d.ptr, E, D_d.ptr, w_d.ptr, u.ptr, -1, 1.0, None, 0, 0.0, None, y.ptr),
+        "radial in 2-D": fn(h, 2, 2, gp2_d.ptr, 4, D_d.ptr, w_d.ptr, u.ptr, 1, 1.0, None, 1, 0.5, None, y.ptr),
+        "kappa_r array, isotropic": fn(h, 2, 3, gp_d.ptr, E, D_d.ptr, w_d.ptr, u.ptr, 1, 1.0, None, 0, 0.0, kr_d.ptr, y.ptr),
+        "anisotropic flag": fn(h, 2, 3, gp_d.ptr, E, D_d.ptr, w_d.ptr, u.ptr, 1, 1.0, None, 2, 0.0, None, y.ptr),
+    }
+    n = E * P
+    state = ctx.zeros((1, helpers.MM_PCG_STATE), np.float64)
+    cases.update({
+        "combine: nothing to combine": lib.mm_pcg_combine(h, None, u.ptr, 1.0, None, n, 1, y.ptr),
+        "combine: mass without p": lib.mm_pcg_combine(h, kr_d.ptr, None, 1.0, None, n, 1, y.ptr),
+        "combine: null out": lib.mm_pcg_combine(h, kr_d.ptr, u.ptr, 1.0, None, n, 1, None),
+        "combine: n": lib.mm_pcg_combine(h, kr_d.ptr, u.ptr, 1.0, None, -1, 1, y.ptr),
+        "scalars: phase": lib.mm_pcg_scalars(h, state.ptr, 1, 7, 1e-10, None),
+        "scalars: rtol": lib.mm_pcg_scalars(h, state.ptr, 1, helpers.MM_PCG_PHASE_BETA, -1.0, None),
+        "scalars: null state": lib.mm_pcg_scalars(h, None, 1, helpers.MM_PCG_PHASE_START, 1e-10, None),
+        "direction: null z": lib.mm_pcg_direction(h, state.ptr, None, n, 1, y.ptr),
+        "direction: null state": lib.mm_pcg_direction(h, None, u.ptr, n, 1, y.ptr),
+        "advance: null r": lib.mm_pcg_advance(h, state.ptr, u.ptr, u.ptr, n, 1, y.ptr, None),
+        "advance: ncomp": lib.mm_pcg_advance(h, state.ptr, u.ptr, u.ptr, n, -1, y.ptr, y.ptr),
+    })
+    for what, rc in cases.items():
+        assert rc == MM_ERR_ARG, what
+    assert M.same_bits(y.numpy(), sentinel)
+    assert not state.numpy().any()
+
+
+def test_vector_updates_bit_for_bit(ctx):
+    """The streaming kernels of the PCG loop against their one-line statements, and the scalars they read from the device."""
+    lib, h = helpers.load_lib(), ctx.handle
+    rng = np.random.default_rng(7)
+    n, ncomp = 100_003, 3
+    mass = rng.uniform(0.5, 1.5, size=n)
+    p, kp, z, x, r = (T.wide(rng, (ncomp, n)) for _ in range(5))
+    tau = 0.125
+    dev = {k: ctx.to_device(v) for k, v in dict(mass=mass, p=p, kp=kp, z=z, x=x, r=r).items()}
+    out = ctx.empty((ncomp, n), np.float64)
+    assert lib.mm_pcg_combine(h, dev["mass"].ptr, dev["p"].ptr, tau, dev["kp"].ptr, n, ncomp, out.ptr) == 0
+    assert M.same_bits(out.numpy(), mass[None] * p + tau * kp)
+    assert lib.mm_pcg_combine(h, dev["mass"].ptr, dev["p"].ptr, tau, None, n, ncomp, out.ptr) == 0
+    assert M.same_bits(out.numpy(), mass[None] * p)
+    assert lib.mm_pcg_combine(h, None, None, -tau, dev["kp"].ptr, n, ncomp, out.ptr) == 0
+    assert M.same_bits(out.numpy(), -tau * kp)
+    # scalars: system 0 converges at once, 1 and 2 go on
+    S = helpers
+    state = np.zeros((ncomp, S.MM_PCG_STATE))
+    state_d = ctx.to_device(state)
+    nact = ctx.zeros((1,), np.int64)
+    assert lib.mm_pcg_scalars(h, state_d.ptr, ncomp, S.MM_PCG_PHASE_START, 1e-3, nact.ptr) == 0
+    assert nact.numpy()[0] == 3
+    state = state_d.numpy()
+    state[:, S.MM_PCG_BB] = [4.0, 4.0, 9.0]
+    state[:, S.MM_PCG_RZ] = [1.0e-6, 4.1e-6, 2.0]                # sqrt: 1e-3 <= 1e-3 * 2 ; 2.02e-3 just above ; far above
+    state_d = ctx.to_device(state)
+    assert lib.mm_pcg_scalars(h, state_d.ptr, ncomp, S.MM_PCG_PHASE_BETA, 1e-3, nact.ptr) == 0
+    got = state_d.numpy()
+    assert nact.numpy()[0] == 2 and list(got[:, S.MM_PCG_ACTIVE]) == [0.0, 1.0, 1.0]
+    assert list(got[:, S.MM_PCG_BETA]) == [0.0, 0.0, 0.0] and list(got[1:, S.MM_PCG_RZ_OLD]) == [4.1e-6, 2.0]
+    got[:, S.MM_PCG_PAP] = [1.0, 3.0, 7.0]
+    got[:, S.MM_PCG_RZ] = [5.0, 1.0e-6, 0.5]
+    state_d = ctx.to_device(got)
+    assert lib.mm_pcg_scalars(h, state_d.ptr, ncomp, S.MM_PCG_PHASE_ALPHA, 1e-3, None) == 0
+    alpha = state_d.numpy()[:, S.MM_PCG_ALPHA]
+    assert list(alpha) == [0.0, 4.1e-6 / 3.0, 2.0 / 7.0]
+    assert lib.mm_pcg_advance(h, state_d.ptr, dev["p"].ptr, dev["kp"].ptr, n, ncomp, dev["x"].ptr, dev["r"].ptr) == 0
+    x_ref, r_ref = x + alpha[:, None] * p, r - alpha[:, None] * kp
+    x_ref[0], r_ref[0] = x[0], r[0]                              # an inactive system is not touched
+    assert M.same_bits(dev["x"].numpy(), x_ref) and M.same_bits(dev["r"].numpy(), r_ref)
+    assert lib.mm_pcg_scalars(h, state_d.ptr, ncomp, S.MM_PCG_PHASE_BETA, 1e-3, nact.ptr) == 0
+    beta = state_d.numpy()[:, S.MM_PCG_BETA]
+    assert nact.numpy()[0] == 1 and list(beta) == [0.0, 0.0, 0.5 / 2.0]   # system 1 has converged now
+    assert lib.mm_pcg_direction(h, state_d.ptr, dev["z"].ptr, n, ncomp, dev["p"].ptr) == 0
+    p_ref = p.copy()
+    p_ref[2] = z[2] + beta[2] * p[2]
+    assert M.same_bits(dev["p"].numpy(), p_ref)

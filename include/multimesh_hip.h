@@ -464,6 +464,7 @@ int mm_last_locate_stats(mm_context *ctx, long long *out4);
 #define MM_KNN_RAN_GENERIC 16  /* k > 32: knn_query_kernel over one grid */
 #define MM_KNN_RAN_LEVELS 32   /* k > 32: knn_query_levels_kernel over density levels */
 #define MM_KNN_RAN_TREE 64     /* the density-adaptive tree */
+#define MM_KNN_RAN_ONE_PASS 128 /* build: mm_interpolate_hex8 sorted the centroids as it computed them (centroid_sort_kernel) */
 int mm_last_knn_kernels(mm_context *ctx, int *mask);
 
 /* Stage timers (hipEvents on the context's stream).  With profiling on, every kernel

@@ -6,6 +6,7 @@
 // coordinate bytes + ndim*8 written); the coordinate gathers hit L2 for a mesh-ordered
 // connectivity.
 #include "mm_common.h"
+#include "mm_grid_cell.h"
 
 template <int NDIM, int NPER>
 __global__ __launch_bounds__(256) void centroid_kernel(i64 nelem, i64 nper_rt,
@@ -103,6 +104,93 @@ __global__ __launch_bounds__(256) void centroid_bbox_kernel(i64 nelem, const i64
         for (int w = 1; w < 256 / 64; ++w) v = threadIdx.x < 3 ? fmin(v, s_box[threadIdx.x][w]) : fmax(v, s_box[threadIdx.x][w]);
         partial[(i64)blockIdx.x * 6 + threadIdx.x] = v;
     }
+}
+
+// One-pass variant (a guessed call of mm_interpolate_hex8 whose context still holds the previous call's cell_start,
+// mm_knn_build_one_pass): the same centroids and box partials, and each centroid goes straight into its place in the
+// cell-sorted records -- guess_start[cell] + (rank from the zeroed per-cell cursor) -- instead of into a centroid array
+// that a count pass and a scatter pass would read again.  The cell is this call's own (cell_of_point on this call's
+// centroid); only the ROOM of each cell is the previous call's, and a record that finds none is dropped: cursor then
+// differs from the guess in that cell and cursor_check_kernel raises the mismatch word.  No store outside [0, nelem).
+// The loop runs whole waves (count_and_rank is called by every lane): the bound is the wave's first element.
+__global__ __launch_bounds__(256) void centroid_sort_kernel(i64 nelem, const i64 *__restrict__ conn,
+                                                            const double *__restrict__ points, GridParams g,
+                                                            const int *__restrict__ guess_start, int *__restrict__ cursor,
+                                                            double *__restrict__ sorted_rec, double *__restrict__ partial)
+{
+    __shared__ double s_box[6][256 / 64];
+    double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    const i64 stride = (i64)gridDim.x * blockDim.x;
+    const int lane = threadIdx.x & 63;
+    i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    i64 idn[8];
+    {
+        const i64 *row = conn + (e < nelem ? e : 0) * 8;
+#pragma unroll
+        for (int p = 0; p < 8; ++p) idn[p] = row[p];
+    }
+    for (; e - lane < nelem; e += stride) {
+        const bool live = e < nelem;
+        i64 id[8];
+#pragma unroll
+        for (int p = 0; p < 8; ++p) id[p] = idn[p];
+        {
+            const i64 *row = conn + (e + stride < nelem ? e + stride : (live ? e : 0)) * 8;
+#pragma unroll
+            for (int p = 0; p < 8; ++p) idn[p] = row[p];
+        }
+        double acc[3] = {0., 0., 0.};
+#pragma unroll
+        for (int p = 0; p < 8; ++p) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) acc[a] = acc[a] + points[id[p] * 3 + a];
+        }
+        double c[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            c[a] = acc[a] / 8.0;   // summed in connectivity order from 0.0, divided (centroid.c:17-22)
+            if (live) {
+                mn[a] = fmin(mn[a], c[a]);
+                mx[a] = fmax(mx[a], c[a]);
+            }
+        }
+        const int cell = live ? cell_of_point(c[0], c[1], c[2], g) : -1;
+        const int rank = count_and_rank(cell, live, cursor);
+        if (live) {
+            const int first = guess_start[cell], room = guess_start[cell + 1] - first;
+            const i64 pos = (i64)first + rank;
+            if (rank >= 0 && rank < room && pos >= 0 && pos < nelem) store_record(sorted_rec + pos * kRec, c[0], c[1], c[2], (int)e);
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+        for (int off = 32; off > 0; off >>= 1) {
+            mn[a] = fmin(mn[a], __shfl_xor(mn[a], off));
+            mx[a] = fmax(mx[a], __shfl_xor(mx[a], off));
+        }
+    const int wave = threadIdx.x >> 6;
+    if (lane == 0)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            s_box[a][wave] = mn[a];
+            s_box[3 + a][wave] = mx[a];
+        }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        double v = s_box[threadIdx.x][0];
+        for (int w = 1; w < 256 / 64; ++w) v = threadIdx.x < 3 ? fmin(v, s_box[threadIdx.x][w]) : fmax(v, s_box[threadIdx.x][w]);
+        partial[(i64)blockIdx.x * 6 + threadIdx.x] = v;
+    }
+}
+
+int mm_launch_centroid_sort(mm_context *ctx, i64 nelem, const i64 *conn, const double *points, const GridParams &g,
+                            const int *guess_start, int *cursor, double *sorted_rec, double *partial, int nblocks)
+{
+    if (nelem == 0) return MM_OK;
+    hipLaunchKernelGGL(centroid_sort_kernel, dim3((unsigned)nblocks), dim3(256), 0, ctx->stream, nelem, conn, points, g,
+                       guess_start, cursor, sorted_rec, partial);
+    MM_HIP_CHECK(hipGetLastError());
+    return MM_OK;
 }
 
 int mm_launch_centroid_bbox(mm_context *ctx, i64 nelem, const i64 *conn, const double *points, double *out,

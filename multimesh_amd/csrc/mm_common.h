@@ -108,6 +108,10 @@ struct mm_context {
         i64 nsrc = 0;
         double box[6] = {0, 0, 0, 0, 0, 0};
         int stat_shift = -1;
+        // MM_BUF_CELL_START / MM_BUF_SORTED_XYZ hold the completed level-0 sort of nsrc sources on the grid of `box`, built
+        // or confirmed by the previous call: the next guessed call may place its records by that cell_start in one pass
+        // (mm_knn_build_one_pass).  Cleared by whatever else writes those two buffers (build_level).
+        bool cells_ok = false;
         int misses = 0;
         long long calls_guessed = 0;   // (mm_debug_grid_guess: what the tests look at)
     } grid_guess;
@@ -153,17 +157,21 @@ void mm_stage_end(mm_context *ctx, int stage);
 // ("The last workgroup of a launch finishes the reduction" was tried for the bounding box and the scans and
 // measured: on this multi-XCD part the device-scope fence every workgroup needs before it takes its ticket writes
 // its XCD's L2 back -- the centroid kernel went from 0.26 to 0.72 ms, a scan's first kernel from 5 to 80 us.)
-//   24..26 (six ints) mismatch flags of a guessed grid (mm_aborted)   2..3 scratch of small readbacks
+//   24..27 (eight ints) mismatch flags of a guessed grid (mm_aborted)   2..3 scratch of small readbacks
+//   54 (h_counters) the one-pass build's per-cell counts differ from the guess (cursor_check_kernel)
 constexpr int kMmStatSlot = 32, kMmBoxSlot = 48, kMmAbortSlot = 24;   // (slots 0..15 are cleared by every locate stage)
+constexpr int kMmCountsBadSlot = 54;
 
-// A call over a GUESSED search grid (mm_interpolate_hex8): abort6 = six ints, non-zero when this call's bounding box is
-// not the one the grid was laid out from.  The kernels that would be ruinously slow on a foreign grid ask first.
+// A call over a GUESSED search grid (mm_interpolate_hex8): abort6 = eight ints; the first six are non-zero when this
+// call's bounding box is not the one the grid was laid out from, the seventh when a one-pass build found other per-cell
+// counts than the ones it placed its records by (the eighth is spare and zero).  The kernels that would be ruinously
+// slow on a foreign grid -- or read stale records -- ask first.
 __device__ __forceinline__ bool mm_aborted(const int *__restrict__ abort6)
 {
     if (!abort6) return false;
     const int4 a = *reinterpret_cast<const int4 *>(abort6);
-    const int2 b = *reinterpret_cast<const int2 *>(abort6 + 4);
-    return (a.x | a.y | a.z | a.w | b.x | b.y) != 0;
+    const int4 b = *reinterpret_cast<const int4 *>(abort6 + 4);
+    return (a.x | a.y | a.z | a.w | b.x | b.y | b.z | b.w) != 0;
 }
 
 // ---- internal launchers (device pointers, no synchronisation) -------------------------

@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "mm_common.h"
+#include "mm_grid_cell.h"
 #include <cstring>
 
 int mm_exclusive_scan_int(mm_context *ctx, const int *counts, i64 n, int *start, int *tile_sums);
@@ -427,6 +428,7 @@ static int build_level(mm_context *ctx, const double *src_d, i64 nsrc, int ndim,
     }
     ix->nsrc = nsrc;
     ix->ndim = ndim;
+    if (use_context_buffers && level == 0) ctx->grid_guess.cells_ok = false;   // (the two buffers are rewritten below)
     int live = 0;
     grid_layout(box, nsrc, ndim, per_cell, ix, &live);
     const i64 ncells = ix->ncells;
@@ -482,7 +484,8 @@ static int build_level(mm_context *ctx, const double *src_d, i64 nsrc, int ndim,
             hipLaunchKernelGGL(bbox_final_kernel, dim3(6), dim3(kBlock), 0, ctx->stream, guessed->box_partial, guessed->box_nblocks,
                                reinterpret_cast<double *>(ctx->h_counters + kBoxSlot),
                                reinterpret_cast<long long *>(ctx->d_counters + kStatSlot), gb6,
-                               reinterpret_cast<int *>(ctx->d_counters + kMmAbortSlot));
+                               reinterpret_cast<int *>(ctx->d_counters + kMmAbortSlot),
+                               reinterpret_cast<long long *>(ctx->h_counters + kMmCountsBadSlot));
         }
     if (nsrc > 0)
         hipLaunchKernelGGL(cell_count_kernel, dim3(gsrc), dim3(kBlock), 0, ctx->stream, src_d, nsrc, ndim, g, cell_of,
@@ -641,6 +644,8 @@ int mm_knn_build_impl(mm_context *ctx, const double *src_d, i64 nsrc, i64 ndim, 
         ctx->grid_guess.valid = !head->fine && extra == 0 && per_cell_level0 == kDefaultPerCell && max_levels > 1;
         ctx->grid_guess.nsrc = nsrc;
         for (int q = 0; q < 6; ++q) ctx->grid_guess.box[q] = box[q];
+        // (head is then the one level-0 grid of this box at the default density, sorted into the context's buffers)
+        ctx->grid_guess.cells_ok = ctx->grid_guess.valid;
     }
     return MM_OK;
 }
@@ -651,9 +656,11 @@ int mm_knn_build_impl(mm_context *ctx, const double *src_d, i64 nsrc, i64 ndim, 
 // this call's box or the grid statistic in mid-call (two host round trips with an idle GPU behind each), and
 // mm_knn_guess_confirmed compares both with the guess after the call's last synchronisation -- a different box or a
 // statistic that asks for density levels or a coarser grid means the call is run again the ordinary way (the kernels
-// are safe on any grid: cell coordinates are clamped).  (Counting the cells inside the centroid kernel as well was
-// measured: that kernel grows by what cell_count_kernel takes on its own, 68 vs 57 us -- the atomics and ranks, not
-// the second read of the centroids, are its cost.)
+// are safe on any grid: cell coordinates are clamped).  This is the guessed build of a context whose cell_start buffer
+// does not hold this grid's sort (grid_guess.cells_ok unset: another build has used the buffers since); the usual guessed
+// call takes mm_knn_build_one_pass below.  (Counting the cells inside the centroid kernel and nothing else was measured:
+// that kernel grows by what cell_count_kernel takes on its own, 68 vs 57 us -- the atomics and ranks, not the second
+// read of the centroids, are its cost; the one-pass build pays them once and drops the scan and the scatter pass.)
 int mm_knn_build_guessed(mm_context *ctx, const double *cen, i64 nelem, const double *box_partial, int box_nblocks,
                          mm_knn_index **out)
 {
@@ -668,11 +675,83 @@ int mm_knn_build_guessed(mm_context *ctx, const double *cen, i64 nelem, const do
                        /*stat_dirty=*/false, &gb);
 }
 
-// After the synchronisation that ends a call built by mm_knn_build_guessed: was the guess this call's own grid?
+// The guessed build in ONE pass over the mesh.  The guess says "the source mesh of the previous call"; then the per-cell
+// counts, and with them cell_start, are the previous call's too, and that array still sits in MM_BUF_CELL_START
+// (grid_guess.cells_ok).  The centroid kernel therefore sorts as it goes (centroid_sort_kernel: record at cell_start[cell] +
+// rank from a zeroed cursor) and neither the centroid array nor a count, scan or scatter pass exists; cell_start is left
+// as it is.  What is guessed is only the ROOM of each cell: cursor_check_kernel compares the cursor with it cell by cell and
+// raises the mismatch word on any difference, which mm_knn_guess_confirmed treats like a foreign box (the call is run
+// again the ordinary way; the expensive kernels in between return at once).  The grid statistic is a function of the
+// counts: confirmed equal counts carry the previous call's verdict, so it is not taken again (stat_shift = -1).
+// Nothing after the build reads a centroid array: the query, the lazy lists and the locate stage use the records.
+// Stage timers: MM_STAGE_CENTROID = cursor fill + the fused kernel, MM_STAGE_KNN_BUILD = box reduction + count check.
+int mm_knn_build_one_pass(mm_context *ctx, const i64 *conn, const double *nodes, i64 nelem, double *box_partial,
+                          int box_nblocks, mm_knn_index **out)
+{
+    *out = nullptr;
+    mm_knn_index *ix = new (std::nothrow) mm_knn_index();
+    if (!ix) {
+        mm_set_error(MM_ERR_ALLOC, "out of host memory");
+        return MM_ERR_ALLOC;
+    }
+    ix->nsrc = nelem;
+    ix->ndim = 3;
+    grid_layout(ctx->grid_guess.box, nelem, 3, kDefaultPerCell, ix, nullptr);
+    const i64 ncells = ix->ncells;
+    const GridParams g = params_of(ix);
+    ix->borrowed = true;
+    // (the sizes of the build that left the buffers: no reallocation, the contents stay)
+    int rc = mm_buffer_get(ctx, MM_BUF_CELL_START, (size_t)(ncells + 1) * sizeof(int), (void **)&ix->cell_start);
+    if (rc == MM_OK) rc = mm_buffer_get(ctx, MM_BUF_SORTED_XYZ, (size_t)(nelem + 1) * kRec * sizeof(double), (void **)&ix->sorted_xyz);
+    if (rc == MM_OK) rc = mm_scratch_begin(ctx, mm_round256((size_t)(ncells + 1) * sizeof(int)) + 1024);
+    int *cursor = rc == MM_OK ? (int *)mm_scratch_take(ctx, (size_t)(ncells + 1) * sizeof(int)) : nullptr;
+    if (rc == MM_OK && !cursor) {
+        mm_set_error(MM_ERR_ALLOC, "scratch carve failed");
+        rc = MM_ERR_ALLOC;
+    }
+    if (rc != MM_OK) {
+        free_index(ix);
+        return rc;
+    }
+    mm_stage_begin(ctx, MM_STAGE_CENTROID);
+    rc = mm_zero_async(ctx, cursor, mm_fill_span((size_t)(ncells + 1) * sizeof(int)));
+    if (rc == MM_OK)
+        rc = mm_launch_centroid_sort(ctx, nelem, conn, nodes, g, ix->cell_start, cursor, ix->sorted_xyz, box_partial, box_nblocks);
+    mm_stage_end(ctx, MM_STAGE_CENTROID);
+    if (rc != MM_OK) {
+        free_index(ix);
+        return rc;
+    }
+    mm_stage_begin(ctx, MM_STAGE_KNN_BUILD);
+    GuessBox gb6;
+    for (int q = 0; q < 6; ++q) gb6.v[q] = ctx->grid_guess.box[q];
+    int *flags = reinterpret_cast<int *>(ctx->d_counters + kMmAbortSlot);
+    long long *counts_bad_h = reinterpret_cast<long long *>(ctx->h_counters + kMmCountsBadSlot);
+    hipLaunchKernelGGL(bbox_final_kernel, dim3(6), dim3(kBlock), 0, ctx->stream, (const double *)box_partial, box_nblocks,
+                       reinterpret_cast<double *>(ctx->h_counters + kBoxSlot), (long long *)nullptr, gb6, flags, counts_bad_h);
+    const i64 want = (ncells + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(cursor_check_kernel, dim3((unsigned)(want > 1024 ? 1024 : want)), dim3(kBlock), 0, ctx->stream,
+                       (const int *)cursor, (const int *)ix->cell_start, ncells, flags, counts_bad_h);
+    mm_stage_end(ctx, MM_STAGE_KNN_BUILD);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        mm_set_error(MM_ERR_HIP, "one-pass kNN build launch: %s", hipGetErrorString(e));
+        free_index(ix);
+        return MM_ERR_HIP;
+    }
+    ctx->grid_guess.stat_shift = -1;
+    ctx->knn_kernels |= MM_KNN_RAN_ONE_PASS;
+    *out = ix;
+    return MM_OK;
+}
+
+// After the synchronisation that ends a call built by mm_knn_build_guessed or mm_knn_build_one_pass: was the guess this
+// call's own grid (and, one pass: were the per-cell counts the ones the records were placed by)?
 bool mm_knn_guess_confirmed(mm_context *ctx)
 {
     const double *h_box = reinterpret_cast<const double *>(ctx->h_counters + kBoxSlot);
     if (memcmp(h_box, ctx->grid_guess.box, 6 * sizeof(double)) != 0) return false;
+    if (ctx->h_counters[kMmCountsBadSlot] != 0) return false;
     if (ctx->grid_guess.stat_shift < 0) return true;   // (a mesh too small for the statistic: the ordinary build skips it too)
     double sparse_count = 0.0;
     const int extra = stat_verdict(ctx, ctx->grid_guess.nsrc, ctx->grid_guess.stat_shift, &sparse_count);

@@ -35,12 +35,7 @@ constexpr int kStatSlot = kMmStatSlot;  // slot of mm_context::d_counters / h_co
 static_assert(kMaxLevels <= 16, "the level statistic has 16 counter slots");
 constexpr int kBoxSlot = kMmBoxSlot;   // six doubles of the pinned h_counters receive the sources' bounding box
 
-struct GridParams {
-    int nx, ny, nz;
-    double lox, loy, loz;
-    double hx, hy, hz;
-    double ihx, ihy, ihz;
-};
+// (GridParams, cell_of_point, count_and_rank and the sorted record: mm_grid_cell.h, shared with mm_centroid.hip)
 
 // ---- bounding box -------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void bbox_partial_kernel(const double *__restrict__ src, i64 nsrc,
@@ -89,12 +84,15 @@ __global__ __launch_bounds__(kBlock) void bbox_partial_kernel(const double *__re
 // box differs from it -- the expensive kernels of a guessed call look at these six words first and return at once when
 // the grid is not theirs (mm_aborted: all sources and targets sit clamped in a few boundary cells of a foreign grid, the
 // ring searches would scan nearly every source for every target), the host runs the call again after its last wait.
+// Words 6 and 7 behind them and *counts_bad_h (pinned) belong to the one-pass build's count check (cursor_check_kernel,
+// launched behind this kernel): every guessed call clears them here.
 struct GuessBox {
     double v[6];
 };
 __global__ __launch_bounds__(kBlock) void bbox_final_kernel(const double *__restrict__ partial, int nblocks,
                                                              double *__restrict__ out, long long *__restrict__ stat16,
-                                                             GuessBox guess = GuessBox(), int *__restrict__ mismatch6 = nullptr)
+                                                             GuessBox guess = GuessBox(), int *__restrict__ mismatch6 = nullptr,
+                                                             long long *__restrict__ counts_bad_h = nullptr)
 {
     // one workgroup per component (grid 6): the threads stride over the per-block partials -- eight independent
     // loads in flight each for the fused pipeline's 2048 partials: ONE round trip (a single wave walking them took
@@ -127,48 +125,29 @@ __global__ __launch_bounds__(kBlock) void bbox_final_kernel(const double *__rest
         for (int wv = 1; wv < kBlock / 64; ++wv) r = a < 3 ? fmin(r, s_part[wv]) : fmax(r, s_part[wv]);
         out[a] = r;
         if (mismatch6) mismatch6[a] = r == guess.v[a] ? 0 : 1;   // (NaN: a mismatch)
+        if (mismatch6 && a == 0) {
+            mismatch6[6] = 0;
+            mismatch6[7] = 0;
+            if (counts_bad_h) *counts_bad_h = 0;
+        }
     }
 }
 
-// ---- cell assignment ----------------------------------------------------------------
-__device__ __forceinline__ int cell_coord(double x, double lo, double ih, int n)
+// One-pass build (mm_knn_build_one_pass): the centroid kernel placed every record by the PREVIOUS call's cell_start;
+// that is this call's sort exactly when every cell received as many records as it has room for.  Any other count -- a
+// cell that overflowed dropped its surplus records, another one kept stale ones -- raises word 6 of the mismatch flags
+// (mm_aborted) and the pinned word mm_knn_guess_confirmed reads.  Grid-stride.
+__global__ __launch_bounds__(kBlock) void cursor_check_kernel(const int *__restrict__ cursor, const int *__restrict__ start,
+                                                              i64 ncells, int *__restrict__ mismatch8,
+                                                              long long *__restrict__ counts_bad_h)
 {
-    double t = (x - lo) * ih;
-    t = fmin(fmax(t, 0.0), (double)(n - 1));  // NaN -> 0, outside -> clamped
-    return (int)t;
-}
-
-// The histogram atomic also hands out the item's rank inside its cell, so the scatter pass needs
-// no second atomic.  Mesh-ordered points arrive in runs of equal cells (neighbours along the
-// fastest axis), and same-address atomics serialise in L2: the first lane of each run of equal
-// cells inside the wave adds the run's length, the others take consecutive ranks behind it.
-// (Random-order input: every run has length 1, nothing lost but a dozen instructions.)
-// Called by every lane of the wave (c = -1, live = false for lanes without an item).
-__device__ __forceinline__ int count_and_rank(int c, bool live, int *__restrict__ counts)
-{
-    const int lane = threadIdx.x & 63;
-    const int prev = __shfl_up(c, 1);
-    const bool head = lane == 0 || c != prev;
-    const unsigned long long heads = __ballot(head);
-    const unsigned long long upto = heads & (~0ull >> (63 - lane));       // heads at lanes <= mine
-    const int head_lane = 63 - __clzll((long long)upto);
-    const unsigned long long after = lane == 63 ? 0ull : heads & (~0ull << (lane + 1));
-    int base = 0;
-    if (head && live) {
-        const int next_head = after ? __ffsll((long long)after) - 1 : 64;
-        base = atomicAdd(&counts[c], next_head - lane);
+    bool bad = false;
+    for (i64 c = (i64)blockIdx.x * blockDim.x + threadIdx.x; c < ncells; c += (i64)gridDim.x * blockDim.x)
+        bad = bad || cursor[c] != start[c + 1] - start[c];
+    if (__any(bad) && (threadIdx.x & 63) == 0) {
+        mismatch8[6] = 1;
+        *counts_bad_h = 1;
     }
-    base = __shfl(base, head_lane);
-    return base + (lane - head_lane);
-}
-
-// the cell of a point (the count and the scatter pass of a counting sort both call this: same arithmetic, same cell)
-__device__ __forceinline__ int cell_of_point(double x, double y, double z, const GridParams &g)
-{
-    const int cx = cell_coord(x, g.lox, g.ihx, g.nx);
-    const int cy = cell_coord(y, g.loy, g.ihy, g.ny);
-    const int cz = cell_coord(z, g.loz, g.ihz, g.nz);
-    return (cx * g.ny + cy) * g.nz + cz;
 }
 
 // With `list` the items are the points list[0 .. *list_count) (a density level's share of the targets).
@@ -391,19 +370,6 @@ __global__ __launch_bounds__(kBlock) void scan_apply_kernel(const int *__restric
     // start[n] = total number of items
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == kBlock - 1) start[n] = excl;
 }
-
-// Sorted records are 32 bytes {x, y, z, original index (as the bits of a double)}: an item is
-// written with two 16-byte stores into its own aligned sector and read back the same way.
-constexpr int kRec = 4;
-
-__device__ __forceinline__ void store_record(double *__restrict__ rec, double x, double y, double z, int id)
-{
-    double2 *r2 = reinterpret_cast<double2 *>(rec);
-    r2[0] = make_double2(x, y);
-    r2[1] = make_double2(z, __longlong_as_double((long long)id));
-}
-
-__device__ __forceinline__ int record_id(double w) { return (int)__double_as_longlong(w); }
 
 __global__ __launch_bounds__(kBlock) void cell_scatter_kernel(const double *__restrict__ src, i64 nsrc, int ndim,
                                                               GridParams g, const int *__restrict__ rank_of,

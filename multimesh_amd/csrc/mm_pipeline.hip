@@ -16,6 +16,8 @@ int mm_knn_query_sorted_impl(mm_context *ctx, const mm_knn_index *ix, const doub
 void mm_clear_status(void);
 int mm_knn_build_guessed(mm_context *ctx, const double *cen, i64 nelem, const double *box_partial, int box_nblocks,
                          mm_knn_index **out);
+int mm_knn_build_one_pass(mm_context *ctx, const i64 *conn, const double *nodes, i64 nelem, double *box_partial,
+                          int box_nblocks, mm_knn_index **out);
 bool mm_knn_guess_confirmed(mm_context *ctx);
 
 // candidates delivered up front when the lists are evaluated lazily (99.9 % of mesh-node targets are
@@ -141,7 +143,9 @@ static int64_t interpolate_hex8_impl(mm_context *ctx, const double *nodes_d, int
     // case: one source mesh, many calls), the grid is GUESSED from that box and the guess is checked against this
     // call's own box after the synchronisation that ends the call; a wrong
     // guess runs the call again the ordinary way (twice wrong: no more guessing in this context).  MM_GRID_GUESS=0
-    // switches it off.
+    // switches it off.  A guessed call whose context also still holds the cell_start of that grid's sort
+    // (grid_guess.cells_ok) guesses the per-cell counts as well and sorts the centroids as it computes them
+    // (mm_knn_build_one_pass); other counts are a miss like another box.
     static const bool guess_on = !(getenv("MM_GRID_GUESS") && atoi(getenv("MM_GRID_GUESS")) == 0);
     // (MM_KNN_LEVELS is read per call by the ordinary build -- tests switch it inside one process -- and a guessed build
     // would ignore it)
@@ -154,6 +158,15 @@ again:
         goto query;
     }
     if (feed && (rc = feed_upload(ctx, feed, 0, 1, 0)) != MM_OK) { result = rc; goto done; }
+    if (guessed && ctx->grid_guess.cells_ok) {
+        // the context still holds the cell_start of this grid's last sort: centroids, box and sort in one pass over
+        // the mesh (no centroid array; mm_knn_build_one_pass brackets both stages itself)
+        ++ctx->grid_guess.calls_guessed;
+        ctx->abort_flags = reinterpret_cast<int *>(ctx->d_counters + kMmAbortSlot);
+        rc = mm_knn_build_one_pass(ctx, (const i64 *)conn_d, nodes_d, nelem, box_partial, kBoxBlocks, &index);
+        if (rc != MM_OK) { result = rc; goto done; }
+        goto query;
+    }
     mm_stage_begin(ctx, MM_STAGE_CENTROID);
     rc = mm_launch_centroid_bbox(ctx, nelem, (const i64 *)conn_d, nodes_d, cen, box_partial, kBoxBlocks);
     mm_stage_end(ctx, MM_STAGE_CENTROID);
@@ -211,6 +224,7 @@ query:
     if (guessed && !mm_knn_guess_confirmed(ctx)) {
         // not this mesh's grid: everything again, the ordinary way (which also leaves the right box for the next call)
         ctx->grid_guess.valid = false;
+        ctx->grid_guess.cells_ok = false;
         ++ctx->grid_guess.misses;
         guessed = false;
         ctx->abort_flags = nullptr;
@@ -221,6 +235,7 @@ query:
         goto again;
     }
     result = ctx->h_counters[0];
+    if (guessed) ctx->grid_guess.cells_ok = true;   // (confirmed: the buffers hold this grid's complete sort)
     // (a long-lived context forgives old misses: every 64 calls that confirmed their guess take one back)
     if (guessed && ctx->grid_guess.misses > 0 && (ctx->grid_guess.calls_guessed & 63) == 0) --ctx->grid_guess.misses;
 

@@ -18,7 +18,7 @@ from . import helpers as H
 from .helpers import MM_FP_EXACT, MM_FP_TOL, MM_KNN_MAX_K, STAGES, MultiMeshHipError, check, load_lib
 
 # MM_KNN_RAN_* in bit order
-KNN_KERNELS = ("lane", "strip", "cell", "list", "generic", "levels", "tree")
+KNN_KERNELS = ("lane", "strip", "cell", "list", "generic", "levels", "tree", "one_pass")
 
 _NP2ITEM = {np.dtype(np.float64): 8, np.dtype(np.int64): 8, np.dtype(np.int32): 4, np.dtype(np.uint8): 1}
 

@@ -198,6 +198,34 @@ int64_t mm_sample_columns_gll(mm_context *ctx, int order, const double *gll_poin
                               int64_t nelem_to_search, double tolerance, double fill_value, int64_t chunk_points,
                               double *out_d, double *points_out_d);
 
+/* The other direction: a regular (depth, latitude, longitude) grid sampled at arbitrary points -- a gridded model onto the
+ * nodes of a mesh.  points_d f64[npoints][3] (an element-nodal [nelem][P][3] array read flat), the axes depth_d
+ * f64[ndepth] (m below 6371000), lat_d f64[nlat] (geocentric degrees), lon_d f64[nlon] (degrees), each STRICTLY ASCENDING
+ * (the caller guarantees it), grid_d f64[ncomp][ndepth][nlat][nlon], out_d f64[ncomp][npoints] (for an element-nodal mesh
+ * the [C][E][P] layout mm_gather_elem reads), latlondepth_out_d (nullable) f64[npoints][3] = (lat, lon, depth) as computed.
+ * Per point, every operation rounded on its own (no fused multiply-add):
+ *   r = sqrt((x*x + y*y) + z*z)   depth = 6371000.0 - r   c = r > 0 ? z / r : 0.0
+ *   lat = 90.0 - acos(c) * (180.0 / pi)   lon = atan2(y, x) * (180.0 / pi)          (the inverse of latlondepth_to_xyz)
+ *   lon_periodic: if (lon < lon[0]) lon += 360.0; if (lon >= lon[0] + 360.0) lon -= 360.0; each once -- the caller
+ *     guarantees -360 <= lon[0] <= 180 and lon[nlon-1] == lon[0] + 360
+ *   per axis a[0..n-1] and value v: inside = (v >= a[0] && v <= a[n-1]) (NaN is outside); clamp mode first sets
+ *     v = min(max(v, a[0]), a[n-1]) and counts the point as inside; i = clip(upper_bound(a, v) - 1, 0, n - 2)
+ *     (np.searchsorted(a, v, side="right") - 1), t = (v - a[i]) / (a[i+1] - a[i]), i1 = i + 1; an axis of length 1 is
+ *     constant along itself: i = i1 = 0, t = 0, always inside
+ *   per component, with lerp(t, p, q) = (1.0 - t) * p + t * q: four lerps along longitude, two of those along latitude,
+ *     one along depth, corners read at (k|k1, j|j1, i|i1).  A NaN corner propagates as IEEE arithmetic propagates it,
+ *     also with weight 0.
+ * So out_d is bit for bit that statement on latlondepth_out_d; the angles themselves are the device's acos / atan2.
+ * outside_mode for points outside the grid: 0 fill (fill_value is written), 1 clamp (the edge value extends; nothing is
+ * outside), 2 keep (out_d[c][n] is left untouched).  ncomp == 0 with latlondepth_out_d is valid (the coordinates alone),
+ * and so is npoints == 0.  Returns the number of points outside the grid (0 in clamp mode; an integer sum, the same on
+ * every run), or a negative MM_ERR_*: MM_ERR_ARG for a null table, ndepth / nlat / nlon < 1 or an unknown mode, nothing is
+ * written then.  Synchronises. */
+int64_t mm_sample_grid(mm_context *ctx, const double *points_d, int64_t npoints, const double *depth_d, int64_t ndepth,
+                       const double *lat_d, int64_t nlat, const double *lon_d, int64_t nlon, const double *grid_d,
+                       int64_t ncomp, int lon_periodic, int outside_mode, double fill_value, double *out_d,
+                       double *latlondepth_out_d);
+
 /* The TRANSPOSE of an interpolation operator: what comes back from the targets to the sources (a gradient on the event
  * mesh -> the inversion mesh, so that <P m, g> = <m, P^T g>; P^T 1 = the coverage map).  Deterministic: the result is bit for
  * bit np.add.at on zeros, i.e. the sequential loop, on every run (no float atomics, no reordering).

@@ -20,6 +20,8 @@ Earth meshes: :func:`map_to_sphere` and :func:`map_to_ellipse` (reference interp
 ``make_spherical`` of the drivers (mapped copies).
 Regular grids: :func:`extract_regular_grid` (reference api.py:600-642), :func:`extract_depth_slice` and
 :func:`extract_cross_section` (what plot_depth_slice / plot_cross_section sample), targets generated on the device.
+Grid import, the other direction: :func:`sample_regular_grid` and :func:`import_regular_grid` put a gridded model
+(:meth:`RegularGrid.from_netcdf`) onto the nodes of a mesh or into a Salvus model (``mm_sample_grid``).
 Beyond the reference: the operator transposes, and the GLL mass matrix with what it weights -- :func:`gll_mass_matrix`,
 :func:`hex8_mass_matrix`, :func:`integrate`, :func:`assemble_gll`, :func:`apply_gll_operator_adjoint`,
 :func:`apply_operator_adjoint`; and the stiffness operator with the smoothing it gives -- :func:`gll_stiffness_apply`,
@@ -1336,6 +1338,37 @@ class RegularGrid:
                 var._FillValue = self.fill_value
                 var[:] = v
 
+    @classmethod
+    def from_netcdf(cls, path):
+        """The inverse of :meth:`to_netcdf`, for any classic netCDF cube (``scipy.io.netcdf_file``): the coordinate
+        variables ``depth``, ``latitude`` and ``longitude``, and every other variable over exactly those three
+        dimensions, in any order -- transposed to (depth, latitude, longitude).  Values equal to a variable's
+        ``_FillValue`` or ``missing_value`` become NaN (``fill_value`` of the result is NaN); the global
+        ``radius_in_meters`` is kept when the file has one.  Other variables are ignored."""
+        from scipy.io import netcdf_file
+
+        with netcdf_file(path, "r", mmap=False) as f:
+            missing = [d for d in DIMS if d not in f.variables]
+            if missing:
+                raise ValueError(f"{path}: no coordinate variable(s) {missing}")
+            coords = {d: np.array(f.variables[d][:], dtype=np.float64).reshape(-1) for d in DIMS}
+            data_vars = {}
+            for name, var in f.variables.items():
+                if name in DIMS or sorted(var.dimensions) != sorted(DIMS):
+                    continue
+                v = np.array(var[:], dtype=np.float64)
+                for attr in ("_FillValue", "missing_value"):
+                    flag = getattr(var, attr, None)
+                    if flag is not None:
+                        flag = np.asarray(flag, dtype=np.float64).reshape(-1)
+                        v[np.isin(v, flag[~np.isnan(flag)])] = np.nan
+                data_vars[name] = np.ascontiguousarray(np.transpose(v, [var.dimensions.index(d) for d in DIMS]))
+            radius = getattr(f, "radius_in_meters", None)
+        grid = cls(coords["depth"], coords["latitude"], coords["longitude"], data_vars)
+        if radius is not None:
+            grid.attrs["radius_in_meters"] = float(np.asarray(radius).reshape(-1)[0])
+        return grid
+
     def __repr__(self):
         shape = ", ".join(f"{d}: {len(self.coords[d])}" for d in DIMS)
         return f"<RegularGrid ({shape}) {list(self.data_vars)} nmissing={self.nmissing}>"
@@ -1420,3 +1453,176 @@ def extract_cross_section(mesh, parameters, lats, lons, depths, make_spherical=T
     values, _ = _sample(mesh, parameters, lats, lons, depths, True, make_spherical, nelem_to_search, tolerance,
                         fill_value, chunk_points, context)
     return values
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# The other direction: a regular latitude x longitude x depth grid onto the points of a mesh (Context.sample_grid).  The
+# host only prepares the grid-sized arrays below; the mesh-sized work -- xyz -> lat/lon/depth, the cell search and the
+# trilinear values -- runs on the device.
+def _ascending_axis(name, values):
+    """(axis ascending, flipped?) of a coordinate; ``ValueError`` unless it is 1-D, finite and strictly monotone."""
+    a = np.array(values, dtype=np.float64)
+    if a.ndim != 1 or a.size < 1 or not np.isfinite(a).all():
+        raise ValueError(f"the {name} axis must be 1-D, finite and not empty")
+    d = np.diff(a)
+    if (d > 0).all():
+        return a, False
+    if (d < 0).all():
+        return np.ascontiguousarray(a[::-1]), True
+    raise ValueError(f"the {name} axis is not strictly monotone")
+
+
+def _is_global_longitude(lon, data):
+    """A longitude axis that goes once round: its span plus one mean spacing is 360 (within 1e-6 of a spacing), or its
+    span is 360 and the first and the last column hold the same data."""
+    if len(lon) < 2:
+        return False
+    span = lon[-1] - lon[0]
+    spacing = span / (len(lon) - 1)
+    if abs(span + spacing - 360.0) <= 1e-6 * spacing:
+        return True
+    return abs(span - 360.0) <= 1e-6 * spacing and np.array_equal(data[..., 0], data[..., -1], equal_nan=True)
+
+
+def prepare_regular_grid(grid, parameters=None, lon_periodic=None):
+    """``(depth, lat, lon, data f64[C, D, LA, LO], parameters, periodic)`` as :meth:`Context.sample_grid` takes them, from
+    a :class:`RegularGrid`: descending axes are flipped to ascending with their data, an axis that is not strictly
+    monotone or not finite raises ``ValueError``.  ``lon_periodic=None`` detects a global longitude axis
+    (:func:`_is_global_longitude`).  A periodic axis is shifted by a multiple of 360 to start in [-180, 180) when it
+    starts outside [-360, 180], and closed: when it ends before ``lon[0] + 360``, the column ``lon[0] + 360`` with the
+    data of column 0 is appended; an end within rounding of it becomes exactly that."""
+    from . import io as mio
+
+    parameters = list(grid.data_vars) if parameters is None else mio.pick_parameters(parameters)
+    unknown = [p for p in parameters if p not in grid.data_vars]
+    if unknown:
+        raise ValueError(f"parameters {unknown} are not in the grid (it holds {list(grid.data_vars)})")
+    axes, flipped = {}, {}
+    for d in DIMS:
+        axes[d], flipped[d] = _ascending_axis(d, grid.coords[d])
+    shape = tuple(len(axes[d]) for d in DIMS)
+    fields = []
+    for p in parameters:
+        v = np.asarray(grid.data_vars[p], dtype=np.float64)
+        if v.shape != shape:
+            raise ValueError(f"{p}: shape {v.shape}, the grid is {shape}")
+        fields.append(v)
+    data = np.stack(fields) if fields else np.zeros((0,) + shape)
+    for ax, d in enumerate(DIMS):
+        if flipped[d]:
+            data = np.flip(data, axis=ax + 1)
+    lon = axes["longitude"]
+    periodic = _is_global_longitude(lon, data) if lon_periodic is None else bool(lon_periodic)
+    if periodic:
+        if not -360.0 <= lon[0] <= 180.0:
+            lon = lon - 360.0 * np.floor((lon[0] + 180.0) / 360.0)
+        end = lon[0] + 360.0
+        spacing = (lon[-1] - lon[0]) / max(len(lon) - 1, 1)
+        if lon[-1] > end + 1e-6 * spacing:
+            raise ValueError("a periodic longitude axis must not span more than 360 degrees")
+        if len(lon) > 1 and abs(lon[-1] - end) <= 1e-6 * spacing:
+            lon = np.concatenate([lon[:-1], [end]])
+        else:
+            lon = np.concatenate([lon, [end]])
+            data = np.concatenate([data, data[..., :1]], axis=-1)
+        if not (np.diff(lon) > 0).all():
+            raise ValueError("the longitude axis cannot be closed at lon[0] + 360")
+    return axes["depth"], axes["latitude"], lon, np.ascontiguousarray(data), parameters, periodic
+
+
+def sample_regular_grid(grid, points, parameters=None, outside="fill", fill_value=np.nan, lon_periodic=None, context=None):
+    """A :class:`RegularGrid` sampled at ``points`` f64[N, 3] (metres, Earth-centred): trilinear in (depth, geocentric
+    latitude, longitude), with ``depth = 6371000 - |p|`` -- the inverse of :func:`latlondepth_to_xyz`, evaluated on the
+    device (:meth:`Context.sample_grid`, where the arithmetic is stated).  ``parameters``: names of ``grid.data_vars``
+    (None: all).  ``outside``: "fill" (points outside the grid get ``fill_value``) or "clamp" (the edge value extends).
+    ``lon_periodic``: None detects a global longitude axis (``0 ... 357.5``, or ``-180 ... 180`` with the first column
+    repeated), which then wraps; see :func:`prepare_regular_grid` for what is done to the axes.  A NaN node makes the
+    values of its eight cells NaN.  Returns (values f64[C, N], number of points outside the grid)."""
+    depth, lat, lon, data, _, periodic = prepare_regular_grid(grid, parameters, lon_periodic)
+    if outside == "keep":
+        raise ValueError('outside="keep" needs values to keep: use import_regular_grid, or Context.sample_grid with out')
+    ctx = context or default_context()
+    values, nmissing = ctx.sample_grid(points, data, depth, lat, lon, outside=outside, fill_value=fill_value,
+                                       lon_periodic=periodic)
+    return values.numpy(), nmissing
+
+
+def import_regular_grid(grid, mesh, parameters=None, outside="keep", fill_value=np.nan, lon_periodic=None,
+                        make_spherical=False, context=None):
+    """A gridded model onto a mesh: every node of ``mesh`` gets the value of ``grid`` at its (geocentric latitude,
+    longitude, depth = 6371000 - |p|), as :func:`sample_regular_grid` gives it.
+
+    ``grid``: a :class:`RegularGrid` or the path of a netCDF file (:meth:`RegularGrid.from_netcdf`).  ``mesh``:
+
+    * a :class:`GllMesh`: ``element_nodal_fields[p]`` becomes a new f64[E, P] array;
+    * a :class:`HexMesh`: nodal fields through ``attach_field``;
+    * a writable Salvus model -- an h5py-like object (:class:`multimesh_amd.io.MemoryH5`) or, with h5py, a path: the
+      columns of ``MODEL/data`` that ``DIMENSION_LABELS`` names are overwritten in place, every other column stays as it
+      is.  A parameter the labels do not hold raises ``ValueError`` before anything is written.
+
+    ``parameters``: None = every variable of the grid.  ``outside``: "keep" (default: nodes outside the grid keep the
+    mesh's value; the field must exist, else ``ValueError``), "fill" or "clamp".  ``make_spherical`` evaluates the
+    coordinates on a copy of the mesh mapped onto its 1-D sphere (:func:`map_to_sphere`), as the extract drivers do; the
+    mesh's own coordinates never change.  Returns the number of nodes outside the grid."""
+    from . import io as mio
+
+    if outside not in ("keep", "fill", "clamp"):
+        raise ValueError(f'outside must be "keep", "fill" or "clamp", got {outside!r}')
+    if not isinstance(grid, RegularGrid):
+        grid = RegularGrid.from_netcdf(grid)
+    depth, lat, lon, data, parameters, periodic = prepare_regular_grid(grid, parameters, lon_periodic)
+
+    def ctx():   # (asked for when the first kernel runs: what is wrong with the arguments is said without a device)
+        return context or default_context()
+
+    def run(points, existing):
+        """existing: name -> array of the points' leading shape (keep mode reads it) -> values f64[C, ...] (host)"""
+        lead = tuple(np.shape(points)[:-1]) if not isinstance(points, DeviceArray) else points.shape[:-1]
+        out = None
+        if outside == "keep":
+            out = np.ascontiguousarray(np.stack([np.asarray(existing[p], dtype=np.float64).reshape(lead)
+                                                 for p in parameters]) if parameters else np.zeros((0,) + lead))
+        values, nmissing = ctx().sample_grid(points, data, depth, lat, lon, outside=outside, fill_value=fill_value,
+                                             lon_periodic=periodic, out=out)
+        return values.numpy().reshape((len(parameters),) + lead), nmissing
+
+    if isinstance(mesh, (GllMesh, HexMesh)):
+        pts = np.asarray(_mesh_points(mesh))
+        if pts.shape[-1] != 3:
+            raise ValueError(f"import_regular_grid needs a 3-D mesh (points of shape {pts.shape})")
+        fields = mesh.element_nodal_fields if isinstance(mesh, GllMesh) else mesh.nodal_fields
+        if outside == "keep":
+            absent = [p for p in parameters if p not in fields]
+            if absent:
+                raise ValueError(f'outside="keep" keeps the mesh\'s values, but it has no field(s) {absent}')
+        values, nmissing = run(_sphere_mapped(mesh, ctx()) if make_spherical else pts, fields)
+        for c, p in enumerate(parameters):
+            if isinstance(mesh, GllMesh):
+                mesh.element_nodal_fields[p] = np.ascontiguousarray(values[c])
+            else:
+                mesh.attach_field(p, values[c])
+        return nmissing
+
+    with mio.open_h5(mesh, "r+") as f:
+        model = f["MODEL/data"]
+        names = mio.dimension_labels(model, 1)
+        unknown = [p for p in parameters if p not in names]
+        if unknown:
+            raise ValueError(f"parameters {unknown} are not in MODEL/data (it holds {names})")
+        points = np.array(f["MODEL/coordinates"][()], dtype=np.float64)
+        if points.ndim != 3 or points.shape[2] != 3:
+            raise ValueError(f"MODEL/coordinates must be [nelem, P, 3], got {points.shape}")
+        columns = {p: names.index(p) for p in parameters}
+        existing = {p: np.array(model[:, columns[p], :], dtype=np.float64) for p in parameters} if outside == "keep" else {}
+        if make_spherical:
+            if "z_node_1D" not in names:
+                raise ValueError("make_spherical needs the model's z_node_1D, which MODEL/data does not hold")
+            order = int(round(points.shape[1] ** (1.0 / 3.0))) - 1
+            z = np.array(model[:, names.index("z_node_1D"), :], dtype=np.float64)
+            sample_at = _sphere_mapped(GllMesh(points, order, {"z_node_1D": z}), ctx())
+        else:
+            sample_at = points
+        values, nmissing = run(sample_at, existing)
+        for c, p in enumerate(parameters):
+            model[:, columns[p], :] = values[c]
+    return nmissing

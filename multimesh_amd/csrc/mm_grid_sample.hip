@@ -1,0 +1,226 @@
+// A regular latitude x longitude x depth grid sampled at arbitrary points: the import direction of the regular-grid
+// drivers (mm_sample_columns_gll is the extract direction).  One lane per point in a grid-stride loop:
+//
+//   r = sqrt((x*x + y*y) + z*z)    depth = 6371000 - r    lat = 90 - acos(r > 0 ? z / r : 0) * (180 / pi)
+//   lon = atan2(y, x) * (180 / pi), wrapped once into [lon[0], lon[0] + 360) on a periodic axis
+//   per axis: i = clip(upper_bound(a, v) - 1, 0, n - 2), t = (v - a[i]) / (a[i + 1] - a[i]); a length-1 axis is constant
+//   value = lerp over longitude (4), then latitude (2), then depth (1), lerp(t, p, q) = (1 - t) * p + t * q
+//
+// Every product, quotient and sum is rounded on its own (the library is built with -ffp-contract=off), so the values are
+// bit for bit the NumPy statement of include/multimesh_hip.h evaluated on the (lat, lon, depth) this kernel computed;
+// those depend on the device's acos and atan2 and are what latlondepth_out_d hands back.
+//
+// Traffic: 24 B read + 8 B per component written per point, plus the eight corners per component, which neighbouring
+// points share (mesh points are ordered in space, so a wave's corners sit in a few cache lines of a cube that is small
+// beside the points).  The axes are staged in LDS when the three together fit kAxisLds doubles and bisected there;
+// longer axes are bisected in global memory.  The outside count is an integer: summed per workgroup, then one atomic per
+// workgroup, so it does not depend on the order of arrival.
+#include "mm_common.h"
+
+#include <limits.h>
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr i64 kMaxBlocks = 2048;    // 256 CUs x 8 workgroups; the grid-stride loop takes the rest
+constexpr int kAxisLds = 2048;      // doubles of LDS for the three axes together (16 KiB: eight workgroups per CU)
+constexpr double kEarthRadius = 6371000.0;
+constexpr double kRadToDeg = 180.0 / 3.14159265358979323846;
+
+enum { kFill = 0, kClamp = 1, kKeep = 2 };
+
+struct GridArgs {
+    const double *points;
+    i64 npoints;
+    const double *depth, *lat, *lon;
+    int ndepth, nlat, nlon;
+    const double *grid;
+    int ncomp;
+    int lon_periodic, mode;
+    double fill;
+    double *out, *lld;
+    unsigned long long *outside;
+};
+
+struct Cell {
+    int i, i1;
+    double t;
+    bool inside;
+};
+
+// np.searchsorted(a, v, side="right") - 1 clipped to [0, n - 2], and the weight in that cell.  NaN is outside (and, in
+// clamp mode, stays NaN: the comparisons are all false for it, so it sorts behind the last node as in NumPy).
+__device__ __forceinline__ Cell find_cell(const double *a, int n, double v, bool clamp)
+{
+    Cell c = {0, 0, 0.0, true};
+    if (n == 1) return c;
+    const double lo = a[0], hi = a[n - 1];
+    if (clamp) {
+        v = v < lo ? lo : v;
+        v = v > hi ? hi : v;
+    } else {
+        c.inside = v >= lo && v <= hi;
+        if (!c.inside) return c;
+    }
+    int b = 0, e = n;   // first index whose node is greater than v
+    while (b < e) {
+        const int mid = (b + e) >> 1;
+        if (!(v < a[mid]))
+            b = mid + 1;
+        else
+            e = mid;
+    }
+    int i = b - 1;
+    i = i < 0 ? 0 : i;
+    i = i > n - 2 ? n - 2 : i;
+    c.i = i;
+    c.i1 = i + 1;
+    c.t = (v - a[i]) / (a[i + 1] - a[i]);
+    return c;
+}
+
+__device__ __forceinline__ double lerp(double t, double p, double q) { return (1.0 - t) * p + t * q; }
+
+__device__ __forceinline__ double sample_one(const double *__restrict__ g, i64 row, i64 plane, const Cell &cd,
+                                             const Cell &ca, const Cell &co)
+{
+    const double *g0 = g + (i64)cd.i * plane, *g1 = g + (i64)cd.i1 * plane;
+    const i64 r0 = (i64)ca.i * row, r1 = (i64)ca.i1 * row;
+    const double a00 = lerp(co.t, g0[r0 + co.i], g0[r0 + co.i1]);
+    const double a01 = lerp(co.t, g0[r1 + co.i], g0[r1 + co.i1]);
+    const double a10 = lerp(co.t, g1[r0 + co.i], g1[r0 + co.i1]);
+    const double a11 = lerp(co.t, g1[r1 + co.i], g1[r1 + co.i1]);
+    return lerp(cd.t, lerp(ca.t, a00, a01), lerp(ca.t, a10, a11));
+}
+
+// NC: components unrolled (1..4), 0: a loop over args.ncomp.  LDS_AXES: the axes are copied to LDS first.
+template <int NC, bool LDS_AXES>
+__global__ __launch_bounds__(kThreads) void grid_sample_kernel(const GridArgs args)
+{
+    __shared__ double s_axes[LDS_AXES ? kAxisLds : 1];
+    __shared__ unsigned s_count[kThreads / 64];
+
+    const int nd = args.ndepth, nla = args.nlat, nlo = args.nlon;
+    const double *depth_a = args.depth, *lat_a = args.lat, *lon_a = args.lon;
+    if (LDS_AXES) {
+        for (int q = threadIdx.x; q < nd + nla + nlo; q += kThreads)
+            s_axes[q] = q < nd ? args.depth[q] : (q < nd + nla ? args.lat[q - nd] : args.lon[q - nd - nla]);
+        __syncthreads();
+        depth_a = s_axes;
+        lat_a = s_axes + nd;
+        lon_a = s_axes + nd + nla;
+    }
+    const int ncomp = NC ? NC : args.ncomp;
+    const i64 row = nlo, plane = (i64)nla * nlo, cube = plane * nd, n = args.npoints;
+    const bool clamp = args.mode == kClamp;
+    const double lon0 = lon_a[0];
+    unsigned outside = 0;
+
+    const i64 stride = (i64)gridDim.x * blockDim.x;
+    for (i64 p = (i64)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += stride) {
+        const double x = args.points[3 * p], y = args.points[3 * p + 1], z = args.points[3 * p + 2];
+        const double r = sqrt((x * x + y * y) + z * z);
+        const double depth = kEarthRadius - r;
+        const double c = r > 0.0 ? z / r : 0.0;
+        const double lat = 90.0 - acos(c) * kRadToDeg;
+        double lon = atan2(y, x) * kRadToDeg;
+        if (args.lon_periodic) {
+            if (lon < lon0) lon += 360.0;
+            if (lon >= lon0 + 360.0) lon -= 360.0;
+        }
+        if (args.lld) {
+            args.lld[3 * p] = lat;
+            args.lld[3 * p + 1] = lon;
+            args.lld[3 * p + 2] = depth;
+        }
+        const Cell cd = find_cell(depth_a, nd, depth, clamp);
+        const Cell ca = find_cell(lat_a, nla, lat, clamp);
+        const Cell co = find_cell(lon_a, nlo, lon, clamp);
+        if (cd.inside && ca.inside && co.inside) {
+            if (NC) {
+#pragma unroll
+                for (int q = 0; q < NC; ++q) args.out[q * n + p] = sample_one(args.grid + q * cube, row, plane, cd, ca, co);
+            } else {
+                for (int q = 0; q < ncomp; ++q) args.out[q * n + p] = sample_one(args.grid + q * cube, row, plane, cd, ca, co);
+            }
+        } else {
+            ++outside;
+            if (args.mode == kFill)
+                for (int q = 0; q < ncomp; ++q) args.out[q * n + p] = args.fill;
+        }
+    }
+
+    // workgroup sum of the outside counts, then one atomic
+    for (int off = 32; off > 0; off >>= 1) outside += __shfl_down(outside, off, 64);
+    if ((threadIdx.x & 63) == 0) s_count[threadIdx.x >> 6] = outside;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned total = 0;
+        for (int w = 0; w < kThreads / 64; ++w) total += s_count[w];
+        if (total) atomicAdd(args.outside, (unsigned long long)total);
+    }
+}
+
+template <bool LDS_AXES>
+void launch(mm_context *ctx, const GridArgs &a, unsigned grid)
+{
+    switch (a.ncomp) {
+    case 1: hipLaunchKernelGGL((grid_sample_kernel<1, LDS_AXES>), dim3(grid), dim3(kThreads), 0, ctx->stream, a); break;
+    case 2: hipLaunchKernelGGL((grid_sample_kernel<2, LDS_AXES>), dim3(grid), dim3(kThreads), 0, ctx->stream, a); break;
+    case 3: hipLaunchKernelGGL((grid_sample_kernel<3, LDS_AXES>), dim3(grid), dim3(kThreads), 0, ctx->stream, a); break;
+    case 4: hipLaunchKernelGGL((grid_sample_kernel<4, LDS_AXES>), dim3(grid), dim3(kThreads), 0, ctx->stream, a); break;
+    default: hipLaunchKernelGGL((grid_sample_kernel<0, LDS_AXES>), dim3(grid), dim3(kThreads), 0, ctx->stream, a); break;
+    }
+}
+
+}  // namespace
+
+extern "C" int64_t mm_sample_grid(mm_context *ctx, const double *points_d, int64_t npoints, const double *depth_d,
+                                  int64_t ndepth, const double *lat_d, int64_t nlat, const double *lon_d, int64_t nlon,
+                                  const double *grid_d, int64_t ncomp, int lon_periodic, int outside_mode,
+                                  double fill_value, double *out_d, double *latlondepth_out_d)
+{
+    MM_REQUIRE(ctx != nullptr, "ctx is null");
+    MM_REQUIRE(npoints >= 0 && ncomp >= 0, "negative size");
+    MM_REQUIRE(depth_d && lat_d && lon_d, "null axis");
+    MM_REQUIRE(ndepth >= 1 && nlat >= 1 && nlon >= 1, "every axis needs at least one node");
+    MM_REQUIRE(outside_mode == kFill || outside_mode == kClamp || outside_mode == kKeep, "outside_mode must be 0, 1 or 2");
+    MM_REQUIRE(ncomp == 0 || (grid_d && (out_d || npoints == 0)), "null grid or output");
+    MM_REQUIRE(points_d != nullptr || npoints == 0, "null points");
+    if (ndepth > INT_MAX || nlat > INT_MAX || nlon > INT_MAX || ncomp > INT_MAX || npoints >= ((i64)1 << 58) ||
+        (ncomp > 0 && npoints > LLONG_MAX / 8 / ncomp)) {
+        mm_set_error(MM_ERR_UNSUPPORTED, "mm_sample_grid: an axis, the component count or the point count is out of range");
+        return MM_ERR_UNSUPPORTED;
+    }
+    if (npoints == 0) return 0;
+    MM_HIP_CHECK(hipSetDevice(ctx->device));
+    unsigned long long *counter = (unsigned long long *)ctx->d_counters;
+    if (mm_zero_async(ctx, counter, sizeof(i64)) != MM_OK) return MM_ERR_HIP;
+    GridArgs a;
+    a.points = points_d;
+    a.npoints = npoints;
+    a.depth = depth_d;
+    a.lat = lat_d;
+    a.lon = lon_d;
+    a.ndepth = (int)ndepth;
+    a.nlat = (int)nlat;
+    a.nlon = (int)nlon;
+    a.grid = grid_d;
+    a.ncomp = (int)ncomp;
+    a.lon_periodic = lon_periodic ? 1 : 0;
+    a.mode = outside_mode;
+    a.fill = fill_value;
+    a.out = out_d;
+    a.lld = latlondepth_out_d;
+    a.outside = counter;
+    const i64 blocks = (npoints + kThreads - 1) / kThreads;
+    const unsigned grid = (unsigned)(blocks < kMaxBlocks ? blocks : kMaxBlocks);
+    if (ndepth + nlat + nlon <= kAxisLds)
+        launch<true>(ctx, a, grid);
+    else
+        launch<false>(ctx, a, grid);
+    MM_HIP_CHECK(hipGetLastError());
+    if (mm_mirror_async(ctx, (long long *)ctx->h_counters, (const long long *)counter, 1) != MM_OK) return MM_ERR_HIP;
+    MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return ctx->h_counters[0];
+}

@@ -768,6 +768,56 @@ class Context:
             return out, int(miss), pts
         return out, int(miss)
 
+    def sample_grid(self, points, grid_values, depth, lat, lon, outside="fill", fill_value=np.nan, lon_periodic=False,
+                    out=None, want_latlondepth=False):
+        """A regular grid sampled at points (``mm_sample_grid``): ``points`` f64[..., 3] (N points, read flat),
+        ``grid_values`` f64[C, D, LA, LO] (or [D, LA, LO]) over the strictly ascending axes ``depth`` f64[D] (m below
+        6371 km), ``lat`` f64[LA] (geocentric degrees) and ``lon`` f64[LO] (degrees; host axes are checked here, device
+        axes are the caller's word).  Trilinear, every operation rounded as include/multimesh_hip.h states; a NaN
+        corner makes the values of its cell NaN.  ``outside``: "fill" (``fill_value``), "clamp" (the edge value
+        extends) or "keep" (``out``, which is then required, keeps its entries).  ``lon_periodic``: the longitude is
+        wrapped into [lon[0], lon[0] + 360), and the axis must start in [-360, 180] and end at ``lon[0] + 360``.
+        Returns (values f64[C, N], number of points outside the grid) or, with ``want_latlondepth``, (values,
+        nmissing, latlondepth f64[N, 3]) -- the (lat, lon, depth) the device computed."""
+        modes = {"fill": 0, "clamp": 1, "keep": 2}
+        if outside not in modes:
+            raise ValueError(f"outside must be one of {sorted(modes)}, got {outside!r}")
+        pts, n = self._points3(points)
+        g = self.asdevice(grid_values, np.float64)
+        if len(g.shape) == 3:
+            g = DeviceArray(self, g.ptr, (1,) + g.shape, g.dtype, owner=False, keepalive=g)
+        axes = []
+        for name, a in (("depth", depth), ("lat", lat), ("lon", lon)):
+            if isinstance(a, np.ndarray) or not hasattr(a, "data_ptr"):
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.ndim != 1 or a.size < 1 or not np.isfinite(a).all() or not (np.diff(a) > 0).all():
+                    raise ValueError(f"the {name} axis must be 1-D, finite and strictly ascending")
+                if name == "lon" and lon_periodic and (not -360.0 <= a[0] <= 180.0 or a[-1] != a[0] + 360.0):
+                    raise ValueError("a periodic lon axis must start in [-360, 180] and end at lon[0] + 360")
+            a = self.asdevice(a, np.float64)
+            if len(a.shape) != 1 or a.shape[0] < 1:
+                raise ValueError(f"the {name} axis must be 1-D with at least one node")
+            axes.append(a)
+        d, la, lo = axes
+        if len(g.shape) != 4 or g.shape[1:] != (d.shape[0], la.shape[0], lo.shape[0]):
+            raise ValueError(f"grid_values must be [C, {d.shape[0]}, {la.shape[0]}, {lo.shape[0]}] over the axes, got {g.shape}")
+        ncomp = g.shape[0]
+        if out is None:
+            if outside == "keep":
+                raise ValueError('outside="keep" keeps the entries of out: pass out')
+            out = self.empty((ncomp, n), np.float64)
+        else:
+            out = self.asdevice(out, np.float64)
+            if len(out.shape) < 2 or out.shape[0] != ncomp or out.size != ncomp * n:
+                raise ValueError("out must be [C, N] (or [C, ...] over the leading shape of points)")
+        lld = self.empty((n, 3), np.float64) if want_latlondepth else None
+        miss = check(self.lib.mm_sample_grid(self.handle, pts.ptr, n, d.ptr, d.shape[0], la.ptr, la.shape[0], lo.ptr,
+                                             lo.shape[0], g.ptr, ncomp, 1 if lon_periodic else 0, modes[outside],
+                                             float(fill_value), out.ptr, lld.ptr if lld else None), "mm_sample_grid")
+        if want_latlondepth:
+            return out, int(miss), lld
+        return out, int(miss)
+
     def interpolate_hex8(self, nodes, connectivity, points, fields, nelem_to_search=20, want_operator=False,
                          out=None):
         """The whole hot path of reference scripts/cli.py:62-100 on resident arrays.

@@ -48,6 +48,7 @@ EXPORTED_SYMBOLS = (
     "mm_set_fp_mode", "mm_get_fp_mode", "mm_last_locate_stats", "mm_last_knn_kernels",
     "mm_source_create", "mm_source_destroy", "mm_interpolate_hex8_on", "mm_points_to_elements", "mm_unique_points_any_order",
     "mm_map_to_sphere", "mm_first_occurrence", "mm_sphere_ratio", "mm_scale_points", "mm_sample_columns_gll",
+    "mm_sample_grid",
     "mm_transpose_create_nodes", "mm_transpose_create_elem", "mm_transpose_apply", "mm_transpose_destroy",
     "mm_gll_mass", "mm_weighted_sum", "mm_divide_rows",
     "mm_gll_diffusion_apply", "mm_pcg_combine", "mm_pcg_scalars", "mm_pcg_direction", "mm_pcg_advance",
@@ -144,6 +145,9 @@ def load_lib():
     lib.mm_sample_columns_gll.restype = C.c_int64
     lib.mm_sample_columns_gll.argtypes = [vp, C.c_int, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, C.c_int,
                                           vp, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int64, vp, vp]
+    lib.mm_sample_grid.restype = C.c_int64
+    lib.mm_sample_grid.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int,
+                                   C.c_double, vp, vp]
     lib.mm_locate_gll_bbox.restype = C.c_int64
     lib.mm_locate_gll_bbox.argtypes = [vp, C.c_int, C.c_int, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp, vp, vp]
     lib.mm_unique_points.restype = C.c_int64

@@ -324,6 +324,29 @@ int mm_gll_diffusion_apply(mm_context *ctx, int order, int dim, const double *gl
                            const double *deriv_d, const double *weights_d, const double *u_d, int64_t ncomp, double kappa_h,
                            const double *kappa_h_d, int anisotropic, double kappa_r, const double *kappa_r_d, double *y_d);
 
+/* The SPATIAL GRADIENT of element-nodal GLL fields, as fields: the physical gradient grad u = G grad_ref u that the stiffness
+ * operator forms at every node, written out per element and NOT assembled (the gradient of a C0 field jumps across element
+ * faces: the copies of a shared node differ), with its norm and, on a 3-D Earth mesh, its split into the radial derivative
+ * and the lateral part -- what first-order regularisation, total variation and maps of |grad m| read.  Every (component,
+ * direction) plane is an ordinary element-nodal field.  The reference has no counterpart.
+ *   gll_points_d, order, dim, deriv_d, the node numbering p = i + m j + m^2 k: as mm_gll_mass (no weights are needed).
+ *   u_d f64[ncomp][nelem][P].  Four nullable outputs, at least one of them given:
+ *   grad_d f64[ncomp][dim][nelem][P];  radial_d, lateral_d (3-D only), norm_d f64[ncomp][nelem][P].
+ * Every product is rounded on its own, every sum starts from its first term and adds in ascending a.  At node (i, j, k):
+ *   J, det, rdet = 1 / det, G[c][d]     : as mm_gll_diffusion_apply (the same expressions, the one division)
+ *   g[0] = sum_a D[i][a] * u[a,j,k]     g[1] = sum_a D[j][a] * u[i,a,k]     g[2] = sum_a D[k][a] * u[i,j,a]
+ *   gr[c] = (G[c][0]*g[0] + G[c][1]*g[1]) + G[c][2]*g[2]                  (2-D: the first two terms)      -> grad_d[comp][c]
+ *   norm = sqrt((gr[0]*gr[0] + gr[1]*gr[1]) + gr[2]*gr[2])                (2-D: sqrt(gr[0]*gr[0] + gr[1]*gr[1])) -> norm_d
+ *   rn = sqrt((x*x + y*y) + z*z),  rh[c] = x[c] / rn (0 where rn == 0)
+ *   s = (rh[0]*gr[0] + rh[1]*gr[1]) + rh[2]*gr[2]                                                          -> radial_d
+ *   l[c] = gr[c] - s*rh[c],  lateral = sqrt((l[0]*l[0] + l[1]*l[1]) + l[2]*l[2])                           -> lateral_d
+ * A node with det == 0 gives the inf or NaN that IEEE arithmetic gives.  Returns MM_OK or a negative MM_ERR_*; MM_ERR_ARG
+ * (nothing is written) for an order or dim without tables, a null table or input, all four outputs null, radial_d or
+ * lateral_d with dim 2, an output that overlaps u_d or another output.  nelem == 0 and ncomp == 0 are valid.  Not
+ * synchronising. */
+int mm_gll_gradient(mm_context *ctx, int order, int dim, const double *gll_points_d, int64_t nelem, const double *deriv_d,
+                    const double *u_d, int64_t ncomp, double *grad_d, double *radial_d, double *lateral_d, double *norm_d);
+
 /* The streaming kernels of a preconditioned conjugate-gradient loop over ncomp independent systems of n unknowns each
  * (vectors f64[ncomp][n]), whose scalars never leave the device.  state_d f64[ncomp][8] holds, per system, the slots below:
  * the dots are written into MM_PCG_RZ, MM_PCG_PAP and MM_PCG_BB by mm_weighted_sum (one call per system with ncomp = 1).

@@ -25,7 +25,8 @@ Grid import, the other direction: :func:`sample_regular_grid` and :func:`import_
 Beyond the reference: the operator transposes, and the GLL mass matrix with what it weights -- :func:`gll_mass_matrix`,
 :func:`hex8_mass_matrix`, :func:`integrate`, :func:`assemble_gll`, :func:`apply_gll_operator_adjoint`,
 :func:`apply_operator_adjoint`; and the stiffness operator with the smoothing it gives -- :func:`gll_stiffness_apply`,
-:func:`gll_roughness`, :func:`smooth_gll`.
+:func:`gll_roughness`, :func:`smooth_gll`; and the gradient that operator integrates, as fields -- :func:`gll_gradient`,
+:func:`gll_gradient_parts`.
 """
 from __future__ import annotations
 
@@ -745,6 +746,55 @@ def smooth_gll(mesh, params, sigma, steps=4, rtol=1e-10, max_iter=2000, layers=N
             sub = tuple(x if x is None or np.ndim(x) == 0 else np.ascontiguousarray(x[mask]) for x in lengths)
             out[:, mask] = run(np.ascontiguousarray(pts[mask]), np.ascontiguousarray(fields[:, mask]), sub)
     return out
+
+
+# ---- the gradient of element-nodal fields, as fields (include/multimesh_hip.h, mm_gll_gradient).  The
+# stiffness operator forms it at every node and folds it into its flux; here it is written out.
+def _gradient(mesh, params, assemble, ctx, wanted):
+    """The planes ``wanted`` (flags of :meth:`Context.gll_gradient`) as NumPy arrays, node-averaged when ``assemble``."""
+    pts, order = _gll_points_order(mesh)
+    synth.gll_derivative_matrix(order)                                            # (ValueError for an order without tables)
+    u = _element_fields(mesh, params, pts.shape[:2])
+    if (wanted.get("radial") or wanted.get("lateral")) and pts.shape[2] != 3:
+        raise ValueError("the radial / lateral split needs a 3-D mesh: on a 2-D mesh use gll_gradient")
+    ctx = ctx or default_context()
+    gp = ctx.to_device(pts)
+    planes = ctx.gll_gradient(order, gp, u, **wanted)
+    planes = planes if isinstance(planes, tuple) else (planes,)
+    if assemble:
+        op = ctx.diffusion(order, gp)                                             # (its smooth(steps=0) IS the node average)
+        try:
+            planes = tuple(op.smooth(DeviceArray(ctx, v.ptr, (int(np.prod(v.shape[:-2])),) + pts.shape[:2], np.float64,
+                                                 owner=False, keepalive=v), steps=0) if v.size else v for v in planes)
+        finally:
+            op.free()
+    return pts, u.shape[0], [v.numpy() for v in planes]
+
+
+def gll_gradient(mesh, params, assemble=False, context=None):
+    """The spatial gradient of element-nodal fields of a :class:`GllMesh` or a Salvus mesh -> f64[C, dim, E, P]:
+    ``grad u = J^-1 grad_ref u`` at every GLL node, with the Jacobian of the element's own geometry (``mm_gll_gradient``,
+    bit for bit the statement of include/multimesh_hip.h; the gradient the stiffness operator of
+    :func:`gll_stiffness_apply` integrates).  ``params``: names of element-nodal fields, or an array [C, E, P] / [E, P].
+    Every ``[c, d]`` plane is an ordinary element-nodal field: it can be integrated, smoothed, gathered or put on a grid.
+
+    The gradient of a continuous field jumps across element faces, so the copies of a shared node differ.  With
+    ``assemble=True`` every plane is replaced by the mass-weighted mean over the copies of each unique node,
+    ``A(M_e v) / A(M_e)`` with ``M_e`` = :func:`gll_mass_matrix` and ``A`` = :func:`assemble_gll` -- the reduction
+    :func:`smooth_gll` applies to input copies that differ; the copies of a node then hold identical bits.  The mean is
+    taken of the planes as the kernel wrote them."""
+    pts, ncomp, (grad,) = _gradient(mesh, params, assemble, context, dict(grad=True))
+    return grad.reshape((ncomp, pts.shape[2]) + pts.shape[:2])
+
+
+def gll_gradient_parts(mesh, params, assemble=False, context=None):
+    """What an Earth model's gradient is read by, on a 3-D mesh: a dict of f64[C, E, P] with ``radial`` = the derivative
+    along ``x / |x|`` (signed), ``lateral`` = the norm of the gradient without its radial part, ``norm`` = ``|grad u|``
+    (``lateral^2 + radial^2 = norm^2`` up to rounding).  Arguments as :func:`gll_gradient`, which is the function for a 2-D
+    mesh (``ValueError`` here).  ``assemble=True`` node-averages every plane as the kernel wrote it: ``norm`` is then the
+    mean of the norms, not the norm of the mean gradient (and likewise ``lateral``)."""
+    pts, ncomp, parts = _gradient(mesh, params, assemble, context, dict(grad=False, radial=True, lateral=True, norm=True))
+    return {name: v.reshape((ncomp,) + pts.shape[:2]) for name, v in zip(("radial", "lateral", "norm"), parts)}
 
 
 def assess_layers(layer_ids, layers, fluid=None, moho_idx=None):

@@ -688,6 +688,38 @@ class Context:
                          None if kappa_r is None else kappa(kappa_r, "kappa_r"),
                          (self.to_device(deriv), self.to_device(weights)))
 
+    # ---- the gradient of element-nodal fields ------------------------------------------------------
+    def gll_gradient(self, shape_order, gll_points, u, grad=True, radial=False, lateral=False, norm=False):
+        """The spatial gradient of u f64[C, E, P] (or [E, P]) over gll_points f64[E, (order+1)^dim, dim], orders 1, 2, 4,
+        per element and not assembled (``mm_gll_gradient``: bit for bit the NumPy statement of include/multimesh_hip.h).
+        Returns the requested device arrays in the order of the flags -- ``grad`` f64[C, dim, E, P], ``radial`` (the
+        derivative along x / |x|), ``lateral`` (the norm of what is left of the gradient) and ``norm``, each f64[C, E, P] --
+        as a tuple, or the array itself when one is asked for.  ``radial`` and ``lateral`` need a 3-D mesh."""
+        from .synth import gll_derivative_matrix   # (ValueError for an order without tables)
+
+        deriv = gll_derivative_matrix(shape_order)
+        gp = self.asdevice(gll_points, np.float64)
+        if len(gp.shape) != 3 or gp.shape[2] not in (2, 3) or gp.shape[1] != (shape_order + 1) ** gp.shape[2]:
+            raise ValueError("gll_points must be [nelem, (order+1)^dim, dim] with dim 2 or 3")
+        nelem, P, dim = gp.shape
+        if not (grad or radial or lateral or norm):
+            raise ValueError("ask for at least one of grad, radial, lateral and norm")
+        if (radial or lateral) and dim != 3:
+            raise ValueError("the radial / lateral split needs a 3-D mesh")
+        v = self.asdevice(u, np.float64)
+        if v.shape == (nelem, P):
+            v = DeviceArray(self, v.ptr, (1,) + v.shape, v.dtype, owner=False, keepalive=v)
+        if len(v.shape) != 3 or v.shape[1:] != (nelem, P):
+            raise ValueError("u must be [C, E, P] (or [E, P]) over gll_points [E, P, dim]")
+        ncomp = v.shape[0]
+        outs = [self.empty((ncomp, dim, nelem, P) if full else (ncomp, nelem, P), np.float64) if want else None
+                for want, full in ((grad, True), (radial, False), (lateral, False), (norm, False))]
+        d_d = self.to_device(deriv)
+        check(self.lib.mm_gll_gradient(self.handle, int(shape_order), dim, gp.ptr, nelem, d_d.ptr, v.ptr, ncomp,
+                                       *(o.ptr if o else None for o in outs)), "mm_gll_gradient")
+        got = tuple(o for o in outs if o is not None)
+        return got[0] if len(got) == 1 else got
+
     # ---- fused ---------------------------------------------------------------------------
     def interpolate_gll(self, shape_order, gll_points, points, element_nodal_fields, nelem_to_search=20,
                         tolerance=1.05, snap_to_nearest=False, want_operator=False, out=None):

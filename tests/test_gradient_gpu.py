@@ -1,0 +1,227 @@
+"""The GLL gradient on the GPU.  mm_gll_gradient is compared BIT for bit with its NumPy statement (tests/gradient_cases.py):
+every output requested together and each one alone (which outputs are written is decided by pointer tests in the kernel:
+a wrong plane offset would hide there), 2-D and 3-D, orders 1, 2 and 4, one and three components, element counts around
+the tile of a 256-thread block (mass_cases.tile_elems), and an Earth chunk whose coordinates of ~6.4e6 m make the
+cancellation in the cofactors real.  Inputs have full mantissas (transpose_cases.wide)."""
+import numpy as np
+import pytest
+
+import diffusion_cases as DC
+import gradient_cases as GC
+import mass_cases as M
+import transpose_cases as T
+from multimesh_amd import api, helpers, synth
+from multimesh_amd.api import GllMesh
+from multimesh_amd.device import Context
+
+pytestmark = pytest.mark.gpu
+
+EPS = M.EPS
+MM_ERR_ARG = -1
+SHAPES = [(1, 2), (2, 2), (4, 2), (1, 3), (2, 3), (4, 3)]
+NAMES = ("grad", "radial", "lateral", "norm")
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    with Context(0) as c:
+        yield c
+
+
+def _tables(order):
+    _, w, D = api.gll_quadrature(order)
+    return w, D
+
+
+def _outputs(dim):
+    return NAMES if dim == 3 else ("grad", "norm")
+
+
+def _raw(ctx, gp, order, u, want):
+    """Straight at the ABI: the outputs named in ``want`` -> dict of NumPy arrays."""
+    _, D = _tables(order)
+    E, P, dim = gp.shape
+    ncomp = u.shape[0]
+    gp_d, u_d, D_d = ctx.to_device(gp), ctx.to_device(u), ctx.to_device(D)
+    out = {name: ctx.empty((ncomp, dim, E, P) if name == "grad" else (ncomp, E, P), np.float64) for name in want}
+    rc = ctx.lib.mm_gll_gradient(ctx.handle, order, dim, gp_d.ptr, E, D_d.ptr, u_d.ptr, ncomp,
+                                 *(out[name].ptr if name in out else None for name in NAMES))
+    assert rc == 0, helpers.load_lib().mm_last_error()
+    return {name: arr.numpy() for name, arr in out.items()}
+
+
+def _check(ctx, gp, order, ncomp, seed, what, alone=True):
+    rng = np.random.default_rng(seed)
+    u = T.wide(rng, (ncomp,) + gp.shape[:2])
+    _, D = _tables(order)
+    ref = dict(zip(NAMES, GC.gradient(gp, order, D, u)))
+    names = _outputs(gp.shape[2])
+    for want in [names] + ([(name,) for name in names] if alone else []):
+        got = _raw(ctx, gp, order, u, want)
+        for name in want:
+            assert got[name].shape == ref[name].shape, (what, want, name)
+            assert M.same_bits(got[name], ref[name]), (what, want, name, int((got[name] != ref[name]).sum()), ref[name].size)
+
+
+# ---------------------------------------------------------------------------------------------- mm_gll_gradient
+@pytest.mark.parametrize("ncomp", [1, 3])
+@pytest.mark.parametrize("order,dim", SHAPES)
+def test_gradient_bit_for_bit_on_gll_meshes(ctx, order, dim, ncomp):
+    gp = synth.gll_mesh(9 if dim == 3 else 30, order, seed=3, dim=dim)
+    _check(ctx, gp, order, ncomp, order * 100 + dim * 10 + ncomp, (order, dim))
+
+
+@pytest.mark.parametrize("order,dim", SHAPES)
+def test_gradient_element_counts_around_a_tile(ctx, order, dim):
+    tile = M.tile_elems(order, dim)
+    gp = synth.gll_mesh(6 if dim == 3 else 16, order, seed=5, dim=dim)            # 125 / 225 elements: >= 3 tile + tile / 2
+    counts = (0, 1, tile - 1, tile, tile + 1, 3 * tile + max(tile // 2, 1))
+    assert max(counts) <= len(gp)
+    for nelem in counts:
+        _check(ctx, np.ascontiguousarray(gp[:nelem]), order, 2, nelem, (order, dim, nelem), alone=False)
+
+
+@pytest.mark.parametrize("order", [1, 2, 4])
+def test_gradient_at_earth_scale(ctx, order):
+    chunk = synth.earth_chunk(order, nlat=5, nlon=6, ellipticity=3.3e-3, topography=3e-4)
+    for ncomp in (1, 3):
+        _check(ctx, chunk["points"], order, ncomp, order, ("earth", order), alone=False)
+
+
+# ---------------------------------------------------------------------------------------------- Context and api
+def test_gradient_through_the_context_and_the_api(ctx):
+    gp = synth.gll_mesh(6, 4, seed=3)
+    _, D = _tables(4)
+    rng = np.random.default_rng(4)
+    u = T.wide(rng, (2,) + gp.shape[:2])
+    grad, radial, lateral, norm = GC.gradient(gp, 4, D, u)
+    got = ctx.gll_gradient(4, gp, u, grad=True, radial=True, lateral=True, norm=True)
+    assert len(got) == 4
+    for g, r in zip(got, (grad, radial, lateral, norm)):
+        assert M.same_bits(g.numpy(), r)
+    assert M.same_bits(ctx.gll_gradient(4, gp, u).numpy(), grad)                              # the default: grad alone
+    assert M.same_bits(ctx.gll_gradient(4, gp, u[0], grad=False, norm=True).numpy(), norm[:1])   # [E, P]: one field
+    lat, nrm = ctx.gll_gradient(4, gp, u, grad=False, lateral=True, norm=True)
+    assert M.same_bits(lat.numpy(), lateral) and M.same_bits(nrm.numpy(), norm)
+    with pytest.raises(ValueError):
+        ctx.gll_gradient(4, gp, u, grad=False)
+    mesh = GllMesh(gp, 4, {"a": u[0], "b": u[1]})
+    assert M.same_bits(api.gll_gradient(mesh, ["a", "b"], context=ctx), grad)
+    assert M.same_bits(api.gll_gradient(mesh, u[1], context=ctx), grad[1:])
+    parts = api.gll_gradient_parts(mesh, ["a", "b"], context=ctx)
+    assert sorted(parts) == ["lateral", "norm", "radial"]
+    assert M.same_bits(parts["radial"], radial) and M.same_bits(parts["lateral"], lateral) and M.same_bits(parts["norm"], norm)
+    # 2-D: the gradient and its norm; no split
+    gp2 = synth.gll_mesh(9, 2, seed=3, dim=2)
+    _, D2 = _tables(2)
+    u2 = T.wide(rng, (1,) + gp2.shape[:2])
+    ref2 = GC.gradient(gp2, 2, D2, u2)
+    assert M.same_bits(api.gll_gradient(GllMesh(gp2, 2), u2, context=ctx), ref2[0])
+    g2, n2 = ctx.gll_gradient(2, gp2, u2, norm=True)
+    assert M.same_bits(g2.numpy(), ref2[0]) and M.same_bits(n2.numpy(), ref2[3])
+    with pytest.raises(ValueError):
+        ctx.gll_gradient(2, gp2, u2, radial=True)
+    with pytest.raises(ValueError):
+        api.gll_gradient_parts(GllMesh(gp2, 2), u2, context=ctx)
+
+
+@pytest.mark.parametrize("order,dim", SHAPES)
+def test_linear_field_gives_the_constant_gradient(ctx, order, dim):
+    """The bound of tests/test_gradient.py, on the device."""
+    gp = synth.gll_mesh(GC.SIDE[dim], order, seed=3, dim=dim)
+    _, D = _tables(order)
+    a = GC.A[:dim]
+    got = api.gll_gradient(GllMesh(gp, order), gp @ a + 0.75, context=ctx)
+    err = np.abs(got[0] - a[:, None, None]).max()
+    bound, multiple = GC.linear_bound(order, dim, D)
+    print(f"order {order} dim {dim}: max |gr - a| = {err:.2e}, bound {bound:.2e} = {multiple:.1f} EPS max|a| cond")
+    assert err <= bound
+
+
+def test_assembled_gradient_is_the_mass_weighted_node_mean(ctx):
+    """assemble=True: every plane becomes A(M_e v) / A(M_e) over the copies of each unique node, of the planes as the kernel
+    wrote them (the norm is the mean of the norms).  Against diffusion_cases.node_mean of the statement's planes, within
+    the bound tests/test_mass_gpu.py puts on a sum over the at most 8 copies of a node, 8 * 2^-52 times the magnitude of
+    what is summed -- here the same mean of the planes' absolute values."""
+    order = 2
+    gp = DC.welded(synth.gll_mesh(5, order, seed=3))
+    w, D = _tables(order)
+    nu, inv = DC.unique_nodes(gp)
+    assert nu == (order * 4 + 1) ** 3
+    rng = np.random.default_rng(11)
+    u = np.stack([np.cos(3.0 * gp[..., 0]) * gp[..., 1] + gp[..., 2] ** 2, rng.normal(size=nu)[inv].reshape(gp.shape[:2])])
+    grad, radial, lateral, norm = GC.gradient(gp, order, D, u)
+    me = M.mass(gp, order, w, D)[0].reshape(-1)
+    Mu = np.zeros(nu)
+    np.add.at(Mu, inv, me)
+    mesh = GllMesh(gp, order)
+    got = {"grad": api.gll_gradient(mesh, u, assemble=True, context=ctx),
+           **api.gll_gradient_parts(mesh, u, assemble=True, context=ctx)}
+    assert got["grad"].shape == grad.shape
+    for name, planes in (("grad", grad), ("radial", radial), ("lateral", lateral), ("norm", norm)):
+        ref = DC.node_mean(planes, inv, me, Mu)[:, inv].reshape(planes.shape)
+        bound = 8 * EPS * DC.node_mean(np.abs(planes), inv, me, Mu)[:, inv].reshape(planes.shape)
+        diff = np.abs(got[name] - ref)
+        print(f"{name}: max |difference| / bound = {(diff / np.maximum(bound, 1e-300)).max():.3e}")
+        assert (diff <= bound).all(), name
+        flat = got[name].reshape(-1, inv.size)
+        per_node = np.empty((flat.shape[0], nu))
+        per_node[:, inv] = flat
+        assert M.same_bits(per_node[:, inv], flat), "copies of a shared node differ"
+    # the copies did differ before: the gradient of a C0 field jumps across element faces
+    assert not M.same_bits(api.gll_gradient(mesh, u, context=ctx), got["grad"])
+    # the mean of the norms is not the norm of the mean
+    mean_grad = got["grad"]
+    assert (got["norm"] >= np.sqrt((mean_grad ** 2).sum(axis=1)) * (1.0 - 16 * EPS)).all()
+
+
+# ---------------------------------------------------------------------------------------------- error paths
+def test_error_paths(ctx):
+    lib = helpers.load_lib()
+    gp = synth.gll_mesh(4, 2, seed=3)
+    gp2 = synth.gll_mesh(5, 2, seed=3, dim=2)
+    E, P, _ = gp.shape
+    E2, P2, _ = gp2.shape
+    _, D = _tables(2)
+    sentinel = np.full((1, 3, E, P), -7.0)
+    big = ctx.to_device(sentinel)                                   # room for any one output, 2-D or 3-D
+    other = ctx.to_device(sentinel)
+    u = ctx.to_device(np.ones((1, E, P)))
+    gp_d, gp2_d, D_d = ctx.to_device(gp), ctx.to_device(gp2), ctx.to_device(D)
+    h, fn = ctx.handle, lib.mm_gll_gradient
+    y, z = big.ptr, other.ptr
+    plane = 8 * E * P
+    cases = {
+        "order": fn(h, 3, 3, gp_d.ptr, E, D_d.ptr, u.ptr, 1, y, None, None, None),
+        "dim 1": fn(h, 2, 1, gp_d.ptr, E, D_d.ptr, u.ptr, 1, y, None, None, None),
+        "dim 4": fn(h, 2, 4, gp_d.ptr, E, D_d.ptr, u.ptr, 1, y, None, None, None),
+        "null D": fn(h, 2, 3, gp_d.ptr, E, None, u.ptr, 1, y, None, None, None),
+        "null points": fn(h, 2, 3, None, E, D_d.ptr, u.ptr, 1, y, None, None, None),
+        "null u": fn(h, 2, 3, gp_d.ptr, E, D_d.ptr, None, 1, y, None, None, None),
+        "nelem": fn(h, 2, 3, gp_d.ptr, -1, D_d.ptr, u.ptr, 1, y, None, None, None),
+        "ncomp": fn(h, 2, 3, gp_d.ptr, E, D_d.ptr, u.ptr, -1, y, None, None, None),
+        "no output": fn(h, 2, 3, gp_d.ptr, E, D_d.ptr, u.ptr, 1, None, None, None, None),
+        "no output, no elements": fn(h, 2, 3, gp_d.ptr, 0, D_d.ptr, u.ptr, 1, None, None, None, None),
+        "radial in 2-D": fn(h, 2, 2, gp2_d.ptr, E2, D_d.ptr, u.ptr, 1, None, y, None, None),
+        "lateral in 2-D": fn(h, 2, 2, gp2_d.ptr, E2, D_d.ptr, u.ptr, 1, z, None, y, None),
+        "grad is u": fn(h, 2, 3, gp_d.ptr, E, D_d.ptr, y, 1, y, None, None, None),
+        "norm is u": fn(h, 2, 3, gp_d.ptr, E, D_d.ptr, y, 1, None, None, None, y),
+        "radial is lateral": fn(h, 2, 3, gp_d.ptr, E, D_d.ptr, u.ptr, 1, None, y, y, None),
+        "norm is grad": fn(h, 2, 3, gp_d.ptr, E, D_d.ptr, u.ptr, 1, y, None, None, y),
+        "norm inside grad": fn(h, 2, 3, gp_d.ptr, E, D_d.ptr, u.ptr, 1, y, None, None, y + 2 * plane),
+        "lateral is norm": fn(h, 2, 3, gp_d.ptr, E, D_d.ptr, u.ptr, 1, None, None, z, z),
+    }
+    assert E2 * P2 <= E * P
+    for what, rc in cases.items():
+        assert rc == MM_ERR_ARG, what
+    assert M.same_bits(big.numpy(), sentinel) and M.same_bits(other.numpy(), sentinel)
+    # nothing to do is not an error, and writes nothing
+    assert fn(h, 2, 3, gp_d.ptr, 0, D_d.ptr, u.ptr, 1, y, None, None, z) == 0
+    assert fn(h, 2, 3, gp_d.ptr, E, D_d.ptr, u.ptr, 0, y, None, None, z) == 0
+    assert fn(h, 2, 3, None, 0, D_d.ptr, None, 1, y, None, None, None) == 0
+    assert M.same_bits(big.numpy(), sentinel) and M.same_bits(other.numpy(), sentinel)
+    # neighbours in one allocation are not an overlap
+    assert fn(h, 2, 3, gp_d.ptr, E, D_d.ptr, u.ptr, 1, None, y, y + plane, y + 2 * plane) == 0
+    ref = GC.gradient(gp, 2, D, np.ones((1, E, P)))
+    got = big.numpy().reshape(3, E, P)
+    assert all(M.same_bits(got[n], ref[n + 1][0]) for n in range(3))

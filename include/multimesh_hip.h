@@ -347,6 +347,43 @@ int mm_gll_diffusion_apply(mm_context *ctx, int order, int dim, const double *gl
 int mm_gll_gradient(mm_context *ctx, int order, int dim, const double *gll_points_d, int64_t nelem, const double *deriv_d,
                     const double *u_d, int64_t ncomp, double *grad_d, double *radial_d, double *lateral_d, double *norm_d);
 
+/* The POLYNOMIAL ORDER of element-nodal GLL values changed on their own mesh: per element, the tensor product of one
+ * rectangular 1-D table R = table_d f64[m_out][m_in] applied to the element's values, m = order + 1, P = m^dim, node
+ * p = i + m j + m^2 k as everywhere.  With R[q][a] = l_a^in(g_q^out) it interpolates onto the GLL nodes of the other order
+ * (up: exact for the polynomial the field is; down: the subsample on the coinciding nodes, whose rows are unit rows); with
+ * the transposed table of the opposite direction it is the transpose of that interpolation; with scale_in_d = the fine mass
+ * and div_out_d = the coarse mass (mm_gll_mass) it is the mass-weighted restriction K_c = M_c^-1 I^T M_f K_f of a sensitivity
+ * kernel in one pass.  Every target node sits in a known element at a known reference coordinate: nothing is searched, no
+ * node can fail, and a node on an element face takes its value from its own element.  The reference has no counterpart.
+ *   layout: where component c of node p of element e sits, the same for in_d (with P_in) and out_d (with P_out):
+ *     0 = [C][E][P], the field planes;  1 = [E][P][C], MODEL/coordinates;  2 = [E][C][P], MODEL/data.
+ *   scale_in_d f64[nelem][P_in] and div_out_d f64[nelem][P_out], each nullable, shared by all components.
+ * Every product is rounded on its own (no fused multiply-add), every sum starts from its first term and adds in ascending
+ * index; 3-D (2-D drops the third sweep and out = t2):
+ *   v[a,b,c]      = in[a,b,c]                        (scale_in_d == NULL)   or   in[a,b,c] * scale_in[e][p_in]
+ *   t1[qi,b,c]    = sum_a R[qi][a] * v[a,b,c]
+ *   t2[qi,qj,c]   = sum_b R[qj][b] * t1[qi,b,c]
+ *   out[qi,qj,qk] = sum_c R[qk][c] * t2[qi,qj,c]     then   / div_out[e][p_out]   (one IEEE division) if given
+ * Nothing is special-cased: 0 * NaN is NaN, so a NaN poisons the outputs of its element whose table entries multiply it.
+ * Returns MM_OK or a negative MM_ERR_*; MM_ERR_ARG (nothing is written) for dim other than 2 or 3, an order other than
+ * 1, 2, 4, order_in == order_out (copy instead), an unknown layout, a size out of range, a null table, a null in_d / out_d,
+ * an out_d that shares a byte with in_d, scale_in_d or div_out_d -- all decided before the context or a device is touched
+ * -- and a null ctx.  nelem == 0 and ncomp == 0 are valid.  Not synchronising. */
+int mm_gll_tensor_apply(mm_context *ctx, int dim, int order_in, int order_out, const double *table_d, int layout,
+                        const double *in_d, double *out_d, int64_t nelem, int64_t ncomp, const double *scale_in_d,
+                        const double *div_out_d);
+
+/* How far two sets of node coordinates of the same elements are apart, element by element, and the size of each element:
+ * what gll_change_order compares before it writes.  a_d, b_d f64[nelem][npts][dim], dim 2 or 3:
+ *   deviation_d[e] = max over p, d of |a[e][p][d] - b[e][p][d]|, NaN where one of these differences is NaN
+ *   edge_d[e]      = fmax over d of (fmax over p of b[e][p][d] - fmin over p of b[e][p][d])   (fmax / fmin pass over a NaN)
+ * Both are exact (one subtraction each, then comparisons), so the order of the reduction does not show.  Returns MM_OK or a
+ * negative MM_ERR_*; MM_ERR_ARG (nothing is written) for dim other than 2 or 3, npts < 1, a size out of range, a null
+ * array, an output that shares a byte with an input or the other output -- all decided before the context or a device is
+ * touched -- and a null ctx.  nelem == 0 is valid.  Not synchronising. */
+int mm_element_deviation(mm_context *ctx, int dim, int64_t npts, const double *a_d, const double *b_d, int64_t nelem,
+                         double *deviation_d, double *edge_d);
+
 /* The streaming kernels of a preconditioned conjugate-gradient loop over ncomp independent systems of n unknowns each
  * (vectors f64[ncomp][n]), whose scalars never leave the device.  state_d f64[ncomp][8] holds, per system, the slots below:
  * the dots are written into MM_PCG_RZ, MM_PCG_PAP and MM_PCG_BB by mm_weighted_sum (one call per system with ncomp = 1).

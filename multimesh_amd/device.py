@@ -720,6 +720,67 @@ class Context:
         got = tuple(o for o in outs if o is not None)
         return got[0] if len(got) == 1 else got
 
+    # ---- the order of element-nodal values, changed on their own mesh ---------------------------------
+    def gll_tensor_apply(self, order_in, order_out, dim, values, layout=0, transpose=False, scale_in=None, div_out=None,
+                         out=None):
+        """Element-nodal values from the GLL nodes of ``order_in`` to those of ``order_out`` on the same elements, orders 1,
+        2, 4, different (``mm_gll_tensor_apply``: bit for bit the NumPy statement of include/multimesh_hip.h).  ``values``
+        by ``layout``: 0 = f64[C, E, P_in] (or [E, P_in]), 1 = f64[E, P_in, C] (coordinates), 2 = f64[E, C, P_in]
+        (``MODEL/data``); the result has the same layout with P_out.  The table is the interpolation
+        :func:`multimesh_amd.synth.gll_order_table` or, with ``transpose``, the transpose of the interpolation
+        ``order_out -> order_in``.  ``scale_in`` f64[E, P_in] multiplies the input, ``div_out`` f64[E, P_out] divides the
+        output (both nullable, shared by the components)."""
+        from .synth import gll_order_table   # (ValueError for an order without tables)
+
+        order_in, order_out, dim, layout = int(order_in), int(order_out), int(dim), int(layout)
+        table = (np.ascontiguousarray(gll_order_table(order_out, order_in).T) if transpose
+                 else gll_order_table(order_in, order_out))
+        if order_in == order_out:
+            raise ValueError("order_in equals order_out: nothing to resample")
+        if dim not in (2, 3) or layout not in (0, 1, 2):
+            raise ValueError("dim must be 2 or 3 and layout 0 ([C, E, P]), 1 ([E, P, C]) or 2 ([E, C, P])")
+        pin, pout = (order_in + 1) ** dim, (order_out + 1) ** dim
+        v = self.asdevice(values, np.float64)
+        if layout == 0 and len(v.shape) == 2:
+            v = DeviceArray(self, v.ptr, (1,) + v.shape, v.dtype, owner=False, keepalive=v)
+        if len(v.shape) != 3 or v.shape[(2, 1, 2)[layout]] != pin:
+            raise ValueError(f"values must hold {pin} nodes per element in layout {layout}, got shape {v.shape}")
+        ncomp, nelem = ((v.shape[0], v.shape[1]), (v.shape[2], v.shape[0]), (v.shape[1], v.shape[0]))[layout]
+        shape = ((ncomp, nelem, pout), (nelem, pout, ncomp), (nelem, ncomp, pout))[layout]
+        scale = div = None
+        if scale_in is not None:
+            scale = self.asdevice(scale_in, np.float64)
+            if scale.shape != (nelem, pin):
+                raise ValueError(f"scale_in must be [{nelem}, {pin}]")
+        if div_out is not None:
+            div = self.asdevice(div_out, np.float64)
+            if div.shape != (nelem, pout):
+                raise ValueError(f"div_out must be [{nelem}, {pout}]")
+        if out is None:
+            out = self.empty(shape, np.float64)
+        else:
+            out = self.asdevice(out, np.float64)
+            if out.shape != shape:
+                raise ValueError(f"out must be {shape}")
+        t_d = self.to_device(table)
+        check(self.lib.mm_gll_tensor_apply(self.handle, dim, order_in, order_out, t_d.ptr, layout, v.ptr, out.ptr, nelem,
+                                           ncomp, scale.ptr if scale else None, div.ptr if div else None),
+              "mm_gll_tensor_apply")
+        return out
+
+    def element_deviation(self, a, b):
+        """Per element of two f64[E, P, dim] coordinate arrays of the same elements: (deviation f64[E], edge f64[E]) = the
+        largest ``|a - b|`` of the element (NaN where a difference is) and the largest bounding-box edge of ``b``
+        (``mm_element_deviation``, include/multimesh_hip.h)."""
+        a, b = self.asdevice(a, np.float64), self.asdevice(b, np.float64)
+        if len(a.shape) != 3 or a.shape[2] not in (2, 3) or a.shape[1] < 1 or b.shape != a.shape:
+            raise ValueError(f"a and b must both be [nelem, P, dim] with dim 2 or 3, got {a.shape} and {b.shape}")
+        nelem, npts, dim = a.shape
+        deviation, edge = self.empty((nelem,), np.float64), self.empty((nelem,), np.float64)
+        check(self.lib.mm_element_deviation(self.handle, dim, npts, a.ptr, b.ptr, nelem, deviation.ptr, edge.ptr),
+              "mm_element_deviation")
+        return deviation, edge
+
     # ---- fused ---------------------------------------------------------------------------
     def interpolate_gll(self, shape_order, gll_points, points, element_nodal_fields, nelem_to_search=20,
                         tolerance=1.05, snap_to_nearest=False, want_operator=False, out=None):

@@ -53,6 +53,7 @@ EXPORTED_SYMBOLS = (
     "mm_gll_mass", "mm_weighted_sum", "mm_divide_rows",
     "mm_gll_diffusion_apply", "mm_pcg_combine", "mm_pcg_scalars", "mm_pcg_direction", "mm_pcg_advance",
     "mm_gll_gradient",
+    "mm_gll_tensor_apply", "mm_element_deviation",
 )
 
 
@@ -192,6 +193,10 @@ def load_lib():
                                            C.c_double, vp, vp]
     lib.mm_gll_gradient.restype = C.c_int
     lib.mm_gll_gradient.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, vp, vp]
+    lib.mm_gll_tensor_apply.restype = C.c_int
+    lib.mm_gll_tensor_apply.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int64, C.c_int64, vp, vp]
+    lib.mm_element_deviation.restype = C.c_int
+    lib.mm_element_deviation.argtypes = [vp, C.c_int, C.c_int64, vp, vp, C.c_int64, vp, vp]
     lib.mm_pcg_combine.restype = C.c_int
     lib.mm_pcg_combine.argtypes = [vp, vp, vp, C.c_double, vp, C.c_int64, C.c_int64, vp]
     lib.mm_pcg_scalars.restype = C.c_int

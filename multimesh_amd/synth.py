@@ -147,6 +147,28 @@ def gll_derivative_matrix(order: int) -> np.ndarray:
     return D
 
 
+def gll_order_table(order_in: int, order_out: int) -> np.ndarray:
+    """R f64[order_out + 1][order_in + 1] with R[q][a] = l_a^in(g_q^out): the Lagrange polynomials of the GLL nodes of
+    ``order_in`` at the GLL nodes of ``order_out`` (:func:`gll_nodes_1d`).  Where an output node coincides with an input
+    node the row is exactly a unit row (the nodes of order 1 are among those of order 2, and those among order 4's);
+    otherwise the entry is the product of (x - g_b) / (g_a - g_b) over b != a in ascending b."""
+    gi, go = gll_nodes_1d(order_in), gll_nodes_1d(order_out)
+    R = np.zeros((len(go), len(gi)))
+    for q, x in enumerate(go):
+        hit = np.flatnonzero(gi == x)
+        if hit.size:
+            R[q, hit[0]] = 1.0
+            continue
+        for a in range(len(gi)):
+            prod = None
+            for b in range(len(gi)):
+                if b != a:
+                    f = (x - gi[b]) / (gi[a] - gi[b])
+                    prod = f if prod is None else prod * f
+            R[q, a] = prod
+    return R
+
+
 def gll_mesh(n: int, order: int, seed: int = 1, jitter: float = 0.2, dim: int = 3):
     """Element-nodal GLL mesh ``f64[nelem, (order+1)^dim, dim]`` (the layout of the reference's
     ``MODEL/coordinates`` / ``mesh.points[mesh.connectivity]``): the control nodes of every element

@@ -98,7 +98,15 @@ int mm_centroid(mm_context *ctx, int64_t ndim, int64_t nelem, int64_t npointsper
  * query = .query: idx_d int64[npts][k] ascending by Euclidean distance (squared distance
  * summed axis by axis in fp64, no fused multiply-add; equal distances ordered by index);
  * rows with fewer than k sources are padded with index nsrc (distance inf) like cKDTree.
- * dist_d (nullable) f64[npts][k] receives the distances.  ndim in {1,2,3}; k <= MM_KNN_MAX_K. */
+ * dist_d (nullable) f64[npts][k] receives the distances.  ndim in {1,2,3}; k <= MM_KNN_MAX_K.
+ * Non-finite coordinates (NaN, +-inf, or finite ones whose squared distance overflows): the call still returns MM_OK.
+ *   targets: the rows of the finite targets are what they are without the others, bit for bit; in the row of a
+ *     non-finite target every index lies in [0, nsrc] (nsrc: the padding) and the row is the same on every kernel
+ *     route the dispatcher can take.
+ *   sources: a source with a NaN coordinate is never nearer than anything (it is not listed); a non-finite source never
+ *     precedes a finite one, and the finite sources' part of every row is the exact kNN over the finite sources.  (An
+ *     infinite source coordinate makes the bounding box's extent along that axis non-finite; the grid then takes one
+ *     cell of unit edge there, which is exact as long as the finite sources span at most that along the axis.) */
 int mm_knn_build(mm_context *ctx, const double *src_d, int64_t nsrc, int64_t ndim,
                  mm_knn_index **out);
 int mm_knn_query(mm_context *ctx, const mm_knn_index *index, const double *pts_d, int64_t npts,
@@ -109,7 +117,11 @@ void mm_knn_destroy(mm_context *ctx, mm_knn_index *index);
  * device arrays, same in-place contract as the legacy symbol.  nelem > 0 enables a bounds
  * guard: candidates outside [0, nelem) (cKDTree's padding) count as "not in hull".
  * conn_is_exodus != 0 applies the reference's host-side column reorder
- * (scripts/cli.py:79-81) on the fly, so the caller can pass the mesh's own connectivity. */
+ * (scripts/cli.py:79-81) on the fly, so the caller can pass the mesh's own connectivity.
+ * Degenerate elements (flat, zero-size, mirrored, tangled, collapsed edges or faces, duplicates) and non-finite node or
+ * point coordinates are not special cases: the stage is the reference's arithmetic on whatever it is given, and every
+ * row -- a NaN weight included -- is what the reference computes from the same arrays (MM_FP_EXACT: bit for bit;
+ * MM_FP_TOL: see there).  A target no candidate accepts, a non-finite one among them, counts as failed and keeps its row. */
 int64_t mm_locate_hex8(mm_context *ctx, int64_t nelem_to_search, int64_t npoints,
                        const int64_t *nearest_element_indices_d, const int64_t *connectivity_d,
                        int64_t nelem, int conn_is_exodus, int64_t *enclosing_elem_indices_d,
@@ -132,6 +144,9 @@ int mm_gather(mm_context *ctx, const double *fields_d, int64_t nsrc, int64_t nco
  * the reference (absent): PARITY UNPINNED, numerics defined in mm_locate_gll.hip / the oracle.
  * gll_points_d f64[nelem][P][dim] with P = (order+1)^dim, control node p = i + (order+1) j + ...;
  * nn_d int64[npoints][k]; elem_d int64[npoints] (-1 = not found); coeffs_d f64[npoints][P].
+ * Degenerate (flat, zero-size, mirrored, folded, duplicated) elements and non-finite coordinates take the same path as
+ * everything else: a transform that fails is NaN and the candidate is skipped, as the acceptance loop states; every row
+ * equals the oracle's on the same arrays.  The same holds for mm_locate_gll_bbox and mm_interpolate_gll.
  * Returns the number of points without an element, or a negative MM_ERR_*. */
 int64_t mm_locate_gll(mm_context *ctx, int order, int dim, int64_t nelem_to_search, int64_t npoints,
                       const int64_t *nearest_element_indices_d, const double *gll_points_d, int64_t nelem,
@@ -485,7 +500,10 @@ int64_t mm_fluid_solid_fix(mm_context *ctx, double *values_d, const double *prev
  * centroid -> search grid -> kNN -> locate -> gather.  connectivity_d is the mesh's own
  * (exodus-order) hex8 connectivity.  enc_d / w_d (nullable) receive the interpolation
  * operator (int64[N][8], f64[N][8]); out_d f64[N][ncomp] (nullable when only the operator is
- * wanted).  Returns the number of failed points or a negative MM_ERR_*. */
+ * wanted).  Non-finite coordinates (the same for mm_interpolate_hex8_on, _host and mm_interpolate_gll): the rows of
+ * the finite targets are what they are without the others; a non-finite target's row is the locate stage's answer over
+ * the list mm_knn_query gives for it; non-finite nodes reach the outputs only through the elements that own them.
+ * Returns the number of failed points or a negative MM_ERR_*. */
 int64_t mm_interpolate_hex8(mm_context *ctx, const double *nodes_d, int64_t nnodes,
                             const int64_t *connectivity_d, int64_t nelem, const double *points_d,
                             int64_t npoints, const double *fields_d, int64_t ncomp,
@@ -532,7 +550,9 @@ int mm_set_lazy_lists(mm_context *ctx, int on);
  *     between the two arithmetics; a solve it cannot certify is repeated in the reference's arithmetic.  Element / node
  *     ids and the failed count stay bit-identical; weights and values agree with the reference to
  *     max(1e-12, 64 eps |x| / h) (|x| / h: coordinate magnitude over element size; 1e-12 on the BASELINE meshes),
- *     relative to max|weight| = 1 resp. max|field|.
+ *     relative to max|weight| = 1 resp. max|field|.  h is the element's shortest edge: on an element with a collapsed
+ *     edge or face (h = 0) the bound is void, and it does not speak about elements that lost their orientation
+ *     (mirrored, tangled); ids and the failed count are bit-identical there too.
  * The environment variable MM_FP_MODE=tol makes MM_FP_TOL the default of new contexts (how a user of the legacy
  * symbols opts in). */
 #define MM_FP_EXACT 0

@@ -11,31 +11,23 @@
 // on its own (-ffp-contract=off), every sum starts from its first term and adds in ascending a, and the one division and the
 // one square root per node are IEEE operations; the order of everything else is written out in include/multimesh_hip.h.
 //
-// mm_gll_diffusion_apply is shaped like gll_mass_kernel (mm_mass.hip): a 256-thread block takes a tile of 256 / P whole
-// elements, which are contiguous in memory; the coordinates (three coalesced 8-byte loads per thread) and one component of u
-// (one load) go into LDS, lane t of the block is node t of the tile.  A lane is the same node (i, j, k) of every tile, so its
-// three rows of D (for the gradient) and three columns of D (for the transposed derivative) live in registers.  J is
-// recomputed from the coordinates of every tile (24 B per node) rather than read as six geometric factors (48 B); G = J^-1,
-// the mass and the unit radius stay in registers over the components of the tile.  Per tile and component: the reference
-// gradient from LDS, the flux, its pull-back written to LDS (one array per direction), a barrier, the transposed derivative
-// from LDS, one store.  Two barriers per tile and component; the next step's loads are issued before the current one is
-// computed.  HBM bytes per node: 24 + 16 C, plus 8 per kappa array.
-//
-// LDS layout.  u and the three pulled-back fluxes are arrays of doubles indexed by the node of the tile, so a tensor line
-// is read with the strides 1, m, m^2 doubles; the 32 lanes of a half-wave (the conflict group of ds_read_b64, 32 banks of
-// 8 bytes) read, along direction d, one address per line that crosses them: lanes that differ only in i_d read the same
-// address (a broadcast), the others are consecutive nodes with i_d removed -- distinct addresses less than 32 doubles apart
-// at m = 5 (i + 25 k, 0 <= i < 5, two values of k), so no two fall on one bank.  The coordinates keep the mass kernel's
-// [node][dim] layout: stride 3 doubles between nodes, odd, so the banks of 32 consecutive nodes are distinct as well.
+// mm_gll_diffusion_apply works on the element tile of mm_gll_tile.h and calls its geometry functions (J, det, G, the
+// unit radius, g, gr) with its own rows of D and line starts; the lane set-up, the loads and the stores are written out
+// here, since the kernel also needs the columns of D.  A lane keeps three rows of D (for the gradient) and three columns
+// of D (for the transposed derivative) in registers.  J is recomputed from the coordinates of every tile (24 B per node)
+// rather than read as six geometric factors (48 B); G = J^-1, the mass and the unit radius stay in registers over the
+// components of the tile.  Per tile and component: the reference gradient from LDS, the flux, its pull-back written to
+// LDS (one array per direction), a barrier, the transposed derivative from LDS, one store.  Every buffer is single: two
+// barriers per tile and component; the next step's loads are issued before the current one is computed.
+// HBM bytes per node: 24 + 16 C, plus 8 per kappa array.
 #include "mm_common.h"
+#include "mm_gll_tile.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr i64 kMaxBlocks = 2048;   // 256 CUs x 8 resident blocks; blocks stride over the rest
+using gll::ipow;
+using gll::kThreads;
 constexpr int kStateStride = 8;    // doubles per component of the PCG state block (MM_PCG_* in the header)
-
-constexpr int ipow(int b, int e) { return e == 0 ? 1 : b * ipow(b, e - 1); }
 
 template <int ORDER, int DIM, bool ANISO>
 __global__ __launch_bounds__(kThreads) void gll_diffusion_kernel(const double *__restrict__ gp, i64 nelem,
@@ -45,12 +37,9 @@ __global__ __launch_bounds__(kThreads) void gll_diffusion_kernel(const double *_
                                                                  const double *__restrict__ kh_a, double kr_s,
                                                                  const double *__restrict__ kr_a, double *__restrict__ y)
 {
-    constexpr int M = ORDER + 1;
-    constexpr int P = ipow(M, DIM);
-    constexpr int TILE = kThreads / P;            // elements per block and step
-    constexpr int TILE_NODES = TILE * P;          // <= 256
-    constexpr int TILE_DOUBLES = TILE_NODES * DIM;
-    constexpr int LOADS = (TILE_DOUBLES + kThreads - 1) / kThreads;
+    using T = gll::Tile<ORDER, DIM>;
+    constexpr int M = T::M, P = T::P, TILE = T::TILE, TILE_NODES = T::TILE_NODES, TILE_DOUBLES = T::TILE_DOUBLES,
+                  LOADS = T::LOADS;
     __shared__ double xs[TILE_DOUBLES];
     __shared__ double us[TILE_NODES];
     __shared__ double fs[DIM][TILE_NODES];
@@ -65,24 +54,22 @@ __global__ __launch_bounds__(kThreads) void gll_diffusion_kernel(const double *_
     const bool node_lane = tid < TILE_NODES;
     const int el = node_lane ? tid / P : 0;
     const int p = node_lane ? tid - el * P : 0;
-    const int i = p % M, j = (p / M) % M, k = DIM == 3 ? p / (M * M) : 0;
-    double di[M], dj[M], dk[M];   // rows of D:    D[i][a]
-    double ti[M], tj[M], tk[M];   // columns of D: D[a][i]
+    const int ix[3] = {p % M, (p / M) % M, DIM == 3 ? p / (M * M) : 0};
+    double row[DIM][M];   // rows of D:    D[i_d][a]
+    double col[DIM][M];   // columns of D: D[a][i_d]
 #pragma unroll
     for (int a = 0; a < M; ++a) {
-        di[a] = tab[i * M + a];
-        dj[a] = tab[j * M + a];
-        dk[a] = tab[k * M + a];
-        ti[a] = tab[a * M + i];
-        tj[a] = tab[a * M + j];
-        tk[a] = tab[a * M + k];
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) row[d][a] = tab[ix[d] * M + a];
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) col[d][a] = tab[a * M + ix[d]];
     }
-    const double wprod = DIM == 3 ? (tab[M * M + k] * tab[M * M + j]) * tab[M * M + i] : tab[M * M + j] * tab[M * M + i];
-    // offsets (in nodes of the tile) of the first node of this lane's three tensor lines
-    const int nbase = el * P;
-    const int node_i = nbase + (p - i);
-    const int node_j = nbase + (p - j * M);
-    const int node_k = nbase + (p - k * M * M);
+    const double *w = tab + M * M;
+    const double wprod = DIM == 3 ? (w[ix[2]] * w[ix[1]]) * w[ix[0]] : w[ix[1]] * w[ix[0]];
+    // offsets (in nodes of the tile) of the first node of this lane's tensor lines
+    int line[DIM];
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) line[d] = el * P + (p - ix[d] * ipow(M, d));
 
     const i64 ntiles = (nelem + TILE - 1) / TILE;
     const i64 nnodes = nelem * P;
@@ -139,76 +126,21 @@ __global__ __launch_bounds__(kThreads) void gll_diffusion_kernel(const double *_
             if (active) {
                 if (c == 0) {
                     double J[3][3];
-                    const int line_i = node_i * DIM, line_j = node_j * DIM, line_k = node_k * DIM;
-#pragma unroll
-                    for (int cc = 0; cc < DIM; ++cc) {
-                        J[0][cc] = di[0] * xs[line_i + cc];
-                        J[1][cc] = dj[0] * xs[line_j + cc];
-                        if constexpr (DIM == 3) J[2][cc] = dk[0] * xs[line_k + cc];
-                    }
-#pragma unroll
-                    for (int a = 1; a < M; ++a) {
-#pragma unroll
-                        for (int cc = 0; cc < DIM; ++cc) {
-                            J[0][cc] = J[0][cc] + di[a] * xs[line_i + a * DIM + cc];
-                            J[1][cc] = J[1][cc] + dj[a] * xs[line_j + a * M * DIM + cc];
-                            if constexpr (DIM == 3) J[2][cc] = J[2][cc] + dk[a] * xs[line_k + a * M * M * DIM + cc];
-                        }
-                    }
-                    double det;
-                    if constexpr (DIM == 3) {
-                        det = (J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) -
-                               J[0][1] * (J[1][0] * J[2][2] - J[1][2] * J[2][0])) +
-                              J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
-                        const double rdet = 1.0 / det;
-                        G[0][0] = (J[1][1] * J[2][2] - J[1][2] * J[2][1]) * rdet;
-                        G[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * rdet;
-                        G[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * rdet;
-                        G[1][0] = (J[1][2] * J[2][0] - J[1][0] * J[2][2]) * rdet;
-                        G[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * rdet;
-                        G[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * rdet;
-                        G[2][0] = (J[1][0] * J[2][1] - J[1][1] * J[2][0]) * rdet;
-                        G[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * rdet;
-                        G[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * rdet;
-                    } else {
-                        det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-                        const double rdet = 1.0 / det;
-                        G[0][0] = J[1][1] * rdet;
-                        G[0][1] = (-J[0][1]) * rdet;
-                        G[1][0] = (-J[1][0]) * rdet;
-                        G[1][1] = J[0][0] * rdet;
-                    }
+                    T::template jacobian<false>(xs, row, line, J);
+                    const double det = T::det(J);
+                    T::inverse(J, det, G);
                     mass = wprod * fabs(det);
                     kh = kh_a ? kh_s * kh_a[node] : kh_s;
                     if constexpr (ANISO) {
                         const double kr = kr_a ? kr_s * kr_a[node] : kr_s;
                         kd = kr - kh;
-                        const double x0 = xs[tid * DIM], x1 = xs[tid * DIM + 1], x2 = xs[tid * DIM + 2];
-                        const double rn = sqrt((x0 * x0 + x1 * x1) + x2 * x2);
-                        const bool off_centre = rn > 0.0;
-                        rh[0] = off_centre ? x0 / rn : 0.0;
-                        rh[1] = off_centre ? x1 / rn : 0.0;
-                        rh[2] = off_centre ? x2 / rn : 0.0;
+                        T::unit_radius(xs, rh);
                     }
                 }
-                // the reference gradient
-                double g[3];
-                g[0] = di[0] * us[node_i];
-                g[1] = dj[0] * us[node_j];
-                if constexpr (DIM == 3) g[2] = dk[0] * us[node_k];
-#pragma unroll
-                for (int a = 1; a < M; ++a) {
-                    g[0] = g[0] + di[a] * us[node_i + a];
-                    g[1] = g[1] + dj[a] * us[node_j + a * M];
-                    if constexpr (DIM == 3) g[2] = g[2] + dk[a] * us[node_k + a * M * M];
-                }
-                // the physical gradient, the flux and its pull-back
-                double gr[3], F[3];
-#pragma unroll
-                for (int cc = 0; cc < DIM; ++cc) {
-                    gr[cc] = G[cc][0] * g[0] + G[cc][1] * g[1];
-                    if constexpr (DIM == 3) gr[cc] = gr[cc] + G[cc][2] * g[2];
-                }
+                // the reference and the physical gradient, the flux and its pull-back
+                double g[3], gr[3], F[3];
+                T::ref_gradient(us, row, line, g);
+                T::phys_gradient(G, g, gr);
                 if constexpr (ANISO) {
                     const double s = (rh[0] * gr[0] + rh[1] * gr[1]) + rh[2] * gr[2];
                     const double ks = kd * s;
@@ -228,18 +160,16 @@ __global__ __launch_bounds__(kThreads) void gll_diffusion_kernel(const double *_
             }
             __syncthreads();
             if (active) {
-                double s0 = ti[0] * fs[0][node_i];
-                double s1 = tj[0] * fs[1][node_j];
-                double s2 = 0.0;
-                if constexpr (DIM == 3) s2 = tk[0] * fs[2][node_k];
+                // the transposed derivative: sum_a D[a][i_d] * f_d[a along d], then over d
+                double sd[DIM];
 #pragma unroll
-                for (int a = 1; a < M; ++a) {
-                    s0 = s0 + ti[a] * fs[0][node_i + a];
-                    s1 = s1 + tj[a] * fs[1][node_j + a * M];
-                    if constexpr (DIM == 3) s2 = s2 + tk[a] * fs[2][node_k + a * M * M];
-                }
-                double out = s0 + s1;
-                if constexpr (DIM == 3) out = out + s2;
+                for (int d = 0; d < DIM; ++d) sd[d] = col[d][0] * fs[d][line[d]];
+#pragma unroll
+                for (int a = 1; a < M; ++a)
+#pragma unroll
+                    for (int d = 0; d < DIM; ++d) sd[d] = sd[d] + col[d][a] * fs[d][line[d] + a * ipow(M, d)];
+                double out = sd[0] + sd[1];
+                if constexpr (DIM == 3) out = out + sd[2];
                 y[c * nnodes + node] = out;
             }
         }
@@ -251,9 +181,7 @@ void launch_diffusion(mm_context *ctx, const double *gp, i64 nelem, const double
                       const double *u, i64 ncomp, double kh_s, const double *kh_a, bool aniso, double kr_s,
                       const double *kr_a, double *y)
 {
-    constexpr int TILE = kThreads / ipow(ORDER + 1, DIM);
-    const i64 ntiles = (nelem + TILE - 1) / TILE;
-    const dim3 grid((unsigned)(ntiles < kMaxBlocks ? ntiles : kMaxBlocks));
+    const dim3 grid(gll::grid_size(nelem, gll::Tile<ORDER, DIM>::TILE));
     if constexpr (DIM == 3) {
         if (aniso) {
             hipLaunchKernelGGL((gll_diffusion_kernel<ORDER, DIM, true>), grid, dim3(kThreads), 0, ctx->stream, gp, nelem, deriv,

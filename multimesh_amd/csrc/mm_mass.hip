@@ -10,22 +10,17 @@
 // the device does only + and *, every product rounded on its own (-ffp-contract=off), every sum from its first term in
 // ascending a.
 //
-// mm_gll_mass is a streaming kernel: 24 B read and 8 B written per node, ~110 flops.  A 256-thread block takes a TILE of
-// 256 / P whole elements (2 at P = 125, 9 at P = 27, 32 at P = 8), which are contiguous in memory: their coordinates go
-// into LDS by coalesced 8-byte loads (three per thread), then lane t of the block is node t of the tile and reads its
-// 3 m neighbours along the three tensor lines from LDS.  A lane is the same node (i, j, k) of every tile its block
-// takes, so its three rows of D and its weight product live in registers for the whole kernel (read once from a copy of
-// the tables in LDS).  Blocks stride over the tiles; the next tile's loads are issued before the current one is computed.
+// mm_gll_mass is a streaming kernel on the element tile of mm_gll_tile.h: 24 B read and 8 B written per node, ~110 flops.
+// Only the coordinates go into LDS, in one buffer: a barrier before it is overwritten and one after, the next tile's loads
+// issued before the current one is computed.
 #include "mm_common.h"
+#include "mm_gll_tile.h"
 
 namespace {
 
-constexpr int kThreads = 256;
+using gll::kThreads;
 constexpr int kWave = 64;
-constexpr i64 kMaxBlocks = 2048;   // 256 CUs x 8 resident blocks; blocks stride over the rest
 constexpr int kChunk = 4096;       // mm_weighted_sum: values per chunk (fixed by the definition, not a launch shape)
-
-constexpr int ipow(int b, int e) { return e == 0 ? 1 : b * ipow(b, e - 1); }
 
 template <int ORDER, int DIM>
 __global__ __launch_bounds__(kThreads) void gll_mass_kernel(const double *__restrict__ gp, i64 nelem,
@@ -34,92 +29,30 @@ __global__ __launch_bounds__(kThreads) void gll_mass_kernel(const double *__rest
                                                             double *__restrict__ mass, double *__restrict__ det_out,
                                                             unsigned long long *__restrict__ nbad)
 {
-    constexpr int M = ORDER + 1;
-    constexpr int P = ipow(M, DIM);
-    constexpr int TILE = kThreads / P;            // elements per block and step
-    constexpr int TILE_DOUBLES = TILE * P * DIM;  // <= 768
-    constexpr int LOADS = (TILE_DOUBLES + kThreads - 1) / kThreads;
-    __shared__ double xs[TILE_DOUBLES];
-    __shared__ double tab[M * M + M];
+    using T = gll::Tile<ORDER, DIM>;
+    __shared__ double xs[T::TILE_DOUBLES];
+    __shared__ double tab[T::TABLE + T::M];
 
     const int tid = threadIdx.x;
-    if (tid < M * M) tab[tid] = deriv[tid];
-    else if (tid < M * M + M) tab[tid] = weights[tid - M * M];
-    __syncthreads();
+    T::load_tables(tab, deriv, weights);
+    const typename T::Lane ln(tab);
+    const double wprod = ln.wprod(tab);
 
-    // this lane's node of the tile
-    const bool node_lane = tid < TILE * P;
-    const int el = node_lane ? tid / P : 0;
-    const int p = node_lane ? tid - el * P : 0;
-    const int i = p % M, j = (p / M) % M, k = DIM == 3 ? p / (M * M) : 0;
-    double di[M], dj[M], dk[M];
-#pragma unroll
-    for (int a = 0; a < M; ++a) {
-        di[a] = tab[i * M + a];
-        dj[a] = tab[j * M + a];
-        dk[a] = tab[k * M + a];
-    }
-    const double wprod = DIM == 3 ? (tab[M * M + k] * tab[M * M + j]) * tab[M * M + i] : tab[M * M + j] * tab[M * M + i];
-    // LDS offsets (in doubles) of the first node of this lane's three tensor lines, and the lines' strides
-    const int base = el * P * DIM;
-    const int line_i = base + (p - i) * DIM;
-    const int line_j = base + (p - j * M) * DIM;
-    const int line_k = base + (p - k * M * M) * DIM;
-
-    const i64 ntiles = (nelem + TILE - 1) / TILE;
+    const i64 ntiles = (nelem + T::TILE - 1) / T::TILE;
     unsigned bad = 0;
-    double stage[LOADS];
+    double stage[T::LOADS];
     i64 tile = blockIdx.x;
-    // valid doubles of a tile: the last one may hold fewer elements
-    auto tile_doubles = [&](i64 t) -> int {
-        const i64 left = nelem - t * TILE;
-        return (int)(left < TILE ? left : TILE) * P * DIM;
-    };
-    auto fetch = [&](i64 t) {
-        const int nd = tile_doubles(t);
-        const double *src = gp + t * (i64)TILE_DOUBLES;
-#pragma unroll
-        for (int r = 0; r < LOADS; ++r) {
-            const int idx = r * kThreads + tid;
-            stage[r] = idx < nd ? src[idx] : 0.0;
-        }
-    };
-    if (tile < ntiles) fetch(tile);
+    if (tile < ntiles) T::fetch_x(gp, nelem, tile, stage);
     for (; tile < ntiles; tile += gridDim.x) {
         __syncthreads();   // (the previous step's reads of xs are done)
-#pragma unroll
-        for (int r = 0; r < LOADS; ++r) {
-            const int idx = r * kThreads + tid;
-            if (idx < TILE_DOUBLES) xs[idx] = stage[r];
-        }
+        T::store_x(xs, stage);
         __syncthreads();
-        const int nd = tile_doubles(tile);
-        if (tile + gridDim.x < ntiles) fetch(tile + gridDim.x);
-        if (node_lane && base < nd) {
+        if (tile + gridDim.x < ntiles) T::fetch_x(gp, nelem, tile + gridDim.x, stage);
+        if (tid < T::tile_nodes(nelem, tile)) {
             double J[3][3];
-#pragma unroll
-            for (int c = 0; c < DIM; ++c) {
-                J[0][c] = di[0] * xs[line_i + c];
-                J[1][c] = dj[0] * xs[line_j + c];
-                if constexpr (DIM == 3) J[2][c] = dk[0] * xs[line_k + c];
-            }
-#pragma unroll
-            for (int a = 1; a < M; ++a) {
-#pragma unroll
-                for (int c = 0; c < DIM; ++c) {
-                    J[0][c] = J[0][c] + di[a] * xs[line_i + a * DIM + c];
-                    J[1][c] = J[1][c] + dj[a] * xs[line_j + a * M * DIM + c];
-                    if constexpr (DIM == 3) J[2][c] = J[2][c] + dk[a] * xs[line_k + a * M * M * DIM + c];
-                }
-            }
-            double det;
-            if constexpr (DIM == 3) {
-                det = (J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) - J[0][1] * (J[1][0] * J[2][2] - J[1][2] * J[2][0])) +
-                      J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
-            } else {
-                det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-            }
-            const i64 node = tile * (i64)(TILE * P) + tid;
+            T::template jacobian<false>(xs, ln.row, ln.line, J);
+            const double det = T::det(J);
+            const i64 node = tile * (i64)T::TILE_NODES + tid;
             mass[node] = wprod * fabs(det);
             if (det_out) det_out[node] = det;
             if (!(det > 0.0)) ++bad;
@@ -136,9 +69,7 @@ template <int ORDER, int DIM>
 void launch_mass(mm_context *ctx, const double *gp, i64 nelem, const double *deriv, const double *weights, double *mass,
                  double *det, unsigned long long *nbad)
 {
-    constexpr int TILE = kThreads / ipow(ORDER + 1, DIM);
-    const i64 ntiles = (nelem + TILE - 1) / TILE;
-    hipLaunchKernelGGL((gll_mass_kernel<ORDER, DIM>), dim3((unsigned)(ntiles < kMaxBlocks ? ntiles : kMaxBlocks)),
+    hipLaunchKernelGGL((gll_mass_kernel<ORDER, DIM>), dim3(gll::grid_size(nelem, gll::Tile<ORDER, DIM>::TILE)),
                        dim3(kThreads), 0, ctx->stream, gp, nelem, deriv, weights, mass, det, nbad);
 }
 

@@ -32,13 +32,12 @@
 // scale_in / div_out stay in registers over the components of a tile in layouts 0 and 1 and are read per step in layout 2.
 // HBM bytes per element and component: 8 (P_in + P_out), plus 8 per node and scale array.
 #include "mm_common.h"
+#include "mm_gll_tile.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr i64 kMaxBlocks = 2048;   // 256 CUs x 8 resident blocks; blocks stride over the rest
-
-constexpr int ipow(int b, int e) { return e == 0 ? 1 : b * ipow(b, e - 1); }
+using gll::ipow;
+using gll::kThreads;
 
 template <int ORDER_IN, int ORDER_OUT, int DIM>
 __global__ __launch_bounds__(kThreads) void gll_tensor_kernel(const double *__restrict__ table, int layout,
@@ -171,8 +170,7 @@ void launch_tensor(mm_context *ctx, const double *table, int layout, const doubl
 {
     constexpr int PI = ipow(ORDER_IN + 1, DIM), PO = ipow(ORDER_OUT + 1, DIM);
     constexpr int TILE = kThreads / (PI > PO ? PI : PO);
-    const i64 ntiles = (nelem + TILE - 1) / TILE;
-    const dim3 grid((unsigned)(ntiles < kMaxBlocks ? ntiles : kMaxBlocks));
+    const dim3 grid(gll::grid_size(nelem, TILE));
     hipLaunchKernelGGL((gll_tensor_kernel<ORDER_IN, ORDER_OUT, DIM>), grid, dim3(kThreads), 0, ctx->stream, table, layout, in,
                        out, nelem, ncomp, scale_in, div_out);
 }
@@ -302,8 +300,7 @@ extern "C" int mm_element_deviation(mm_context *ctx, int dim, int64_t npts, cons
     MM_REQUIRE(ctx != nullptr, "ctx is null");
     if (nelem == 0) return MM_OK;
     MM_HIP_CHECK(hipSetDevice(ctx->device));
-    const i64 nblocks = (nelem + kThreads / kWave - 1) / (kThreads / kWave);
-    const dim3 grid((unsigned)(nblocks < kMaxBlocks ? nblocks : kMaxBlocks));
+    const dim3 grid(gll::grid_size(nelem, kThreads / kWave));   // one wave per element
     if (dim == 2)
         hipLaunchKernelGGL(element_deviation_kernel<2>, grid, dim3(kThreads), 0, ctx->stream, a_d, b_d, npts, nelem, deviation_d,
                            edge_d);

@@ -23,8 +23,18 @@ CHUNK, LANES = 4096, 256
 
 
 def tile_elems(order, dim):
-    """Elements that share one 256-thread block of mm_gll_mass (mm_mass.hip): as many whole elements as fit."""
+    """Elements that share one 256-thread block of the GLL element tile (TILE of multimesh_amd/csrc/mm_gll_tile.h, on which
+    mm_gll_mass, mm_gll_gradient and mm_gll_diffusion_apply work): as many whole elements as fit."""
     return 256 // (order + 1) ** dim
+
+
+MAX_BLOCKS = 2048    # kMaxBlocks of mm_gll_tile.h: the blocks of a launch stride over the tiles beyond it
+# (order, side, elements): the first ``elements`` elements of synth.gll_mesh(side, order), 3-D counts just past two tiles
+# per block, where a block takes a third tile -- so both halves of a double buffer are refilled and a short tile arrives
+# as a prefetched step.
+#   order 4 (2 elements per tile): 4098 tiles, the last one short; blocks 0 and 1 take three steps, the rest two
+#   order 2 (9 per tile, 243 of 256 lanes hold a node): 4097 tiles, the last one of 5 elements; block 0 takes three steps
+MULTI_TILE = ((4, 22, 8195), (2, 35, 36869))
 
 
 # ------------------------------------------------------------------------------------------------ tables, independently

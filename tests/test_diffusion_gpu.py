@@ -8,7 +8,8 @@ matrices within the bound its stopping rule gives:
   ||u - u*||_M <= steps * rtol * ||f||_M.
 
 A 256-thread block of the kernel takes a tile of 256 // P whole elements (mass_cases.tile_elems): the element counts
-below include one below, exactly and one above a tile, and counts that leave a broken last tile."""
+below include one below, exactly and one above a tile, counts that leave a broken last tile, and two
+(mass_cases.MULTI_TILE) at which a block takes a tile, a prefetched second one and a third through its single LDS buffers."""
 import math
 
 import numpy as np
@@ -97,6 +98,15 @@ def test_apply_element_counts_around_a_tile(ctx, order, dim):
             _check_apply(ctx, sub, order, 2, "arrays", nelem, (order, dim, nelem))
             if dim == 3:
                 _check_apply(ctx, sub, order, 1, "aniso", nelem, (order, dim, nelem))
+
+
+@pytest.mark.parametrize("mode", ["iso", "aniso"])
+@pytest.mark.parametrize("ncomp", [2, 3])
+@pytest.mark.parametrize("order,side,nelem", M.MULTI_TILE)
+def test_apply_blocks_that_take_three_tiles(ctx, order, side, nelem, ncomp, mode):
+    gp = np.ascontiguousarray(synth.gll_mesh(side, order, seed=5)[:nelem])
+    assert len(gp) == nelem > 2 * M.MAX_BLOCKS * M.tile_elems(order, 3)
+    _check_apply(ctx, gp, order, ncomp, mode, nelem + ncomp, ("multi-tile", order, nelem))
 
 
 @pytest.mark.parametrize("order", [1, 2, 4])

@@ -1,7 +1,8 @@
 """The GLL gradient on the GPU.  mm_gll_gradient is compared BIT for bit with its NumPy statement (tests/gradient_cases.py):
 every output requested together and each one alone (which outputs are written is decided by pointer tests in the kernel:
 a wrong plane offset would hide there), 2-D and 3-D, orders 1, 2 and 4, one and three components, element counts around
-the tile of a 256-thread block (mass_cases.tile_elems), and an Earth chunk whose coordinates of ~6.4e6 m make the
+the tile of a 256-thread block (mass_cases.tile_elems), counts at which a block takes three tiles (mass_cases.MULTI_TILE:
+both halves of the kernel's double buffers are refilled), and an Earth chunk whose coordinates of ~6.4e6 m make the
 cancellation in the cofactors real.  Inputs have full mantissas (transpose_cases.wide)."""
 import numpy as np
 import pytest
@@ -79,6 +80,15 @@ def test_gradient_element_counts_around_a_tile(ctx, order, dim):
     assert max(counts) <= len(gp)
     for nelem in counts:
         _check(ctx, np.ascontiguousarray(gp[:nelem]), order, 2, nelem, (order, dim, nelem), alone=False)
+
+
+@pytest.mark.parametrize("ncomp", [2, 3])
+@pytest.mark.parametrize("order,side,nelem", M.MULTI_TILE)
+def test_gradient_blocks_that_take_three_tiles(ctx, order, side, nelem, ncomp):
+    """Two components restore the parity of the value buffer across a tile, three flip it."""
+    gp = np.ascontiguousarray(synth.gll_mesh(side, order, seed=5)[:nelem])
+    assert len(gp) == nelem > 2 * M.MAX_BLOCKS * M.tile_elems(order, 3)
+    _check(ctx, gp, order, ncomp, nelem + ncomp, ("multi-tile", order, nelem), alone=False)
 
 
 @pytest.mark.parametrize("order", [1, 2, 4])

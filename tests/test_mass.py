@@ -149,3 +149,13 @@ def test_argument_validation_needs_no_gpu():
     assert lib.mm_divide_rows(None, None, None, 0, 1, None) == -1
     with pytest.raises(ValueError):
         api.gll_quadrature(3)
+
+
+def test_multi_tile_cases_reach_a_third_step():
+    """mass_cases.MULTI_TILE is what its comment says: tiles, the short last tile, and the blocks that take three steps."""
+    expect = {4: (4098, 1, 2), 2: (4097, 5, 1)}                  # order -> tiles, elements of the last tile, blocks with 3 steps
+    for order, side, nelem in M.MULTI_TILE:
+        tile = M.tile_elems(order, 3)
+        ntiles = -(-nelem // tile)
+        assert nelem <= (side - 1) ** 3
+        assert (ntiles, nelem - (ntiles - 1) * tile, ntiles - 2 * M.MAX_BLOCKS) == expect[order]

@@ -4,7 +4,9 @@ conservation of int K dV are asserted within term-count bounds (n terms added in
 where they are asserted.
 
 A 256-thread block of mm_gll_mass takes a tile of 256 // P whole elements (mass_cases.tile_elems): the element counts
-below include one below, exactly and one above a tile, and counts that leave a broken last tile."""
+below include one below, exactly and one above a tile, counts that leave a broken last tile, and two
+(mass_cases.MULTI_TILE) with more tiles than twice the blocks of a launch, where a block takes a tile, a prefetched second
+one and a third."""
 import math
 
 import numpy as np
@@ -59,6 +61,14 @@ def test_mass_element_counts_around_a_tile(ctx, order, dim):
     for nelem in (0, 1, tile - 1, tile, tile + 1, 3 * tile + max(tile // 2, 1), len(gp)):
         if 0 <= nelem <= len(gp):
             _check_mass(ctx, np.ascontiguousarray(gp[:nelem]), order, (order, dim, nelem))
+
+
+@pytest.mark.parametrize("order,side,nelem", M.MULTI_TILE)
+def test_mass_blocks_that_take_three_tiles(ctx, order, side, nelem):
+    gp = np.ascontiguousarray(synth.gll_mesh(side, order, seed=5)[:nelem])
+    assert len(gp) == nelem > 2 * M.MAX_BLOCKS * M.tile_elems(order, 3)
+    _, n_bad = _check_mass(ctx, gp, order, ("multi-tile", order, nelem))
+    assert n_bad == 0
 
 
 @pytest.mark.parametrize("order", [1, 2, 4])

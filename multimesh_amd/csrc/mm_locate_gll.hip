@@ -20,7 +20,14 @@
 // lanes of a wave mostly work on the same element and their control-node loads collapse to one
 // cache line per instruction instead of up to 64.  (An element-centric LDS-tiled variant is the
 // next step, see DESIGN.md.)
+//
+// Each step once: gll_judge is THE ACCEPTANCE RULE, gll_settle the end of an unfound target, GllWaveQueue the wave's
+// re-queue, gll_next_candidate the id skip -- shared by locate_gll_first_pass_kernel (which owns the LDS staging turns)
+// and locate_gll_pass_kernel (which owns the queue it reads and the walk loop); the bounding-box kernel has its own
+// control flow and shares the id skip and gll_store_row.  The host helpers are named gll_* as well.
 #include <math.h>
+
+#include <type_traits>
 
 #include "mm_common.h"
 #include "mm_newton_hex8.h"
@@ -351,7 +358,37 @@ struct GllEmit {
     int *elem_defer = nullptr;    // [N]
 };
 
-// found == false: the reference's "-1 and zero coefficients"; NumPy's field[-1] is the LAST element
+// The values of one target from {element, xi}: store(c, sum_p coeff_p(xi) * fields[c][e][p]) per component, in NumPy's
+// row-sum order (Gll::weighted_sum); a target that was not found reads the LAST element with zero coefficients, like
+// NumPy's field[-1] * 0.  (LEAN: the 125 coefficient products do not depend on c -- left alone, the compiler forms them
+// all in front of the component loop: 250 registers, one wave per SIMD; weighted_sum<true> forms them row by row.)
+template <int ORDER, int DIM, bool LEAN, typename STORE>
+__device__ __forceinline__ void gll_target_values(i64 e, const double *xi, bool found, const double *__restrict__ fields,
+                                                  i64 nelem, int ncomp, STORE store)
+{
+    using G = Gll<ORDER, DIM>;
+    double g[G::n];
+    gll_nodes<ORDER>(g);
+    double l[DIM][G::n], dl[DIM][G::n];
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) lagrange_1d<ORDER>(g, found ? xi[d] : 0.0, l[d], dl[d]);
+    const i64 ef = found ? e : nelem - 1;
+    for (int c = 0; c < ncomp; ++c)
+        store(c, G::template weighted_sum<LEAN>(l, !found, fields + ((i64)c * nelem + ef) * G::P));
+}
+
+// Row i of the operator: the element and its P coefficients, or the reference's "-1 and zero coefficients"
+template <int ORDER, int DIM>
+__device__ __forceinline__ void gll_store_row(i64 *__restrict__ elem, double *__restrict__ coeffs, i64 i, i64 e,
+                                              const double (&xi)[DIM], bool found)
+{
+    using G = Gll<ORDER, DIM>;
+    elem[i] = found ? e : -1;
+    if (found) G::coefficients(xi, coeffs + i * G::P);
+    else
+        for (int p = 0; p < G::P; ++p) coeffs[i * G::P + p] = 0.0;
+}
+
 template <int ORDER, int DIM, bool DEFER = false>
 __device__ __forceinline__ void gll_emit(const GllEmit &em, i64 i, i64 e, const double (&xi)[DIM], bool found, i64 nelem)
 {
@@ -361,36 +398,21 @@ __device__ __forceinline__ void gll_emit(const GllEmit &em, i64 i, i64 e, const 
         for (int d = 0; d < DIM; ++d) em.xi_defer[i * DIM + d] = found ? xi[d] : 0.0;
         return;
     }
-    using G = Gll<ORDER, DIM>;
-    constexpr int P = G::P;
-    if (em.elem) em.elem[i] = found ? e : -1;
-    if (em.coeffs) {
-        if (found) G::coefficients(xi, em.coeffs + i * P);
-        else
-            for (int p = 0; p < P; ++p) em.coeffs[i * P + p] = 0.0;
-    }
-    if (em.out) {
-        double g[G::n];
-        gll_nodes<ORDER>(g);
-        double l[DIM][G::n], dl[DIM][G::n];
-#pragma unroll
-        for (int d = 0; d < DIM; ++d) lagrange_1d<ORDER>(g, found ? xi[d] : 0.0, l[d], dl[d]);
-        const i64 ef = found ? e : nelem - 1;
-        for (int c = 0; c < em.ncomp; ++c)
-            em.out[i * em.ncomp + c] = G::weighted_sum(l, !found, em.fields + ((i64)c * nelem + ef) * P);
-    }
+    if (em.coeffs) gll_store_row<ORDER, DIM>(em.elem, em.coeffs, i, e, xi, found);   // (the two come together)
+    if (em.out)
+        gll_target_values<ORDER, DIM, false>(e, xi, found, em.fields, nelem, em.ncomp,
+                                             [&](int c, double v) { em.out[i * em.ncomp + c] = v; });
 }
 
-// The deferred half of gll_emit (GllEmit::xi_defer): out[i][c] = sum_p coeff_p(xi_i) * field[c][elem_i][p], the
-// coefficients and the sum formed exactly as there (NumPy's row-sum order; a target that was not found reads the LAST
-// element with zero coefficients like NumPy's field[-1] * 0).  One lane per target; neighbouring targets lie in the same
-// or neighbouring elements, so a wave's loads of a field row fall on a few lines.
+// The deferred half of gll_emit (GllEmit::xi_defer): out[i][c] point-major.  One lane per target; neighbouring targets
+// lie in the same or neighbouring elements, so a wave's loads of a field row fall on a few lines.
 template <int ORDER, int DIM>
 __global__ __launch_bounds__(256, kGllValuesWaves) void gll_values_kernel(i64 npoints, const int *__restrict__ elem,
                                                          const double *__restrict__ xi_all,
                                                          const double *__restrict__ fields, i64 nelem, int ncomp,
                                                          double *__restrict__ out)
 {
+    // (its own copy of gll_target_values<LEAN>, which see: through that function cfg5's gather stage ran 0.542 ms, not 0.534)
     using G = Gll<ORDER, DIM>;
     constexpr int P = G::P;
     const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -403,25 +425,151 @@ __global__ __launch_bounds__(256, kGllValuesWaves) void gll_values_kernel(i64 np
 #pragma unroll
     for (int d = 0; d < DIM; ++d) lagrange_1d<ORDER>(g, found ? xi_all[i * DIM + d] : 0.0, l[d], dl[d]);
     const i64 ef = found ? (i64)e : nelem - 1;
-    for (int c = 0; c < ncomp; ++c) {
-        // (the 125 coefficient products do not depend on c: left alone, the compiler forms them all in front of this loop
-        // and keeps them in 250 registers -- one wave per SIMD; weighted_sum<LEAN> forms them row by row)
+    for (int c = 0; c < ncomp; ++c)
         out[i * ncomp + c] = G::template weighted_sum<true>(l, !found, fields + ((i64)c * nelem + ef) * P);
-    }
 }
+
+constexpr int kGllLazyK = 8;   // candidates asked of the kNN stage up front by mm_interpolate_gll
+constexpr int kGllWalkFrom = 1; // passes that advance one candidate before the lanes walk their lists (round 4: 1 -- with the
+                                // values formed in a kernel of their own the one-candidate passes 1 and 2 cost more than they save: 3.12 -> 2.92 ms)
+
+// The next valid candidate of a list row: j moves past ids outside [0, nelem); returns the id at j, or -1 with
+// j == kavail when the row is used up.
+template <typename IDX>
+__device__ __forceinline__ i64 gll_next_candidate(const IDX *__restrict__ row, int kavail, i64 nelem, int &j)
+{
+    for (; j < kavail; ++j) {
+        const i64 e = (i64)row[j];
+        if (e >= 0 && e < nelem) return e;
+    }
+    return -1;
+}
+
+// The least-outside candidate a target has seen so far.  With snap_to_nearest it travels between the passes in two
+// scratch arrays: best_state [N][kGllSnapDoubles] (val, then xi -- DIM + 1 of each row's doubles are used) and
+// best_elem_state [N]; locate_gll_run budgets and carves them by the byte counts below.
+constexpr int kGllSnapDoubles = 4;
+constexpr size_t kGllSnapStateBytes = kGllSnapDoubles * sizeof(double), kGllSnapElemBytes = sizeof(i64);   // per target
+template <int DIM>
+struct GllBest {
+    double val = 10e9;
+    i64 elem = 0;
+    double xi[DIM];
+    __device__ __forceinline__ GllBest()
+    {
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) xi[d] = 10e9;
+    }
+    __device__ __forceinline__ void load(const double *__restrict__ state, const i64 *__restrict__ elem_state, i64 i)
+    {
+        val = state[i * (DIM + 1)];
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) xi[d] = state[i * (DIM + 1) + 1 + d];
+        elem = elem_state[i];
+    }
+    __device__ __forceinline__ void save(double *__restrict__ state, i64 *__restrict__ elem_state, i64 i) const
+    {
+        state[i * (DIM + 1)] = val;
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) state[i * (DIM + 1) + 1 + d] = xi[d];
+        elem_state[i] = elem;
+    }
+};
+
+// THE ACCEPTANCE RULE (reference interpolator.py:1181-1233, the oracle's mmo_locate_gll): xi = the inverse transform of
+// target i in candidate e.  A NaN is skipped; otherwise the candidate becomes the least-outside one if max |xi_d| is
+// smaller than the best so far, and it is accepted -- emitted, true returned -- when every |xi_d| < tolerance.
+template <int ORDER, int DIM, bool DEFER>
+__device__ __forceinline__ bool gll_judge(const double (&xi)[DIM], i64 e, GllBest<DIM> &best, double tolerance,
+                                          const GllEmit &em, i64 i, i64 nelem)
+{
+    bool isnan_any = false;
+    double worst = 0.0;
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) {
+        if (xi[d] != xi[d]) isnan_any = true;
+        if (fabs(xi[d]) > worst) worst = fabs(xi[d]);
+    }
+    if (isnan_any) return false;
+    if (worst < best.val) {
+        best.val = worst;
+        best.elem = e;
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) best.xi[d] = xi[d];
+    }
+    bool inside = true;
+#pragma unroll
+    for (int d = 0; d < DIM; ++d)
+        if (!(fabs(xi[d]) < tolerance)) inside = false;
+    if (inside) gll_emit<ORDER, DIM, DEFER>(em, i, e, xi, true, nelem);
+    return inside;
+}
+
+// A target this pass did not find, next candidate j of k: re-queued (returns true; the snap state saved) while
+// candidates are left -- also when the short list is used up and the full one is needed -- else emitted: the
+// least-outside candidate clamped to +-1.02 under snap_to_nearest, or "not found" (`missing`).
+template <int ORDER, int DIM, bool DEFER>
+__device__ __forceinline__ bool gll_settle(i64 i, int j, i64 k, int snap_to_nearest, GllBest<DIM> &best,
+                                           double *__restrict__ best_state, i64 *__restrict__ best_elem_state,
+                                           const GllEmit &em, i64 nelem, bool &missing)
+{
+    if (j < k) {
+        if (snap_to_nearest) best.save(best_state, best_elem_state, i);
+        return true;
+    }
+    if (snap_to_nearest) {
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) {
+            double v = best.xi[d];
+            if (v < -1.02) v = -1.02;
+            if (v > 1.02) v = 1.02;
+            best.xi[d] = v;
+        }
+        gll_emit<ORDER, DIM, DEFER>(em, i, best.elem, best.xi, true, nelem);
+    } else {
+        gll_emit<ORDER, DIM, DEFER>(em, i, 0, best.xi, false, nelem);
+        missing = true;
+    }
+    return false;
+}
+
+// Re-queue entries {target, next candidate} are batched per wave in LDS and flushed with one global atomic per ~200
+// entries: when a further trip (up to 64 entries) might not fit, and after the wave's last trip.
+constexpr int kGllWaveQueue = 256;
+constexpr int kGllWaveQueueFlush = kGllWaveQueue - 64;
+struct GllWaveQueue {
+    int2 *slots;   // [kGllWaveQueue] in LDS, the wave's own
+    int held = 0;
+    unsigned long long missing_total = 0;
+    // every lane of the wave, once per trip
+    __device__ __forceinline__ void end_trip(bool requeue, i64 i, int j, bool missing, bool last_trip,
+                                             int2 *__restrict__ q_out, int *__restrict__ q_out_count)
+    {
+        const int lane = threadIdx.x;
+        missing_total += __popcll(__ballot(missing));
+        const unsigned long long vote = __ballot(requeue);
+        if (requeue) slots[held + __popcll(vote & ((1ull << lane) - 1ull))] = make_int2((int)i, j);
+        held += __popcll(vote);
+        if (held > kGllWaveQueueFlush || (last_trip && held > 0)) {
+            int base = 0;
+            if (lane == 0) base = atomicAdd(q_out_count, held);
+            base = __shfl(base, 0);
+            for (int t = lane; t < held; t += 64) q_out[base + t] = slots[t];
+            held = 0;
+        }
+    }
+    __device__ __forceinline__ void finish(unsigned long long *__restrict__ nmissing) const
+    {
+        if (threadIdx.x == 0 && missing_total) atomicAdd(nmissing, missing_total);
+    }
+};
 
 // Control flow of reference interpolator.py:1181-1233 (see the oracle's mmo_locate_gll), scheduled
 // as COMPACTING PASSES like the hex8 locate: a pass performs at most one inverse transform per
 // still-open target (candidate j of its list) and re-queues the unresolved ones densely as (target,
 // j+1), so a wave never waits for its unluckiest lane's whole candidate walk.  k passes are launched
 // (each advances every open target by at least one candidate), the late ones over a nearly empty
-// queue.  With snap_to_nearest the least-outside candidate seen so far travels in per-target state
-// arrays.  Re-queue entries are batched per wave in LDS (one global atomic per ~200 entries).
-constexpr int kGllWaveQueue = 256;
-constexpr int kGllLazyK = 8;   // candidates asked of the kNN stage up front by mm_interpolate_gll
-constexpr int kGllWalkFrom = 1; // passes that advance one candidate before the lanes walk their lists (round 4: 1 -- with the
-                                // values formed in a kernel of their own the one-candidate passes 1 and 2 cost more than they save: 3.12 -> 2.92 ms)
-
+// queue.  This kernel owns the per-lane schedule: the queue it reads and the `walk` loop.
 template <int ORDER, int DIM, typename IDX, bool DEFER = false>
 __global__ __launch_bounds__(64, kGllWaves) void locate_gll_pass_kernel(i64 k, int kavail, i64 npoints,
                                                              const IDX *__restrict__ nn,
@@ -433,16 +581,14 @@ __global__ __launch_bounds__(64, kGllWaves) void locate_gll_pass_kernel(i64 k, i
                                                              const int2 *__restrict__ q_in,
                                                              const int *__restrict__ q_in_count,
                                                              int2 *__restrict__ q_out, int *__restrict__ q_out_count,
-                                                             double *__restrict__ best_state,   // [N][DIM+1]
-                                                             i64 *__restrict__ best_elem_state,  // [N]
+                                                             double *__restrict__ best_state,
+                                                             i64 *__restrict__ best_elem_state,
                                                              int walk)
 {
     using G = Gll<ORDER, DIM>;
     constexpr int P = G::P;
     __shared__ int2 s_queue[kGllWaveQueue];
-    const int lane = threadIdx.x;
-    int held = 0;
-    unsigned long long missing_total = 0;
+    GllWaveQueue wq{s_queue};
 
     const i64 total = q_in ? (i64)*q_in_count : npoints;
     const i64 stride = (i64)gridDim.x * blockDim.x;
@@ -450,11 +596,10 @@ __global__ __launch_bounds__(64, kGllWaves) void locate_gll_pass_kernel(i64 k, i
     const i64 trips = (total + stride - 1) / stride;
     for (i64 trip = 0; trip < trips; ++trip) {
         const i64 q = first + trip * stride;
-        const bool active = q < total;
         bool requeue = false, missing = false;
         i64 i = 0;
         int j = 0;
-        if (active) {
+        if (q < total) {
             if (q_in) {
                 const int2 e = q_in[q];
                 i = e.x;
@@ -465,92 +610,25 @@ __global__ __launch_bounds__(64, kGllWaves) void locate_gll_pass_kernel(i64 k, i
             double pnt[DIM];
 #pragma unroll
             for (int d = 0; d < DIM; ++d) pnt[d] = points[i * DIM + d];
-            // least-outside candidate so far (fresh in the first pass)
-            double best_xi[DIM];
-            double best_val = 10e9;
-            i64 best_elem = 0;
-#pragma unroll
-            for (int d = 0; d < DIM; ++d) best_xi[d] = 10e9;
-            if (snap_to_nearest && q_in) {
-                best_val = best_state[i * (DIM + 1)];
-#pragma unroll
-                for (int d = 0; d < DIM; ++d) best_xi[d] = best_state[i * (DIM + 1) + 1 + d];
-                best_elem = best_elem_state[i];
-            }
+            GllBest<DIM> best;   // (fresh in the first pass)
+            if (snap_to_nearest && q_in) best.load(best_state, best_elem_state, i);
             bool found = false;
             do {   // one candidate, or (walk) one after the other until the point is found or the list ends
-                // next valid candidate; this array holds the first kavail <= k of the target's list
-                while (j < kavail) {
-                    const i64 e = (i64)nn[i * kavail + j];
-                    if (e >= 0 && e < nelem) break;
-                    ++j;
-                }
-                if (j >= kavail) break;
-                const i64 e = (i64)nn[i * kavail + j];
+                // (this array holds the first kavail <= k of the target's list)
+                const i64 e = gll_next_candidate(nn + i * kavail, kavail, nelem, j);
+                if (e < 0) break;
                 double xi[DIM];
                 G::inverse_transform(pnt, gll_points + e * (i64)(P * DIM), xi);
-                bool isnan_any = false;
-                double worst = 0.0;
-#pragma unroll
-                for (int d = 0; d < DIM; ++d) {
-                    if (xi[d] != xi[d]) isnan_any = true;
-                    if (fabs(xi[d]) > worst) worst = fabs(xi[d]);
-                }
-                if (!isnan_any) {
-                    if (worst < best_val) {
-                        best_val = worst;
-                        best_elem = e;
-#pragma unroll
-                        for (int d = 0; d < DIM; ++d) best_xi[d] = xi[d];
-                    }
-                    bool inside = true;
-#pragma unroll
-                    for (int d = 0; d < DIM; ++d)
-                        if (!(fabs(xi[d]) < tolerance)) inside = false;
-                    if (inside) {
-                        gll_emit<ORDER, DIM, DEFER>(em, i, e, xi, true, nelem);
-                        found = true;
-                    }
-                }
+                found = gll_judge<ORDER, DIM, DEFER>(xi, e, best, tolerance, em, i, nelem);
                 ++j;
             } while (walk && !found);
-            if (!found) {
-                if (j < k) {
-                    requeue = true;   // also: the short list is used up and the full one is needed
-                    if (snap_to_nearest) {
-                        best_state[i * (DIM + 1)] = best_val;
-#pragma unroll
-                        for (int d = 0; d < DIM; ++d) best_state[i * (DIM + 1) + 1 + d] = best_xi[d];
-                        best_elem_state[i] = best_elem;
-                    }
-                } else if (snap_to_nearest) {
-#pragma unroll
-                    for (int d = 0; d < DIM; ++d) {
-                        double v = best_xi[d];
-                        if (v < -1.02) v = -1.02;
-                        if (v > 1.02) v = 1.02;
-                        best_xi[d] = v;
-                    }
-                    gll_emit<ORDER, DIM, DEFER>(em, i, best_elem, best_xi, true, nelem);
-                } else {
-                    gll_emit<ORDER, DIM, DEFER>(em, i, 0, best_xi, false, nelem);
-                    missing = true;
-                }
-            }
+            if (!found)
+                requeue = gll_settle<ORDER, DIM, DEFER>(i, j, k, snap_to_nearest, best, best_state, best_elem_state, em,
+                                                        nelem, missing);
         }
-        missing_total += __popcll(__ballot(missing));
-        const unsigned long long vote = __ballot(requeue);
-        if (requeue) s_queue[held + __popcll(vote & ((1ull << lane) - 1ull))] = make_int2((int)i, j);
-        held += __popcll(vote);
-        if (held > kGllWaveQueue - 64 || (trip == trips - 1 && held > 0)) {
-            int base = 0;
-            if (lane == 0) base = atomicAdd(q_out_count, held);
-            base = __shfl(base, 0);
-            for (int t = lane; t < held; t += 64) q_out[base + t] = s_queue[t];
-            held = 0;
-        }
+        wq.end_trip(requeue, i, j, missing, trip == trips - 1, q_out, q_out_count);
     }
-    if (lane == 0 && missing_total) atomicAdd(nmissing, missing_total);
+    wq.finish(nmissing);
 }
 
 // First pass with the control nodes in LDS.  Targets arrive sorted by their first candidate element
@@ -558,7 +636,8 @@ __global__ __launch_bounds__(64, kGllWaves) void locate_gll_pass_kernel(i64 k, i
 // of them are copied into LDS once per solve (coalesced) and every Newton step reads them from there -- all
 // lanes of an element the same address (broadcast) -- instead of going back to L1/L2 for 3 KB per step.  A
 // wave with more distinct elements (thinly populated elements) takes further turns of the stage/solve
-// loop.  Same arithmetic, same results as locate_gll_pass_kernel with q_in == null.
+// loop.  Same arithmetic, same results as locate_gll_pass_kernel with q_in == null.  This kernel owns the staging
+// turns, kStaged, the pinned per-lane offset and the wave fences.
 template <int ORDER, int DIM, typename IDX, bool DEFER = false>
 __global__ __launch_bounds__(64, kGllWaves) void locate_gll_first_pass_kernel(
     i64 k, int kavail, i64 npoints, const IDX *__restrict__ nn, const double *__restrict__ gll_points, i64 nelem,
@@ -574,13 +653,12 @@ __global__ __launch_bounds__(64, kGllWaves) void locate_gll_first_pass_kernel(
     constexpr int P = G::P;
     constexpr int kNodeDoubles = P * DIM;
     __shared__ int2 s_queue[kGllWaveQueue];
+    GllWaveQueue wq{s_queue};
     // elements staged per turn: two at order 4 in 3-D (3 KB each; four measured slower: 7.9 vs 7.6 ms at cfg5's
     // shape -- a tenth of the waves span more than two elements, every wave pays the LDS), more for small elements
     constexpr int kStaged = kNodeDoubles <= 81 ? 4 : 2;
     __shared__ double s_ctrl[kStaged][kNodeDoubles];
     const int lane = threadIdx.x;
-    int held = 0;
-    unsigned long long missing_total = 0;
 
     const i64 stride = (i64)gridDim.x * blockDim.x;
     const i64 first = (i64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -598,20 +676,11 @@ __global__ __launch_bounds__(64, kGllWaves) void locate_gll_first_pass_kernel(
             i = order ? (i64)order[q] : q;
 #pragma unroll
             for (int d = 0; d < DIM; ++d) pnt[d] = points[i * DIM + d];
-            // first valid candidate
-            while (j < kavail) {
-                e = (i64)nn[i * kavail + j];
-                if (e >= 0 && e < nelem) break;
-                ++j;
-            }
+            e = gll_next_candidate(nn + i * kavail, kavail, nelem, j);
         }
-        bool pending = active && j < kavail;
+        bool pending = e >= 0;
         bool found = false;
-        double best_xi[DIM];
-        double best_val = 10e9;
-        i64 best_elem = 0;
-#pragma unroll
-        for (int d = 0; d < DIM; ++d) best_xi[d] = 10e9;
+        GllBest<DIM> best;
         while (__any(pending)) {
             // the (up to) kStaged elements of this turn: the first pending lane's, the first other one, ...
             int which = -1;   // this lane's element among the staged ones (an offset into s_ctrl)
@@ -636,29 +705,7 @@ __global__ __launch_bounds__(64, kGllWaves) void locate_gll_first_pass_kernel(
                 // twice the LDS reads per Newton step at order 4 with two arrays)
                 asm volatile("" : "+v"(which));
                 G::inverse_transform(pnt, &s_ctrl[0][0] + which, xi);
-                bool isnan_any = false;
-                double worst = 0.0;
-#pragma unroll
-                for (int d = 0; d < DIM; ++d) {
-                    if (xi[d] != xi[d]) isnan_any = true;
-                    if (fabs(xi[d]) > worst) worst = fabs(xi[d]);
-                }
-                if (!isnan_any) {
-                    if (worst < best_val) {
-                        best_val = worst;
-                        best_elem = e;
-#pragma unroll
-                        for (int d = 0; d < DIM; ++d) best_xi[d] = xi[d];
-                    }
-                    bool inside = true;
-#pragma unroll
-                    for (int d = 0; d < DIM; ++d)
-                        if (!(fabs(xi[d]) < tolerance)) inside = false;
-                    if (inside) {
-                        gll_emit<ORDER, DIM, DEFER>(em, i, e, xi, true, nelem);
-                        found = true;
-                    }
-                }
+                found = gll_judge<ORDER, DIM, DEFER>(xi, e, best, tolerance, em, i, nelem);
                 ++j;
                 pending = false;
             }
@@ -666,42 +713,12 @@ __global__ __launch_bounds__(64, kGllWaves) void locate_gll_first_pass_kernel(
             __builtin_amdgcn_wave_barrier();   // every lane is done with the staged nodes
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         }
-        if (active && !found) {
-            if (j < k) {
-                requeue = true;
-                if (snap_to_nearest) {
-                    best_state[i * (DIM + 1)] = best_val;
-#pragma unroll
-                    for (int d = 0; d < DIM; ++d) best_state[i * (DIM + 1) + 1 + d] = best_xi[d];
-                    best_elem_state[i] = best_elem;
-                }
-            } else if (snap_to_nearest) {
-#pragma unroll
-                for (int d = 0; d < DIM; ++d) {
-                    double v = best_xi[d];
-                    if (v < -1.02) v = -1.02;
-                    if (v > 1.02) v = 1.02;
-                    best_xi[d] = v;
-                }
-                gll_emit<ORDER, DIM, DEFER>(em, i, best_elem, best_xi, true, nelem);
-            } else {
-                gll_emit<ORDER, DIM, DEFER>(em, i, 0, best_xi, false, nelem);
-                missing = true;
-            }
-        }
-        missing_total += __popcll(__ballot(missing));
-        const unsigned long long vote = __ballot(requeue);
-        if (requeue) s_queue[held + __popcll(vote & ((1ull << lane) - 1ull))] = make_int2((int)i, j);
-        held += __popcll(vote);
-        if (held > kGllWaveQueue - 64 || (trip == trips - 1 && held > 0)) {
-            int base = 0;
-            if (lane == 0) base = atomicAdd(q_out_count, held);
-            base = __shfl(base, 0);
-            for (int t = lane; t < held; t += 64) q_out[base + t] = s_queue[t];
-            held = 0;
-        }
+        if (active && !found)
+            requeue = gll_settle<ORDER, DIM, DEFER>(i, j, k, snap_to_nearest, best, best_state, best_elem_state, em, nelem,
+                                                    missing);
+        wq.end_trip(requeue, i, j, missing, trip == trips - 1, q_out, q_out_count);
     }
-    if (lane == 0 && missing_total) atomicAdd(nmissing, missing_total);
+    wq.finish(nmissing);
 }
 
 template <int CTRL>
@@ -767,6 +784,20 @@ __global__ __launch_bounds__(256) void gather_elem_kernel(const double *__restri
 struct GllLazy {
     const mm_knn_index *index;
     int *nn_full;   // [N][k], rows filled on demand
+};
+
+// The fused entries' candidate lists: kavail per target up front (all k, or kGllLazyK when evaluated lazily), int32 rows
+struct GllLists {
+    bool lazy;
+    int kavail;
+    int *nn = nullptr, *nn_full = nullptr;
+    GllLists(const mm_context *ctx, i64 k) : lazy(ctx->lazy_lists && k > kGllLazyK), kavail(lazy ? kGllLazyK : (int)k) {}
+    int get(mm_context *ctx, i64 rows, i64 k)
+    {
+        int rc = mm_buffer_get(ctx, MM_BUF_NN, (size_t)rows * kavail * sizeof(int), (void **)&nn);
+        if (rc == MM_OK && lazy) rc = mm_buffer_get(ctx, MM_BUF_NN_FULL, (size_t)rows * k * sizeof(int), (void **)&nn_full);
+        return rc;
+    }
 };
 
 __global__ __launch_bounds__(256) void gll_queue_ids_kernel(const int2 *__restrict__ q, const int *__restrict__ q_count,
@@ -880,9 +911,9 @@ __global__ __launch_bounds__(64, kGllWaves) void locate_gll_v1_kernel(i64 k, i64
         double nearest_d2 = INFINITY;
         bool found = false;
         double xi[DIM];
-        for (i64 j = 0; j < k && !found; ++j) {
-            const i64 e = nn[i * k + j];
-            if (e < 0 || e >= nelem) continue;
+        for (int j = 0; !found; ++j) {
+            const i64 e = gll_next_candidate(nn + i * k, (int)k, nelem, j);
+            if (e < 0) break;
             const double *b = boxes + e * (i64)(3 * DIM);
             bool inside = true;
 #pragma unroll
@@ -896,8 +927,7 @@ __global__ __launch_bounds__(64, kGllWaves) void locate_gll_v1_kernel(i64 k, i64
                 for (int d = 0; d < DIM; ++d)
                     if (!(fabs(xi[d]) <= 1.04)) ok = false;   // NaN fails the comparison too
                 if (ok) {
-                    elem[i] = e;
-                    G::coefficients(xi, coeffs + i * P);
+                    gll_store_row<ORDER, DIM>(elem, coeffs, i, e, xi, true);
                     found = true;
                 }
             } else {
@@ -916,8 +946,7 @@ __global__ __launch_bounds__(64, kGllWaves) void locate_gll_v1_kernel(i64 k, i64
         if (!found) {
             const i64 ind = first_inside >= 0 ? first_inside : nearest;
             if (ind < 0) {
-                elem[i] = -1;
-                for (int p = 0; p < P; ++p) coeffs[i * P + p] = 0.0;
+                gll_store_row<ORDER, DIM>(elem, coeffs, i, -1, xi, false);
                 hard = true;
             } else {
                 const i64 e = nn[i * k + ind];
@@ -934,8 +963,7 @@ __global__ __launch_bounds__(64, kGllWaves) void locate_gll_v1_kernel(i64 k, i64
 #pragma unroll
                     for (int d = 0; d < DIM; ++d) xi[d] = hard_xi[d];
                 }
-                elem[i] = e;
-                G::coefficients(xi, coeffs + i * P);
+                gll_store_row<ORDER, DIM>(elem, coeffs, i, e, xi, true);
             }
         }
     }
@@ -990,6 +1018,53 @@ int mm_knn_build_impl(mm_context *ctx, const double *src_d, i64 nsrc, i64 ndim, 
 int mm_knn_query_impl(mm_context *ctx, const mm_knn_index *ix, const double *pts_d, i64 npts, i64 k, void *idx_d,
                       double *dist_d, bool idx_is_int32);
 
+// MM_REQUIRE on behalf of the entry point `who` (a helper's or a lambda's own __func__ would name the wrong function)
+#define MM_REQUIRE_AS(who, cond, msg) \
+    do { if (!(cond)) { mm_set_error(MM_ERR_ARG, "%s: %s", who, msg); return MM_ERR_ARG; } } while (0)
+
+// calls f(std::integral_constant<int, ORDER>, std::integral_constant<int, DIM>) for the (order, dim) the kernels are
+// instantiated for; the entry points have refused every other pair before
+template <typename F>
+static void gll_dispatch(int order, int dim, F &&f)
+{
+#define MM_GLL_PAIR(O, D) if (order == O && dim == D) f(std::integral_constant<int, O>{}, std::integral_constant<int, D>{});
+    MM_GLL_PAIR(1, 2) MM_GLL_PAIR(1, 3) MM_GLL_PAIR(2, 2) MM_GLL_PAIR(2, 3) MM_GLL_PAIR(4, 2) MM_GLL_PAIR(4, 3)
+#undef MM_GLL_PAIR
+}
+
+// Visiting order: *visit = the targets counting-sorted by their first candidate element (invalid ids: the last bin),
+// carved from the call's scratch, which the caller has sized with gll_visit_bytes; null when there is nothing to sort by.
+static size_t gll_visit_bytes(i64 npoints, i64 nelem)
+{
+    const i64 nbins = nelem + 1, ntiles = (nbins + 1023) / 1024;
+    return mm_round256((size_t)npoints * sizeof(int2)) + mm_round256((size_t)npoints * sizeof(int)) +
+           2 * mm_round256((size_t)(nbins + 1) * sizeof(int)) + mm_round256((size_t)ntiles * sizeof(int));
+}
+
+template <typename IDX>
+static int gll_visit_order(mm_context *ctx, const char *who, const IDX *nn, int kavail, i64 npoints, i64 nelem,
+                           const int **visit)
+{
+    *visit = nullptr;
+    if (kavail <= 0 || nelem <= 0) return MM_OK;
+    const i64 nbins = nelem + 1, ntiles = (nbins + 1023) / 1024;
+    int2 *key_rank = (int2 *)mm_scratch_take(ctx, (size_t)npoints * sizeof(int2));
+    int *ord = (int *)mm_scratch_take(ctx, (size_t)npoints * sizeof(int));
+    int *counts = (int *)mm_scratch_take(ctx, (size_t)(nbins + 1) * sizeof(int));
+    int *start = (int *)mm_scratch_take(ctx, (size_t)(nbins + 1) * sizeof(int));
+    int *tile_sums = (int *)mm_scratch_take(ctx, (size_t)ntiles * sizeof(int));
+    MM_REQUIRE_AS(who, key_rank && ord && counts && start && tile_sums, "scratch carve failed");
+    MM_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)(nbins + 1) * sizeof(int), ctx->stream));
+    const unsigned gp = (unsigned)((npoints + 255) / 256);
+    hipLaunchKernelGGL((gll_key_kernel<IDX>), dim3(gp), dim3(256), 0, ctx->stream, (i64)kavail, npoints, nn, nelem,
+                       key_rank, counts);
+    const int rc = mm_exclusive_scan_int(ctx, counts, nbins, start, tile_sums);
+    if (rc != MM_OK) return rc;
+    hipLaunchKernelGGL(gll_order_kernel, dim3(gp), dim3(256), 0, ctx->stream, npoints, key_rank, start, ord);
+    *visit = ord;
+    return MM_OK;
+}
+
 // The locate stage on ctx->stream: visiting order, passes, no synchronisation.  nn holds the first
 // kavail (<= k) candidates of every target (kavail < k only with `lazy`).  The number of targets
 // that were not found is added to ctx->d_counters[0].
@@ -999,62 +1074,69 @@ static int locate_gll_run(mm_context *ctx, int order, int dim, i64 k, int kavail
                           int snap_to_nearest, const GllEmit &em, const GllLazy *lazy)
 {
     unsigned long long *nm = (unsigned long long *)ctx->d_counters;
-    // scratch: visiting order, two pass queues, their counters, snap state
-    const int *visit = nullptr;
-    const i64 nbins = nelem + 1;
-    const i64 ntiles = (nbins + 1023) / 1024;
-    int rc = mm_scratch_begin(ctx, 3 * mm_round256((size_t)npoints * sizeof(int2)) +
-                                       2 * mm_round256((size_t)npoints * sizeof(int)) +
-                                       2 * mm_round256((size_t)(nbins + 1) * sizeof(int)) +
-                                       mm_round256((size_t)ntiles * sizeof(int)) +
-                                       (snap_to_nearest ? mm_round256((size_t)npoints * 5 * sizeof(double)) : 0) +
-                                       mm_round256(sizeof(int) * (MM_KNN_MAX_K + 8)) + 4096);
+    // scratch: two pass queues, their counters, the ids of the open targets, snap state, visiting order
+    const size_t snap = snap_to_nearest ? (size_t)npoints : 0;   // rows of the snap state
+    int rc = mm_scratch_begin(ctx, 2 * mm_round256((size_t)npoints * sizeof(int2)) +
+                                       mm_round256(sizeof(int) * (MM_KNN_MAX_K + 8)) +
+                                       mm_round256((size_t)npoints * sizeof(int)) + mm_round256(snap * kGllSnapStateBytes) +
+                                       mm_round256(snap * kGllSnapElemBytes) +
+                                       gll_visit_bytes(npoints, nelem) + 4096);
     if (rc != MM_OK) return rc;
     int2 *qa = (int2 *)mm_scratch_take(ctx, (size_t)npoints * sizeof(int2));
     int2 *qb = (int2 *)mm_scratch_take(ctx, (size_t)npoints * sizeof(int2));
     int *counters = (int *)mm_scratch_take(ctx, sizeof(int) * (MM_KNN_MAX_K + 8));
     int *id_list = (int *)mm_scratch_take(ctx, (size_t)npoints * sizeof(int));
-    double *best_state = snap_to_nearest ? (double *)mm_scratch_take(ctx, (size_t)npoints * 4 * sizeof(double)) : nullptr;
-    i64 *best_elem_state = snap_to_nearest ? (i64 *)mm_scratch_take(ctx, (size_t)npoints * sizeof(i64)) : nullptr;
+    double *best_state = snap ? (double *)mm_scratch_take(ctx, snap * kGllSnapStateBytes) : nullptr;
+    i64 *best_elem_state = snap ? (i64 *)mm_scratch_take(ctx, snap * kGllSnapElemBytes) : nullptr;
     MM_REQUIRE(qa && qb && counters && id_list && (!snap_to_nearest || (best_state && best_elem_state)),
                "scratch carve failed");
     MM_HIP_CHECK(hipMemsetAsync(counters, 0, sizeof(int) * (MM_KNN_MAX_K + 8), ctx->stream));
-    if (k > 0 && nelem > 0) {
-        int2 *key_rank = (int2 *)mm_scratch_take(ctx, (size_t)npoints * sizeof(int2));
-        int *ord = (int *)mm_scratch_take(ctx, (size_t)npoints * sizeof(int));
-        int *counts = (int *)mm_scratch_take(ctx, (size_t)(nbins + 1) * sizeof(int));
-        int *start = (int *)mm_scratch_take(ctx, (size_t)(nbins + 1) * sizeof(int));
-        int *tile_sums = (int *)mm_scratch_take(ctx, (size_t)ntiles * sizeof(int));
-        MM_REQUIRE(key_rank && ord && counts && start && tile_sums, "scratch carve failed");
-        MM_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)(nbins + 1) * sizeof(int), ctx->stream));
-        const unsigned gp = (unsigned)((npoints + 255) / 256);
-        hipLaunchKernelGGL((gll_key_kernel<IDX>), dim3(gp), dim3(256), 0, ctx->stream, (i64)kavail, npoints, nn, nelem,
-                           key_rank, counts);
-        rc = mm_exclusive_scan_int(ctx, counts, nbins, start, tile_sums);
-        if (rc != MM_OK) return rc;
-        hipLaunchKernelGGL(gll_order_kernel, dim3(gp), dim3(256), 0, ctx->stream, npoints, key_rank, start, ord);
-        visit = ord;
-    }
-    rc = MM_OK;
+    const int *visit = nullptr;
+    rc = gll_visit_order(ctx, __func__, nn, kavail, npoints, nelem, &visit);
+    if (rc != MM_OK) return rc;
     // (deferred values: only the fused pipeline's int32 lists ask for them)
     constexpr bool kCanDefer = sizeof(IDX) == sizeof(int);
     const bool defer = kCanDefer && em.xi_defer != nullptr;
-#define MM_GLL_CASE(O, D)                                                                                          \
-    if (order == O && dim == D) {                                                                                  \
-        if (defer)                                                                                                 \
-            rc = launch_locate<O, D, IDX, kCanDefer>(ctx, k, kavail, npoints, nn, gll_points_d, nelem, points_d,   \
-                                                     tolerance, snap_to_nearest, em, nm, visit, qa, qb, counters,  \
-                                                     best_state, best_elem_state, lazy, id_list);                  \
-        else                                                                                                       \
-            rc = launch_locate<O, D, IDX>(ctx, k, kavail, npoints, nn, gll_points_d, nelem, points_d, tolerance,   \
-                                          snap_to_nearest, em, nm, visit, qa, qb, counters, best_state,            \
-                                          best_elem_state, lazy, id_list);                                         \
-    }
-    MM_GLL_CASE(1, 2) MM_GLL_CASE(1, 3) MM_GLL_CASE(2, 2) MM_GLL_CASE(2, 3) MM_GLL_CASE(4, 2) MM_GLL_CASE(4, 3)
-#undef MM_GLL_CASE
+    gll_dispatch(order, dim, [&](auto o, auto d) {
+        constexpr int O = decltype(o)::value, D = decltype(d)::value;
+        rc = defer ? launch_locate<O, D, IDX, kCanDefer>(ctx, k, kavail, npoints, nn, gll_points_d, nelem, points_d,
+                                                         tolerance, snap_to_nearest, em, nm, visit, qa, qb, counters,
+                                                         best_state, best_elem_state, lazy, id_list)
+                   : launch_locate<O, D, IDX>(ctx, k, kavail, npoints, nn, gll_points_d, nelem, points_d, tolerance,
+                                              snap_to_nearest, em, nm, visit, qa, qb, counters, best_state,
+                                              best_elem_state, lazy, id_list);
+    });
     if (rc != MM_OK) return rc;
     MM_HIP_CHECK(hipGetLastError());
     return MM_OK;
+}
+
+// mm_locate_gll and mm_locate_gll_bbox: their argument rules; the counter cleared before `stage` and read back after it
+template <typename F>
+static int64_t gll_staged_call(const char *who, mm_context *ctx, int order, int dim, int64_t k, int64_t npoints,
+                               const int64_t *nn_d, const double *gll_points_d, int64_t nelem, const double *points_d,
+                               const int64_t *elem_d, const double *coeffs_d, F &&stage)
+{
+    MM_REQUIRE_AS(who, ctx != nullptr, "ctx is null");
+    MM_REQUIRE_AS(who, order == 1 || order == 2 || order == 4, "order must be 1, 2 or 4");
+    MM_REQUIRE_AS(who, dim == 2 || dim == 3, "dim must be 2 or 3");
+    MM_REQUIRE_AS(who, k >= 0 && npoints >= 0 && nelem >= 0, "negative size");
+    MM_REQUIRE_AS(who, k <= MM_KNN_MAX_K, "nelem_to_search must be <= MM_KNN_MAX_K");
+    MM_REQUIRE_AS(who, npoints == 0 || (elem_d && coeffs_d && points_d), "null array");
+    MM_REQUIRE_AS(who, npoints == 0 || k == 0 || (nn_d && gll_points_d), "null array");
+    MM_REQUIRE_AS(who, npoints < (int64_t)0x7fffffff && nelem < (int64_t)0x7ffffff0, "too many targets / elements");
+    MM_HIP_CHECK(hipSetDevice(ctx->device));
+    mm_stage_reset(ctx);
+    MM_HIP_CHECK(hipMemsetAsync(ctx->d_counters, 0, sizeof(i64), ctx->stream));
+    if (npoints > 0) {
+        mm_stage_begin(ctx, MM_STAGE_LOCATE);
+        const int rc = stage(who);
+        mm_stage_end(ctx, MM_STAGE_LOCATE);
+        if (rc != MM_OK) return rc;
+    }
+    MM_HIP_CHECK(hipMemcpyAsync(ctx->h_counters, ctx->d_counters, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
+    MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return ctx->h_counters[0];
 }
 
 extern "C" int64_t mm_locate_gll(mm_context *ctx, int order, int dim, int64_t k, int64_t npoints,
@@ -1062,28 +1144,12 @@ extern "C" int64_t mm_locate_gll(mm_context *ctx, int order, int dim, int64_t k,
                                  const double *points_d, double tolerance, int snap_to_nearest, int64_t *elem_d,
                                  double *coeffs_d)
 {
-    MM_REQUIRE(ctx != nullptr, "ctx is null");
-    MM_REQUIRE(order == 1 || order == 2 || order == 4, "order must be 1, 2 or 4");
-    MM_REQUIRE(dim == 2 || dim == 3, "dim must be 2 or 3");
-    MM_REQUIRE(k >= 0 && npoints >= 0 && nelem >= 0, "negative size");
-    MM_REQUIRE(k <= MM_KNN_MAX_K, "nelem_to_search must be <= MM_KNN_MAX_K");
-    MM_REQUIRE(npoints == 0 || (elem_d && coeffs_d && points_d), "null array");
-    MM_REQUIRE(npoints == 0 || k == 0 || (nn_d && gll_points_d), "null array");
-    MM_REQUIRE(npoints < (int64_t)0x7fffffff && nelem < (int64_t)0x7ffffff0, "too many targets / elements");
-    MM_HIP_CHECK(hipSetDevice(ctx->device));
-    mm_stage_reset(ctx);
-    MM_HIP_CHECK(hipMemsetAsync(ctx->d_counters, 0, sizeof(i64), ctx->stream));
-    if (npoints > 0) {
-        mm_stage_begin(ctx, MM_STAGE_LOCATE);
-        GllEmit em = {(i64 *)elem_d, coeffs_d, nullptr, nullptr, 0};
-        int rc = locate_gll_run<i64>(ctx, order, dim, k, (int)k, npoints, (const i64 *)nn_d, gll_points_d, nelem,
-                                     points_d, tolerance, snap_to_nearest, em, nullptr);
-        mm_stage_end(ctx, MM_STAGE_LOCATE);
-        if (rc != MM_OK) return rc;
-    }
-    MM_HIP_CHECK(hipMemcpyAsync(ctx->h_counters, ctx->d_counters, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
-    MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return ctx->h_counters[0];
+    return gll_staged_call(__func__, ctx, order, dim, k, npoints, nn_d, gll_points_d, nelem, points_d, elem_d, coeffs_d,
+                           [&](const char *) {
+        const GllEmit em = {(i64 *)elem_d, coeffs_d, nullptr, nullptr, 0};
+        return locate_gll_run<i64>(ctx, order, dim, k, (int)k, npoints, (const i64 *)nn_d, gll_points_d, nelem, points_d,
+                                   tolerance, snap_to_nearest, em, nullptr);
+    });
 }
 
 // Mean of the control nodes of every element, summed in node order like NumPy's mean(axis=1)
@@ -1103,6 +1169,54 @@ __global__ __launch_bounds__(256) void centroid_nodal_kernel(i64 nelem, int P, c
         for (int a = 0; a < DIM; ++a) acc[a] = acc[a] + row[p * DIM + a];
 #pragma unroll
     for (int a = 0; a < DIM; ++a) out[e * DIM + a] = acc[a] / (double)P;
+}
+
+// mm_interpolate_gll and mm_sample_columns_gll: the elements' centroid tree (`timed`: as two stages of the call's timers)
+static int gll_centroid_tree(mm_context *ctx, int order, int dim, const double *gll_points_d, i64 nelem, bool timed,
+                             mm_knn_index **ix)
+{
+    const int P = dim == 3 ? (order + 1) * (order + 1) * (order + 1) : (order + 1) * (order + 1);
+    double *cen = nullptr;
+    int rc = mm_buffer_get(ctx, MM_BUF_CENTROID, (size_t)nelem * dim * sizeof(double), (void **)&cen);
+    if (rc != MM_OK) return rc;
+    if (timed) mm_stage_begin(ctx, MM_STAGE_CENTROID);
+    const dim3 g((unsigned)((nelem + 255) / 256)), b(256);
+    if (dim == 3) hipLaunchKernelGGL((centroid_nodal_kernel<3>), g, b, 0, ctx->stream, nelem, P, gll_points_d, cen);
+    else hipLaunchKernelGGL((centroid_nodal_kernel<2>), g, b, 0, ctx->stream, nelem, P, gll_points_d, cen);
+    if (timed) {
+        mm_stage_end(ctx, MM_STAGE_CENTROID);
+        mm_stage_begin(ctx, MM_STAGE_KNN_BUILD);
+    }
+    rc = mm_knn_build_impl(ctx, cen, nelem, dim, ix, /*use_context_buffers=*/true, nullptr, 0);
+    if (timed) mm_stage_end(ctx, MM_STAGE_KNN_BUILD);
+    return rc;
+}
+
+static int gll_clear_missing(mm_context *ctx)
+{
+    const hipError_t e = hipMemsetAsync(ctx->d_counters, 0, sizeof(i64), ctx->stream);
+    if (e != hipSuccess) mm_set_error(MM_ERR_HIP, "memset: %s", hipGetErrorString(e));
+    return e == hipSuccess ? MM_OK : MM_ERR_HIP;
+}
+
+// The end of both calls: the number of missing targets read back (or rc, after the stream has drained), the tree given up
+static int64_t gll_finish(mm_context *ctx, int rc, mm_knn_index *ix, const char *what)
+{
+    int64_t result = rc;
+    if (rc == MM_OK) {
+        hipError_t e = hipMemcpyAsync(ctx->h_counters, ctx->d_counters, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) {
+            mm_set_error(MM_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+            result = MM_ERR_HIP;
+        } else {
+            result = ctx->h_counters[0];
+        }
+    } else {
+        (void)hipStreamSynchronize(ctx->stream);
+    }
+    if (ix) mm_knn_destroy(nullptr, ix);   // borrowed arrays stay in the context cache
+    return result;
 }
 
 // The GLL form of the whole path on resident arrays (reference interpolator.py:931-977, and the core of
@@ -1128,43 +1242,18 @@ extern "C" int64_t mm_interpolate_gll(mm_context *ctx, int order, int dim, const
     MM_HIP_CHECK(hipSetDevice(ctx->device));
     mm_stage_reset(ctx);
     if (npoints == 0) return 0;
-    const int P = dim == 3 ? (order + 1) * (order + 1) * (order + 1) : (order + 1) * (order + 1);
-
-    double *cen = nullptr;
-    int rc = mm_buffer_get(ctx, MM_BUF_CENTROID, (size_t)nelem * dim * sizeof(double), (void **)&cen);
-    if (rc != MM_OK) return rc;
-    mm_stage_begin(ctx, MM_STAGE_CENTROID);
-    {
-        const dim3 g((unsigned)((nelem + 255) / 256)), b(256);
-        if (dim == 3) hipLaunchKernelGGL((centroid_nodal_kernel<3>), g, b, 0, ctx->stream, nelem, P, gll_points_d, cen);
-        else hipLaunchKernelGGL((centroid_nodal_kernel<2>), g, b, 0, ctx->stream, nelem, P, gll_points_d, cen);
-    }
-    mm_stage_end(ctx, MM_STAGE_CENTROID);
 
     mm_knn_index *ix = nullptr;
-    mm_stage_begin(ctx, MM_STAGE_KNN_BUILD);
-    rc = mm_knn_build_impl(ctx, cen, nelem, dim, &ix, /*use_context_buffers=*/true, nullptr, 0);
-    mm_stage_end(ctx, MM_STAGE_KNN_BUILD);
+    int rc = gll_centroid_tree(ctx, order, dim, gll_points_d, nelem, /*timed=*/true, &ix);
     if (rc != MM_OK) return rc;
-
-    const bool lazy_on = ctx->lazy_lists && k > kGllLazyK;
-    const int kavail = lazy_on ? kGllLazyK : (int)k;
-    int *nn = nullptr, *nn_full = nullptr;
-    rc = mm_buffer_get(ctx, MM_BUF_NN, (size_t)npoints * kavail * sizeof(int), (void **)&nn);
-    if (rc == MM_OK && lazy_on)
-        rc = mm_buffer_get(ctx, MM_BUF_NN_FULL, (size_t)npoints * k * sizeof(int), (void **)&nn_full);
+    GllLists ls(ctx, k);
+    rc = ls.get(ctx, npoints, k);
     if (rc == MM_OK) {
         mm_stage_begin(ctx, MM_STAGE_KNN_QUERY);
-        rc = mm_knn_query_impl(ctx, ix, points_d, npoints, kavail, nn, nullptr, /*idx_is_int32=*/true);
+        rc = mm_knn_query_impl(ctx, ix, points_d, npoints, ls.kavail, ls.nn, nullptr, /*idx_is_int32=*/true);
         mm_stage_end(ctx, MM_STAGE_KNN_QUERY);
     }
-    if (rc == MM_OK) {
-        hipError_t e = hipMemsetAsync(ctx->d_counters, 0, sizeof(i64), ctx->stream);
-        if (e != hipSuccess) {
-            mm_set_error(MM_ERR_HIP, "memset: %s", hipGetErrorString(e));
-            rc = MM_ERR_HIP;
-        }
-    }
+    if (rc == MM_OK) rc = gll_clear_missing(ctx);
     if (rc == MM_OK) {
         mm_stage_begin(ctx, MM_STAGE_LOCATE);
         GllEmit em = {(i64 *)elem_out_d, coeffs_out_d, ncomp > 0 ? fields_d : nullptr, ncomp > 0 ? out_d : nullptr,
@@ -1175,20 +1264,19 @@ extern "C" int64_t mm_interpolate_gll(mm_context *ctx, int order, int dim, const
             rc = mm_buffer_get(ctx, MM_BUF_W, (size_t)npoints * dim * sizeof(double), (void **)&em.xi_defer);
             if (rc == MM_OK) rc = mm_buffer_get(ctx, MM_BUF_ENC, (size_t)npoints * sizeof(int), (void **)&em.elem_defer);
         }
-        GllLazy lz = {ix, nn_full};
+        GllLazy lz = {ix, ls.nn_full};
         if (rc == MM_OK)
-            rc = locate_gll_run<int>(ctx, order, dim, k, kavail, npoints, nn, gll_points_d, nelem, points_d, tolerance,
-                                     snap_to_nearest, em, lazy_on ? &lz : nullptr);
+            rc = locate_gll_run<int>(ctx, order, dim, k, ls.kavail, npoints, ls.nn, gll_points_d, nelem, points_d,
+                                     tolerance, snap_to_nearest, em, ls.lazy ? &lz : nullptr);
         mm_stage_end(ctx, MM_STAGE_LOCATE);
         if (rc == MM_OK && defer) {
             mm_stage_begin(ctx, MM_STAGE_GATHER);
             const dim3 g((unsigned)((npoints + 255) / 256)), b(256);
-#define MM_GLL_VALUES(O, D)                                                                                           \
-    if (order == O && dim == D)                                                                                       \
-        hipLaunchKernelGGL((gll_values_kernel<O, D>), g, b, 0, ctx->stream, (i64)npoints, (const int *)em.elem_defer,  \
-                           (const double *)em.xi_defer, fields_d, (i64)nelem, (int)ncomp, out_d);
-            MM_GLL_VALUES(1, 2) MM_GLL_VALUES(1, 3) MM_GLL_VALUES(2, 2) MM_GLL_VALUES(2, 3) MM_GLL_VALUES(4, 2) MM_GLL_VALUES(4, 3)
-#undef MM_GLL_VALUES
+            gll_dispatch(order, dim, [&](auto o, auto d) {
+                hipLaunchKernelGGL((gll_values_kernel<decltype(o)::value, decltype(d)::value>), g, b, 0, ctx->stream,
+                                   (i64)npoints, (const int *)em.elem_defer, (const double *)em.xi_defer, fields_d,
+                                   (i64)nelem, (int)ncomp, out_d);
+            });
             mm_stage_end(ctx, MM_STAGE_GATHER);
             if (hipGetLastError() != hipSuccess) {
                 mm_set_error(MM_ERR_HIP, "gll_values_kernel launch failed");
@@ -1196,21 +1284,7 @@ extern "C" int64_t mm_interpolate_gll(mm_context *ctx, int order, int dim, const
             }
         }
     }
-    int64_t result = rc;
-    if (rc == MM_OK) {
-        hipError_t e = hipMemcpyAsync(ctx->h_counters, ctx->d_counters, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            mm_set_error(MM_ERR_HIP, "pipeline: %s", hipGetErrorString(e));
-            result = MM_ERR_HIP;
-        } else {
-            result = ctx->h_counters[0];
-        }
-    } else {
-        (void)hipStreamSynchronize(ctx->stream);
-    }
-    if (ix) mm_knn_destroy(nullptr, ix);   // borrowed arrays stay in the context cache
-    return result;
+    return gll_finish(ctx, rc, ix, "pipeline");
 }
 
 // ---- mm_sample_columns_gll: a model sampled on latitude x longitude x depth columns --------------------------------
@@ -1246,8 +1320,6 @@ __global__ __launch_bounds__(256, kGllValuesWaves) void gll_column_values_kernel
                                                                  int ncomp, double fill, i64 stride,
                                                                  double *__restrict__ out)
 {
-    using G = Gll<ORDER, 3>;
-    constexpr int P = G::P;
     const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= npoints) return;
     const int e = elem[i];
@@ -1255,13 +1327,8 @@ __global__ __launch_bounds__(256, kGllValuesWaves) void gll_column_values_kernel
         for (int c = 0; c < ncomp; ++c) out[(i64)c * stride + i] = fill;
         return;
     }
-    double g[G::n];
-    gll_nodes<ORDER>(g);
-    double l[3][G::n], dl[3][G::n];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) lagrange_1d<ORDER>(g, xi_all[i * 3 + d], l[d], dl[d]);
-    for (int c = 0; c < ncomp; ++c)
-        out[(i64)c * stride + i] = G::template weighted_sum<true>(l, false, fields + ((i64)c * nelem + e) * P);
+    gll_target_values<ORDER, 3, true>((i64)e, xi_all + i * 3, true, fields, nelem, ncomp,
+                                      [&](int c, double v) { out[(i64)c * stride + i] = v; });
 }
 
 // Targets per chunk a call takes when the caller leaves it open (see MM_SAMPLE_CHUNK_BYTES in the header).
@@ -1299,80 +1366,48 @@ extern "C" int64_t mm_sample_columns_gll(mm_context *ctx, int order, const doubl
     MM_HIP_CHECK(hipSetDevice(ctx->device));
     mm_stage_reset(ctx);
     if (total == 0) return 0;
-    constexpr int P_of[5] = {0, 8, 27, 0, 125};
-    const int P = P_of[order];
 
-    double *cen = nullptr;
-    int rc = mm_buffer_get(ctx, MM_BUF_CENTROID, (size_t)nelem * 3 * sizeof(double), (void **)&cen);
-    if (rc != MM_OK) return rc;
-    hipLaunchKernelGGL((centroid_nodal_kernel<3>), dim3((unsigned)((nelem + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (i64)nelem, P, gll_points_d, cen);
     mm_knn_index *ix = nullptr;
-    rc = mm_knn_build_impl(ctx, cen, nelem, 3, &ix, /*use_context_buffers=*/true, nullptr, 0);
+    int rc = gll_centroid_tree(ctx, order, 3, gll_points_d, nelem, /*timed=*/false, &ix);
     if (rc != MM_OK) return rc;
-
-    const bool lazy_on = ctx->lazy_lists && k > kGllLazyK;
-    const int kavail = lazy_on ? kGllLazyK : (int)k;
-    i64 chunk = chunk_points > 0 ? chunk_points : sample_chunk_auto(k, kavail, lazy_on, points_out_d != nullptr);
+    GllLists ls(ctx, k);
+    i64 chunk = chunk_points > 0 ? chunk_points : sample_chunk_auto(k, ls.kavail, ls.lazy, points_out_d != nullptr);
     if (chunk > MM_SAMPLE_CHUNK_MAX) chunk = MM_SAMPLE_CHUNK_MAX;   // the locate stage's int32 target indices
     if (chunk > total) chunk = total;
-    int *nn = nullptr, *nn_full = nullptr, *elem = nullptr;
+    int *elem = nullptr;
     double *xi = nullptr, *pts_buf = nullptr;
-    rc = mm_buffer_get(ctx, MM_BUF_NN, (size_t)chunk * kavail * sizeof(int), (void **)&nn);
-    if (rc == MM_OK && lazy_on) rc = mm_buffer_get(ctx, MM_BUF_NN_FULL, (size_t)chunk * k * sizeof(int), (void **)&nn_full);
+    rc = ls.get(ctx, chunk, k);
     if (rc == MM_OK) rc = mm_buffer_get(ctx, MM_BUF_W, (size_t)chunk * 3 * sizeof(double), (void **)&xi);
     if (rc == MM_OK) rc = mm_buffer_get(ctx, MM_BUF_ENC, (size_t)chunk * sizeof(int), (void **)&elem);
     if (rc == MM_OK && !points_out_d)
         rc = mm_buffer_get(ctx, MM_BUF_SAMPLE_POINTS, (size_t)chunk * 3 * sizeof(double), (void **)&pts_buf);
-    if (rc == MM_OK) {
-        hipError_t e = hipMemsetAsync(ctx->d_counters, 0, sizeof(i64), ctx->stream);
-        if (e != hipSuccess) {
-            mm_set_error(MM_ERR_HIP, "memset: %s", hipGetErrorString(e));
-            rc = MM_ERR_HIP;
-        }
-    }
+    if (rc == MM_OK) rc = gll_clear_missing(ctx);
     GllEmit em = {nullptr, nullptr, nullptr, nullptr, 0};
     em.xi_defer = xi;
     em.elem_defer = elem;
-    const GllLazy lz = {ix, nn_full};
+    const GllLazy lz = {ix, ls.nn_full};
     for (i64 t0 = 0; rc == MM_OK && t0 < total; t0 += chunk) {
         const i64 n = total - t0 < chunk ? total - t0 : chunk;
         double *pts = points_out_d ? points_out_d + 3 * t0 : pts_buf;
         const dim3 g((unsigned)((n + 255) / 256)), b(256);
         hipLaunchKernelGGL(sample_points_kernel, g, b, 0, ctx->stream, t0, n, ncol, (i64)nlon, paired, lat_d, lon_d,
                            radius_d, pts);
-        rc = mm_knn_query_impl(ctx, ix, pts, n, kavail, nn, nullptr, /*idx_is_int32=*/true);
+        rc = mm_knn_query_impl(ctx, ix, pts, n, ls.kavail, ls.nn, nullptr, /*idx_is_int32=*/true);
         if (rc == MM_OK)
-            rc = locate_gll_run<int>(ctx, order, 3, k, kavail, n, nn, gll_points_d, nelem, pts, tolerance, 0, em,
-                                     lazy_on ? &lz : nullptr);
-        if (rc == MM_OK && ncomp > 0) {
-#define MM_GLL_COLUMNS(O)                                                                                             \
-    if (order == O)                                                                                                   \
-        hipLaunchKernelGGL((gll_column_values_kernel<O>), g, b, 0, ctx->stream, n, (const int *)elem, (const double *)xi, \
-                           fields_d, (i64)nelem, (int)ncomp, fill_value, total, out_d + t0);
-            MM_GLL_COLUMNS(1) MM_GLL_COLUMNS(2) MM_GLL_COLUMNS(4)
-#undef MM_GLL_COLUMNS
-        }
+            rc = locate_gll_run<int>(ctx, order, 3, k, ls.kavail, n, ls.nn, gll_points_d, nelem, pts, tolerance, 0, em,
+                                     ls.lazy ? &lz : nullptr);
+        if (rc == MM_OK && ncomp > 0)
+            gll_dispatch(order, 3, [&](auto o, auto) {
+                hipLaunchKernelGGL((gll_column_values_kernel<decltype(o)::value>), g, b, 0, ctx->stream, n,
+                                   (const int *)elem, (const double *)xi, fields_d, (i64)nelem, (int)ncomp, fill_value,
+                                   total, out_d + t0);
+            });
         if (rc == MM_OK && hipGetLastError() != hipSuccess) {
             mm_set_error(MM_ERR_HIP, "mm_sample_columns_gll: kernel launch failed");
             rc = MM_ERR_HIP;
         }
     }
-    int64_t result = rc;
-    if (rc == MM_OK) {
-        hipError_t e = hipMemcpyAsync(ctx->h_counters, ctx->d_counters, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            mm_set_error(MM_ERR_HIP, "mm_sample_columns_gll: %s", hipGetErrorString(e));
-            result = MM_ERR_HIP;
-        } else {
-            result = ctx->h_counters[0];
-        }
-    } else {
-        (void)hipStreamSynchronize(ctx->stream);
-    }
-    mm_knn_destroy(nullptr, ix);   // borrowed arrays stay in the context cache
-    return result;
+    return gll_finish(ctx, rc, ix, "mm_sample_columns_gll");
 }
 
 extern "C" int mm_gather_elem(mm_context *ctx, const double *fields_d, int64_t nelem, int64_t ncomp,
@@ -1407,62 +1442,26 @@ extern "C" int64_t mm_locate_gll_bbox(mm_context *ctx, int order, int dim, int64
                                       const int64_t *nn_d, const double *gll_points_d, int64_t nelem,
                                       const double *points_d, int64_t *elem_d, double *coeffs_d)
 {
-    MM_REQUIRE(ctx != nullptr, "ctx is null");
-    MM_REQUIRE(order == 1 || order == 2 || order == 4, "order must be 1, 2 or 4");
-    MM_REQUIRE(dim == 2 || dim == 3, "dim must be 2 or 3");
-    MM_REQUIRE(k >= 0 && npoints >= 0 && nelem >= 0, "negative size");
-    MM_REQUIRE(k <= MM_KNN_MAX_K, "nelem_to_search must be <= MM_KNN_MAX_K");
-    MM_REQUIRE(npoints == 0 || (elem_d && coeffs_d && points_d), "null array");
-    MM_REQUIRE(npoints == 0 || k == 0 || (nn_d && gll_points_d), "null array");
-    MM_REQUIRE(npoints < (int64_t)0x7fffffff && nelem < (int64_t)0x7ffffff0, "too many targets / elements");
-    MM_HIP_CHECK(hipSetDevice(ctx->device));
-    mm_stage_reset(ctx);
-    MM_HIP_CHECK(hipMemsetAsync(ctx->d_counters, 0, sizeof(i64), ctx->stream));
-    if (npoints > 0) {
-        mm_stage_begin(ctx, MM_STAGE_LOCATE);
-        const i64 nbins = nelem + 1;
-        const i64 ntiles = (nbins + 1023) / 1024;
-        int rc = mm_scratch_begin(ctx, mm_round256((size_t)(nelem > 0 ? nelem : 1) * 9 * sizeof(double)) +
-                                           mm_round256((size_t)npoints * sizeof(int2)) +
-                                           mm_round256((size_t)npoints * sizeof(int)) +
-                                           2 * mm_round256((size_t)(nbins + 1) * sizeof(int)) +
-                                           mm_round256((size_t)ntiles * sizeof(int)) + 4096);
+    return gll_staged_call(__func__, ctx, order, dim, k, npoints, nn_d, gll_points_d, nelem, points_d, elem_d, coeffs_d,
+                           [&](const char *who) -> int {
+        const size_t box_bytes = (size_t)(nelem > 0 ? nelem : 1) * 9 * sizeof(double);
+        int rc = mm_scratch_begin(ctx, mm_round256(box_bytes) + gll_visit_bytes(npoints, nelem) + 4096);
         if (rc != MM_OK) return rc;
-        double *boxes = (double *)mm_scratch_take(ctx, (size_t)(nelem > 0 ? nelem : 1) * 9 * sizeof(double));
-        MM_REQUIRE(boxes != nullptr, "scratch carve failed");
+        double *boxes = (double *)mm_scratch_take(ctx, box_bytes);
+        MM_REQUIRE_AS(who, boxes != nullptr, "scratch carve failed");
         const int *visit = nullptr;
-        if (k > 0 && nelem > 0) {
-            int2 *key_rank = (int2 *)mm_scratch_take(ctx, (size_t)npoints * sizeof(int2));
-            int *ord = (int *)mm_scratch_take(ctx, (size_t)npoints * sizeof(int));
-            int *counts = (int *)mm_scratch_take(ctx, (size_t)(nbins + 1) * sizeof(int));
-            int *start = (int *)mm_scratch_take(ctx, (size_t)(nbins + 1) * sizeof(int));
-            int *tile_sums = (int *)mm_scratch_take(ctx, (size_t)ntiles * sizeof(int));
-            MM_REQUIRE(key_rank && ord && counts && start && tile_sums, "scratch carve failed");
-            MM_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)(nbins + 1) * sizeof(int), ctx->stream));
-            const unsigned gp = (unsigned)((npoints + 255) / 256);
-            hipLaunchKernelGGL(gll_key_kernel, dim3(gp), dim3(256), 0, ctx->stream, k, npoints, (const i64 *)nn_d, nelem,
-                               key_rank, counts);
-            rc = mm_exclusive_scan_int(ctx, counts, nbins, start, tile_sums);
-            if (rc != MM_OK) return rc;
-            hipLaunchKernelGGL(gll_order_kernel, dim3(gp), dim3(256), 0, ctx->stream, npoints, key_rank, start, ord);
-            visit = ord;
-        }
+        rc = gll_visit_order(ctx, who, (const i64 *)nn_d, (int)k, npoints, nelem, &visit);
+        if (rc != MM_OK) return rc;
         unsigned long long *nh = (unsigned long long *)ctx->d_counters;
         const unsigned ge = (unsigned)((nelem + 255) / 256), gt = (unsigned)((npoints + 63) / 64);
-#define MM_GLL_V1_CASE(O, D)                                                                                          \
-    if (order == O && dim == D) {                                                                                     \
-        if (nelem > 0)                                                                                                \
-            hipLaunchKernelGGL((gll_box_kernel<O, D>), dim3(ge), dim3(256), 0, ctx->stream, nelem, gll_points_d, boxes); \
-        hipLaunchKernelGGL((locate_gll_v1_kernel<O, D>), dim3(gt), dim3(64), 0, ctx->stream, k, npoints,             \
-                           (const i64 *)nn_d, gll_points_d, nelem, boxes, points_d, (i64 *)elem_d, coeffs_d, nh, visit); \
-    }
-        MM_GLL_V1_CASE(1, 2) MM_GLL_V1_CASE(1, 3) MM_GLL_V1_CASE(2, 2) MM_GLL_V1_CASE(2, 3) MM_GLL_V1_CASE(4, 2)
-        MM_GLL_V1_CASE(4, 3)
-#undef MM_GLL_V1_CASE
-        mm_stage_end(ctx, MM_STAGE_LOCATE);
+        gll_dispatch(order, dim, [&](auto o, auto d) {
+            constexpr int O = decltype(o)::value, D = decltype(d)::value;
+            if (nelem > 0)
+                hipLaunchKernelGGL((gll_box_kernel<O, D>), dim3(ge), dim3(256), 0, ctx->stream, nelem, gll_points_d, boxes);
+            hipLaunchKernelGGL((locate_gll_v1_kernel<O, D>), dim3(gt), dim3(64), 0, ctx->stream, k, npoints,
+                               (const i64 *)nn_d, gll_points_d, nelem, boxes, points_d, (i64 *)elem_d, coeffs_d, nh, visit);
+        });
         MM_HIP_CHECK(hipGetLastError());
-    }
-    MM_HIP_CHECK(hipMemcpyAsync(ctx->h_counters, ctx->d_counters, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
-    MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return ctx->h_counters[0];
+        return MM_OK;
+    });
 }

@@ -692,6 +692,40 @@ def test_gll_bbox_variant_equals_the_oracle(ctx, order, dim):
     assert outside.sum() > 100 and np.abs(c_o[outside].sum(axis=1) - 1).max() < 1e-12
 
 
+def gll_lists_with_invalid_ids(order, dim):
+    """500 targets with k = 6 candidate lists of which about a third carry ids outside [0, nelem) -- -1 and nelem, at
+    the head, in the middle, or in every place of the row (fixed seed) -> (mesh, targets, lists, rows wholly invalid)."""
+    gp = synth.gll_mesh(5 if dim == 3 else 12, order, seed=4, jitter=0.25, dim=dim)
+    nelem = len(gp)
+    rng = np.random.default_rng(100 * order + dim)
+    pts = rng.uniform(-0.02, 1.02, size=(500, dim))
+    nn = O.knn_ckdtree(gp.mean(axis=1), pts, 6)[0].copy()
+    kind = rng.integers(0, 9, size=len(pts))            # 0: head, 1: middle, 2: the whole row, 3..8: untouched
+    bad = rng.choice([-1, nelem], size=nn.shape)
+    nn[kind == 0, :2] = bad[kind == 0, :2]
+    nn[kind == 1, 2:4] = bad[kind == 1, 2:4]
+    nn[kind == 2] = bad[kind == 2]
+    return gp, pts, nn, kind == 2
+
+
+@pytest.mark.parametrize("order,dim", [(1, 2), (4, 3)])
+def test_gll_staged_locates_skip_invalid_candidate_ids(ctx, order, dim):
+    # the visiting order (invalid first candidates sort into the last bin) and the id skip are one piece of code for
+    # mm_locate_gll and mm_locate_gll_bbox: elements, coefficients and counts bit for bit as the oracle's
+    gp, pts, nn, empty = gll_lists_with_invalid_ids(order, dim)
+    assert empty.sum() > 0 and ((nn < 0) | (nn >= len(gp))).any(axis=1).sum() > len(pts) // 4
+    for snap in (False, True):
+        elem, co, miss = ctx.locate_gll(order, nn, gp, pts, tolerance=1.05, snap_to_nearest=snap)
+        elem_o, co_o, miss_o = O.locate_gll(order, nn, gp, pts, tolerance=1.05, snap_to_nearest=snap)
+        assert miss == miss_o and (snap or miss >= empty.sum() > 0)
+        assert np.array_equal(elem.numpy(), elem_o) and np.array_equal(co.numpy(), co_o)
+        assert snap or (elem_o[empty] == -1).all()
+    elem, co, hard = ctx.locate_gll_bbox(order, nn, gp, pts)
+    elem_o, co_o, hard_o = O.locate_gll_v1(order, nn, gp, pts)
+    assert hard == hard_o and hard >= empty.sum()
+    assert np.array_equal(elem.numpy(), elem_o) and np.array_equal(co.numpy(), co_o)
+
+
 @pytest.mark.parametrize("k", [1, 2, 24, 25])
 def test_knn_list_capacities_that_are_not_a_multiple_of_four(ctx, k):
     # K = 1, 2 and 25 give list capacities of 9, 10 and 37: the last batch of four of the rank loop

@@ -6,6 +6,7 @@
 #include <stdio.h>
 
 #include "multimesh_hip.h"
+#include "mm_scratch_layout.h"
 
 typedef long long i64;
 
@@ -25,6 +26,15 @@ void mm_set_error(int code, const char *fmt, ...);
     do {                                                                                \
         if (!(cond)) {                                                                  \
             mm_set_error(MM_ERR_ARG, "%s: %s", __func__, msg);                          \
+            return MM_ERR_ARG;                                                          \
+        }                                                                               \
+    } while (0)
+
+// MM_REQUIRE on behalf of the entry point `who` (a helper's or a lambda's own __func__ would name the wrong function)
+#define MM_REQUIRE_AS(who, cond, msg)                                                   \
+    do {                                                                                \
+        if (!(cond)) {                                                                  \
+            mm_set_error(MM_ERR_ARG, "%s: %s", who, msg);                               \
             return MM_ERR_ARG;                                                          \
         }                                                                               \
     } while (0)
@@ -127,11 +137,9 @@ struct mm_context {
     hipEvent_t ev_copy[3] = {nullptr, nullptr, nullptr};
 };
 
-// Reserve `total` bytes of scratch for the current call (may reallocate), then carve with
-// mm_scratch_take.  All carve sizes are rounded up to 256 B.
-int mm_scratch_begin(mm_context *ctx, size_t total);
-void *mm_scratch_take(mm_context *ctx, size_t bytes);
-static inline size_t mm_round256(size_t b) { return (b + 255) & ~(size_t)255; }
+// The scratch of a call: the drivers state their arrays in an mm_scratch_layout and commit it (mm_scratch_layout.h, which
+// also declares mm_round256 and the two primitives under commit(): reserve, then carve piece by piece; mm_context.hip
+// defines them and no driver calls them itself).  All carve sizes are rounded up to 256 B.
 // bytes to clear for a carve of `b` bytes: whole 256-byte units (the carve is rounded up to them, and an odd
 // tail costs a second fill dispatch) -- except under MM_GUARD_ALLOC, where the carve ends with its array
 static inline size_t mm_fill_span(size_t b) { return mm_guard_alloc() ? b : mm_round256(b); }
@@ -206,6 +214,27 @@ int mm_knn_query_list_impl(mm_context *ctx, const mm_knn_index *ix, const double
                            int *idx_d, const int *list, const int *list_count, i64 list_len_hint);
 int mm_launch_gather(mm_context *ctx, const double *fields, i64 nsrc, i64 ncomp, const i64 *ids,
                      const double *w, i64 npoints, i64 P, double *out, int out_point_major);
+// (mm_context.hip) the status mm_last_status reports back to MM_OK
+void mm_clear_status(void);
+// (mm_knn.hip) exclusive prefix sum of n ints on ctx->stream: start[0..n]; tile_sums: scratch of ceil(n / 1024) ints
+int mm_exclusive_scan_int(mm_context *ctx, const int *counts, i64 n, int *start, int *tile_sums);
+// (mm_unique.hip) the stable LSD radix sort of 64-bit keys with 32-bit values, and the bytes of scratch it asks for
+size_t mm_radix_sort_scratch(i64 n);
+int mm_radix_sort_pairs(mm_context *ctx, unsigned long long *ka, unsigned long long *kb, unsigned *va, unsigned *vb, i64 n,
+                        int first_shift, int end_shift, void *scratch, bool *in_a);
+// (mm_knn.hip) the kNN index without the stage timers: build -- plain, over a guessed grid, in one pass over the mesh --,
+// the check of a guess after the call's last synchronisation, and the queries
+int mm_knn_build_impl(mm_context *ctx, const double *src_d, i64 nsrc, i64 ndim, mm_knn_index **out,
+                      bool use_context_buffers, const double *box_partial_d, int box_nblocks, bool hex8_centroids = false);
+int mm_knn_build_guessed(mm_context *ctx, const double *cen, i64 nelem, const double *box_partial, int box_nblocks,
+                         mm_knn_index **out);
+int mm_knn_build_one_pass(mm_context *ctx, const i64 *conn, const double *nodes, i64 nelem, double *box_partial,
+                          int box_nblocks, mm_knn_index **out);
+bool mm_knn_guess_confirmed(mm_context *ctx);
+int mm_knn_query_impl(mm_context *ctx, const mm_knn_index *ix, const double *pts_d, i64 npts, i64 k, void *idx_d,
+                      double *dist_d, bool idx_is_int32);
+int mm_knn_query_sorted_impl(mm_context *ctx, const mm_knn_index *ix, const double *pts_d, i64 npts, i64 k, int *idx_d,
+                             const double **tsorted_out);
 
 // The density-adaptive part of a kNN index (mm_knn_tree.inc.h): the sources in Morton order.
 struct mm_knn_tree {

@@ -20,18 +20,13 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include <memory>
 #include <new>
 #include <type_traits>
 
 #include "mm_common.h"
 #include "mm_grid_cell.h"
 #include <cstring>
-
-int mm_exclusive_scan_int(mm_context *ctx, const int *counts, i64 n, int *start, int *tile_sums);
-// (mm_unique.hip: the stable LSD radix sort of 64-bit keys with 32-bit values)
-size_t mm_radix_sort_scratch(i64 n);
-int mm_radix_sort_pairs(mm_context *ctx, unsigned long long *ka, unsigned long long *kb, unsigned *va, unsigned *vb, i64 n,
-                        int first_shift, int end_shift, void *scratch, bool *in_a);
 
 namespace {
 #include "mm_knn_grid.inc.h"
@@ -56,9 +51,12 @@ __global__ __launch_bounds__(kBlock) void target_scatter_kernel(const int *__res
     store_record(tsorted + pos * kRec, x, y, z, (int)p);
 }
 
-// scratch of the lane kernel's work-item prepass (knn_query_typed carves it)
+// What serves level 0 of a query (choose_lane) and, for the lane kernel, the scratch of its work-item prepass
+// (knn_query_typed puts it into the call's layout)
 constexpr int kLaneMaxK = 20;
 struct LaneWork {
+    bool use_lane;       // knn_lane_kernel instead of the strip / cell kernels
+    bool probe;          // ... if the occupied strips turn out well filled: decided after the sort (lane_probe_readback)
     int Z;
     int T, W;            // thin layers per cell layer, half-width of a target's window in thin layers
     int sorted_rows;     // rows and hand-overs by position in the cell-sorted order
@@ -299,6 +297,14 @@ void free_index(mm_knn_index *ix)
     delete ix;
 }
 
+// An index (a tree) under construction: freed on every way out but the one that releases it to the caller.
+struct IndexDeleter {
+    void operator()(mm_knn_index *ix) const { free_index(ix); }
+    void operator()(mm_knn_tree *tr) const { free_tree(tr); }
+};
+using IndexOwner = std::unique_ptr<mm_knn_index, IndexDeleter>;
+using TreeOwner = std::unique_ptr<mm_knn_tree, IndexDeleter>;
+
 }  // namespace
 
 // Exclusive prefix sum of n ints on the context's stream: start[0..n] (start[n] = total).
@@ -421,7 +427,8 @@ static int build_level(mm_context *ctx, const double *src_d, i64 nsrc, int ndim,
     const int slot_cells = level == 0 ? (int)MM_BUF_CELL_START : (int)MM_BUF_LEVELS + 2 * (level - 1);
     const int slot_xyz = level == 0 ? (int)MM_BUF_SORTED_XYZ : (int)MM_BUF_LEVELS + 2 * (level - 1) + 1;
     *out = nullptr;
-    mm_knn_index *ix = new (std::nothrow) mm_knn_index();
+    IndexOwner owner(new (std::nothrow) mm_knn_index());
+    mm_knn_index *ix = owner.get();
     if (!ix) {
         mm_set_error(MM_ERR_ALLOC, "out of host memory");
         return MM_ERR_ALLOC;
@@ -445,37 +452,27 @@ static int build_level(mm_context *ctx, const double *src_d, i64 nsrc, int ndim,
         int brc = mm_buffer_get(ctx, slot_cells, (size_t)(ncells + 1) * sizeof(int), (void **)&ix->cell_start);
         if (brc == MM_OK)
             brc = mm_buffer_get(ctx, slot_xyz, (size_t)(nsrc + 1) * kRec * sizeof(double), (void **)&ix->sorted_xyz);
-        if (brc != MM_OK) {
-            free_index(ix);
-            return brc;
-        }
+        if (brc != MM_OK) return brc;
     } else {
         e = mm_raw_alloc(ctx->device, (void **)&ix->cell_start, (size_t)(ncells + 1) * sizeof(int));
         if (e == hipSuccess)
             e = mm_raw_alloc(ctx->device, (void **)&ix->sorted_xyz, (size_t)(nsrc + 1) * kRec * sizeof(double));
         if (e != hipSuccess) {
             mm_set_error(MM_ERR_ALLOC, "kNN index allocation failed: %s", hipGetErrorString(e));
-            free_index(ix);
             return MM_ERR_ALLOC;
         }
     }
     const int ntiles = (int)((ncells + kScanTile - 1) / kScanTile);
-    size_t need = mm_round256((size_t)(nsrc > 0 ? nsrc : 1) * sizeof(int)) +     // rank of every source in its cell
-                  mm_round256((size_t)(ncells + 1) * sizeof(int)) +              // counts
-                  mm_round256((size_t)ntiles * sizeof(int)) + 4096;
-    int rc = mm_scratch_begin(ctx, need);
-    if (rc != MM_OK) { free_index(ix); return rc; }
-    int *cell_of = (int *)mm_scratch_take(ctx, (size_t)(nsrc > 0 ? nsrc : 1) * sizeof(int));   // rank of every source in its cell
-    int *counts = (int *)mm_scratch_take(ctx, (size_t)(ncells + 1) * sizeof(int));
-    int *tile_sums = (int *)mm_scratch_take(ctx, (size_t)ntiles * sizeof(int));
-    if (!cell_of || !counts || !tile_sums) {
-        mm_set_error(MM_ERR_ALLOC, "scratch carve failed");
-        free_index(ix);
-        return MM_ERR_ALLOC;
-    }
+    int *cell_of, *counts, *tile_sums;
+    mm_scratch_layout lay;
+    lay.add(&cell_of, (size_t)(nsrc > 0 ? nsrc : 1));   // rank of every source in its cell
+    lay.add(&counts, (size_t)(ncells + 1));
+    lay.add(&tile_sums, (size_t)ntiles);
+    int rc = lay.commit(ctx, __func__);
+    if (rc != MM_OK) return rc;
     // (whole 256-byte units -- the carve is rounded up to them --: an odd tail costs a second fill dispatch)
     rc = mm_zero_async(ctx, counts, mm_fill_span((size_t)(ncells + 1) * sizeof(int)));
-    if (rc != MM_OK) { free_index(ix); return rc; }
+    if (rc != MM_OK) return rc;
     const unsigned gsrc = (unsigned)((nsrc + kBlock - 1) / kBlock);
     if (guessed)   // this call's own box goes to the pinned mirror, where mm_knn_guess_confirmed finds it at the end of the call
         {
@@ -511,7 +508,6 @@ static int build_level(mm_context *ctx, const double *src_d, i64 nsrc, int ndim,
         if (e == hipSuccess) e = hipEventRecord(ctx->ev_misc, ctx->stream);
         if (e != hipSuccess) {
             mm_set_error(MM_ERR_HIP, "grid statistic: %s", hipGetErrorString(e));
-            free_index(ix);
             return MM_ERR_HIP;
         }
     }
@@ -521,7 +517,6 @@ static int build_level(mm_context *ctx, const double *src_d, i64 nsrc, int ndim,
     e = hipGetLastError();
     if (e != hipSuccess) {
         mm_set_error(MM_ERR_HIP, "kNN build launch: %s", hipGetErrorString(e));
-        free_index(ix);
         return MM_ERR_HIP;
     }
     if (guessed) *guessed->stat_shift = want_stat ? sample_shift : -1;
@@ -529,7 +524,6 @@ static int build_level(mm_context *ctx, const double *src_d, i64 nsrc, int ndim,
         e = hipEventSynchronize(ctx->ev_misc);
         if (e != hipSuccess) {
             mm_set_error(MM_ERR_HIP, "grid statistic: %s", hipGetErrorString(e));
-            free_index(ix);
             return MM_ERR_HIP;
         }
         double sparse_count = 0.0;
@@ -544,7 +538,7 @@ static int build_level(mm_context *ctx, const double *src_d, i64 nsrc, int ndim,
             fprintf(stderr, " -> level mask 0x%x\n", *level_extra);
         }
     }
-    *out = ix;
+    *out = owner.release();
     return MM_OK;
 }
 
@@ -568,13 +562,11 @@ int mm_knn_build_impl(mm_context *ctx, const double *src_d, i64 nsrc, i64 ndim, 
             hipLaunchKernelGGL(bbox_final_kernel, dim3(6), dim3(kBlock), 0, ctx->stream, box_partial_d, box_nblocks, h_box, stat16);
         } else {
             const int nblocks = (int)((nsrc + kBlock - 1) / kBlock < 1024 ? (nsrc + kBlock - 1) / kBlock : 1024);
-            int rc = mm_scratch_begin(ctx, (size_t)nblocks * 6 * sizeof(double) + 1024);
+            double *partial;
+            mm_scratch_layout lay;
+            lay.add(&partial, (size_t)nblocks * 6);
+            const int rc = lay.commit(ctx, __func__);
             if (rc != MM_OK) return rc;
-            double *partial = (double *)mm_scratch_take(ctx, (size_t)nblocks * 6 * sizeof(double));
-            if (!partial) {
-                mm_set_error(MM_ERR_ALLOC, "scratch carve failed");
-                return MM_ERR_ALLOC;
-            }
             hipLaunchKernelGGL(bbox_partial_kernel, dim3(nblocks), dim3(kBlock), 0, ctx->stream, src_d, nsrc, (int)ndim, partial);
             hipLaunchKernelGGL(bbox_final_kernel, dim3(6), dim3(kBlock), 0, ctx->stream, partial, nblocks, h_box, stat16);
         }
@@ -591,18 +583,19 @@ int mm_knn_build_impl(mm_context *ctx, const double *src_d, i64 nsrc, i64 ndim, 
     int max_levels = kMaxLevels;
     if (const char *env = getenv("MM_KNN_LEVELS")) max_levels = atoi(env) < 1 ? 1 : (atoi(env) > kMaxLevels ? kMaxLevels : atoi(env));
     int extra = 0;
-    mm_knn_index *head = nullptr;
+    IndexOwner head;   // (the index under construction, with the levels and the tree hung on it so far)
     int rc = MM_OK;
     double per_cell_level0 = per_cell;
     for (int scale = 1;; scale *= 2) {
         per_cell_level0 = per_cell;
         double sparse = 0.0;
+        mm_knn_index *level0 = nullptr;
         rc = build_level(ctx, src_d, nsrc, (int)ndim, box, per_cell, use_context_buffers, 0, max_levels > 1 ? &extra : nullptr,
-                         &head, &sparse, /*stat_dirty=*/scale > 1 || nsrc == 0);
+                         &level0, &sparse, /*stat_dirty=*/scale > 1 || nsrc == 0);
         if (rc != MM_OK) return rc;
+        head.reset(level0);
         if (scale >= 4 || !(sparse > kSparseShare)) break;
-        free_index(head);   // a large sparse region: cells of twice the volume
-        head = nullptr;
+        head.reset();   // a large sparse region: cells of twice the volume
         per_cell *= 2.0;
     }
     // a graded cloud: the adaptive index instead of a stack of denser grids (MM_KNN_TREE, see tree_mode)
@@ -615,33 +608,27 @@ int mm_knn_build_impl(mm_context *ctx, const double *src_d, i64 nsrc, i64 ndim, 
         // cloud asks for levels at all)
         const bool deepest = (extra & (1 << (kMaxLevels - 2))) != 0, mesh_graded = (box_partial_d != nullptr || hex8_centroids) && extra != 0;
         if (cube && (mode == 1 || (mode == -1 && (deepest || mesh_graded) && max_levels > 1))) {
-            rc = tree_build(ctx, head, src_d, nsrc, box, use_context_buffers);
-            if (rc != MM_OK) {
-                free_index(head);
-                return rc;
-            }
+            rc = tree_build(ctx, head.get(), src_d, nsrc, box, use_context_buffers);
+            if (rc != MM_OK) return rc;
             extra = 0x10000;   // (no density levels; not a plain grid either: see grid_guess below)
         }
     }
-    mm_knn_index *tail = head;
+    mm_knn_index *tail = head.get();
     for (int l = 1; l < max_levels; ++l) {
         per_cell /= kLevelRatio;
         if (!(extra & (1 << (l - 1)))) continue;
         if ((double)nsrc / per_cell > (double)kLevelMaxCells) break;
         mm_knn_index *lvl = nullptr;
         rc = build_level(ctx, src_d, nsrc, (int)ndim, box, per_cell, use_context_buffers, l, nullptr, &lvl);
-        if (rc != MM_OK) {
-            free_index(head);
-            return rc;
-        }
+        if (rc != MM_OK) return rc;
         tail->fine = lvl;
         tail = lvl;
     }
-    *out = head;
+    *out = head.release();
     // the fused pipeline's next call over a source mesh of this size may start from this grid (mm_knn_build_guessed):
     // only the plain case -- one level, laid out at the default density
     if (use_context_buffers && box_partial_d && ndim == 3) {
-        ctx->grid_guess.valid = !head->fine && extra == 0 && per_cell_level0 == kDefaultPerCell && max_levels > 1;
+        ctx->grid_guess.valid = !(*out)->fine && extra == 0 && per_cell_level0 == kDefaultPerCell && max_levels > 1;
         ctx->grid_guess.nsrc = nsrc;
         for (int q = 0; q < 6; ++q) ctx->grid_guess.box[q] = box[q];
         // (head is then the one level-0 grid of this box at the default density, sorted into the context's buffers)
@@ -689,7 +676,8 @@ int mm_knn_build_one_pass(mm_context *ctx, const i64 *conn, const double *nodes,
                           int box_nblocks, mm_knn_index **out)
 {
     *out = nullptr;
-    mm_knn_index *ix = new (std::nothrow) mm_knn_index();
+    IndexOwner owner(new (std::nothrow) mm_knn_index());
+    mm_knn_index *ix = owner.get();
     if (!ix) {
         mm_set_error(MM_ERR_ALLOC, "out of host memory");
         return MM_ERR_ALLOC;
@@ -703,25 +691,17 @@ int mm_knn_build_one_pass(mm_context *ctx, const i64 *conn, const double *nodes,
     // (the sizes of the build that left the buffers: no reallocation, the contents stay)
     int rc = mm_buffer_get(ctx, MM_BUF_CELL_START, (size_t)(ncells + 1) * sizeof(int), (void **)&ix->cell_start);
     if (rc == MM_OK) rc = mm_buffer_get(ctx, MM_BUF_SORTED_XYZ, (size_t)(nelem + 1) * kRec * sizeof(double), (void **)&ix->sorted_xyz);
-    if (rc == MM_OK) rc = mm_scratch_begin(ctx, mm_round256((size_t)(ncells + 1) * sizeof(int)) + 1024);
-    int *cursor = rc == MM_OK ? (int *)mm_scratch_take(ctx, (size_t)(ncells + 1) * sizeof(int)) : nullptr;
-    if (rc == MM_OK && !cursor) {
-        mm_set_error(MM_ERR_ALLOC, "scratch carve failed");
-        rc = MM_ERR_ALLOC;
-    }
-    if (rc != MM_OK) {
-        free_index(ix);
-        return rc;
-    }
+    int *cursor;
+    mm_scratch_layout lay;
+    lay.add(&cursor, (size_t)(ncells + 1));
+    if (rc == MM_OK) rc = lay.commit(ctx, __func__);
+    if (rc != MM_OK) return rc;
     mm_stage_begin(ctx, MM_STAGE_CENTROID);
     rc = mm_zero_async(ctx, cursor, mm_fill_span((size_t)(ncells + 1) * sizeof(int)));
     if (rc == MM_OK)
         rc = mm_launch_centroid_sort(ctx, nelem, conn, nodes, g, ix->cell_start, cursor, ix->sorted_xyz, box_partial, box_nblocks);
     mm_stage_end(ctx, MM_STAGE_CENTROID);
-    if (rc != MM_OK) {
-        free_index(ix);
-        return rc;
-    }
+    if (rc != MM_OK) return rc;
     mm_stage_begin(ctx, MM_STAGE_KNN_BUILD);
     GuessBox gb6;
     for (int q = 0; q < 6; ++q) gb6.v[q] = ctx->grid_guess.box[q];
@@ -736,12 +716,11 @@ int mm_knn_build_one_pass(mm_context *ctx, const i64 *conn, const double *nodes,
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         mm_set_error(MM_ERR_HIP, "one-pass kNN build launch: %s", hipGetErrorString(e));
-        free_index(ix);
         return MM_ERR_HIP;
     }
     ctx->grid_guess.stat_shift = -1;
     ctx->knn_kernels |= MM_KNN_RAN_ONE_PASS;
-    *out = ix;
+    *out = owner.release();
     return MM_OK;
 }
 
@@ -788,7 +767,8 @@ static int tree_mode()
 static int tree_build(mm_context *ctx, mm_knn_index *ix, const double *src_d, i64 nsrc, const double *box,
                       bool use_context_buffers)
 {
-    mm_knn_tree *tr = new (std::nothrow) mm_knn_tree();
+    TreeOwner owner(new (std::nothrow) mm_knn_tree());
+    mm_knn_tree *tr = owner.get();
     if (!tr) {
         mm_set_error(MM_ERR_ALLOC, "out of host memory");
         return MM_ERR_ALLOC;
@@ -818,25 +798,17 @@ static int tree_build(mm_context *ctx, mm_knn_index *ix, const double *src_d, i6
             rc = MM_ERR_ALLOC;
         }
     }
-    if (rc != MM_OK) {
-        free_tree(tr);
-        return rc;
-    }
-    const size_t need = mm_round256(n_sz * sizeof(u64)) + 2 * mm_round256(n_sz * sizeof(unsigned)) + mm_radix_sort_scratch(nsrc) + 1024;
-    rc = mm_scratch_begin(ctx, need);
-    if (rc != MM_OK) {
-        free_tree(tr);
-        return rc;
-    }
-    u64 *key_b = (u64 *)mm_scratch_take(ctx, n_sz * sizeof(u64));
-    unsigned *val_a = (unsigned *)mm_scratch_take(ctx, n_sz * sizeof(unsigned));
-    unsigned *val_b = (unsigned *)mm_scratch_take(ctx, n_sz * sizeof(unsigned));
-    void *radix = mm_scratch_take(ctx, mm_radix_sort_scratch(nsrc));
-    if (!key_b || !val_a || !val_b || !radix) {
-        mm_set_error(MM_ERR_ALLOC, "scratch carve failed");
-        free_tree(tr);
-        return MM_ERR_ALLOC;
-    }
+    if (rc != MM_OK) return rc;
+    u64 *key_b;
+    unsigned *val_a, *val_b;
+    void *radix;
+    mm_scratch_layout lay;
+    lay.add(&key_b, n_sz);
+    lay.add(&val_a, n_sz);
+    lay.add(&val_b, n_sz);
+    lay.add(&radix, mm_radix_sort_scratch(nsrc));
+    rc = lay.commit(ctx, __func__);
+    if (rc != MM_OK) return rc;
     const TreeParams tp = tree_params_of(tr);
     const unsigned gsrc = (unsigned)((nsrc + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(tree_keys_kernel, dim3(gsrc), dim3(kBlock), 0, ctx->stream, src_d, nsrc, 3, 3, tp, (const int *)nullptr,
@@ -846,7 +818,6 @@ static int tree_build(mm_context *ctx, mm_knn_index *ix, const double *src_d, i6
     rc = mm_radix_sort_pairs(ctx, tr->keys, key_b, val_a, val_b, nsrc, 0, kTreeBits, radix, &in_a);
     if (rc != MM_OK || !in_a) {
         if (rc == MM_OK) mm_set_error(MM_ERR_HIP, "kNN tree: the sort ended in the wrong buffer");
-        free_tree(tr);
         return rc != MM_OK ? rc : MM_ERR_HIP;
     }
     hipLaunchKernelGGL(tree_records_kernel, dim3(gsrc), dim3(kBlock), 0, ctx->stream, src_d, 3, 3, val_a, nsrc, (const int *)nullptr, tr->xyz);
@@ -856,10 +827,9 @@ static int tree_build(mm_context *ctx, mm_knn_index *ix, const double *src_d, i6
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         mm_set_error(MM_ERR_HIP, "kNN tree build launch: %s", hipGetErrorString(e));
-        free_tree(tr);
         return MM_ERR_HIP;
     }
-    ix->tree = tr;
+    ix->tree = owner.release();
     return MM_OK;
 }
 
@@ -895,6 +865,105 @@ static void tree_ring(mm_context *ctx, const mm_knn_index *ix, const double *pts
 // lists shorter than this go straight to the ring search (sparse targets fill no 64-lane rounds)
 constexpr i64 kTreeRingListMax = 65536;
 
+// The environment knobs of the query path, read in ONE place (the choice of the kernel takes them as input).
+// MM_KNN_FORCE_LIST -- like MM_KNN_LEVELS and MM_KNN_TREE in the build -- is read per call on purpose: tests switch them
+// inside one process.  Every other knob is read once per process; whether MM_KNN_KERNEL is set at all is also asked per
+// call (a forced kernel is never probed).  (launch_fast reads MM_KNN_KERNEL=strip|cell itself, once.)
+struct QueryKnobs {
+    const char *force_kernel;     // MM_KNN_KERNEL=lane|strip|cell, as the first query of the process found it
+    bool kernel_set_now;          // MM_KNN_KERNEL is in the environment of this call
+    int lane_z, lane_t, lane_w;   // MM_KNN_LANE_Z / _T / _W (0: unset): tests of the thin-layer variants
+    bool force_list;              // MM_KNN_FORCE_LIST: every target through the list-mode kernel (tests of that kernel only)
+    bool debug;                   // MM_KNN_DEBUG: a line per level / tree pass on stderr (synchronises)
+};
+static QueryKnobs query_knobs()
+{
+    static const char *force_kernel = getenv("MM_KNN_KERNEL");
+    static const int lane_z = getenv("MM_KNN_LANE_Z") ? atoi(getenv("MM_KNN_LANE_Z")) : 0;
+    static const int lane_t = getenv("MM_KNN_LANE_T") ? atoi(getenv("MM_KNN_LANE_T")) : 0;
+    static const int lane_w = getenv("MM_KNN_LANE_W") ? atoi(getenv("MM_KNN_LANE_W")) : 0;
+    static const bool debug = getenv("MM_KNN_DEBUG") != nullptr;
+    QueryKnobs kn;
+    kn.force_kernel = force_kernel;
+    kn.kernel_set_now = getenv("MM_KNN_KERNEL") != nullptr;
+    kn.lane_z = lane_z;
+    kn.lane_t = lane_t;
+    kn.lane_w = lane_w;
+    kn.force_list = getenv("MM_KNN_FORCE_LIST") != nullptr;
+    kn.debug = debug;
+    return kn;
+}
+
+// The scratch of one tree pass, stated once (tsorted: null here when the caller's rows go by sorted position -- the records
+// then live in MM_BUF_TSORTED).
+namespace {
+struct TreeScratch {
+    u64 *key_a = nullptr, *key_b = nullptr;
+    unsigned *val_a = nullptr, *val_b = nullptr;
+    void *radix = nullptr;
+    int *flag = nullptr, *rank = nullptr, *scan_sums = nullptr;
+    TreeItem *items = nullptr;
+    int *fb_list = nullptr;
+    int *fb_count = nullptr;   // [0] hand-overs, [1] work items, [2] of the hand-overs: by overflow, [3] passed to the second pass
+    double *tsorted = nullptr;
+
+    void add(mm_scratch_layout &lay, i64 n, i64 npts, bool sorted_rows)
+    {
+        const size_t n_sz = (size_t)n;
+        lay.add(&key_a, n_sz);
+        lay.add(&key_b, n_sz);
+        lay.add(&val_a, n_sz);
+        lay.add(&val_b, n_sz);
+        lay.add(&radix, mm_radix_sort_scratch(n));
+        lay.add(&flag, n_sz + 1);
+        lay.add(&rank, n_sz + 1);
+        lay.add(&scan_sums, (size_t)((n + 1 + kScanTile - 1) / kScanTile));
+        lay.add(&items, n_sz + 1);
+        lay.add(&fb_list, (size_t)npts);
+        lay.add(&fb_count, 64);
+        if (!sorted_rows) lay.add(&tsorted, n_sz * kRec);
+    }
+};
+}  // namespace
+
+// The work items of a tree pass: the n targets in Morton order (records in tsorted), the node each one is served from, one
+// item per run of at most 256 targets of one node.  *nitems: their number, read back -- it sizes the launch: one small wait
+// (a graded cloud's pass takes milliseconds).
+static int tree_work_items(mm_context *ctx, const mm_knn_index *ix, const TreeScratch &ts, const double *pts_d, i64 n, int pstride,
+                           const int *list, const int *list_count, int kout, bool second_pass, double *tsorted, i64 *nitems)
+{
+    const mm_knn_tree *tr = ix->tree;
+    const unsigned gn = (unsigned)((n + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(tree_keys_kernel, dim3(gn), dim3(kBlock), 0, ctx->stream, pts_d, n, ix->ndim, pstride, tree_params_of(tr), list,
+                       list_count, ts.key_a, ts.val_a);
+    bool in_a = true;
+    int rc = mm_radix_sort_pairs(ctx, ts.key_a, ts.key_b, ts.val_a, ts.val_b, n, 0, kTreeBits, ts.radix, &in_a);
+    if (rc != MM_OK) return rc;
+    const u64 *tkeys = in_a ? ts.key_a : ts.key_b;
+    const unsigned *tvals = in_a ? ts.val_a : ts.val_b;
+    u64 *node = in_a ? ts.key_b : ts.key_a;   // (the sort's other buffer is free now)
+    hipLaunchKernelGGL(tree_records_kernel, dim3(gn), dim3(kBlock), 0, ctx->stream, pts_d, ix->ndim, pstride, tvals, n, list_count, tsorted);
+    int cell_min = tree_cell_min(kout);
+    int tile_max = kTreeTileMax;
+    if (second_pass) {
+        // what the first windows could not serve -- too full for the tile, or a k-th neighbour beyond the margin --: margins
+        // of ~1.8 local spacings instead of ~1.3 (cells of 3 x the sources), laid out for 70 % of the tile
+        cell_min = kout <= 8 ? 3 * cell_min : (3 * cell_min) / 2;
+        tile_max = (7 * tile_max) / 10;
+    }
+    hipLaunchKernelGGL(tree_target_node_kernel, dim3(gn), dim3(kBlock), 0, ctx->stream, tkeys, n, list_count, tr->keys,
+                       (int)ix->nsrc, tr->coarse, tr->level, cell_min, tile_max, node);
+    hipLaunchKernelGGL(tree_item_flags_kernel, dim3(gn), dim3(kBlock), 0, ctx->stream, node, n, list_count, kWave * kLaneRounds, ts.flag);
+    if ((rc = mm_exclusive_scan_int(ctx, ts.flag, n, ts.rank, ts.scan_sums)) != MM_OK) return rc;
+    int *nitems_d = ts.fb_count + 1;
+    hipLaunchKernelGGL(tree_items_kernel, dim3(gn), dim3(kBlock), 0, ctx->stream, node, n, list_count, ts.flag, ts.rank, tr->keys,
+                       (int)ix->nsrc, tr->coarse, ts.items, nitems_d);
+    MM_HIP_CHECK(hipMemcpyAsync(ctx->h_counters + 2, nitems_d, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    *nitems = (i64) * reinterpret_cast<const int *>(ctx->h_counters + 2);
+    return MM_OK;
+}
+
 // A query through the tree: the targets (all of them, or those of a device-side list whose length list_len the caller has
 // read back) in Morton order, one work item per run of at most 256 targets of one node, the lane kernel's TREE
 // instantiation, and the ring search over the level-0 grid for what it hands over.  Rows by the targets' own index, or --
@@ -920,79 +989,34 @@ static int tree_query(mm_context *ctx, const mm_knn_index *ix, const double *pts
     }
     const size_t n_sz = (size_t)n;
     const bool sorted_rows = !list && tsorted_out != nullptr;
-    const int scan_tiles = (int)((n + 1 + kScanTile - 1) / kScanTile);
-    const size_t need = 2 * mm_round256(n_sz * sizeof(u64)) + 2 * mm_round256(n_sz * sizeof(unsigned)) + mm_radix_sort_scratch(n) +
-                        2 * mm_round256((n_sz + 1) * sizeof(int)) + mm_round256((size_t)scan_tiles * sizeof(int)) +
-                        mm_round256((n_sz + 1) * sizeof(TreeItem)) + (sorted_rows ? 0 : mm_round256(n_sz * kRec * sizeof(double))) +
-                        mm_round256((size_t)npts * sizeof(int)) + 256 + 4096;
-    int rc = mm_scratch_begin(ctx, need);
+    TreeScratch ts;
+    mm_scratch_layout lay;
+    ts.add(lay, n, npts, sorted_rows);
+    int rc = lay.commit(ctx, __func__);
     if (rc != MM_OK) return rc;
-    u64 *key_a = (u64 *)mm_scratch_take(ctx, n_sz * sizeof(u64));
-    u64 *key_b = (u64 *)mm_scratch_take(ctx, n_sz * sizeof(u64));
-    unsigned *val_a = (unsigned *)mm_scratch_take(ctx, n_sz * sizeof(unsigned));
-    unsigned *val_b = (unsigned *)mm_scratch_take(ctx, n_sz * sizeof(unsigned));
-    void *radix = mm_scratch_take(ctx, mm_radix_sort_scratch(n));
-    int *flag = (int *)mm_scratch_take(ctx, (n_sz + 1) * sizeof(int));
-    int *rank = (int *)mm_scratch_take(ctx, (n_sz + 1) * sizeof(int));
-    int *scan_sums = (int *)mm_scratch_take(ctx, (size_t)scan_tiles * sizeof(int));
-    TreeItem *items = (TreeItem *)mm_scratch_take(ctx, (n_sz + 1) * sizeof(TreeItem));
-    int *fb_list = (int *)mm_scratch_take(ctx, (size_t)npts * sizeof(int));
-    int *fb_count = (int *)mm_scratch_take(ctx, 256);   // [0] hand-overs, [1] work items, [2] of the hand-overs: by overflow, [3] passed to the second pass
+    int *const fb_count = ts.fb_count;
     int *down_list = nullptr;
     if (!second_pass) {
         // (outlives this pass's scratch: the second pass carves the pool anew)
         rc = mm_buffer_get(ctx, MM_BUF_TREE_DOWN, (n_sz + 64) * sizeof(int), (void **)&down_list);   // (the list, then its length)
         if (rc != MM_OK) return rc;
     }
-    double *tsorted = nullptr;
+    double *tsorted = ts.tsorted;
     if (sorted_rows) {
         // (outlives this call's scratch: the locate stage reads it)
         rc = mm_buffer_get(ctx, MM_BUF_TSORTED, (size_t)npts * kRec * sizeof(double), (void **)&tsorted);
         if (rc != MM_OK) return rc;
-    } else {
-        tsorted = (double *)mm_scratch_take(ctx, n_sz * kRec * sizeof(double));
-    }
-    if (!key_a || !key_b || !val_a || !val_b || !radix || !flag || !rank || !scan_sums || !items || !fb_list || !fb_count || !tsorted) {
-        mm_set_error(MM_ERR_ALLOC, "scratch carve failed");
-        return MM_ERR_ALLOC;
     }
     if ((rc = mm_zero_async(ctx, fb_count, 256)) != MM_OK) return rc;
-    const TreeParams tp = tree_params_of(tr);
-    const unsigned gn = (unsigned)((n + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(tree_keys_kernel, dim3(gn), dim3(kBlock), 0, ctx->stream, pts_d, n, ix->ndim, pstride, tp, list, list_count, key_a, val_a);
-    bool in_a = true;
-    rc = mm_radix_sort_pairs(ctx, key_a, key_b, val_a, val_b, n, 0, kTreeBits, radix, &in_a);
-    if (rc != MM_OK) return rc;
-    const u64 *tkeys = in_a ? key_a : key_b;
-    const unsigned *tvals = in_a ? val_a : val_b;
-    u64 *node = in_a ? key_b : key_a;   // (the sort's other buffer is free now)
-    hipLaunchKernelGGL(tree_records_kernel, dim3(gn), dim3(kBlock), 0, ctx->stream, pts_d, ix->ndim, pstride, tvals, n, list_count, tsorted);
-    int cell_min = tree_cell_min(kout);
-    int tile_max = kTreeTileMax;
-    if (second_pass) {
-        // what the first windows could not serve -- too full for the tile, or a k-th neighbour beyond the margin --: margins
-        // of ~1.8 local spacings instead of ~1.3 (cells of 3 x the sources), laid out for 70 % of the tile
-        cell_min = kout <= 8 ? 3 * cell_min : (3 * cell_min) / 2;
-        tile_max = (7 * tile_max) / 10;
-    }
-    hipLaunchKernelGGL(tree_target_node_kernel, dim3(gn), dim3(kBlock), 0, ctx->stream, tkeys, n, list_count, tr->keys,
-                       (int)ix->nsrc, tr->coarse, tr->level, cell_min, tile_max, node);
-    hipLaunchKernelGGL(tree_item_flags_kernel, dim3(gn), dim3(kBlock), 0, ctx->stream, node, n, list_count, kWave * kLaneRounds, flag);
-    if ((rc = mm_exclusive_scan_int(ctx, flag, n, rank, scan_sums)) != MM_OK) return rc;
-    int *nitems_d = fb_count + 1;
-    hipLaunchKernelGGL(tree_items_kernel, dim3(gn), dim3(kBlock), 0, ctx->stream, node, n, list_count, flag, rank, tr->keys,
-                       (int)ix->nsrc, tr->coarse, items, nitems_d);
-    // the number of work items sizes the launch: one small wait (a graded cloud's pass takes milliseconds)
-    MM_HIP_CHECK(hipMemcpyAsync(ctx->h_counters + 2, nitems_d, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    const i64 nitems = (i64) * reinterpret_cast<const int *>(ctx->h_counters + 2);
+    i64 nitems = 0;
+    if ((rc = tree_work_items(ctx, ix, ts, pts_d, n, pstride, list, list_count, kout, second_pass, tsorted, &nitems)) != MM_OK) return rc;
     if (nitems > 0) {
         TreeArgs ta;
-        ta.tp = tp;
+        ta.tp = tree_params_of(tr);
         ta.keys = tr->keys;
         ta.coarse = tr->coarse;
-        ta.items = items;
-        ta.nitems = nitems_d;
+        ta.items = ts.items;
+        ta.nitems = fb_count + 1;
         const unsigned wgs = (unsigned)(8 * (nitems / 8 + 1));
         const GridParams g = params_of(ix);
         // thin layers per cell layer and half-width of a target's first window (a tree window has at most 6 cell layers:
@@ -1003,15 +1027,14 @@ static int tree_query(mm_context *ctx, const mm_knn_index *ix, const double *pts
             constexpr int K = decltype(KK)::value;
             hipLaunchKernelGGL((knn_lane_kernel<K, IDX, true>), dim3(wgs), dim3(kWave), 0, ctx->stream, g, ix->nsrc,
                                (const int *)nullptr, (const double *)tr->xyz, ix->ndim, kout, (const int *)nullptr,
-                               (const double *)tsorted, idx_d, dist_d, fb_list, fb_count, (const int2 *)nullptr, 0, 1,
+                               (const double *)tsorted, idx_d, dist_d, ts.fb_list, fb_count, (const int2 *)nullptr, 0, 1,
                                kWave * kLaneRounds, sorted_rows ? 1 : 0, down_list, down_list ? fb_count + 3 : (int *)nullptr,
                                kLaneThin, K <= 8 ? kLaneWin : kLaneThin, ta);
         });
         if (!list) mm_stage_end(ctx, MM_STAGE_KNN_CELL);
     }
     MM_HIP_CHECK(hipGetLastError());
-    static const bool dbg_query = getenv("MM_KNN_DEBUG") != nullptr;
-    if (dbg_query) {
+    if (query_knobs().debug) {
         int h[4] = {0, 0, 0, 0};
         MM_HIP_CHECK(hipMemcpyAsync(h, fb_count, 4 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
         MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
@@ -1021,7 +1044,7 @@ static int tree_query(mm_context *ctx, const mm_knn_index *ix, const double *pts
     }
     // what the windows could not certify: the tree's own ring search (cells of the target's node size, then coarser)
     tree_ring<IDX>(ctx, ix, sorted_rows ? (const double *)tsorted : pts_d, sorted_rows ? kRec : pstride, npts, kout, idx_d, dist_d,
-                   fb_list, fb_count);
+                   ts.fb_list, fb_count);
     MM_HIP_CHECK(hipGetLastError());
     if (down_list && nitems > 0) {
         // windows too full for the tile: their targets once more (rows as in this pass: by sorted position or own index)
@@ -1040,6 +1063,156 @@ static int tree_query(mm_context *ctx, const mm_knn_index *ix, const double *pts
     return MM_OK;
 }
 
+// Which kernel serves level 0 of a query over the grids (no device work; `lane_hint`: the verdict an earlier query of
+// these sizes read back, see lane_probe_readback).  One lane per target (knn_lane_kernel) when there is a single grid that
+// is deep in z, the lists are short and there are enough targets per cell to fill 64-lane rounds; otherwise the strip /
+// cell kernels.  MM_KNN_KERNEL=lane|strip|cell forces a kernel (tuning and tests only).
+static LaneWork choose_lane(const mm_context *ctx, const mm_knn_index *ix, i64 npts, i64 k, const int *list0, bool want_sorted_rows,
+                            const QueryKnobs &kn)
+{
+    LaneWork w = {};
+    const bool lane_base = !ix->fine && ix->dims[2] >= 6 && k <= kLaneMaxK;
+    bool use_lane = lane_base && npts >= 2 * ix->ncells;
+    // Targets that fill only a part of the grid -- one rank's share of a sharded target set: a slab with the full problem's
+    // density inside it and nothing outside -- fail the average test above although every strip that holds targets is as
+    // full as ever (round 4: a 1/8 shard of the metric's targets took 3.1 ms in the strip kernel, 0.25 ms here).  What
+    // matters is targets per OCCUPIED strip, which only the device knows after the sort: the first query of a context
+    // with these sizes reads the number of work items back (one small wait) and the verdict is kept for the next ones.
+    bool probe = false;
+    if (lane_base && !use_lane && npts >= kLaneProbeMin && !kn.kernel_set_now) {
+        if (ctx->lane_hint.valid && ctx->lane_hint.npts == npts && ctx->lane_hint.ncells == ix->ncells) use_lane = ctx->lane_hint.dense;
+        else probe = use_lane = true;   // (set up as for the lane kernel; decided after the targets are sorted)
+    }
+    // with density levels: level 0 only (every target starts there; strips too full for the tile are passed
+    // down), and only for the short lists the lane kernel is best at
+    if (!kn.force_kernel && ix->fine && ix->dims[2] >= 6 && k <= 8 && npts >= 2 * ix->ncells) use_lane = true;
+    if (kn.force_kernel) use_lane = strcmp(kn.force_kernel, "lane") == 0 && !ix->fine && ix->dims[2] >= 2 && k <= kLaneMaxK;
+    // MM_KNN_FORCE_LIST: every target through the list-mode kernel (tests of that kernel only)
+    if (kn.force_list || list0) use_lane = probe = false;
+    w.use_lane = use_lane;
+    w.probe = probe;
+    w.sorted_rows = use_lane && !ix->fine && want_sorted_rows ? 1 : 0;
+    if (!use_lane) return w;
+    w.Z = kn.lane_z >= 1 && kn.lane_z <= kLaneZMax ? kn.lane_z : kLaneZ;
+    if (w.Z > ix->dims[2]) w.Z = ix->dims[2];
+    // thin layers: (Z + 2) T of them must fit the 64 lanes of the prefix sum; the window never reaches past one
+    // cell layer (W <= T).  MM_KNN_LANE_Z / _T / _W: tests of the thin-layer variants.
+    w.T = kn.lane_t >= 1 ? kn.lane_t : kLaneThin;
+    while (w.T > 1 && (w.Z + 2) * w.T > kLaneThinMax) --w.T;
+    w.W = kn.lane_w >= 1 ? kn.lane_w : (w.T == kLaneThin ? kLaneWin : w.T);
+    if (w.W > w.T) w.W = w.T;
+    const i64 nstrips = (ix->dims[2] + w.Z - 1) / w.Z;
+    w.nstrips_total = (i64)ix->dims[0] * ix->dims[1] * nstrips;
+    // (slots: 8 per row of the permuted list, so up to 7 more than items; a multiple of 8 = the grid)
+    w.max_items = (w.nstrips_total + npts / (kWave * kLaneRounds) + 16 + 7) / 8 * 8;
+    return w;
+}
+
+// A probing query (choose_lane), after level 0's sort: targets per occupied strip from the work-item count of the lane
+// kernel's own prepass, read back once.  The verdict goes to *lane and into ctx->lane_hint for the next queries of these sizes.
+static int lane_probe_readback(mm_context *ctx, const mm_knn_index *ix, const GridParams &gl, i64 npts, const int *start, LaneWork *lane)
+{
+    const int per_item = kWave * kLaneRounds;
+    const int nt = (int)((lane->nstrips_total + kScanTile - 1) / kScanTile);
+    hipLaunchKernelGGL(lane_items_sums_kernel, dim3(nt), dim3(kBlock), 0, ctx->stream, gl, start, lane->Z, per_item,
+                       lane->nstrips_total, lane->tile_sums, lane->items, lane->max_items);
+    hipLaunchKernelGGL(lane_items_offsets_kernel, dim3(1), dim3(kBlock), 0, ctx->stream, lane->tile_sums, nt);
+    MM_HIP_CHECK(hipMemcpyAsync(ctx->h_counters + 2, lane->tile_sums + nt, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    const i64 items = (i64) * reinterpret_cast<const int *>(ctx->h_counters + 2);
+    lane->use_lane = items > 0 && npts >= kLaneProbeTargetsPerItem * items;
+    lane->probe = false;
+    lane->sorted_rows = lane->sorted_rows && lane->use_lane ? 1 : 0;
+    ctx->lane_hint.valid = true;
+    ctx->lane_hint.npts = npts;
+    ctx->lane_hint.ncells = ix->ncells;
+    ctx->lane_hint.dense = lane->use_lane;
+    return MM_OK;
+}
+
+// Lists of more than 32: the generic ring-expansion kernel for every target (in the grid that suits it, when the cloud has
+// density levels).
+template <typename IDX>
+static int query_long_lists(mm_context *ctx, const mm_knn_index *ix, const double *pts_d, i64 npts, int kout, IDX *idx_d, double *dist_d)
+{
+    const LevelTable lv = level_table_of(ix, kMaxLevels);
+    ctx->knn_kernels |= ix->fine ? MM_KNN_RAN_LEVELS : MM_KNN_RAN_GENERIC;
+    with_k(kListKs{}, kout, [&](auto KK) {
+        constexpr int K = decltype(KK)::value;
+        if (ix->fine)
+            hipLaunchKernelGGL((knn_query_levels_kernel<K, IDX>), dim3((unsigned)((npts + kBlock - 1) / kBlock)),
+                               dim3(kBlock), 0, ctx->stream, lv, ix->nsrc, pts_d, ix->ndim, kout, idx_d, dist_d,
+                               (const int *)nullptr, (const int *)nullptr, kListKeepMax, npts, -1);
+        else
+            launch_generic<K, IDX>(ctx, ix, params_of(ix), pts_d, npts, kout, idx_d, dist_d, nullptr, nullptr);
+    });
+    MM_HIP_CHECK(hipGetLastError());
+    return MM_OK;
+}
+
+// The scratch of one density level of a query (knn_query_typed adds every level's to its layout in one loop).
+namespace {
+struct LevelScratch {
+    int *cell_of = nullptr;         // rank of every target in its cell
+    int *down_list = nullptr;       // targets passed down (levels with a denser one below)
+    int *counts = nullptr, *start = nullptr, *tile_sums = nullptr;
+    unsigned *strip_list = nullptr;   // strips that hold targets (denser levels, and every level of a caller's list)
+    double *tsorted = nullptr;      // cell-sorted target records (MM_BUF_TSORTED instead when the rows go by sorted position)
+
+    // (level 0's counts are in the layout already: right behind the counters, see knn_query_typed)
+    void add(mm_scratch_layout &lay, const mm_knn_index *l, int level, i64 npts, bool have_list, bool sorted_rows)
+    {
+        lay.add(&cell_of, (size_t)npts);
+        if (l->fine) lay.add(&down_list, (size_t)npts);
+        if (level > 0) lay.add(&counts, (size_t)(l->ncells + 1));
+        lay.add(&start, (size_t)(l->ncells + 1));
+        lay.add(&tile_sums, (size_t)((l->ncells + kScanTile - 1) / kScanTile));
+        if (level > 0 || have_list) lay.add(&strip_list, (size_t)npts);
+        if (!sorted_rows) lay.add(&tsorted, (size_t)npts * kRec);
+    }
+};
+}  // namespace
+
+// One density level of a query: its share of the targets (`list`; null: all of them) is counting-sorted by the level's
+// cells and visited strip by strip.  counts_zeroed: level 0's counts were cleared with the counters.
+template <typename IDX>
+static int query_level(mm_context *ctx, const mm_knn_index *ix, const mm_knn_index *l, int level, int nlevels, const LevelScratch &s,
+                       const double *pts_d, i64 npts, int kout, IDX *idx_d, double *dist_d, const double **tsorted_out,
+                       const int *list, const int *list_count, int *fb_list, int *fb_count, bool counts_zeroed,
+                       LaneWork *lane, const QueryKnobs &kn)
+{
+    const GridParams gl = params_of(l);
+    const i64 ncells = l->ncells;
+    int *down_count = fb_count + 64 * (1 + level);
+    int *strip_count = down_count + 1;
+    // the targets' counting sort.  (Round 4 also ran it AHEAD of a guessed call -- its grid is known before the centroids
+    // exist -- on a second stream beside the centroid kernel and the source sort: no gain, 3.51 vs 3.48 ms per step; they
+    // are all bandwidth-bound and simply share the HBM.)
+    if (!counts_zeroed)
+        if (mm_zero_async(ctx, s.counts, mm_fill_span((size_t)(ncells + 1) * sizeof(int))) != MM_OK) return MM_ERR_HIP;
+    int rc = sort_targets(ctx, gl, ncells, l->ndim, pts_d, npts, list, list_count, s.cell_of, s.counts, s.start, s.tile_sums, s.tsorted);
+    if (rc != MM_OK) return rc;
+    if (lane->probe && level == 0) {
+        if ((rc = lane_probe_readback(ctx, ix, gl, npts, s.start, lane)) != MM_OK) return rc;
+        if (lane->sorted_rows) *tsorted_out = s.tsorted;
+    }
+    with_k(kFastKs{}, kout, [&](auto KK) {
+        launch_fast<decltype(KK)::value, IDX>(ctx, l, gl, pts_d, npts, kout, s.start, s.tsorted, idx_d, dist_d, fb_list, fb_count,
+                                              s.down_list, down_count, level == 0, s.strip_list, strip_count,
+                                              lane->use_lane && level == 0 ? lane : nullptr);
+    });
+    MM_HIP_CHECK(hipGetLastError());
+    if (kn.debug) {
+        int h[2] = {0, 0};
+        MM_HIP_CHECK(hipMemcpyAsync(h, fb_count, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        MM_HIP_CHECK(hipMemcpyAsync(h + 1, down_count, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        fprintf(stderr, "[mm_knn] level %d of %d (%lld cells): %d targets for the generic kernel so far, %d passed down "
+                        "(%lld targets in the query)\n", level, nlevels, (long long)ncells, h[0], h[1], (long long)npts);
+    }
+    return MM_OK;
+}
+
 // tsorted_out (nullable): the caller can take the rows in the cell-sorted order of the targets; on return
 // *tsorted_out = the sorted target records {x, y, z, index} (context buffer, valid until the next query) when the
 // rows were written in that order, null when they are in the targets' own order (paths without the lane kernel).
@@ -1054,196 +1227,62 @@ static int knn_query_typed(mm_context *ctx, const mm_knn_index *ix, const double
     if (npts == 0 || k == 0) return MM_OK;
     MM_REQUIRE(npts < (i64)0x7fffffff, "too many targets for one query");
     const int kout = (int)k;
+    const QueryKnobs kn = query_knobs();
     // a graded cloud with the adaptive index (lists the lane kernel can hold; a list only when its length is known here)
-    if (ix->tree && k <= kLaneMaxK && (!list0 || list0_len >= 0) && !getenv("MM_KNN_FORCE_LIST"))
+    if (ix->tree && k <= kLaneMaxK && (!list0 || list0_len >= 0) && !kn.force_list)
         return tree_query<IDX>(ctx, ix, pts_d, npts, kout, idx_d, dist_d, tsorted_out, list0, list0_count, list0_len);
-    if (k > 32) {
-        // long lists: generic ring-expansion kernel for every target (in the grid that suits it, when
-        // the cloud has density levels)
-        const LevelTable lv = level_table_of(ix, kMaxLevels);
-        ctx->knn_kernels |= ix->fine ? MM_KNN_RAN_LEVELS : MM_KNN_RAN_GENERIC;
-        with_k(kListKs{}, kout, [&](auto KK) {
-            constexpr int K = decltype(KK)::value;
-            if (ix->fine)
-                hipLaunchKernelGGL((knn_query_levels_kernel<K, IDX>), dim3((unsigned)((npts + kBlock - 1) / kBlock)),
-                                   dim3(kBlock), 0, ctx->stream, lv, ix->nsrc, pts_d, ix->ndim, kout, idx_d, dist_d,
-                                   (const int *)nullptr, (const int *)nullptr, kListKeepMax, npts, -1);
-            else
-                launch_generic<K, IDX>(ctx, ix, params_of(ix), pts_d, npts, kout, idx_d, dist_d, nullptr, nullptr);
-        });
-        MM_HIP_CHECK(hipGetLastError());
-        return MM_OK;
-    }
+    if (k > 32) return query_long_lists<IDX>(ctx, ix, pts_d, npts, kout, idx_d, dist_d);
     // One pass per density level: the level's share of the targets is counting-sorted by its cells and
     // visited strip by strip; targets whose strip is too full for the tile go down to the next level
     // (a device-side list), everything else the level cannot place goes to its generic kernel.
+    LaneWork lane = choose_lane(ctx, ix, npts, k, list0, tsorted_out != nullptr, kn);
     int nlevels = 0;
-    size_t need = 1024;
-    for (const mm_knn_index *l = ix; l; l = l->fine) {
-        const i64 nc = l->ncells;
-        const int nt = (int)((nc + kScanTile - 1) / kScanTile);
-        need += mm_round256((size_t)npts * sizeof(int)) +               // rank of every target in its cell
-                (l->fine ? mm_round256((size_t)npts * sizeof(int)) : 0) +   // targets passed down
-                ((l != ix || list0) ? mm_round256((size_t)npts * sizeof(unsigned)) : 0) +   // strips that hold targets
-                mm_round256((size_t)npts * kRec * sizeof(double)) +     // cell-sorted target records
-                2 * mm_round256((size_t)(nc + 1) * sizeof(int)) +       // counts, start
-                mm_round256((size_t)nt * sizeof(int)) + 256;
-        ++nlevels;
+    for (const mm_knn_index *l = ix; l; l = l->fine) ++nlevels;
+    MM_REQUIRE(nlevels <= kMaxLevels, "more density levels than the build lays out");
+    // scratch: the stragglers of all levels (one list) and the counters -- one block, zeroed by ONE fill: the stragglers'
+    // counter, then every level's {passed down, strips} counters --, level 0's cell counts right behind them, ADJACENT so
+    // that the one fill clears both (checked below), the lane kernel's work items, then level by level
+    int *fb_list, *fb_count;
+    LevelScratch lvs[kMaxLevels];
+    const size_t counter_ints = 64 * (size_t)(1 + nlevels);
+    mm_scratch_layout lay;
+    lay.add(&fb_list, (size_t)npts);
+    lay.add(&fb_count, counter_ints);
+    lay.add(&lvs[0].counts, (size_t)(ix->ncells + 1));
+    if (lane.use_lane) {
+        lay.add(&lane.tile_sums, (size_t)((lane.nstrips_total + kScanTile) / kScanTile + 2));
+        lay.add(&lane.items, (size_t)lane.max_items);
     }
-    need += mm_round256((size_t)npts * sizeof(int)) + 256 * (size_t)(2 + nlevels);   // stragglers of all levels (one list), counters
-    // One lane per target (knn_lane_kernel) when there is a single grid that is deep in z, the lists are
-    // short and there are enough targets per cell to fill 64-lane rounds; otherwise the strip / cell kernels.
-    // MM_KNN_KERNEL=lane|strip|cell forces a kernel (tuning and tests only).
-    static const char *force_kernel = getenv("MM_KNN_KERNEL");
-    LaneWork lane_work;
-    const bool lane_base = !ix->fine && ix->dims[2] >= 6 && k <= kLaneMaxK;
-    bool use_lane = lane_base && npts >= 2 * ix->ncells;
-    // Targets that fill only a part of the grid -- one rank's share of a sharded target set: a slab with the full problem's
-    // density inside it and nothing outside -- fail the average test above although every strip that holds targets is as
-    // full as ever (round 4: a 1/8 shard of the metric's targets took 3.1 ms in the strip kernel, 0.25 ms here).  What
-    // matters is targets per OCCUPIED strip, which only the device knows after the sort: the first query of a context
-    // with these sizes reads the number of work items back (one small wait) and the verdict is kept for the next ones.
-    bool lane_probe = false;
-    if (lane_base && !use_lane && npts >= kLaneProbeMin && !getenv("MM_KNN_KERNEL")) {
-        if (ctx->lane_hint.valid && ctx->lane_hint.npts == npts && ctx->lane_hint.ncells == ix->ncells) use_lane = ctx->lane_hint.dense;
-        else lane_probe = use_lane = true;   // (set up as for the lane kernel; decided after the targets are sorted)
+    if (!kn.force_list) {
+        int level = 0;
+        for (const mm_knn_index *l = ix; l; l = l->fine, ++level) lvs[level].add(lay, l, level, npts, list0 != nullptr, lane.sorted_rows != 0);
     }
-    // with density levels: level 0 only (every target starts there; strips too full for the tile are passed
-    // down), and only for the short lists the lane kernel is best at
-    if (!force_kernel && ix->fine && ix->dims[2] >= 6 && k <= 8 && npts >= 2 * ix->ncells) use_lane = true;
-    if (force_kernel) use_lane = strcmp(force_kernel, "lane") == 0 && !ix->fine && ix->dims[2] >= 2 && k <= kLaneMaxK;
-    // MM_KNN_FORCE_LIST: every target through the list-mode kernel (tests of that kernel only)
-    // (MM_KNN_FORCE_LIST here and MM_KNN_LEVELS in the build are read per call on purpose: tests switch them inside one
-    // process; every other knob is read once)
-    const bool force_list = getenv("MM_KNN_FORCE_LIST") != nullptr;
-    if (force_list || list0) use_lane = lane_probe = false;
-    bool sorted_rows = use_lane && !ix->fine && tsorted_out != nullptr;
-    lane_work.sorted_rows = sorted_rows ? 1 : 0;
-    if (use_lane) {
-        static const int force_z = getenv("MM_KNN_LANE_Z") ? atoi(getenv("MM_KNN_LANE_Z")) : 0;
-        lane_work.Z = force_z >= 1 && force_z <= kLaneZMax ? force_z : kLaneZ;
-        if (lane_work.Z > ix->dims[2]) lane_work.Z = ix->dims[2];
-        // thin layers: (Z + 2) T of them must fit the 64 lanes of the prefix sum; the window never reaches past one
-        // cell layer (W <= T).  MM_KNN_LANE_Z / _T / _W: tests of the thin-layer variants.
-        static const int force_t = getenv("MM_KNN_LANE_T") ? atoi(getenv("MM_KNN_LANE_T")) : 0;
-        static const int force_w = getenv("MM_KNN_LANE_W") ? atoi(getenv("MM_KNN_LANE_W")) : 0;
-        lane_work.T = force_t >= 1 ? force_t : kLaneThin;
-        while (lane_work.T > 1 && (lane_work.Z + 2) * lane_work.T > kLaneThinMax) --lane_work.T;
-        lane_work.W = force_w >= 1 ? force_w : (lane_work.T == kLaneThin ? kLaneWin : lane_work.T);
-        if (lane_work.W > lane_work.T) lane_work.W = lane_work.T;
-        const i64 nstrips = (ix->dims[2] + lane_work.Z - 1) / lane_work.Z;
-        lane_work.nstrips_total = (i64)ix->dims[0] * ix->dims[1] * nstrips;
-        // (slots: 8 per row of the permuted list, so up to 7 more than items; a multiple of 8 = the grid)
-        lane_work.max_items = (lane_work.nstrips_total + npts / (kWave * kLaneRounds) + 16 + 7) / 8 * 8;
-        need += mm_round256((size_t)((lane_work.nstrips_total + kScanTile) / kScanTile + 2) * sizeof(int)) +
-                mm_round256((size_t)lane_work.max_items * sizeof(int2)) + 1024;
-    }
-    int rc = mm_scratch_begin(ctx, need);
+    int rc = lay.commit(ctx, __func__);
     if (rc != MM_OK) return rc;
-    int *fb_list = (int *)mm_scratch_take(ctx, (size_t)npts * sizeof(int));
-    // (one block, zeroed by ONE fill: the stragglers' counter, then every level's {passed down, strips} counters)
-    int *fb_count = (int *)mm_scratch_take(ctx, 256 * (size_t)(1 + nlevels));
-    // (level 0's cell counts right behind the counters: ONE fill clears both)
-    int *counts0 = (int *)mm_scratch_take(ctx, (size_t)(ix->ncells + 1) * sizeof(int));
-    if (!fb_list || !fb_count || !counts0) {
-        mm_set_error(MM_ERR_ALLOC, "scratch carve failed");
-        return MM_ERR_ALLOC;
+    if (lane.sorted_rows) {
+        // (outlives this call's scratch: the locate stage reads it)
+        rc = mm_buffer_get(ctx, MM_BUF_TSORTED, (size_t)npts * kRec * sizeof(double), (void **)&lvs[0].tsorted);
+        if (rc != MM_OK) return rc;
+        if (!lane.probe) *tsorted_out = lvs[0].tsorted;
     }
-    if (use_lane) {
-        lane_work.tile_sums = (int *)mm_scratch_take(ctx, (size_t)((lane_work.nstrips_total + kScanTile) / kScanTile + 2) * sizeof(int));
-        lane_work.items = (int2 *)mm_scratch_take(ctx, (size_t)lane_work.max_items * sizeof(int2));
-        if (!lane_work.tile_sums || !lane_work.items) {
-            mm_set_error(MM_ERR_ALLOC, "scratch carve failed");
-            return MM_ERR_ALLOC;
-        }
-    }
-    const bool one_fill = !force_list && (char *)counts0 == (char *)fb_count + 256 * (size_t)(1 + nlevels);   // (not so under MM_GUARD_ALLOC)
-    {
-        const int zrc = mm_zero_async(ctx, fb_count, 256 * (size_t)(1 + nlevels) + (one_fill ? mm_round256((size_t)(ix->ncells + 1) * sizeof(int)) : 0));
-        if (zrc != MM_OK) return zrc;
-    }
-    const unsigned gpts = (unsigned)((npts + kBlock - 1) / kBlock);
+    const bool one_fill = !kn.force_list && mm_scratch_adjacent(fb_count, counter_ints * sizeof(int), lvs[0].counts);   // (not so under MM_GUARD_ALLOC)
+    rc = mm_zero_async(ctx, fb_count, counter_ints * sizeof(int) + (one_fill ? mm_round256((size_t)(ix->ncells + 1) * sizeof(int)) : 0));
+    if (rc != MM_OK) return rc;
+    if (kn.force_list)
+        hipLaunchKernelGGL(list_all_kernel, dim3((unsigned)((npts + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, fb_list, fb_count, npts);
     const int *list = list0, *list_count = list0_count;   // level 0: every target (or the caller's list)
     int level = 0;
-    if (force_list)
-        hipLaunchKernelGGL(list_all_kernel, dim3(gpts), dim3(kBlock), 0, ctx->stream, fb_list, fb_count, npts);
-    for (const mm_knn_index *l = ix; l && !force_list; l = l->fine, ++level) {
-        const GridParams gl = params_of(l);
-        const i64 ncells = l->ncells;
-        const int ntiles = (int)((ncells + kScanTile - 1) / kScanTile);
-        int *cell_of = (int *)mm_scratch_take(ctx, (size_t)npts * sizeof(int));   // rank of every target in its cell
-        int *down_list = l->fine ? (int *)mm_scratch_take(ctx, (size_t)npts * sizeof(int)) : nullptr;
-        int *counts = level == 0 ? counts0 : (int *)mm_scratch_take(ctx, (size_t)(ncells + 1) * sizeof(int));
-        int *start = (int *)mm_scratch_take(ctx, (size_t)(ncells + 1) * sizeof(int));
-        int *tile_sums = (int *)mm_scratch_take(ctx, (size_t)ntiles * sizeof(int));
-        int *down_count = fb_count + 64 * (1 + level);
-        int *strip_count = down_count + 1;
-        unsigned *strip_list = (level > 0 || list0) ? (unsigned *)mm_scratch_take(ctx, (size_t)npts * sizeof(unsigned)) : nullptr;
-        double *tsorted = nullptr;
-        if (sorted_rows) {
-            // (outlives this call's scratch: the locate stage reads it)
-            int brc = mm_buffer_get(ctx, MM_BUF_TSORTED, (size_t)npts * kRec * sizeof(double), (void **)&tsorted);
-            if (brc != MM_OK) return brc;
-            if (!lane_probe) *tsorted_out = tsorted;
-        } else {
-            tsorted = (double *)mm_scratch_take(ctx, (size_t)npts * kRec * sizeof(double));
-        }
-        if (!tsorted || !cell_of || !counts || !start || !tile_sums || !down_count || (l->fine && !down_list) ||
-            ((level > 0 || list0) && !strip_list)) {
-            mm_set_error(MM_ERR_ALLOC, "scratch carve failed");
-            return MM_ERR_ALLOC;
-        }
-        // the targets' counting sort.  (Round 4 also ran it AHEAD of a guessed call -- its grid is known before the centroids
-        // exist -- on a second stream beside the centroid kernel and the source sort: no gain, 3.51 vs 3.48 ms per step; they
-        // are all bandwidth-bound and simply share the HBM.)
-        if (!(level == 0 && one_fill))
-            if (mm_zero_async(ctx, counts, mm_fill_span((size_t)(ncells + 1) * sizeof(int))) != MM_OK) return MM_ERR_HIP;
-        {
-            const int src_rc = sort_targets(ctx, gl, ncells, l->ndim, pts_d, npts, list, list_count, cell_of, counts, start, tile_sums, tsorted);
-            if (src_rc != MM_OK) return src_rc;
-        }
-        if (lane_probe && level == 0) {
-            // targets per occupied strip: the work-item count of the lane kernel's own prepass, read back once
-            const int per_item = kWave * kLaneRounds;
-            const int nt = (int)((lane_work.nstrips_total + kScanTile - 1) / kScanTile);
-            hipLaunchKernelGGL(lane_items_sums_kernel, dim3(nt), dim3(kBlock), 0, ctx->stream, gl, start, lane_work.Z, per_item,
-                               lane_work.nstrips_total, lane_work.tile_sums, lane_work.items, lane_work.max_items);
-            hipLaunchKernelGGL(lane_items_offsets_kernel, dim3(1), dim3(kBlock), 0, ctx->stream, lane_work.tile_sums, nt);
-            MM_HIP_CHECK(hipMemcpyAsync(ctx->h_counters + 2, lane_work.tile_sums + nt, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-            MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-            const i64 items = (i64) * reinterpret_cast<const int *>(ctx->h_counters + 2);
-            use_lane = items > 0 && npts >= kLaneProbeTargetsPerItem * items;
-            ctx->lane_hint.valid = true;
-            ctx->lane_hint.npts = npts;
-            ctx->lane_hint.ncells = ix->ncells;
-            ctx->lane_hint.dense = use_lane;
-            lane_probe = false;
-            sorted_rows = sorted_rows && use_lane;
-            lane_work.sorted_rows = sorted_rows ? 1 : 0;
-            if (sorted_rows) *tsorted_out = tsorted;
-        }
-        with_k(kFastKs{}, kout, [&](auto KK) {
-            launch_fast<decltype(KK)::value, IDX>(ctx, l, gl, pts_d, npts, kout, start, tsorted, idx_d, dist_d, fb_list, fb_count,
-                                                  down_list, down_count, level == 0, strip_list, strip_count,
-                                                  use_lane && level == 0 ? &lane_work : nullptr);
-        });
-        MM_HIP_CHECK(hipGetLastError());
-        static const bool dbg_query = getenv("MM_KNN_DEBUG") != nullptr;
-        if (dbg_query) {
-            int h[2] = {0, 0};
-            MM_HIP_CHECK(hipMemcpyAsync(h, fb_count, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-            MM_HIP_CHECK(hipMemcpyAsync(h + 1, down_count, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-            MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-            fprintf(stderr, "[mm_knn] level %d of %d (%lld cells): %d targets for the generic kernel so far, %d passed down "
-                            "(%lld targets in the query)\n", level, nlevels, (long long)ncells, h[0], h[1], (long long)npts);
-        }
-        list = down_list;
-        list_count = down_count;
+    for (const mm_knn_index *l = ix; l && !kn.force_list; l = l->fine, ++level) {
+        rc = query_level<IDX>(ctx, ix, l, level, nlevels, lvs[level], pts_d, npts, kout, idx_d, dist_d, tsorted_out, list, list_count,
+                              fb_list, fb_count, level == 0 && one_fill, &lane, kn);
+        if (rc != MM_OK) return rc;
+        list = lvs[level].down_list;
+        list_count = fb_count + 64 * (1 + level);
     }
     // what no level could place: the generic kernel, once, every target in the grid that suits its home cell
     const LevelTable lv = level_table_of(ix, kMaxLevels);
     with_k(kFastKs{}, kout, [&](auto KK) {
-        launch_list<decltype(KK)::value, IDX>(ctx, ix, lv, sorted_rows ? *tsorted_out : pts_d, sorted_rows ? kRec : ix->ndim, npts,
+        launch_list<decltype(KK)::value, IDX>(ctx, ix, lv, lane.sorted_rows ? *tsorted_out : pts_d, lane.sorted_rows ? kRec : ix->ndim, npts,
                                               kout, idx_d, dist_d, fb_list, fb_count, kListKeepMax);
     });
     MM_HIP_CHECK(hipGetLastError());

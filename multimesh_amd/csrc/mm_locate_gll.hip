@@ -447,9 +447,8 @@ __device__ __forceinline__ i64 gll_next_candidate(const IDX *__restrict__ row, i
 
 // The least-outside candidate a target has seen so far.  With snap_to_nearest it travels between the passes in two
 // scratch arrays: best_state [N][kGllSnapDoubles] (val, then xi -- DIM + 1 of each row's doubles are used) and
-// best_elem_state [N]; locate_gll_run budgets and carves them by the byte counts below.
+// best_elem_state [N]; locate_gll_run puts them into its scratch layout.
 constexpr int kGllSnapDoubles = 4;
-constexpr size_t kGllSnapStateBytes = kGllSnapDoubles * sizeof(double), kGllSnapElemBytes = sizeof(i64);   // per target
 template <int DIM>
 struct GllBest {
     double val = 10e9;
@@ -1012,16 +1011,6 @@ __global__ __launch_bounds__(256) void gll_order_kernel(i64 npoints, const int2 
 
 }  // namespace
 
-int mm_exclusive_scan_int(mm_context *ctx, const int *counts, i64 n, int *start, int *tile_sums);
-int mm_knn_build_impl(mm_context *ctx, const double *src_d, i64 nsrc, i64 ndim, mm_knn_index **out,
-                      bool use_context_buffers, const double *box_partial_d, int box_nblocks, bool hex8_centroids = false);
-int mm_knn_query_impl(mm_context *ctx, const mm_knn_index *ix, const double *pts_d, i64 npts, i64 k, void *idx_d,
-                      double *dist_d, bool idx_is_int32);
-
-// MM_REQUIRE on behalf of the entry point `who` (a helper's or a lambda's own __func__ would name the wrong function)
-#define MM_REQUIRE_AS(who, cond, msg) \
-    do { if (!(cond)) { mm_set_error(MM_ERR_ARG, "%s: %s", who, msg); return MM_ERR_ARG; } } while (0)
-
 // calls f(std::integral_constant<int, ORDER>, std::integral_constant<int, DIM>) for the (order, dim) the kernels are
 // instantiated for; the entry points have refused every other pair before
 template <typename F>
@@ -1032,38 +1021,45 @@ static void gll_dispatch(int order, int dim, F &&f)
 #undef MM_GLL_PAIR
 }
 
-// Visiting order: *visit = the targets counting-sorted by their first candidate element (invalid ids: the last bin),
-// carved from the call's scratch, which the caller has sized with gll_visit_bytes; null when there is nothing to sort by.
-static size_t gll_visit_bytes(i64 npoints, i64 nelem)
-{
-    const i64 nbins = nelem + 1, ntiles = (nbins + 1023) / 1024;
-    return mm_round256((size_t)npoints * sizeof(int2)) + mm_round256((size_t)npoints * sizeof(int)) +
-           2 * mm_round256((size_t)(nbins + 1) * sizeof(int)) + mm_round256((size_t)ntiles * sizeof(int));
-}
+// Visiting order: the targets counting-sorted by their first candidate element (invalid ids: the last bin).  add() puts
+// its arrays into the caller's layout -- none when there is nothing to sort by --, run() sorts after the caller's commit;
+// *visit = the order, or null.
+namespace {
+struct GllVisit {
+    int2 *key_rank = nullptr;
+    int *ord = nullptr, *counts = nullptr, *start = nullptr, *tile_sums = nullptr;
+    i64 npoints = 0, nbins = 0;
+    int kavail = 0;
 
-template <typename IDX>
-static int gll_visit_order(mm_context *ctx, const char *who, const IDX *nn, int kavail, i64 npoints, i64 nelem,
-                           const int **visit)
-{
-    *visit = nullptr;
-    if (kavail <= 0 || nelem <= 0) return MM_OK;
-    const i64 nbins = nelem + 1, ntiles = (nbins + 1023) / 1024;
-    int2 *key_rank = (int2 *)mm_scratch_take(ctx, (size_t)npoints * sizeof(int2));
-    int *ord = (int *)mm_scratch_take(ctx, (size_t)npoints * sizeof(int));
-    int *counts = (int *)mm_scratch_take(ctx, (size_t)(nbins + 1) * sizeof(int));
-    int *start = (int *)mm_scratch_take(ctx, (size_t)(nbins + 1) * sizeof(int));
-    int *tile_sums = (int *)mm_scratch_take(ctx, (size_t)ntiles * sizeof(int));
-    MM_REQUIRE_AS(who, key_rank && ord && counts && start && tile_sums, "scratch carve failed");
-    MM_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)(nbins + 1) * sizeof(int), ctx->stream));
-    const unsigned gp = (unsigned)((npoints + 255) / 256);
-    hipLaunchKernelGGL((gll_key_kernel<IDX>), dim3(gp), dim3(256), 0, ctx->stream, (i64)kavail, npoints, nn, nelem,
-                       key_rank, counts);
-    const int rc = mm_exclusive_scan_int(ctx, counts, nbins, start, tile_sums);
-    if (rc != MM_OK) return rc;
-    hipLaunchKernelGGL(gll_order_kernel, dim3(gp), dim3(256), 0, ctx->stream, npoints, key_rank, start, ord);
-    *visit = ord;
-    return MM_OK;
-}
+    void add(mm_scratch_layout &lay, int kavail_, i64 npoints_, i64 nelem)
+    {
+        if (kavail_ <= 0 || nelem <= 0) return;
+        kavail = kavail_;
+        npoints = npoints_;
+        nbins = nelem + 1;
+        lay.add(&key_rank, (size_t)npoints);
+        lay.add(&ord, (size_t)npoints);
+        lay.add(&counts, (size_t)(nbins + 1));
+        lay.add(&start, (size_t)(nbins + 1));
+        lay.add(&tile_sums, (size_t)((nbins + 1023) / 1024));
+    }
+    template <typename IDX>
+    int run(mm_context *ctx, const IDX *nn, const int **visit) const
+    {
+        *visit = nullptr;
+        if (!ord) return MM_OK;
+        MM_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)(nbins + 1) * sizeof(int), ctx->stream));
+        const unsigned gp = (unsigned)((npoints + 255) / 256);
+        hipLaunchKernelGGL((gll_key_kernel<IDX>), dim3(gp), dim3(256), 0, ctx->stream, (i64)kavail, npoints, nn, nbins - 1,
+                           key_rank, counts);
+        const int rc = mm_exclusive_scan_int(ctx, counts, nbins, start, tile_sums);
+        if (rc != MM_OK) return rc;
+        hipLaunchKernelGGL(gll_order_kernel, dim3(gp), dim3(256), 0, ctx->stream, npoints, key_rank, start, ord);
+        *visit = ord;
+        return MM_OK;
+    }
+};
+}  // namespace
 
 // The locate stage on ctx->stream: visiting order, passes, no synchronisation.  nn holds the first
 // kavail (<= k) candidates of every target (kavail < k only with `lazy`).  The number of targets
@@ -1076,23 +1072,26 @@ static int locate_gll_run(mm_context *ctx, int order, int dim, i64 k, int kavail
     unsigned long long *nm = (unsigned long long *)ctx->d_counters;
     // scratch: two pass queues, their counters, the ids of the open targets, snap state, visiting order
     const size_t snap = snap_to_nearest ? (size_t)npoints : 0;   // rows of the snap state
-    int rc = mm_scratch_begin(ctx, 2 * mm_round256((size_t)npoints * sizeof(int2)) +
-                                       mm_round256(sizeof(int) * (MM_KNN_MAX_K + 8)) +
-                                       mm_round256((size_t)npoints * sizeof(int)) + mm_round256(snap * kGllSnapStateBytes) +
-                                       mm_round256(snap * kGllSnapElemBytes) +
-                                       gll_visit_bytes(npoints, nelem) + 4096);
+    int2 *qa, *qb;
+    int *counters, *id_list;
+    double *best_state = nullptr;
+    i64 *best_elem_state = nullptr;
+    GllVisit order_work;
+    mm_scratch_layout lay;
+    lay.add(&qa, (size_t)npoints);
+    lay.add(&qb, (size_t)npoints);
+    lay.add(&counters, (size_t)(MM_KNN_MAX_K + 8));
+    lay.add(&id_list, (size_t)npoints);
+    if (snap) {
+        lay.add(&best_state, snap * kGllSnapDoubles);
+        lay.add(&best_elem_state, snap);
+    }
+    order_work.add(lay, kavail, npoints, nelem);
+    int rc = lay.commit(ctx, __func__, MM_ERR_ARG);   // (MM_ERR_ARG: this stage has always reported a failed carve with MM_REQUIRE)
     if (rc != MM_OK) return rc;
-    int2 *qa = (int2 *)mm_scratch_take(ctx, (size_t)npoints * sizeof(int2));
-    int2 *qb = (int2 *)mm_scratch_take(ctx, (size_t)npoints * sizeof(int2));
-    int *counters = (int *)mm_scratch_take(ctx, sizeof(int) * (MM_KNN_MAX_K + 8));
-    int *id_list = (int *)mm_scratch_take(ctx, (size_t)npoints * sizeof(int));
-    double *best_state = snap ? (double *)mm_scratch_take(ctx, snap * kGllSnapStateBytes) : nullptr;
-    i64 *best_elem_state = snap ? (i64 *)mm_scratch_take(ctx, snap * kGllSnapElemBytes) : nullptr;
-    MM_REQUIRE(qa && qb && counters && id_list && (!snap_to_nearest || (best_state && best_elem_state)),
-               "scratch carve failed");
     MM_HIP_CHECK(hipMemsetAsync(counters, 0, sizeof(int) * (MM_KNN_MAX_K + 8), ctx->stream));
     const int *visit = nullptr;
-    rc = gll_visit_order(ctx, __func__, nn, kavail, npoints, nelem, &visit);
+    rc = order_work.run(ctx, nn, &visit);
     if (rc != MM_OK) return rc;
     // (deferred values: only the fused pipeline's int32 lists ask for them)
     constexpr bool kCanDefer = sizeof(IDX) == sizeof(int);
@@ -1444,13 +1443,15 @@ extern "C" int64_t mm_locate_gll_bbox(mm_context *ctx, int order, int dim, int64
 {
     return gll_staged_call(__func__, ctx, order, dim, k, npoints, nn_d, gll_points_d, nelem, points_d, elem_d, coeffs_d,
                            [&](const char *who) -> int {
-        const size_t box_bytes = (size_t)(nelem > 0 ? nelem : 1) * 9 * sizeof(double);
-        int rc = mm_scratch_begin(ctx, mm_round256(box_bytes) + gll_visit_bytes(npoints, nelem) + 4096);
+        double *boxes;
+        GllVisit order_work;
+        mm_scratch_layout lay;
+        lay.add(&boxes, (size_t)(nelem > 0 ? nelem : 1) * 9);
+        order_work.add(lay, (int)k, npoints, nelem);
+        int rc = lay.commit(ctx, who, MM_ERR_ARG);   // (MM_ERR_ARG, as MM_REQUIRE_AS reported it)
         if (rc != MM_OK) return rc;
-        double *boxes = (double *)mm_scratch_take(ctx, box_bytes);
-        MM_REQUIRE_AS(who, boxes != nullptr, "scratch carve failed");
         const int *visit = nullptr;
-        rc = gll_visit_order(ctx, who, (const i64 *)nn_d, (int)k, npoints, nelem, &visit);
+        rc = order_work.run(ctx, (const i64 *)nn_d, &visit);
         if (rc != MM_OK) return rc;
         unsigned long long *nh = (unsigned long long *)ctx->d_counters;
         const unsigned ge = (unsigned)((nelem + 255) / 256), gt = (unsigned)((npoints + 63) / 64);

@@ -804,9 +804,8 @@ static i64 resident_workgroups(mm_context *ctx, FN fn)
     return (i64)per_cu * cus;
 }
 
-// Launch the whole locate stage on ctx->stream (no synchronisation).  Scratch: the long queue,
-// the reference-order list and their counters come from the context's scratch pool, so this must be the only
-// scratch user between mm_scratch_begin calls of the caller -- it calls mm_scratch_begin itself.
+// Launch the whole locate stage on ctx->stream (no synchronisation).  It takes nothing from the context's scratch pool:
+// the reference-order lists live in MM_BUF_LOC_SLOW and the counters in the context's counter array (see below).
 template <typename IDX>
 static int launch_locate_typed(mm_context *ctx, i64 k, i64 npoints, const IDX *nn, const i64 *conn, i64 nelem,
                                int conn_is_exodus, const Emit &em, const double *nodes, const double *pts,

@@ -158,18 +158,20 @@ extern "C" int mm_weighted_sum(mm_context *ctx, const double *mass_d, const doub
     MM_REQUIRE(out_d != nullptr && (mass_d != nullptr || n == 0), "null array");
     MM_HIP_CHECK(hipSetDevice(ctx->device));
     // the partial sums of every level but the last: level 0 has chunks_of(n) per component, level 1 chunks_of(that) ...
-    i64 level_n = chunks_of(n);
-    size_t need = 0;
-    for (i64 m = level_n; m > 1; m = chunks_of(m)) need += mm_round256((size_t)(m * ncomp) * sizeof(double));
-    if (need) {
-        const int rc = mm_scratch_begin(ctx, need);
+    // (n < 2^42 and 4096 values per chunk: at most three such levels)
+    double *partial[4] = {nullptr, nullptr, nullptr, nullptr};
+    mm_scratch_layout lay;
+    int nlevels = 0;
+    for (i64 m = chunks_of(n); m > 1; m = chunks_of(m)) lay.add(&partial[nlevels++], (size_t)(m * ncomp));
+    if (nlevels) {
+        const int rc = lay.commit(ctx, __func__);
         if (rc != MM_OK) return rc;
     }
     const double *a = mass_d, *f = fields_d;
     i64 sa = 0, count = n;
-    for (;;) {
+    for (int level = 0;; ++level) {
         const i64 nchunks = chunks_of(count);
-        double *dst = nchunks == 1 ? out_d : (double *)mm_scratch_take(ctx, (size_t)(nchunks * ncomp) * sizeof(double));
+        double *dst = nchunks == 1 ? out_d : partial[level];
         hipLaunchKernelGGL(weighted_sum_kernel, dim3((unsigned)nchunks, (unsigned)ncomp), dim3(kThreads), 0, ctx->stream, a,
                            sa, f, count, dst);
         if (nchunks == 1) break;

@@ -7,19 +7,6 @@
 
 #include "mm_common.h"
 
-int mm_knn_build_impl(mm_context *ctx, const double *src_d, i64 nsrc, i64 ndim, mm_knn_index **out,
-                      bool use_context_buffers, const double *box_partial_d, int box_nblocks, bool hex8_centroids = false);
-int mm_knn_query_impl(mm_context *ctx, const mm_knn_index *ix, const double *pts_d, i64 npts, i64 k, void *idx_d,
-                      double *dist_d, bool idx_is_int32);
-int mm_knn_query_sorted_impl(mm_context *ctx, const mm_knn_index *ix, const double *pts_d, i64 npts, i64 k, int *idx_d,
-                             const double **tsorted_out);
-void mm_clear_status(void);
-int mm_knn_build_guessed(mm_context *ctx, const double *cen, i64 nelem, const double *box_partial, int box_nblocks,
-                         mm_knn_index **out);
-int mm_knn_build_one_pass(mm_context *ctx, const i64 *conn, const double *nodes, i64 nelem, double *box_partial,
-                          int box_nblocks, mm_knn_index **out);
-bool mm_knn_guess_confirmed(mm_context *ctx);
-
 // candidates delivered up front when the lists are evaluated lazily (99.9 % of mesh-node targets are
 // resolved within them; see mm_set_lazy_lists)
 static const int64_t kLazyK = 8;

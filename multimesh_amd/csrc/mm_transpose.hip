@@ -34,10 +34,6 @@
 
 #include "mm_common.h"
 
-size_t mm_radix_sort_scratch(i64 n);
-int mm_radix_sort_pairs(mm_context *ctx, unsigned long long *ka, unsigned long long *kb, unsigned *va, unsigned *vb, i64 n,
-                        int first_shift, int end_shift, void *scratch, bool *in_a);
-
 // (public handle: global namespace)
 struct mm_transpose {
     int device = 0;

@@ -27,8 +27,6 @@
 
 #include "mm_common.h"
 
-int mm_exclusive_scan_int(mm_context *ctx, const int *counts, i64 n, int *start, int *tile_sums);
-
 namespace {
 
 constexpr int kBlock = 256;
@@ -364,31 +362,25 @@ extern "C" int64_t mm_unique_points(mm_context *ctx, const double *points_d, int
     const int sort_tiles = (int)((n + kTile - 1) / kTile);
     const i64 ncounts = (i64)kBins * sort_tiles;
     const int count_tiles = (int)((ncounts + 1 + kScanTileItems - 1) / kScanTileItems);
-    const size_t need = 2 * mm_round256(n_sz * sizeof(u64)) + 2 * mm_round256(n_sz * sizeof(unsigned)) +
-                        2 * mm_round256((n_sz + 1) * sizeof(int)) + mm_round256((size_t)ntiles * sizeof(int)) +
-                        2 * mm_round256((size_t)(ncounts + 1) * sizeof(int)) + mm_round256((size_t)count_tiles * sizeof(int)) +
-                        2 * mm_round256((n_sz / 4 + 1) * sizeof(unsigned)) + mm_round256(sizeof(int) * (1 + 5 * (size_t)kMaxLongRuns)) +
-                        4096;
-    int rc = mm_scratch_begin(ctx, need);
+    u64 *key_a, *key_b;
+    unsigned *ord_a, *ord_b, *sub_a, *sub_b;
+    int *head, *before, *tile_sums, *counts, *offsets, *count_sums, *long_runs;
+    mm_scratch_layout lay;
+    lay.add(&key_a, n_sz);
+    lay.add(&key_b, n_sz);
+    lay.add(&ord_a, n_sz);
+    lay.add(&ord_b, n_sz);
+    lay.add(&head, n_sz + 1);
+    lay.add(&before, n_sz + 1);
+    lay.add(&tile_sums, (size_t)ntiles);
+    lay.add(&counts, (size_t)(ncounts + 1));
+    lay.add(&offsets, (size_t)(ncounts + 1));
+    lay.add(&count_sums, (size_t)count_tiles);
+    lay.add(&long_runs, 1 + 5 * (size_t)kMaxLongRuns);   // count, starts, lengths, table
+    lay.add(&sub_a, n_sz / 4 + 1);
+    lay.add(&sub_b, n_sz / 4 + 1);
+    int rc = lay.commit(ctx, __func__);
     if (rc != MM_OK) return rc;
-    u64 *key_a = (u64 *)mm_scratch_take(ctx, n_sz * sizeof(u64));
-    u64 *key_b = (u64 *)mm_scratch_take(ctx, n_sz * sizeof(u64));
-    unsigned *ord_a = (unsigned *)mm_scratch_take(ctx, n_sz * sizeof(unsigned));
-    unsigned *ord_b = (unsigned *)mm_scratch_take(ctx, n_sz * sizeof(unsigned));
-    int *head = (int *)mm_scratch_take(ctx, (n_sz + 1) * sizeof(int));
-    int *before = (int *)mm_scratch_take(ctx, (n_sz + 1) * sizeof(int));
-    int *tile_sums = (int *)mm_scratch_take(ctx, (size_t)ntiles * sizeof(int));
-    int *counts = (int *)mm_scratch_take(ctx, (size_t)(ncounts + 1) * sizeof(int));
-    int *offsets = (int *)mm_scratch_take(ctx, (size_t)(ncounts + 1) * sizeof(int));
-    int *count_sums = (int *)mm_scratch_take(ctx, (size_t)count_tiles * sizeof(int));
-    int *long_runs = (int *)mm_scratch_take(ctx, sizeof(int) * (1 + 5 * (size_t)kMaxLongRuns));   // count, starts, lengths, table
-    unsigned *sub_a = (unsigned *)mm_scratch_take(ctx, (n_sz / 4 + 1) * sizeof(unsigned));
-    unsigned *sub_b = (unsigned *)mm_scratch_take(ctx, (n_sz / 4 + 1) * sizeof(unsigned));
-    if (!key_a || !key_b || !ord_a || !ord_b || !head || !before || !tile_sums || !counts || !offsets || !count_sums ||
-        !long_runs || !sub_a || !sub_b) {
-        mm_set_error(MM_ERR_ALLOC, "scratch carve failed");
-        return MM_ERR_ALLOC;
-    }
 
     const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
     // stable sort of (ka, va)[0 .. cnt) by the keys' 64 bits with (kb, vb) as the other buffer; eight passes, so the

@@ -14,8 +14,6 @@
 // the same bits (np.unique(axis=0) keeps every such row apart): it hashes by its own index and claims a slot of its own.
 #include "mm_common.h"
 
-int mm_exclusive_scan_int(mm_context *ctx, const int *counts, i64 n, int *start, int *tile_sums);
-
 namespace {
 
 typedef unsigned long long u64;
@@ -119,20 +117,17 @@ int64_t unique_any_order(mm_context *ctx, const double *pts, i64 n, double *uniq
     while ((u64)tsize < 2ull * (u64)n) tsize <<= 1;
     const size_t n_sz = (size_t)n;
     const int ntiles = (int)((n + 1 + kScanTileItems - 1) / kScanTileItems);
-    const size_t need = mm_round256((size_t)tsize * sizeof(int)) + mm_round256(n_sz * sizeof(unsigned)) + mm_round256(n_sz * sizeof(int)) +
-                        2 * mm_round256((n_sz + 1) * sizeof(int)) + mm_round256((size_t)ntiles * sizeof(int)) + 2048;
-    int rc = mm_scratch_begin(ctx, need);
+    int *table, *rep, *flag, *rank, *tile_sums;
+    unsigned *slot_of;
+    mm_scratch_layout lay;
+    lay.add(&table, (size_t)tsize);
+    lay.add(&slot_of, n_sz);
+    lay.add(&rep, n_sz);
+    lay.add(&flag, n_sz + 1);
+    lay.add(&rank, n_sz + 1);
+    lay.add(&tile_sums, (size_t)ntiles);
+    int rc = lay.commit(ctx, __func__);
     if (rc != MM_OK) return rc;
-    int *table = (int *)mm_scratch_take(ctx, (size_t)tsize * sizeof(int));
-    unsigned *slot_of = (unsigned *)mm_scratch_take(ctx, n_sz * sizeof(unsigned));
-    int *rep = (int *)mm_scratch_take(ctx, n_sz * sizeof(int));
-    int *flag = (int *)mm_scratch_take(ctx, (n_sz + 1) * sizeof(int));
-    int *rank = (int *)mm_scratch_take(ctx, (n_sz + 1) * sizeof(int));
-    int *tile_sums = (int *)mm_scratch_take(ctx, (size_t)ntiles * sizeof(int));
-    if (!table || !slot_of || !rep || !flag || !rank || !tile_sums) {
-        mm_set_error(MM_ERR_ALLOC, "scratch carve failed");
-        return MM_ERR_ALLOC;
-    }
     MM_HIP_CHECK(hipMemsetAsync(table, 0xff, (size_t)tsize * sizeof(int), ctx->stream));
     const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
     hipLaunchKernelGGL((unique_insert_kernel<DIM>), grid, block, 0, ctx->stream, pts, n, table, tsize - 1u, slot_of);

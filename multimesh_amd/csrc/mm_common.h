@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <memory>
+
 #include "multimesh_hip.h"
 #include "mm_scratch_layout.h"
 
@@ -264,3 +266,10 @@ struct mm_knn_index {
     mm_knn_tree *tree = nullptr;   // graded clouds: the adaptive index that serves them instead of density levels (owned)
     bool graded() const { return fine != nullptr || tree != nullptr; }
 };
+
+// An index under construction, or built for one call of the fused pipeline: destroyed on every way out but the one that
+// releases it to the caller.  (Hidden visibility: one type in every unit, and the library exports nothing of it.)
+struct __attribute__((visibility("hidden"))) mm_index_deleter {
+    void operator()(mm_knn_index *ix) const { mm_knn_destroy(nullptr, ix); }
+};
+using IndexOwner = std::unique_ptr<mm_knn_index, mm_index_deleter>;

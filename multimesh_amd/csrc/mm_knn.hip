@@ -297,13 +297,12 @@ void free_index(mm_knn_index *ix)
     delete ix;
 }
 
-// An index (a tree) under construction: freed on every way out but the one that releases it to the caller.
-struct IndexDeleter {
-    void operator()(mm_knn_index *ix) const { free_index(ix); }
+// A tree under construction: freed on every way out but the one that releases it to the caller (an index: IndexOwner,
+// mm_common.h).
+struct TreeDeleter {
     void operator()(mm_knn_tree *tr) const { free_tree(tr); }
 };
-using IndexOwner = std::unique_ptr<mm_knn_index, IndexDeleter>;
-using TreeOwner = std::unique_ptr<mm_knn_tree, IndexDeleter>;
+using TreeOwner = std::unique_ptr<mm_knn_tree, TreeDeleter>;
 
 }  // namespace
 

@@ -773,7 +773,7 @@ __global__ __launch_bounds__(kPassBlock, kPassWaves) void locate_pass_kernel(i64
 
 }  // namespace
 
-// The instance of the pass kernel for a launch (all instances share one signature).
+// The instances of the stage's kernels for a launch (the instances of one kernel share one signature).
 template <typename IDX>
 struct PassFn {
     typedef void (*type)(i64, i64, const IDX *, const i64 *, i64, Emit, const double *, const double *, int *, int *,
@@ -781,12 +781,44 @@ struct PassFn {
 };
 
 template <typename IDX, bool FAST>
-static typename PassFn<IDX>::type pass_kernel_for(bool exodus, bool sorted, bool nid32)
+static typename PassFn<IDX>::type pass_kernel_in_mode(bool exodus, bool sorted, bool nid32)
 {
 #define MM_PASS_PICK(EX, SO) (nid32 ? locate_pass_kernel<EX, IDX, SO, int, FAST> : locate_pass_kernel<EX, IDX, SO, i64, FAST>)
     if (sorted) return exodus ? MM_PASS_PICK(true, true) : MM_PASS_PICK(false, true);
     return exodus ? MM_PASS_PICK(true, false) : MM_PASS_PICK(false, false);
 #undef MM_PASS_PICK
+}
+
+template <typename IDX>
+static typename PassFn<IDX>::type pass_kernel_for(bool exodus, bool sorted, bool nid32, bool fast)
+{
+    return fast ? pass_kernel_in_mode<IDX, true>(exodus, sorted, nid32) : pass_kernel_in_mode<IDX, false>(exodus, sorted, nid32);
+}
+
+template <typename IDX>
+struct GroupFn {
+    typedef void (*type)(i64, i64, const IDX *, const i64 *, i64, Emit, const double *, const double *, unsigned long long *,
+                         const int *, const int *, int, int, const int *);
+};
+
+// (a group is half a wave for lists up to 32 candidates, else a wave)
+template <typename IDX>
+static typename GroupFn<IDX>::type group_kernel_for(bool exodus, i64 k)
+{
+    if (exodus) return k <= 32 ? locate_hex8_group_kernel<true, IDX, 32> : locate_hex8_group_kernel<true, IDX, 64>;
+    return k <= 32 ? locate_hex8_group_kernel<false, IDX, 32> : locate_hex8_group_kernel<false, IDX, 64>;
+}
+
+template <typename IDX>
+struct LoopFn {
+    typedef void (*type)(i64, i64, const IDX *, const i64 *, i64, Emit, const double *, const double *, unsigned long long *,
+                         const int *, const int *, int, const int *, int);
+};
+
+template <typename IDX>
+static typename LoopFn<IDX>::type loop_kernel_for(bool exodus)
+{
+    return exodus ? locate_hex8_kernel<true, IDX> : locate_hex8_kernel<false, IDX>;
 }
 
 // workgroups of `fn` the device keeps resident (the pass kernel is launched with exactly that many)
@@ -804,145 +836,171 @@ static i64 resident_workgroups(mm_context *ctx, FN fn)
     return (i64)per_cu * cus;
 }
 
+// What the steps of one locate stage share: the launch's arguments and the stage's lists and counters.
+template <typename IDX>
+struct LocateStage {
+    mm_context *ctx;
+    i64 npoints;
+    const i64 *conn;
+    i64 nelem;
+    bool exodus;
+    Emit em;
+    const double *nodes, *pts;
+    i64 *d_nfailed;
+    int zero_failed;
+    // the failed-point counter and the stage's own 16 counters ([15] length of the reference-order list, [14] of the
+    // second pass's, [13] the solves MM_FP_TOL repeated exactly) sit in one block of the context's counter array (mm_common.h)
+    int *counters;
+    bool fast, nid32;    // MM_FP_TOL; node ids in 32 bits (the caller has told us how many nodes there are: fewer registers across the solve)
+    i64 full_grid;       // workgroups of one thread per target
+    int *slow, *slow2;   // MM_BUF_LOC_SLOW: the reference-order list and the second pass's (taken once there are targets)
+};
+
+// what is left for the reference-order kernels: lists of k candidates and the targets that walk them
+template <typename IDX>
+struct SlowLists {
+    i64 k;
+    const IDX *nn;
+    int *list, *count;
+};
+
+// ONE fill clears the failed-point counter and the stage's counters when they sit in one block
+template <typename IDX>
+static int clear_counters(const LocateStage<IDX> &st)
+{
+    if (st.d_nfailed == st.ctx->d_counters)
+        return mm_zero_async(st.ctx, st.ctx->d_counters, 16 * sizeof(i64)) != MM_OK ? MM_ERR_HIP : MM_OK;
+    MM_HIP_CHECK(hipMemsetAsync(st.d_nfailed, 0, sizeof(i64), st.ctx->stream));
+    MM_HIP_CHECK(hipMemsetAsync(st.counters, 0, 16 * sizeof(int), st.ctx->stream));
+    return MM_OK;
+}
+
+// ONE launch over all targets.  Persistent waves: exactly as many workgroups as the device keeps
+// resident, so that every wave lives for the whole pass and its private queues see a long stream
+// of targets.
+// (tsorted: rows nn[] and the records are in the kNN stage's cell-sorted order; the reference-order kernels
+// work on the targets' own indices either way)
+// Returns the workgroups of the pass kernel the device keeps resident (the second pass's cap).
+template <typename IDX>
+static i64 first_pass(const LocateStage<IDX> &st, i64 k, const IDX *nn, const mm_lazy_lists *lazy, const double *tsorted)
+{
+    mm_context *ctx = st.ctx;
+    const typename PassFn<IDX>::type fn = pass_kernel_for<IDX>(st.exodus, tsorted != nullptr, st.nid32, st.fast);
+    const i64 resident = resident_workgroups(ctx, fn);
+    const i64 grid = resident < st.full_grid ? resident : st.full_grid;
+    // (walk order of the sorted targets: see the kernel; the kNN grid's x dimension comes with the lazy lists)
+    const int planes = (tsorted && lazy && lazy->index && !lazy->index->graded()) ? lazy->index->dims[0] : 0;
+    mm_stage_begin(ctx, MM_STAGE_LOCATE_PASS0);
+    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kPassBlock), 0, ctx->stream, k, st.npoints, nn, st.conn, st.nelem, st.em,
+                       st.nodes, tsorted ? tsorted : st.pts, st.slow, st.counters + 15, (const int *)nullptr,
+                       (const int *)nullptr, 0, planes, kPassPanel, st.counters + 13, (const int *)ctx->abort_flags);
+    mm_stage_end(ctx, MM_STAGE_LOCATE_PASS0);
+    return resident;
+}
+
+// Lazily evaluated lists: the targets the first pass left have only seen the nearest k of k_full candidates -- fetch
+// their full lists now; the reference-order kernels start again at candidate 0 anyway.
+template <typename IDX>
+static int fetch_full_lists(const LocateStage<IDX> &st, i64 k, i64 resident, const mm_lazy_lists *lazy, SlowLists<IDX> *left)
+{
+    mm_context *ctx = st.ctx;
+    // A graded cloud (the index has density levels) leaves long lists here -- elongated elements whose centroid
+    // is not among a target's eight nearest --: worth one small readback to send them through the tiled kernels
+    // instead of the list-mode ones.  A uniform mesh (no levels) leaves none or a handful: no readback.
+    i64 list_len = -1;
+    if (lazy->index->graded()) {
+        MM_HIP_CHECK(hipMemcpyAsync(ctx->h_counters + 1, left->count, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        list_len = (i64) * reinterpret_cast<const int *>(ctx->h_counters + 1);
+    }
+    const int rc = mm_knn_query_list_impl(ctx, lazy->index, st.pts, st.npoints, lazy->k_full, lazy->nn_full, left->list,
+                                          left->count, list_len);
+    if (rc != MM_OK) return rc;
+    left->k = lazy->k_full;
+    left->nn = reinterpret_cast<const IDX *>(lazy->nn_full);
+    if (list_len < MM_LONG_LIST_MIN) return MM_OK;
+    // a long list: its targets walk the REST of their candidates (from the k-th on) in a second launch of
+    // the pass kernel; only what finds no acceptance there either is left to the reference-order kernels
+    // (which start again at candidate 0: smallest-error fallback, failures)
+    i64 g2 = (list_len + kPassBlock - 1) / kPassBlock;
+    if (g2 > resident) g2 = resident;
+    hipLaunchKernelGGL(pass_kernel_for<IDX>(st.exodus, false, st.nid32, st.fast), dim3((unsigned)g2), dim3(kPassBlock), 0,
+                       ctx->stream, left->k, st.npoints, left->nn, st.conn, st.nelem, st.em, st.nodes, st.pts, st.slow2,
+                       st.counters + 14, (const int *)left->list, (const int *)left->count, (int)k, 0, 0, st.counters + 13,
+                       (const int *)ctx->abort_flags);
+    left->list = st.slow2;
+    left->count = st.counters + 14;
+    return MM_OK;
+}
+
+// Out of candidates without an acceptance: the reference's order.  Two launches, one of which returns at once: lists up
+// to kGroupListMax take one candidate per lane (a target's critical path is ONE solve), longer ones the loop (see
+// locate_hex8_group_kernel).
+template <typename IDX>
+static void reference_order(const LocateStage<IDX> &st, const SlowLists<IDX> &left)
+{
+    mm_context *ctx = st.ctx;
+    unsigned long long *nfailed = (unsigned long long *)st.d_nfailed;
+    const bool groups = left.k <= 64;
+    if (groups) {
+        i64 ggrid = (st.npoints * (left.k <= 32 ? 32 : 64) + 255) / 256;
+        if (ggrid > 8192) ggrid = 8192;
+        if (ggrid < 1) ggrid = 1;
+        hipLaunchKernelGGL(group_kernel_for<IDX>(st.exodus, left.k), dim3((unsigned)ggrid), dim3(256), 0, ctx->stream, left.k,
+                           st.npoints, left.nn, st.conn, st.nelem, st.em, st.nodes, st.pts, nfailed, (const int *)left.list,
+                           (const int *)left.count, st.zero_failed, kGroupListMax, (const int *)ctx->abort_flags);
+    }
+    i64 sgrid = st.full_grid >> 3;
+    if (sgrid < 256) sgrid = st.full_grid < 256 ? st.full_grid : 256;
+    hipLaunchKernelGGL(loop_kernel_for<IDX>(st.exodus), dim3((unsigned)sgrid), dim3(256), 0, ctx->stream, left.k, st.npoints,
+                       left.nn, st.conn, st.nelem, st.em, st.nodes, st.pts, nfailed, (const int *)left.list,
+                       (const int *)left.count, st.zero_failed, (const int *)ctx->abort_flags, groups ? kGroupListMax : -1);
+}
+
+// diagnostic (MM_LOCATE_DEBUG): sizes of the pass queues and of the reference-order list (synchronises)
+static int dump_counters(mm_context *ctx, const int *counters, i64 npoints)
+{
+    int h[16];
+    MM_HIP_CHECK(hipMemcpyAsync(h, counters, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    fprintf(stderr, "[mm_locate] %lld targets; reference-order list %d\n", (long long)npoints, h[15]);
+#ifdef MM_LOCATE_COUNT
+    fprintf(stderr, "[mm_locate] rounds %d (slow tiers %d), active lanes %d, solves %d, accepted %d, sent to the next tier %d, "
+                    "candidates dropped by the box test %d\n", h[0], h[6], h[1], h[2], h[3], h[5], h[4]);
+#endif
+    return MM_OK;
+}
+
 // Launch the whole locate stage on ctx->stream (no synchronisation).  It takes nothing from the context's scratch pool:
-// the reference-order lists live in MM_BUF_LOC_SLOW and the counters in the context's counter array (see below).
+// the reference-order lists live in MM_BUF_LOC_SLOW and the counters in the context's counter array.
 template <typename IDX>
 static int launch_locate_typed(mm_context *ctx, i64 k, i64 npoints, const IDX *nn, const i64 *conn, i64 nelem,
                                int conn_is_exodus, const Emit &em, const double *nodes, const double *pts,
                                i64 *d_nfailed, int zero_failed, const mm_lazy_lists *lazy, const double *tsorted)
 {
-    // the failed-point counter and the stage's own 16 counters ([15] length of the reference-order list, [14] of the
-    // second pass's, [13] the solves MM_FP_TOL repeated exactly) sit in one block of the context's counter array (mm_common.h): ONE
-    // fill clears both
     int *counters = reinterpret_cast<int *>(ctx->d_counters + 8);
-    if (d_nfailed == ctx->d_counters) {
-        if (mm_zero_async(ctx, ctx->d_counters, 16 * sizeof(i64)) != MM_OK) return MM_ERR_HIP;
-    } else {
-        MM_HIP_CHECK(hipMemsetAsync(d_nfailed, 0, sizeof(i64), ctx->stream));
-        MM_HIP_CHECK(hipMemsetAsync(counters, 0, 16 * sizeof(int), ctx->stream));
-    }
+    LocateStage<IDX> st{ctx, npoints, conn, nelem, conn_is_exodus != 0, em, nodes, pts, d_nfailed, zero_failed, counters,
+                        ctx->fp_mode == MM_FP_TOL, em.nnodes > 0 && em.nnodes < (i64)0x7fffffff, (npoints + 255) / 256};
+    int rc = clear_counters(st);
+    if (rc != MM_OK) return rc;
     if (npoints == 0 || k == 0) return MM_OK;
     MM_REQUIRE(npoints < (i64)0x7fffffff, "too many targets for one launch");
-    const int block = 256;
-    const i64 full_grid = (npoints + block - 1) / block;
-    const bool fast = ctx->fp_mode == MM_FP_TOL;
-
     // (a buffer of its own, not the scratch pool: a long list's on-demand neighbour query carves the pool anew)
     char *slow_block = nullptr;
     const size_t list_bytes = mm_round256((size_t)npoints * sizeof(int));
-    int rc = mm_buffer_get(ctx, MM_BUF_LOC_SLOW, 2 * list_bytes, (void **)&slow_block);
+    rc = mm_buffer_get(ctx, MM_BUF_LOC_SLOW, 2 * list_bytes, (void **)&slow_block);
     if (rc != MM_OK) return rc;
-    int *slow = (int *)slow_block;
-    int *slow2 = (int *)(slow_block + list_bytes);
-    int *slow_count = counters + 15;
-    int *unsure_count = counters + 13;
-    // (node ids in 32 bits when the caller has told us how many nodes there are: fewer registers across the solve)
-    const bool nid32 = em.nnodes > 0 && em.nnodes < (i64)0x7fffffff;
-    // (tsorted: rows nn[] and the records are in the kNN stage's cell-sorted order; the reference-order kernel
-    // below works on the targets' own indices either way)
-    const typename PassFn<IDX>::type first_fn = fast ? pass_kernel_for<IDX, true>(conn_is_exodus != 0, tsorted != nullptr, nid32)
-                                                     : pass_kernel_for<IDX, false>(conn_is_exodus != 0, tsorted != nullptr, nid32);
-    const i64 resident = resident_workgroups(ctx, first_fn);
-    const i64 grid = resident < full_grid ? resident : full_grid;
-    // ONE launch over all targets.  Persistent waves: exactly as many workgroups as the device keeps
-    // resident, so that every wave lives for the whole pass and its private queues see a long stream
-    // of targets.
-    mm_stage_begin(ctx, MM_STAGE_LOCATE_PASS0);
-    {
-        dim3 g_((unsigned)grid), b_(block);
-        // (walk order of the sorted targets: see the kernel; the kNN grid's x dimension comes with the lazy lists)
-        const int planes = (tsorted && lazy && lazy->index && !lazy->index->graded()) ? lazy->index->dims[0] : 0;
-        hipLaunchKernelGGL(first_fn, g_, b_, 0, ctx->stream, k, npoints, nn, conn, nelem, em, nodes, tsorted ? tsorted : pts,
-                           slow, slow_count, (const int *)nullptr, (const int *)nullptr, 0, planes, kPassPanel, unsure_count,
-                           (const int *)ctx->abort_flags);
-    }
-    mm_stage_end(ctx, MM_STAGE_LOCATE_PASS0);
-    // out of candidates without an acceptance: reference-order kernel
-    {
-        // lazily evaluated lists: these targets have only seen the nearest k of k_full candidates --
-        // fetch their full lists now; the reference-order kernel starts again at candidate 0 anyway
-        i64 k_slow = k;
-        const IDX *nn_slow = nn;
-        if (lazy && sizeof(IDX) == sizeof(int)) {
-            // A graded cloud (the index has density levels) leaves long lists here -- elongated elements whose centroid
-            // is not among a target's eight nearest --: worth one small readback to send them through the tiled kernels
-            // instead of the list-mode ones.  A uniform mesh (no levels) leaves none or a handful: no readback.
-            i64 list_len = -1;
-            if (lazy->index->graded()) {
-                MM_HIP_CHECK(hipMemcpyAsync(ctx->h_counters + 1, slow_count, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-                MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-                list_len = (i64) * reinterpret_cast<const int *>(ctx->h_counters + 1);
-            }
-            int lrc = mm_knn_query_list_impl(ctx, lazy->index, pts, npoints, lazy->k_full, lazy->nn_full, slow,
-                                             slow_count, list_len);
-            if (lrc != MM_OK) return lrc;
-            k_slow = lazy->k_full;
-            nn_slow = reinterpret_cast<const IDX *>(lazy->nn_full);
-            if (list_len >= MM_LONG_LIST_MIN) {
-                // a long list: its targets walk the REST of their candidates (from the k-th on) in a second launch of
-                // the pass kernel; only what finds no acceptance there either is left to the reference-order kernel
-                // (which starts again at candidate 0: smallest-error fallback, failures)
-                int *slow2_count = counters + 14;
-                i64 g2 = (list_len + kPassBlock - 1) / kPassBlock;
-                if (g2 > resident) g2 = resident;
-                dim3 g_((unsigned)g2), b_(block);
-                const bool nid32b = em.nnodes > 0 && em.nnodes < (i64)0x7fffffff;
-                hipLaunchKernelGGL((fast ? pass_kernel_for<IDX, true>(conn_is_exodus != 0, false, nid32b)
-                                         : pass_kernel_for<IDX, false>(conn_is_exodus != 0, false, nid32b)),
-                                   g_, b_, 0, ctx->stream, k_slow, npoints, nn_slow, conn, nelem, em, nodes, pts, slow2, slow2_count,
-                                   (const int *)slow, (const int *)slow_count, (int)k, 0, 0, unsure_count,
-                                   (const int *)ctx->abort_flags);
-                slow = slow2;
-                slow_count = slow2_count;
-            }
-        }
-        i64 sgrid = full_grid >> 3;
-        if (sgrid < 256) sgrid = full_grid < 256 ? full_grid : 256;
-        dim3 g((unsigned)sgrid), b(block);
-        // Two launches, one of which returns at once: lists up to kGroupListMax take one candidate per lane (a target's
-        // critical path is ONE solve), longer ones the loop (see locate_hex8_group_kernel).
-        if (k_slow <= 64) {
-            i64 ggrid = (npoints * (k_slow <= 32 ? 32 : 64) + 255) / 256;
-            if (ggrid > 8192) ggrid = 8192;
-            if (ggrid < 1) ggrid = 1;
-            dim3 gg((unsigned)ggrid);
-#define MM_GROUP(EX, GG)                                                                                                   \
-    hipLaunchKernelGGL((locate_hex8_group_kernel<EX, IDX, GG>), gg, b, 0, ctx->stream, k_slow, npoints, nn_slow, conn, nelem, em, \
-                       nodes, pts, (unsigned long long *)d_nfailed, slow, slow_count, zero_failed, kGroupListMax,                \
-                       (const int *)ctx->abort_flags)
-            if (conn_is_exodus) {
-                if (k_slow <= 32) MM_GROUP(true, 32);
-                else MM_GROUP(true, 64);
-            } else {
-                if (k_slow <= 32) MM_GROUP(false, 32);
-                else MM_GROUP(false, 64);
-            }
-#undef MM_GROUP
-        }
-        const int loop_min = k_slow <= 64 ? kGroupListMax : -1;
-        if (conn_is_exodus)
-            hipLaunchKernelGGL((locate_hex8_kernel<true, IDX>), g, b, 0, ctx->stream, k_slow, npoints, nn_slow, conn,
-                               nelem, em, nodes, pts, (unsigned long long *)d_nfailed, slow, slow_count, zero_failed,
-                               (const int *)ctx->abort_flags, loop_min);
-        else
-            hipLaunchKernelGGL((locate_hex8_kernel<false, IDX>), g, b, 0, ctx->stream, k_slow, npoints, nn_slow, conn,
-                               nelem, em, nodes, pts, (unsigned long long *)d_nfailed, slow, slow_count, zero_failed,
-                               (const int *)ctx->abort_flags, loop_min);
-    }
+    st.slow = (int *)slow_block;
+    st.slow2 = (int *)(slow_block + list_bytes);
+
+    const i64 resident = first_pass(st, k, nn, lazy, tsorted);
+    SlowLists<IDX> left{k, nn, st.slow, counters + 15};
+    if (lazy && sizeof(IDX) == sizeof(int)) rc = fetch_full_lists(st, k, resident, lazy, &left);
+    if (rc != MM_OK) return rc;
+    reference_order(st, left);
     MM_HIP_CHECK(hipGetLastError());
     static const bool dbg_locate = getenv("MM_LOCATE_DEBUG") != nullptr;
-    if (dbg_locate) {
-        // diagnostic: sizes of the pass queues and of the reference-order list (synchronises)
-        int h[16];
-        MM_HIP_CHECK(hipMemcpyAsync(h, counters, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-        MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        fprintf(stderr, "[mm_locate] %lld targets; reference-order list %d\n", (long long)npoints, h[15]);
-#ifdef MM_LOCATE_COUNT
-        fprintf(stderr, "[mm_locate] rounds %d (slow tiers %d), active lanes %d, solves %d, accepted %d, sent to the next tier %d, "
-                        "candidates dropped by the box test %d\n", h[0], h[6], h[1], h[2], h[3], h[5], h[4]);
-#endif
-    }
-    return MM_OK;
+    return dbg_locate ? dump_counters(ctx, st.counters, npoints) : MM_OK;
 }
 
 // nn_is_int32 / zero_failed: the fused pipeline's int32 candidate lists and un-zeroed private
@@ -1001,8 +1059,8 @@ extern "C" int64_t mm_locate_hex8(mm_context *ctx, int64_t k, int64_t npoints, c
                                    (i64 *)enc_d, nodes_d, w_d, pts_d, ctx->d_counters, 0, nullptr, 0, 0, nullptr, nullptr);
     mm_stage_end(ctx, MM_STAGE_LOCATE);
     if (rc != MM_OK) return rc;
-    MM_HIP_CHECK(hipMemcpyAsync(ctx->h_counters, ctx->d_counters, sizeof(i64), hipMemcpyDeviceToHost,
-                                ctx->stream));
+    rc = mm_mirror_async(ctx, (long long *)ctx->h_counters, (const long long *)ctx->d_counters, 1);
+    if (rc != MM_OK) return rc;
     MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return ctx->h_counters[0];
 }

@@ -55,183 +55,253 @@ struct mm_source {
     int device = 0;
 };
 
+// The argument checks the device-pointer and the host-array entries share, reported in the name of `who`: the host entry
+// makes them before it takes its buffers, and the pipeline then only adds its own two (on k between these, as ever).
+static int require_sizes(const char *who, const mm_context *ctx, int64_t nnodes, int64_t nelem, int64_t npoints, int64_t ncomp)
+{
+    MM_REQUIRE_AS(who, ctx != nullptr, "ctx is null");
+    MM_REQUIRE_AS(who, nnodes >= 1 && nelem >= 1, "empty source mesh");
+    MM_REQUIRE_AS(who, npoints >= 0 && ncomp >= 0, "negative size");
+    return MM_OK;
+}
+
+static int require_arrays(const char *who, int64_t npoints, int64_t ncomp, const void *nodes, const void *conn,
+                          const void *points, const void *fields, const void *out)
+{
+    MM_REQUIRE_AS(who, nodes && conn, "null mesh array");
+    MM_REQUIRE_AS(who, npoints == 0 || points, "null target array");
+    MM_REQUIRE_AS(who, ncomp == 0 || out == nullptr || fields, "null field array");
+    return MM_OK;
+}
+
+// One call of the fused pipeline: its arguments (device pointers) and what is derived from them once.
+struct hex8_call {
+    const double *nodes;
+    int64_t nnodes;
+    const i64 *conn;
+    int64_t nelem;
+    const double *points;
+    int64_t npoints;
+    const double *fields;
+    int64_t ncomp, k;
+    double *out;
+    const mm_source *resident;
+    // lazily evaluated candidate lists (mm_set_lazy_lists): the kNN stage delivers the kq nearest, the
+    // full k only on demand inside the locate stage (lazy.nn_full; lazy.index is the attempt's)
+    int64_t kq;
+    mm_lazy_lists lazy;
+    // Few components: the interpolated values are formed inside the locate stage, at the point of
+    // acceptance, and the operator rows are only materialised when the caller asks for them (both
+    // pointers).  Many components: 8 gathers per component inside the register-heavy locate kernel
+    // cost more than writing the rows and streaming them through the gather kernel.
+    bool want_values, fuse_gather;
+    // Intermediates come from the context's grow-only buffer cache: after the first call with a
+    // given problem size there is no allocation, free or extra synchronisation in here.
+    double *cen, *box_partial;
+    int *nn;  // candidate lists stay int32 inside the pipeline (half the bytes of the public int64)
+    i64 *enc;   // the caller's rows, the context's private ones (values wanted, gather not fused), or null
+    double *w;
+};
+
+// Checks the arguments (host_checked: the host-array entry has made the shared checks), resets the stage timers
+// and -- when there are targets -- takes the call's buffers.
+static int describe_call(mm_context *ctx, const double *nodes_d, int64_t nnodes, const int64_t *conn_d, int64_t nelem,
+                         const double *points_d, int64_t npoints, const double *fields_d, int64_t ncomp, int64_t k,
+                         double *out_d, int64_t *enc_d, double *w_d, const mm_source *resident, bool host_checked,
+                         hex8_call *call)
+{
+    static const char *const who = "interpolate_hex8_impl";
+    int rc = MM_OK;
+    if (!host_checked && (rc = require_sizes(who, ctx, nnodes, nelem, npoints, ncomp)) != MM_OK) return rc;
+    MM_REQUIRE_AS(who, k >= 1 && k <= MM_KNN_MAX_K, "nelem_to_search must be in 1..MM_KNN_MAX_K");
+    if (!host_checked && (rc = require_arrays(who, npoints, ncomp, nodes_d, conn_d, points_d, fields_d, out_d)) != MM_OK) return rc;
+    MM_REQUIRE_AS(who, nelem < (int64_t)0x7fffffff, "too many elements");
+    MM_HIP_CHECK(hipSetDevice(ctx->device));
+    mm_stage_reset(ctx);
+    *call = hex8_call{nodes_d, nnodes, (const i64 *)conn_d, nelem, points_d, npoints, fields_d, ncomp, k, out_d, resident};
+    call->kq = (ctx->lazy_lists && k > kLazyK) ? kLazyK : k;
+    call->lazy.k_full = k;
+    call->want_values = out_d && ncomp > 0;
+    call->fuse_gather = call->want_values && ncomp <= kFuseGatherMaxComp;
+    if (npoints == 0) return MM_OK;
+
+    const size_t np = (size_t)npoints;
+    if (!resident) {
+        rc = mm_buffer_get(ctx, MM_BUF_CENTROID, (size_t)nelem * 3 * sizeof(double), (void **)&call->cen);
+        if (rc == MM_OK) rc = mm_buffer_get(ctx, MM_BUF_BOX_PARTIAL, (size_t)kBoxBlocks * 6 * sizeof(double), (void **)&call->box_partial);
+    }
+    if (rc == MM_OK) rc = mm_buffer_get(ctx, MM_BUF_NN, np * (size_t)call->kq * sizeof(int), (void **)&call->nn);
+    if (rc == MM_OK && call->kq < k) rc = mm_buffer_get(ctx, MM_BUF_NN_FULL, np * (size_t)k * sizeof(int), (void **)&call->lazy.nn_full);
+    if (enc_d && w_d) {
+        call->enc = (i64 *)enc_d;
+        call->w = w_d;
+    } else if (call->want_values && !call->fuse_gather) {
+        if (rc == MM_OK) rc = mm_buffer_get(ctx, MM_BUF_ENC, np * 8 * sizeof(i64), (void **)&call->enc);
+        if (rc == MM_OK) rc = mm_buffer_get(ctx, MM_BUF_W, np * 8 * sizeof(double), (void **)&call->w);
+    }
+    if (rc != MM_OK) (void)hipStreamSynchronize(ctx->stream);
+    return rc;
+}
+
+// The search grid is laid out from the bounding box of the centroids, which the host would have to wait for in
+// mid-call.  When the previous call of this context left the box of a source mesh of the same size (the usual
+// case: one source mesh, many calls), the grid is GUESSED from that box and the guess is checked against this
+// call's own box after the synchronisation that ends the call; a wrong
+// guess runs the call again the ordinary way (twice wrong: no more guessing in this context).  MM_GRID_GUESS=0
+// switches it off.  A guessed call whose context also still holds the cell_start of that grid's sort
+// (grid_guess.cells_ok) guesses the per-cell counts as well and sorts the centroids as it computes them
+// (mm_knn_build_one_pass); other counts are a miss like another box.
+static bool may_guess(const mm_context *ctx, const hex8_call &call)
+{
+    static const bool guess_on = !(getenv("MM_GRID_GUESS") && atoi(getenv("MM_GRID_GUESS")) == 0);
+    // (MM_KNN_LEVELS is read per call by the ordinary build -- tests switch it inside one process -- and a guessed build
+    // would ignore it)
+    return guess_on && ctx->grid_guess.valid && ctx->grid_guess.nsrc == call.nelem && ctx->grid_guess.misses < 2 &&
+           !getenv("MM_KNN_LEVELS") && !call.resident;
+}
+
+// What a guessed call that ran to its end leaves in the context.
+static void settle_guess(mm_context *ctx, bool confirmed)
+{
+    if (!confirmed) {
+        // not this mesh's grid (the call is run again the ordinary way, which also leaves the right box for the next call)
+        ctx->grid_guess.valid = false;
+        ctx->grid_guess.cells_ok = false;
+        ++ctx->grid_guess.misses;
+        return;
+    }
+    ctx->grid_guess.cells_ok = true;   // (the buffers hold this grid's complete sort)
+    // (a long-lived context forgives old misses: every 64 calls that confirmed their guess take one back)
+    if (ctx->grid_guess.misses > 0 && (ctx->grid_guess.calls_guessed & 63) == 0) --ctx->grid_guess.misses;
+}
+
+// From here to the end of a guessed attempt the ring searches and the locate kernels return at once when this call's
+// box (or per-cell counts) turn out not to be the guessed ones: bbox_final_kernel sets the flags on the device.
+static void begin_guessed_build(mm_context *ctx)
+{
+    ++ctx->grid_guess.calls_guessed;
+    ctx->abort_flags = reinterpret_cast<int *>(ctx->d_counters + kMmAbortSlot);
+}
+
+// The index for this attempt: the resident source's (borrowed), or one built into `built` -- in one pass over the mesh
+// when the context still holds the cell_start of the guessed grid's last sort, else centroids first.
+static int index_for_attempt(mm_context *ctx, const hex8_call &call, bool guessed, IndexOwner *built, const mm_knn_index **index)
+{
+    if (call.resident) {
+        *index = call.resident->index;   // centroids and grid are there: straight to the query
+        return MM_OK;
+    }
+    mm_knn_index *made = nullptr;
+    int rc = MM_OK;
+    if (guessed && ctx->grid_guess.cells_ok) {
+        // centroids, box and sort in one pass (no centroid array; mm_knn_build_one_pass brackets both stages itself)
+        begin_guessed_build(ctx);
+        rc = mm_knn_build_one_pass(ctx, call.conn, call.nodes, call.nelem, call.box_partial, kBoxBlocks, &made);
+    } else {
+        mm_stage_begin(ctx, MM_STAGE_CENTROID);
+        rc = mm_launch_centroid_bbox(ctx, call.nelem, call.conn, call.nodes, call.cen, call.box_partial, kBoxBlocks);
+        mm_stage_end(ctx, MM_STAGE_CENTROID);
+        if (rc != MM_OK) return rc;
+        mm_stage_begin(ctx, MM_STAGE_KNN_BUILD);
+        if (guessed) {
+            begin_guessed_build(ctx);
+            rc = mm_knn_build_guessed(ctx, call.cen, call.nelem, call.box_partial, kBoxBlocks, &made);
+        } else {
+            rc = mm_knn_build_impl(ctx, call.cen, call.nelem, 3, &made, true, call.box_partial, kBoxBlocks);
+        }
+        mm_stage_end(ctx, MM_STAGE_KNN_BUILD);
+    }
+    built->reset(made);
+    *index = made;
+    return rc;
+}
+
+// The stages of one attempt, each host upload just before the stage that needs it (feed may be null); ends with the
+// synchronisation after which the failed-point count is in the pinned mirror.
+static int64_t run_stages(mm_context *ctx, const hex8_call &call, const mm_host_feed *feed, bool guessed, IndexOwner *built)
+{
+    const bool lazily = call.kq < call.k;
+    int rc = MM_OK;
+    if (feed && (rc = feed_upload(ctx, feed, 0, 1, 0)) != MM_OK) return rc;
+    mm_lazy_lists lazy = call.lazy;
+    if ((rc = index_for_attempt(ctx, call, guessed, built, &lazy.index)) != MM_OK) return rc;
+
+    if (feed && (rc = feed_upload(ctx, feed, 2, 2, 1)) != MM_OK) return rc;
+    mm_stage_begin(ctx, MM_STAGE_KNN_QUERY);
+    // (the candidate rows come back in the cell-sorted order of the targets whenever the lane kernel serves the
+    // query: the locate stage then walks the targets in that order, tsorted = their records)
+    // (only with lazily evaluated lists: the reference-order kernel then reads the FULL lists, which are rows
+    // by the targets' own indices; with eager lists it reads these rows and needs them in that order)
+    const double *tsorted = nullptr;
+    rc = mm_knn_query_sorted_impl(ctx, lazy.index, call.points, call.npoints, call.kq, call.nn, lazily ? &tsorted : nullptr);
+    mm_stage_end(ctx, MM_STAGE_KNN_QUERY);
+    if (rc != MM_OK) return rc;
+
+    // locate + gather: scripts/cli.py:86-100.  MM_STAGE_GATHER stays empty on the fused path (mm_gather is
+    // the stand-alone A9 for callers that keep the operator).
+    // rows (and values) of failed points must read as zero (the reference's callers zero-initialise,
+    // scripts/cli.py:77-78): the reference-order locate kernel, the only place a point can fail,
+    // writes them (no 1.3 GB memset up front)
+    if (feed && (rc = feed_upload(ctx, feed, 3, 3, 2)) != MM_OK) return rc;
+    mm_stage_begin(ctx, MM_STAGE_LOCATE);
+    rc = mm_launch_locate_hex8(ctx, call.kq, call.npoints, call.nn, /*int32=*/true, call.conn, call.nelem, /*exodus=*/1,
+                               call.enc, call.nodes, call.w, call.points, ctx->d_counters, /*zero_failed=*/1,
+                               call.fuse_gather ? call.fields : nullptr, call.nnodes, call.ncomp, call.out,
+                               lazily ? &lazy : nullptr, tsorted);
+    mm_stage_end(ctx, MM_STAGE_LOCATE);
+    if (rc != MM_OK) return rc;
+    if (call.want_values && !call.fuse_gather) {
+        mm_stage_begin(ctx, MM_STAGE_GATHER);
+        rc = mm_launch_gather(ctx, call.fields, call.nnodes, call.ncomp, call.enc, call.w, call.npoints, 8, call.out, 1);
+        mm_stage_end(ctx, MM_STAGE_GATHER);
+        if (rc != MM_OK) return rc;
+    }
+
+    rc = mm_mirror_async(ctx, (long long *)ctx->h_counters, (const long long *)ctx->d_counters, 1);
+    if (rc != MM_OK) return rc;
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        mm_set_error(MM_ERR_HIP, "mm_interpolate_hex8: %s", hipGetErrorString(e));
+        return MM_ERR_HIP;
+    }
+    return ctx->h_counters[0];
+}
+
+// One attempt at the call: the number of failed points, or a negative status after synchronising the stream.  The index
+// the attempt built lives until here (its arrays are borrowed from the context cache and stay).
+static int64_t attempt(mm_context *ctx, const hex8_call &call, const mm_host_feed *feed, bool guessed)
+{
+    IndexOwner built;
+    ctx->abort_flags = nullptr;
+    const int64_t result = run_stages(ctx, call, feed, guessed, &built);
+    ctx->abort_flags = nullptr;
+    if (result < 0) (void)hipStreamSynchronize(ctx->stream);
+    return result;
+}
+
 static int64_t interpolate_hex8_impl(mm_context *ctx, const double *nodes_d, int64_t nnodes,
                                      const int64_t *conn_d, int64_t nelem, const double *points_d,
                                      int64_t npoints, const double *fields_d, int64_t ncomp, int64_t k,
                                      double *out_d, int64_t *enc_d, double *w_d, const mm_host_feed *feed,
                                      const mm_source *resident = nullptr)
 {
-    MM_REQUIRE(ctx != nullptr, "ctx is null");
-    MM_REQUIRE(nnodes >= 1 && nelem >= 1, "empty source mesh");
-    MM_REQUIRE(npoints >= 0 && ncomp >= 0, "negative size");
-    MM_REQUIRE(k >= 1 && k <= MM_KNN_MAX_K, "nelem_to_search must be in 1..MM_KNN_MAX_K");
-    MM_REQUIRE(nodes_d && conn_d, "null mesh array");
-    MM_REQUIRE(npoints == 0 || points_d, "null target array");
-    MM_REQUIRE(ncomp == 0 || out_d == nullptr || fields_d, "null field array");
-    MM_REQUIRE(nelem < (int64_t)0x7fffffff, "too many elements");
-    MM_HIP_CHECK(hipSetDevice(ctx->device));
-    mm_stage_reset(ctx);
+    hex8_call call;
+    const int rc = describe_call(ctx, nodes_d, nnodes, conn_d, nelem, points_d, npoints, fields_d, ncomp, k, out_d, enc_d, w_d,
+                                 resident, /*host_checked=*/feed != nullptr, &call);
+    if (rc != MM_OK) return rc;
     if (npoints == 0) return 0;
-
-    // Intermediates come from the context's grow-only buffer cache: after the first call with a
-    // given problem size there is no allocation, free or extra synchronisation in here.
-    double *cen = nullptr, *box_partial = nullptr;
-    int *nn = nullptr;  // candidate lists stay int32 inside the pipeline (half the bytes of the public int64)
-    i64 *enc = (i64 *)enc_d;
-    double *w = w_d;
-    mm_knn_index *index = nullptr;
-    int64_t result = MM_ERR_HIP;
-    hipError_t e = hipSuccess;
-    int rc = MM_OK;
-    bool guessed = false;
-
-#define MM_PIPE_FAIL(code, msg)                                        \
-    do {                                                               \
-        mm_set_error(code, "mm_interpolate_hex8: %s", msg);            \
-        result = code;                                                 \
-        goto done;                                                     \
-    } while (0)
-
-    // lazily evaluated candidate lists (mm_set_lazy_lists): the kNN stage delivers the kq nearest, the
-    // full k only on demand inside the locate stage
-    const int64_t kq = (ctx->lazy_lists && k > kLazyK) ? kLazyK : k;
-    int *nn_full = nullptr;
-    const double *tsorted = nullptr;
-    mm_lazy_lists lazy;
-    if (!resident) {
-        rc = mm_buffer_get(ctx, MM_BUF_CENTROID, (size_t)nelem * 3 * sizeof(double), (void **)&cen);
-        if (rc == MM_OK) rc = mm_buffer_get(ctx, MM_BUF_BOX_PARTIAL, (size_t)kBoxBlocks * 6 * sizeof(double), (void **)&box_partial);
-    }
-    if (rc == MM_OK) rc = mm_buffer_get(ctx, MM_BUF_NN, (size_t)npoints * (size_t)kq * sizeof(int), (void **)&nn);
-    if (rc == MM_OK && kq < k)
-        rc = mm_buffer_get(ctx, MM_BUF_NN_FULL, (size_t)npoints * (size_t)k * sizeof(int), (void **)&nn_full);
-    // Few components: the interpolated values are formed inside the locate stage, at the point of
-    // acceptance, and the operator rows are only materialised when the caller asks for them (both
-    // pointers).  Many components: 8 gathers per component inside the register-heavy locate kernel
-    // cost more than writing the rows and streaming them through the gather kernel.
-    const bool want_values = out_d && ncomp > 0;
-    const bool fuse_gather = want_values && ncomp <= kFuseGatherMaxComp;
-    if (!(enc && w)) {
-        enc = nullptr;
-        w = nullptr;
-        if (want_values && !fuse_gather) {
-            if (rc == MM_OK) rc = mm_buffer_get(ctx, MM_BUF_ENC, (size_t)npoints * 8 * sizeof(i64), (void **)&enc);
-            if (rc == MM_OK) rc = mm_buffer_get(ctx, MM_BUF_W, (size_t)npoints * 8 * sizeof(double), (void **)&w);
+    const bool guessed = may_guess(ctx, call);
+    int64_t result = attempt(ctx, call, feed, guessed);
+    if (guessed && result >= 0) {
+        const bool confirmed = mm_knn_guess_confirmed(ctx);
+        settle_guess(ctx, confirmed);
+        if (!confirmed) {
+            // everything again without the guess -- and without the feed: the device copies of host arrays are in place
+            mm_stage_reset(ctx);
+            result = attempt(ctx, call, nullptr, false);
         }
     }
-    if (rc != MM_OK) { result = rc; goto done; }
-
-    // rows (and values) of failed points must read as zero (the reference's callers zero-initialise,
-    // scripts/cli.py:77-78): the reference-order locate kernel, the only place a point can fail,
-    // writes them (no 1.3 GB memset up front)
-
-    // The search grid is laid out from the bounding box of the centroids, which the host would have to wait for in
-    // mid-call.  When the previous call of this context left the box of a source mesh of the same size (the usual
-    // case: one source mesh, many calls), the grid is GUESSED from that box and the guess is checked against this
-    // call's own box after the synchronisation that ends the call; a wrong
-    // guess runs the call again the ordinary way (twice wrong: no more guessing in this context).  MM_GRID_GUESS=0
-    // switches it off.  A guessed call whose context also still holds the cell_start of that grid's sort
-    // (grid_guess.cells_ok) guesses the per-cell counts as well and sorts the centroids as it computes them
-    // (mm_knn_build_one_pass); other counts are a miss like another box.
-    static const bool guess_on = !(getenv("MM_GRID_GUESS") && atoi(getenv("MM_GRID_GUESS")) == 0);
-    // (MM_KNN_LEVELS is read per call by the ordinary build -- tests switch it inside one process -- and a guessed build
-    // would ignore it)
-    guessed = guess_on && ctx->grid_guess.valid && ctx->grid_guess.nsrc == nelem && ctx->grid_guess.misses < 2 &&
-              !getenv("MM_KNN_LEVELS") && !resident;
-again:
-    ctx->abort_flags = nullptr;
-    if (resident) {
-        index = resident->index;   // centroids and grid are there: straight to the query
-        goto query;
-    }
-    if (feed && (rc = feed_upload(ctx, feed, 0, 1, 0)) != MM_OK) { result = rc; goto done; }
-    if (guessed && ctx->grid_guess.cells_ok) {
-        // the context still holds the cell_start of this grid's last sort: centroids, box and sort in one pass over
-        // the mesh (no centroid array; mm_knn_build_one_pass brackets both stages itself)
-        ++ctx->grid_guess.calls_guessed;
-        ctx->abort_flags = reinterpret_cast<int *>(ctx->d_counters + kMmAbortSlot);
-        rc = mm_knn_build_one_pass(ctx, (const i64 *)conn_d, nodes_d, nelem, box_partial, kBoxBlocks, &index);
-        if (rc != MM_OK) { result = rc; goto done; }
-        goto query;
-    }
-    mm_stage_begin(ctx, MM_STAGE_CENTROID);
-    rc = mm_launch_centroid_bbox(ctx, nelem, (const i64 *)conn_d, nodes_d, cen, box_partial, kBoxBlocks);
-    mm_stage_end(ctx, MM_STAGE_CENTROID);
-    if (rc != MM_OK) { result = rc; goto done; }
-
-    mm_stage_begin(ctx, MM_STAGE_KNN_BUILD);
-    ctx->abort_flags = nullptr;
-    if (guessed) {
-        ++ctx->grid_guess.calls_guessed;
-        // (from here to the end of the call the ring searches and the locate kernels return at once when this call's box
-        // turns out not to be the guessed one: bbox_final_kernel sets the flags on the device)
-        ctx->abort_flags = reinterpret_cast<int *>(ctx->d_counters + kMmAbortSlot);
-        rc = mm_knn_build_guessed(ctx, cen, nelem, box_partial, kBoxBlocks, &index);
-    } else {
-        rc = mm_knn_build_impl(ctx, cen, nelem, 3, &index, true, box_partial, kBoxBlocks);
-    }
-    mm_stage_end(ctx, MM_STAGE_KNN_BUILD);
-    if (rc != MM_OK) { result = rc; goto done; }
-
-query:
-    if (feed && (rc = feed_upload(ctx, feed, 2, 2, 1)) != MM_OK) { result = rc; goto done; }
-    mm_stage_begin(ctx, MM_STAGE_KNN_QUERY);
-    // (the candidate rows come back in the cell-sorted order of the targets whenever the lane kernel serves the
-    // query: the locate stage then walks the targets in that order, tsorted = their records)
-    // (only with lazily evaluated lists: the reference-order kernel then reads the FULL lists, which are rows
-    // by the targets' own indices; with eager lists it reads these rows and needs them in that order)
-    rc = mm_knn_query_sorted_impl(ctx, index, points_d, npoints, kq, nn, kq < k ? &tsorted : nullptr);
-    mm_stage_end(ctx, MM_STAGE_KNN_QUERY);
-    if (rc != MM_OK) { result = rc; goto done; }
-
-    // locate + gather: scripts/cli.py:86-100.  MM_STAGE_GATHER stays empty on this path (mm_gather is
-    // the stand-alone A9 for callers that keep the operator).
-    if (feed && (rc = feed_upload(ctx, feed, 3, 3, 2)) != MM_OK) { result = rc; goto done; }
-    mm_stage_begin(ctx, MM_STAGE_LOCATE);
-    lazy.index = index;
-    lazy.k_full = k;
-    lazy.nn_full = nn_full;
-    rc = mm_launch_locate_hex8(ctx, kq, npoints, nn, /*int32=*/true, (const i64 *)conn_d, nelem, /*exodus=*/1, enc,
-                               nodes_d, w, points_d, ctx->d_counters, /*zero_failed=*/1,
-                               fuse_gather ? fields_d : nullptr, nnodes, ncomp, out_d,
-                               kq < k ? &lazy : nullptr, tsorted);
-    mm_stage_end(ctx, MM_STAGE_LOCATE);
-    if (rc != MM_OK) { result = rc; goto done; }
-    if (want_values && !fuse_gather) {
-        mm_stage_begin(ctx, MM_STAGE_GATHER);
-        rc = mm_launch_gather(ctx, fields_d, nnodes, ncomp, enc, w, npoints, 8, out_d, 1);
-        mm_stage_end(ctx, MM_STAGE_GATHER);
-        if (rc != MM_OK) { result = rc; goto done; }
-    }
-
-    rc = mm_mirror_async(ctx, (long long *)ctx->h_counters, (const long long *)ctx->d_counters, 1);
-    if (rc != MM_OK) { result = rc; goto done; }
-    e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) MM_PIPE_FAIL(MM_ERR_HIP, hipGetErrorString(e));
-    if (guessed && !mm_knn_guess_confirmed(ctx)) {
-        // not this mesh's grid: everything again, the ordinary way (which also leaves the right box for the next call)
-        ctx->grid_guess.valid = false;
-        ctx->grid_guess.cells_ok = false;
-        ++ctx->grid_guess.misses;
-        guessed = false;
-        ctx->abort_flags = nullptr;
-        mm_knn_destroy(nullptr, index);
-        index = nullptr;
-        feed = nullptr;   // (the device copies of host arrays are in place)
-        mm_stage_reset(ctx);
-        goto again;
-    }
-    result = ctx->h_counters[0];
-    if (guessed) ctx->grid_guess.cells_ok = true;   // (confirmed: the buffers hold this grid's complete sort)
-    // (a long-lived context forgives old misses: every 64 calls that confirmed their guess take one back)
-    if (guessed && ctx->grid_guess.misses > 0 && (ctx->grid_guess.calls_guessed & 63) == 0) --ctx->grid_guess.misses;
-
-done:
-    ctx->abort_flags = nullptr;
-    if (result < 0) (void)hipStreamSynchronize(ctx->stream);
-    if (index && !resident) mm_knn_destroy(nullptr, index);  // borrowed arrays stay in the context cache
     return result;
-#undef MM_PIPE_FAIL
 }
 
 // Debugging aid (not part of the drop-in surface): out4 = {a guess is held, calls that had to be run again, calls
@@ -331,12 +401,9 @@ extern "C" int64_t mm_interpolate_hex8_host(mm_context *ctx, const double *nodes
                                             int64_t npoints, const double *fields_h, int64_t ncomp, int64_t k,
                                             double *out_h, int64_t *enc_h, double *w_h)
 {
-    MM_REQUIRE(ctx != nullptr, "ctx is null");
-    MM_REQUIRE(nnodes >= 1 && nelem >= 1, "empty source mesh");
-    MM_REQUIRE(npoints >= 0 && ncomp >= 0, "negative size");
-    MM_REQUIRE(nodes_h && conn_h, "null mesh array");
-    MM_REQUIRE(npoints == 0 || points_h, "null target array");
-    MM_REQUIRE(ncomp == 0 || out_h == nullptr || fields_h, "null field array");
+    int rc = require_sizes(__func__, ctx, nnodes, nelem, npoints, ncomp);
+    if (rc == MM_OK) rc = require_arrays(__func__, npoints, ncomp, nodes_h, conn_h, points_h, fields_h, out_h);
+    if (rc != MM_OK) return rc;
     MM_REQUIRE((enc_h == nullptr) == (w_h == nullptr), "enc and w go together");
     MM_HIP_CHECK(hipSetDevice(ctx->device));
     if (npoints == 0) return 0;
@@ -345,43 +412,39 @@ extern "C" int64_t mm_interpolate_hex8_host(mm_context *ctx, const double *nodes
         for (int q = 0; q < 3; ++q) MM_HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_copy[q], hipEventDisableTiming));
     }
     const bool want_values = out_h && ncomp > 0;
+    const size_t out_bytes = (size_t)npoints * (size_t)ncomp * sizeof(double);
+    const size_t enc_bytes = (size_t)npoints * 8 * sizeof(i64), w_bytes = (size_t)npoints * 8 * sizeof(double);
+    const struct {
+        const void *src;
+        size_t bytes;
+        int slot;
+    } arrays[4] = {{nodes_h, (size_t)nnodes * 3 * sizeof(double), MM_BUF_H_NODES},
+                   {conn_h, (size_t)nelem * 8 * sizeof(int64_t), MM_BUF_H_CONN},
+                   {points_h, (size_t)npoints * 3 * sizeof(double), MM_BUF_H_POINTS},
+                   {fields_h, want_values ? (size_t)ncomp * (size_t)nnodes * sizeof(double) : 0, MM_BUF_H_FIELDS}};
     mm_host_feed feed;
-    feed.src[0] = nodes_h;
-    feed.bytes[0] = (size_t)nnodes * 3 * sizeof(double);
-    feed.src[1] = conn_h;
-    feed.bytes[1] = (size_t)nelem * 8 * sizeof(int64_t);
-    feed.src[2] = points_h;
-    feed.bytes[2] = (size_t)npoints * 3 * sizeof(double);
-    feed.src[3] = fields_h;
-    feed.bytes[3] = want_values ? (size_t)ncomp * (size_t)nnodes * sizeof(double) : 0;
-    static const int slot[4] = {MM_BUF_H_NODES, MM_BUF_H_CONN, MM_BUF_H_POINTS, MM_BUF_H_FIELDS};
-    for (int a = 0; a < 4; ++a) {
-        int rc = mm_buffer_get(ctx, slot[a], feed.bytes[a], &feed.dst[a]);
-        if (rc != MM_OK) return rc;
+    for (int a = 0; a < 4 && rc == MM_OK; ++a) {
+        feed.src[a] = arrays[a].src;
+        feed.bytes[a] = arrays[a].bytes;
+        rc = mm_buffer_get(ctx, arrays[a].slot, arrays[a].bytes, &feed.dst[a]);
     }
     double *out_d = nullptr;
     i64 *enc_d = nullptr;
     double *w_d = nullptr;
-    if (want_values) {
-        int rc = mm_buffer_get(ctx, MM_BUF_H_OUT, (size_t)npoints * (size_t)ncomp * sizeof(double), (void **)&out_d);
-        if (rc != MM_OK) return rc;
-    }
-    if (enc_h) {
-        int rc = mm_buffer_get(ctx, MM_BUF_ENC, (size_t)npoints * 8 * sizeof(i64), (void **)&enc_d);
-        if (rc == MM_OK) rc = mm_buffer_get(ctx, MM_BUF_W, (size_t)npoints * 8 * sizeof(double), (void **)&w_d);
-        if (rc != MM_OK) return rc;
-    }
+    if (rc == MM_OK && want_values) rc = mm_buffer_get(ctx, MM_BUF_H_OUT, out_bytes, (void **)&out_d);
+    if (rc == MM_OK && enc_h) rc = mm_buffer_get(ctx, MM_BUF_ENC, enc_bytes, (void **)&enc_d);
+    if (rc == MM_OK && enc_h) rc = mm_buffer_get(ctx, MM_BUF_W, w_bytes, (void **)&w_d);
+    if (rc != MM_OK) return rc;
     // the uploads overwrite buffers the previous call's kernels may still read
     MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     const int64_t nfailed = interpolate_hex8_impl(ctx, (const double *)feed.dst[0], nnodes, (const int64_t *)feed.dst[1], nelem,
                                                   (const double *)feed.dst[2], npoints, (const double *)feed.dst[3],
                                                   want_values ? ncomp : 0, k, out_d, (int64_t *)enc_d, w_d, &feed);
     if (nfailed < 0) return nfailed;
-    if (want_values)
-        MM_HIP_CHECK(hipMemcpyAsync(out_h, out_d, (size_t)npoints * (size_t)ncomp * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (want_values) MM_HIP_CHECK(hipMemcpyAsync(out_h, out_d, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
     if (enc_h) {
-        MM_HIP_CHECK(hipMemcpyAsync(enc_h, enc_d, (size_t)npoints * 8 * sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
-        MM_HIP_CHECK(hipMemcpyAsync(w_h, w_d, (size_t)npoints * 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        MM_HIP_CHECK(hipMemcpyAsync(enc_h, enc_d, enc_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        MM_HIP_CHECK(hipMemcpyAsync(w_h, w_d, w_bytes, hipMemcpyDeviceToHost, ctx->stream));
     }
     MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return nfailed;
@@ -458,64 +521,105 @@ static int legacy_fail(const char *what)
     return mm_last_status();
 }
 
+// A failed runtime call of the legacy symbol `who`, as its status.
+static int legacy_hip(const char *who, hipError_t e)
+{
+    if (e == hipSuccess) return MM_OK;
+    mm_set_error(MM_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return MM_ERR_HIP;
+}
+
+// A host array into the context's cache slot `slot` (grow-only: no hipMalloc / hipFree per call), on the context's stream.
+static int legacy_upload(mm_context *ctx, const char *who, int slot, const void *src_h, size_t bytes, void **dst_d)
+{
+    const int rc = mm_buffer_get(ctx, slot, bytes, dst_d);
+    if (rc != MM_OK) return rc;
+    return legacy_hip(who, hipMemcpyAsync(*dst_d, src_h, bytes, hipMemcpyHostToDevice, ctx->stream));
+}
+
+// The number of rows an index array on the device implies -- the reference's signatures do not carry the element and
+// node counts --: largest entry + 1.  A negative `what` is refused before any kernel dereferences it.  Synchronises.
+static int legacy_count_rows(mm_context *ctx, const char *who, const char *what, const void *index_d, size_t n, i64 *rows)
+{
+    i64 lo = 0, hi = -1;
+    const int rc = device_minmax(ctx, (const i64 *)index_d, n, &lo, &hi);
+    if (rc != MM_OK) return rc;
+    if (lo < 0) {
+        mm_set_error(MM_ERR_ARG, "%s: negative %s", who, what);
+        return MM_ERR_ARG;
+    }
+    *rows = hi + 1;
+    return MM_OK;
+}
+
+static int legacy_centroid(long long ndim, long long nelem, long long nper, const long long *connectivity, const double *points,
+                           double *centroid_out)
+{
+    static const char *const who = "centroid";
+    if (ndim < 1 || ndim > 3 || nper < 1 || !connectivity || !points || !centroid_out) {
+        mm_set_error(MM_ERR_ARG, "centroid: bad argument");
+        return MM_ERR_ARG;
+    }
+    mm_context *ctx = legacy_context();
+    if (!ctx) return MM_ERR_HIP;   // (mm_context_create has set the status that legacy_fail reports)
+    const size_t nconn = (size_t)nelem * (size_t)nper, out_bytes = (size_t)nelem * ndim * sizeof(double);
+    void *d_conn = nullptr, *d_pts = nullptr, *d_out = nullptr;
+    i64 npoints = 0;   // (the signature does not carry it)
+    int rc = mm_buffer_get(ctx, MM_BUF_L_W, out_bytes, &d_out);
+    if (rc == MM_OK) rc = legacy_upload(ctx, who, MM_BUF_L_CONN, connectivity, nconn * sizeof(i64), &d_conn);
+    if (rc == MM_OK) rc = legacy_count_rows(ctx, who, "node id", d_conn, nconn, &npoints);
+    if (rc == MM_OK) rc = legacy_upload(ctx, who, MM_BUF_L_NODES, points, (size_t)npoints * ndim * sizeof(double), &d_pts);
+    if (rc == MM_OK) rc = mm_centroid(ctx, ndim, nelem, nper, (const int64_t *)d_conn, (const double *)d_pts, (double *)d_out);
+    if (rc == MM_OK) rc = legacy_hip(who, hipMemcpyAsync(centroid_out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (rc == MM_OK) rc = legacy_hip(who, hipStreamSynchronize(ctx->stream));
+    return rc;
+}
+
 extern "C" void centroid(long long ndim, long long nelem, long long nper, long long *connectivity, double *points,
                          double *centroid_out)
 {
     std::lock_guard<std::mutex> lock(g_legacy_mutex);
     mm_clear_status();
     if (nelem <= 0) return;
-    if (ndim < 1 || ndim > 3 || nper < 1 || !connectivity || !points || !centroid_out) {
-        mm_set_error(MM_ERR_ARG, "centroid: bad argument");
-        (void)legacy_fail("centroid");
-        return;
+    if (legacy_centroid(ndim, nelem, nper, connectivity, points, centroid_out) != MM_OK) (void)legacy_fail("centroid");
+}
+
+// The reference's exodus_2_gll flow calls this symbol once per GLL point of the element (scripts/cli.py:183-195: 125
+// calls on the same mesh), and six hipMalloc / hipFree pairs of mesh-sized buffers per call cost more than the kernels:
+// the device copies live in the context's cache.
+static int64_t legacy_locate(long long k, long long npoints, const long long *nn, const long long *connectivity, long long *enc,
+                             const double *nodes, double *weights, const double *points)
+{
+    static const char *const who = "triLinearInterpolator";
+    if (!nn || !connectivity || !enc || !nodes || !weights || !points) {
+        mm_set_error(MM_ERR_ARG, "triLinearInterpolator: null array");
+        return MM_ERR_ARG;
     }
     mm_context *ctx = legacy_context();
-    if (!ctx) {
-        (void)legacy_fail("centroid");
-        return;
-    }
-    const size_t nconn = (size_t)nelem * (size_t)nper;
-    // device copies from the context's grow-only cache (no hipMalloc / hipFree per call)
-    void *d_conn = nullptr, *d_pts = nullptr, *d_out = nullptr;
-    if (mm_buffer_get(ctx, MM_BUF_L_CONN, nconn * sizeof(i64), &d_conn) != MM_OK ||
-        mm_buffer_get(ctx, MM_BUF_L_W, (size_t)nelem * ndim * sizeof(double), &d_out) != MM_OK) {
-        (void)legacy_fail("centroid");
-        return;
-    }
-    hipError_t e = hipMemcpyAsync(d_conn, connectivity, nconn * sizeof(i64), hipMemcpyHostToDevice, ctx->stream);
-    // the number of points the signature does not carry: largest node id + 1, found on the device
-    i64 id_lo = 0, id_hi = -1;
-    if (e == hipSuccess && device_minmax(ctx, (const i64 *)d_conn, nconn, &id_lo, &id_hi) != MM_OK) {
-        (void)legacy_fail("centroid");
-        return;
-    }
-    if (e == hipSuccess && id_lo < 0) {
-        mm_set_error(MM_ERR_ARG, "centroid: negative node id");
-        (void)legacy_fail("centroid");
-        return;
-    }
-    const i64 npoints = id_hi + 1;
-    if (e == hipSuccess && mm_buffer_get(ctx, MM_BUF_L_NODES, (size_t)npoints * ndim * sizeof(double), &d_pts) != MM_OK) {
-        (void)legacy_fail("centroid");
-        return;
-    }
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(d_pts, points, (size_t)npoints * ndim * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) {
-        mm_set_error(MM_ERR_HIP, "centroid: %s", hipGetErrorString(e));
-        (void)legacy_fail("centroid");
-        return;
-    }
-    if (mm_centroid(ctx, ndim, nelem, nper, (const int64_t *)d_conn, (const double *)d_pts, (double *)d_out) != MM_OK) {
-        (void)legacy_fail("centroid");
-        return;
-    }
-    e = hipMemcpyAsync(centroid_out, d_out, (size_t)nelem * ndim * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-        mm_set_error(MM_ERR_HIP, "centroid: %s", hipGetErrorString(e));
-        (void)legacy_fail("centroid");
-    }
+    if (!ctx) return MM_ERR_HIP;   // (mm_context_create has set the status that legacy_fail reports)
+    const size_t nnn = (size_t)npoints * (size_t)k;
+    const size_t enc_bytes = (size_t)npoints * 8 * sizeof(i64), w_bytes = (size_t)npoints * 8 * sizeof(double);
+    void *d_nn = nullptr, *d_conn = nullptr, *d_enc = nullptr, *d_nodes = nullptr, *d_w = nullptr, *d_pts = nullptr;
+    i64 nelem = 0, nnodes = 0;   // (sizes the signature does not carry; nn is counted first: it says how many connectivity rows there are)
+    int rc = mm_buffer_get(ctx, MM_BUF_L_ENC, enc_bytes, &d_enc);
+    if (rc == MM_OK) rc = mm_buffer_get(ctx, MM_BUF_L_W, w_bytes, &d_w);
+    if (rc == MM_OK) rc = legacy_upload(ctx, who, MM_BUF_L_NN, nn, nnn * sizeof(i64), &d_nn);
+    if (rc == MM_OK) rc = legacy_upload(ctx, who, MM_BUF_L_PTS, points, (size_t)npoints * 3 * sizeof(double), &d_pts);
+    if (rc == MM_OK) rc = legacy_count_rows(ctx, who, "element index", d_nn, nnn, &nelem);
+    if (rc == MM_OK) rc = legacy_upload(ctx, who, MM_BUF_L_CONN, connectivity, (size_t)nelem * 8 * sizeof(i64), &d_conn);
+    if (rc == MM_OK) rc = legacy_count_rows(ctx, who, "node id", d_conn, (size_t)nelem * 8, &nnodes);
+    if (rc == MM_OK) rc = legacy_upload(ctx, who, MM_BUF_L_NODES, nodes, (size_t)nnodes * 3 * sizeof(double), &d_nodes);
+    // in-place contract: rows of failed points keep the caller's contents
+    if (rc == MM_OK) rc = legacy_hip(who, hipMemcpyAsync(d_enc, enc, enc_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (rc == MM_OK) rc = legacy_hip(who, hipMemcpyAsync(d_w, weights, w_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (rc != MM_OK) return rc;
+    const int64_t nfailed = mm_locate_hex8(ctx, k, npoints, (const int64_t *)d_nn, (const int64_t *)d_conn, nelem, 0,
+                                           (int64_t *)d_enc, (const double *)d_nodes, (double *)d_w, (const double *)d_pts);
+    if (nfailed < 0) return nfailed;
+    rc = legacy_hip(who, hipMemcpyAsync(enc, d_enc, enc_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (rc == MM_OK) rc = legacy_hip(who, hipMemcpyAsync(weights, d_w, w_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (rc == MM_OK) rc = legacy_hip(who, hipStreamSynchronize(ctx->stream));
+    return rc != MM_OK ? rc : nfailed;
 }
 
 extern "C" long long triLinearInterpolator(long long k, long long npoints, long long *nn, long long *connectivity,
@@ -524,62 +628,6 @@ extern "C" long long triLinearInterpolator(long long k, long long npoints, long 
     std::lock_guard<std::mutex> lock(g_legacy_mutex);
     mm_clear_status();
     if (npoints <= 0 || k <= 0) return 0;  // the reference's loops do nothing
-    if (!nn || !connectivity || !enc || !nodes || !weights || !points) {
-        mm_set_error(MM_ERR_ARG, "triLinearInterpolator: null array");
-        return legacy_fail("triLinearInterpolator");
-    }
-    mm_context *ctx = legacy_context();
-    if (!ctx) return legacy_fail("triLinearInterpolator");
-    // sizes the reference signature does not carry: largest index + 1, found on the DEVICE after the upload
-    const size_t nnn = (size_t)npoints * (size_t)k;
-    // device copies from the context's grow-only cache: the reference's exodus_2_gll flow calls this symbol once per
-    // GLL point of the element (scripts/cli.py:183-195: 125 calls on the same mesh), and six hipMalloc / hipFree pairs
-    // of mesh-sized buffers per call cost more than the kernels
-    void *d_nn = nullptr, *d_conn = nullptr, *d_enc = nullptr, *d_nodes = nullptr, *d_w = nullptr, *d_pts = nullptr;
-    if (mm_buffer_get(ctx, MM_BUF_L_NN, nnn * sizeof(i64), &d_nn) != MM_OK ||
-        mm_buffer_get(ctx, MM_BUF_L_ENC, (size_t)npoints * 8 * sizeof(i64), &d_enc) != MM_OK ||
-        mm_buffer_get(ctx, MM_BUF_L_W, (size_t)npoints * 8 * sizeof(double), &d_w) != MM_OK ||
-        mm_buffer_get(ctx, MM_BUF_L_PTS, (size_t)npoints * 3 * sizeof(double), &d_pts) != MM_OK)
-        return legacy_fail("triLinearInterpolator");
-    hipStream_t s = ctx->stream;
-    hipError_t e = hipMemcpyAsync(d_nn, nn, nnn * sizeof(i64), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_pts, points, (size_t)npoints * 3 * sizeof(double), hipMemcpyHostToDevice, s);
-    i64 lo = 0, hi = -1;
-    if (e == hipSuccess && device_minmax(ctx, (const i64 *)d_nn, nnn, &lo, &hi) != MM_OK) return legacy_fail("triLinearInterpolator");
-    if (e == hipSuccess && lo < 0) {
-        mm_set_error(MM_ERR_ARG, "triLinearInterpolator: negative element index");
-        return legacy_fail("triLinearInterpolator");
-    }
-    const i64 nelem = hi + 1;
-    if (e == hipSuccess && mm_buffer_get(ctx, MM_BUF_L_CONN, (size_t)nelem * 8 * sizeof(i64), &d_conn) != MM_OK)
-        return legacy_fail("triLinearInterpolator");
-    if (e == hipSuccess) e = hipMemcpyAsync(d_conn, connectivity, (size_t)nelem * 8 * sizeof(i64), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && device_minmax(ctx, (const i64 *)d_conn, (size_t)nelem * 8, &lo, &hi) != MM_OK) return legacy_fail("triLinearInterpolator");
-    if (e == hipSuccess && lo < 0) {
-        mm_set_error(MM_ERR_ARG, "triLinearInterpolator: negative node id");
-        return legacy_fail("triLinearInterpolator");
-    }
-    const i64 nnodes = hi + 1;
-    if (e == hipSuccess && mm_buffer_get(ctx, MM_BUF_L_NODES, (size_t)nnodes * 3 * sizeof(double), &d_nodes) != MM_OK)
-        return legacy_fail("triLinearInterpolator");
-    if (e == hipSuccess) e = hipMemcpyAsync(d_nodes, nodes, (size_t)nnodes * 3 * sizeof(double), hipMemcpyHostToDevice, s);
-    // in-place contract: rows of failed points keep the caller's contents
-    if (e == hipSuccess) e = hipMemcpyAsync(d_enc, enc, (size_t)npoints * 8 * sizeof(i64), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_w, weights, (size_t)npoints * 8 * sizeof(double), hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) {
-        mm_set_error(MM_ERR_HIP, "triLinearInterpolator: %s", hipGetErrorString(e));
-        return legacy_fail("triLinearInterpolator");
-    }
-    const int64_t nfailed = mm_locate_hex8(ctx, k, npoints, (const int64_t *)d_nn, (const int64_t *)d_conn, nelem, 0,
-                                           (int64_t *)d_enc, (const double *)d_nodes, (double *)d_w,
-                                           (const double *)d_pts);
-    if (nfailed < 0) return legacy_fail("triLinearInterpolator");
-    e = hipMemcpyAsync(enc, d_enc, (size_t)npoints * 8 * sizeof(i64), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(weights, d_w, (size_t)npoints * 8 * sizeof(double), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-        mm_set_error(MM_ERR_HIP, "triLinearInterpolator: %s", hipGetErrorString(e));
-        return legacy_fail("triLinearInterpolator");
-    }
-    return nfailed;
+    const int64_t nfailed = legacy_locate(k, npoints, nn, connectivity, enc, nodes, weights, points);
+    return nfailed < 0 ? legacy_fail("triLinearInterpolator") : nfailed;
 }

@@ -227,6 +227,24 @@ def test_long_on_demand_lists_and_their_second_pass(ctx, k):
     assert st["reference_order"] >= D.LONG_LIST_MIN and st["second_pass"] > 0
 
 
+def test_long_on_demand_lists_second_pass_tol_against_exact(ctx, ctx_tol):
+    # the second launch of the pass kernel (the rest of a long list's candidates) in MM_FP_TOL: node ids and the failed
+    # count as in MM_FP_EXACT, weights and values within tests/test_fp_tol_gpu.py's bound
+    k = min(D.LONG_KS)
+    pa, ca, pb, fields, _ = D.graded_mesh()
+    got = {}
+    for mode, c in (("exact", ctx), ("tol", ctx_tol)):
+        vals, enc, w, nf = c.interpolate_hex8(pa, ca, pb, fields, nelem_to_search=k, want_operator=True)
+        got[mode] = (vals.numpy(), enc.numpy(), w.numpy(), nf, c.last_locate_stats())
+    (vals_e, enc_e, w_e, nf_e, st_e), (vals_t, enc_t, w_t, nf_t, st_t) = got["exact"], got["tol"]
+    dw, dv = np.abs(w_t - w_e).max(), np.abs(vals_t - vals_e).max()
+    print(f"k = {k}: lists {st_t}, max |dw| {dw:.3e}, max |dv| {dv:.3e}, failed {nf_t}")
+    assert st_t["reference_order"] >= D.LONG_LIST_MIN and st_t["second_pass"] > 0
+    assert {key: st_t[key] for key in ("reference_order", "second_pass")} == {key: st_e[key] for key in ("reference_order", "second_pass")}
+    assert nf_t == nf_e and np.array_equal(enc_t, enc_e)
+    assert close_tol(w_t, w_e, 1e-12) and close_tol(vals_t, vals_e, 1e-12 * 8 * np.abs(fields).max())
+
+
 def outside_stats_and_rows(ctx, nfar, k, tol=None):
     pa, ca, pb, fields, nn = D.outside_mesh(nfar)
     lists = []

@@ -164,3 +164,92 @@ def test_a_miss_at_a_realistic_size_is_cheap():
             fresh.close()
     finally:
         c.close()
+
+
+def _small_case():
+    """Mesh A (3375 elements, 5000 targets, four field components) and the same connectivity scaled and shifted."""
+    pa, ca = synth.hex_mesh(16, seed=1, jitter=0.3)
+    pb = np.random.default_rng(5).uniform(0.05, 0.95, size=(5000, 3))
+    shift = np.array([3.0, -1.0, 0.25])
+    pa2, pb2 = pa * 1.5 + shift, pb * 1.5 + shift
+
+    def four(p):
+        f = synth.vector_field(p)
+        return np.ascontiguousarray(np.concatenate([f, -f[:1] * 0.5]))
+
+    return (pa, ca, pb, four(pa)), (pa2, ca, pb2, four(pa2))
+
+
+def _device_call(c, mesh, ncomp, want_operator):
+    pa, ca, pb, f = mesh
+    out = c.interpolate_hex8(pa, ca, pb, np.ascontiguousarray(f[:ncomp]), nelem_to_search=20, want_operator=want_operator)
+    return [x.numpy() for x in out[:-1]] + [out[-1]]
+
+
+def _fresh_call(mesh, ncomp, want_operator):
+    from multimesh_amd.device import Context
+
+    c = Context(0)
+    try:
+        return _device_call(c, mesh, ncomp, want_operator)
+    finally:
+        c.close()
+
+
+def _same(a, b):
+    return len(a) == len(b) and a[-1] == b[-1] and all(np.array_equal(x, y) for x, y in zip(a[:-1], b[:-1]))
+
+
+@pytest.mark.parametrize("ncomp,want_operator", [(4, False), (1, True)])
+def test_missed_guess_through_the_host_entry(ncomp, want_operator):
+    # The call that is run again after a wrong guess gets no host feed (the device copies are in place).  Four components
+    # without the operator: more than the locate kernels gather themselves (kFuseGatherMaxComp = 3), so the rows live in
+    # the context's private buffers and the separate gather runs after the second attempt; one component with the
+    # operator: the rows are the caller's.
+    from multimesh_amd.device import Context
+
+    mesh_a, mesh_b = _small_case()
+    ref_a, ref_b = _fresh_call(mesh_a, ncomp, want_operator), _fresh_call(mesh_b, ncomp, want_operator)
+    c = Context(0)
+    try:
+        def host(mesh):
+            pa, ca, pb, f = mesh
+            out = c.interpolate_hex8_host(pa, ca, pb, np.ascontiguousarray(f[:ncomp]), nelem_to_search=20,
+                                          want_operator=want_operator)
+            return [np.asarray(x) for x in out[:-1]] + [out[-1]]
+
+        assert _same(host(mesh_a), ref_a)
+        assert _guess_state(c) == {"valid": 1, "misses": 0, "guessed": 0, "nsrc": len(mesh_a[1])}
+        assert _same(host(mesh_a), ref_a)                 # guessed, confirmed
+        s = _guess_state(c)
+        assert s["guessed"] == 1 and s["misses"] == 0 and s["valid"] == 1
+        assert _same(host(mesh_b), ref_b)                 # guessed from mesh A's box: wrong, run again without the feed
+        s = _guess_state(c)
+        assert s["guessed"] == 2 and s["misses"] == 1 and s["valid"] == 1   # (the second run left mesh B's box)
+    finally:
+        c.close()
+
+
+def test_resident_source_between_guessed_calls():
+    # A call on a resident source neither guesses nor disturbs the guess the context holds: the call after it is guessed
+    # like the one before it.
+    from multimesh_amd.device import Context
+
+    mesh_a, _ = _small_case()
+    pa, ca, pb, f = mesh_a
+    f1 = np.ascontiguousarray(f[:1])
+    ref = _fresh_call(mesh_a, 1, True)
+    c = Context(0)
+    try:
+        assert _same(_device_call(c, mesh_a, 1, True), ref)
+        src = c.source(pa, ca)
+        assert _same(_device_call(c, mesh_a, 1, True), ref)          # guessed, confirmed
+        assert _guess_state(c) == {"valid": 1, "misses": 0, "guessed": 1, "nsrc": len(ca)}
+        out = src.interpolate(pb, f1, nelem_to_search=20, want_operator=True)
+        assert _same([x.numpy() for x in out[:-1]] + [out[-1]], ref)
+        assert _guess_state(c) == {"valid": 1, "misses": 0, "guessed": 1, "nsrc": len(ca)}
+        assert _same(_device_call(c, mesh_a, 1, True), ref)          # guessed, confirmed
+        assert _guess_state(c) == {"valid": 1, "misses": 0, "guessed": 2, "nsrc": len(ca)}
+        src.free()
+    finally:
+        c.close()

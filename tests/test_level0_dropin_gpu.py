@@ -109,3 +109,51 @@ def test_125_consecutive_calls_like_exodus_2_gll(golden, capsys):
     with capsys.disabled():
         print(f"\n[level 0] 124 warm triLinearInterpolator calls (68,921 nodes, 20,000 points): {per_call_ms:.2f} ms per call")
     assert np.abs(first[1].sum(axis=1) - 1.0).max() < 1e-12
+
+
+def test_bad_indices_are_refused_and_the_next_call_is_served():
+    """A negative element index or node id is found by the reduction over the uploaded array, before any kernel
+    dereferences it: negative status, the caller's arrays untouched -- and the process-wide context with its buffer
+    cache serves the next call as if nothing had happened."""
+    from multimesh_amd import synth
+    from multimesh_amd.device import Context
+    from scipy.spatial import cKDTree
+
+    lib = reference_style_lib()
+    lib.mm_last_error.restype = C.c_char_p
+    lib.mm_last_status.restype = C.c_int
+    pa, ca = synth.hex_mesh(6, seed=1)
+    conn = np.ascontiguousarray(synth.reorder_hex8(ca))
+    pts = np.ascontiguousarray(np.random.default_rng(5).uniform(0.05, 0.95, size=(200, 3)))
+    with Context(0) as c:
+        cen_ref = c.centroid(ca, pa).numpy()
+        _, nn = cKDTree(cen_ref, balanced_tree=False).query(pts, k=20)
+        nn = np.ascontiguousarray(nn)
+        enc_ref, w_ref, nf_ref = c.locate_hex8(nn, conn, pa, pts)
+        enc_ref, w_ref = enc_ref.numpy(), w_ref.numpy()
+
+    def good_locate():
+        enc, w = np.zeros((len(pts), 8), dtype=np.int64), np.zeros((len(pts), 8))
+        assert lib.triLinearInterpolator(20, len(pts), nn, conn, enc, pa, w, pts) == nf_ref
+        assert np.array_equal(enc, enc_ref) and np.array_equal(w, w_ref)
+
+    good_locate()
+    nn_bad, conn_bad = nn.copy(), conn.copy()
+    nn_bad[17, 3] = -1
+    conn_bad[nn[0, 0], 2] = -1
+    for nn_x, conn_x, message in ((nn_bad, conn, b"negative element index"), (nn, conn_bad, b"negative node id")):
+        enc, w = np.full((len(pts), 8), 7, dtype=np.int64), np.full((len(pts), 8), 0.25)
+        status = lib.triLinearInterpolator(20, len(pts), nn_x, conn_x, enc, pa, w, pts)
+        assert status < 0 and status == lib.mm_last_status()
+        assert message in lib.mm_last_error()
+        assert (enc == 7).all() and (w == 0.25).all()
+        good_locate()
+
+    ca_bad = ca.copy()
+    ca_bad[40, 5] = -1
+    cen = np.full((len(ca), 3), -3.0)
+    lib.centroid(3, len(ca), 8, ca_bad, pa, cen)
+    assert lib.mm_last_status() < 0 and b"negative node id" in lib.mm_last_error()
+    assert (cen == -3.0).all()
+    lib.centroid(3, len(ca), 8, ca, pa, cen)
+    assert lib.mm_last_status() == 0 and np.array_equal(cen, cen_ref)

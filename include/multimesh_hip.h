@@ -399,6 +399,59 @@ int mm_gll_tensor_apply(mm_context *ctx, int dim, int order_in, int order_out, c
 int mm_element_deviation(mm_context *ctx, int dim, int64_t npts, const double *a_d, const double *b_d, int64_t nelem,
                          double *deviation_d, double *edge_d);
 
+/* RADIAL 1-D PROFILES: the radial bin of every point, a mass-weighted sum per bin in one pass, and a 1-D table (radius ->
+ * value, with discontinuities) evaluated on the nodes.  The reference has no counterpart.
+ *
+ * mm_radial_bins: points_d f64[n][3]; edges_d f64[nbins + 1], strictly ascending and finite (checked on the device:
+ * MM_ERR_ARG otherwise, nothing is written); bin_d int32[n]; radius_out_d f64[n] or NULL.
+ *   r = sqrt((x*x + y*y) + z*z)            (every product and sum rounded on its own: bit for bit NumPy)
+ *   b = upper_bound(edges, r) - 1, so that edges[b] <= r < edges[b + 1]; r == edges[nbins] belongs to bin nbins - 1;
+ *   b = -1 for r < edges[0], r > edges[nbins] and a NaN r.
+ * Returns the number of -1 entries (an integer sum, the same on every run) or a negative MM_ERR_*: MM_ERR_ARG for a null
+ * ctx or array, n < 0 or nbins outside [1, 2^20].  n == 0 is valid.  Synchronises. */
+int64_t mm_radial_bins(mm_context *ctx, const double *points_d, int64_t n, const double *edges_d, int64_t nbins,
+                       int32_t *bin_d, double *radius_out_d);
+
+/* out_d[c][b] = sum over the i with bin_d[i] == b of mass_d[i] * fields_d[c][i], for all bins in ONE pass over the arrays
+ * per component.  mass_d f64[n]; fields_d f64[ncomp][n], or NULL with ncomp == 1: the sum of the mass (the volume per bin);
+ * bin_d int32[n] (entries < 0 or >= nbins belong to no bin); square 0 / 1; out_d f64[ncomp][nbins]; count_d int64[nbins] or
+ * NULL: the number of members of every bin (integer atomics).  Deterministic: no float atomics, and the order of every sum
+ * is fixed by this definition, not by a launch shape.  For bin b,
+ *   t[i] = mass[i] * f[i]   (square: (mass[i] * f[i]) * f[i];  without fields: mass[i]), every product rounded on its own,
+ *          where bin[i] == b, and +0.0 elsewhere WHATEVER f[i] is (a NaN outside a bin does not reach it),
+ * padded with +0.0 to whole chunks of 4096 values, then mm_weighted_sum's rule with every lane sum STARTING FROM +0.0:
+ *   in a chunk, lane l of 256 computes ((((+0.0 + t[l]) + t[l + 256]) + ...) + t[l + 3840]);
+ *   the 256 lane sums are halved eight times, s[l] = s[l] + s[l + h] for h = 128, 64, ... 1; s[0] is the chunk's sum;
+ *   the chunk sums of bin b are summed by the same rule (as t) until one value is left.
+ * A partial sum that starts from +0.0 is never -0.0, so adding +0.0 never changes it: skipping the non-members is bit for
+ * bit this statement.  No result is -0.0; an empty bin is +0.0.  n == 0 gives zeros.
+ * Scratch: 8 B * nbins * ceil(n / 4096) for one component at a time (the components are summed one after the other).
+ * MM_ERR_ARG (nothing is written) for a null ctx or array, a negative size, nbins outside [1, 2^20], ncomp >= 65536,
+ * n >= 2^42, fields_d NULL with ncomp > 1; MM_ERR_UNSUPPORTED when nbins * ceil(n / 4096^2) reaches 2^31.  ncomp == 0 is
+ * valid (only count_d is filled).  Not synchronising. */
+int mm_binned_weighted_sum(mm_context *ctx, const double *mass_d, const double *fields_d, const int32_t *bin_d, int64_t n,
+                           int64_t ncomp, int64_t nbins, int square, double *out_d, int64_t *count_d);
+
+/* A 1-D table on the nodes, optionally fused with the perturbation arithmetic.  points_d f64[ngroups][P][3], P nodes per
+ * element, 1 <= P <= 256 (P = 1: a point cloud, hex8 nodes); radius_d f64[m] ascending, a REPEATED radius marks a
+ * discontinuity; values_d f64[ncomp][m]; in_d f64[ncomp][ngroups * P] (modes 1-4, else ignored); out_d of that shape, may
+ * be in_d.  The layers are the maximal strictly ascending runs of radius_d; a run of length 1 (m == 1, three equal radii),
+ * a descending step or a non-finite radius is refused with MM_ERR_ARG (the table is read back and checked on the host,
+ * nothing is written).
+ *   the layer of an element, decided once by its centre: c = (((X[0] + X[1]) + ...) + X[P-1]) / P per coordinate,
+ *     rc = sqrt((cx*cx + cy*cy) + cz*cz); the layer with r_lo <= rc < r_hi; below the first layer the first, above the last
+ *     the last; a NaN rc makes every output of the element NaN.  A node on a discontinuity therefore takes the side of its
+ *     own element however its radius rounds; with P = 1 a point on a discontinuity takes the upper side.
+ *   the value at a node, within the layer's rows [a, b]: r = sqrt((x*x + y*y) + z*z), r' = min(max(r, R[a]), R[b]),
+ *     i = clip(upper_bound(R[a..b], r') - 1, a, b - 1), t = (r' - R[i]) / (R[i+1] - R[i]),
+ *     ref = (1.0 - t) * V[i] + t * V[i+1], every operation rounded on its own.
+ *   mode 0: out = ref   1: out = in - ref   2: out = (in - ref) / ref   3: out = in + ref   4: out = ref + in * ref
+ * The table is held in LDS when m * (1 + ncomp) <= 4096 doubles, else read from global memory.  MM_ERR_ARG also for a null
+ * ctx or array, a negative size, P outside [1, 256], an unknown mode, in_d NULL in modes 1-4, ncomp >= 65536.
+ * ngroups == 0 and ncomp == 0 are valid.  Synchronises once before its kernel is queued (the table check), not after. */
+int mm_radial_model_apply(mm_context *ctx, const double *points_d, int64_t ngroups, int64_t P, const double *radius_d,
+                          const double *values_d, int64_t m, int64_t ncomp, int mode, const double *in_d, double *out_d);
+
 /* The streaming kernels of a preconditioned conjugate-gradient loop over ncomp independent systems of n unknowns each
  * (vectors f64[ncomp][n]), whose scalars never leave the device.  state_d f64[ncomp][8] holds, per system, the slots below:
  * the dots are written into MM_PCG_RZ, MM_PCG_PAP and MM_PCG_BB by mm_weighted_sum (one call per system with ncomp = 1).

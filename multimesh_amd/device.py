@@ -654,6 +654,95 @@ class Context:
         check(self.lib.mm_divide_rows(self.handle, a.ptr, d.ptr, d.size, a.size // max(d.size, 1), out.ptr), "mm_divide_rows")
         return out
 
+    # ---- radial 1-D profiles: bins, binned sums, a 1-D table on the nodes -----------------------------
+    def radial_bins(self, points, edges, want_radius=False):
+        """The radial bin of every point (``mm_radial_bins``): points f64[..., 3] (N points, read flat), edges
+        f64[nbins + 1] strictly ascending and finite (``ValueError`` otherwise).  ``edges[b] <= |p| < edges[b + 1]``, the
+        last edge belongs to the last bin, -1 outside the edges and for a NaN radius.  Returns (bin int32[N] on the device,
+        number of -1 entries) or, with ``want_radius``, (bin, noutside, radius f64[N])."""
+        pts, n = self._points3(points)
+        e = self.asdevice(edges, np.float64)
+        if len(e.shape) != 1 or e.shape[0] < 2:
+            raise ValueError("edges must be 1-D with at least two entries")
+        bins = self.empty((n,), np.int32)
+        radius = self.empty((n,), np.float64) if want_radius else None
+        rc = self.lib.mm_radial_bins(self.handle, pts.ptr, n, e.ptr, e.shape[0] - 1, bins.ptr, radius.ptr if radius else None)
+        if rc == -1:   # MM_ERR_ARG
+            raise ValueError(self.lib.mm_last_error().decode())
+        check(rc, "mm_radial_bins")
+        return (bins, int(rc), radius) if want_radius else (bins, int(rc))
+
+    def binned_weighted_sum(self, mass, bins, nbins, fields=None, square=False, want_count=False):
+        """``out[c][b] = sum over bins[i] == b of mass[i] * fields[c][i]`` (``square``: ``(mass * f) * f``) for all bins in
+        one pass per component (``mm_binned_weighted_sum``): deterministic, in the fixed order include/multimesh_hip.h
+        states.  mass f64[...] (any shape, N values), bins int32[N] (entries outside [0, nbins) belong to no bin), fields
+        f64[C, ...] over the shape of mass, the shape of mass (one field), or None: the sum of the mass per bin.  Returns
+        f64[C, nbins] (NumPy) or, with ``want_count``, (sums, count int64[nbins])."""
+        m = self.asdevice(mass, np.float64)
+        b = self.asdevice(bins, np.int32)
+        if b.size != m.size:
+            raise ValueError("bins must hold one entry per value of mass")
+        nbins = int(nbins)
+        if nbins < 1:
+            raise ValueError("nbins must be at least 1")
+        ncomp, f = 1, None
+        if fields is not None:
+            f = self.asdevice(fields, np.float64)
+            if f.shape == m.shape:
+                ncomp = 1
+            elif f.shape[1:] == m.shape:
+                ncomp = f.shape[0]
+            else:
+                raise ValueError("fields must be [C, ...] over the shape of mass, or the shape of mass")
+        out = self.empty((ncomp, nbins), np.float64)
+        count = self.empty((nbins,), np.int64) if want_count else None
+        check(self.lib.mm_binned_weighted_sum(self.handle, m.ptr, f.ptr if f else None, b.ptr, m.size, ncomp, nbins,
+                                              1 if square else 0, out.ptr, count.ptr if count else None),
+              "mm_binned_weighted_sum")
+        return (out.numpy(), count.numpy()) if want_count else out.numpy()
+
+    def radial_model_apply(self, points, radius, values, mode=0, values_in=None, out=None):
+        """A 1-D table evaluated on the nodes (``mm_radial_model_apply``): points f64[G, P, 3] (P nodes per element, at
+        most 256; the element's centre picks the layer) or f64[N, 3] (P = 1), radius f64[m] ascending with a repeated
+        radius at every discontinuity, values f64[C, m] (or f64[m]).  ``mode`` 0: the table's value ``ref``; with
+        ``values_in`` f64[C, G * P] (any shape of that size): 1 ``in - ref``, 2 ``(in - ref) / ref``, 3 ``in + ref``,
+        4 ``ref + in * ref``.  ``out`` may be ``values_in``.  Returns f64[C, G, P] (or [C, N]) on the device.  A table
+        that is not a set of layers raises ``ValueError``."""
+        pts = self.asdevice(points, np.float64)
+        if len(pts.shape) not in (2, 3) or pts.shape[-1] != 3:
+            raise ValueError("points must be [G, P, 3] or [N, 3]")
+        ngroups, P = (pts.shape[0], pts.shape[1]) if len(pts.shape) == 3 else (pts.shape[0], 1)
+        if not 1 <= P <= 256:
+            raise ValueError("P must lie in [1, 256]")
+        r = self.asdevice(radius, np.float64)
+        v = self.asdevice(values, np.float64)
+        if len(r.shape) != 1 or v.shape[-1:] != r.shape or len(v.shape) > 2:
+            raise ValueError("radius must be [m] and values [C, m] (or [m])")
+        ncomp = v.shape[0] if len(v.shape) == 2 else 1
+        if mode not in (0, 1, 2, 3, 4):
+            raise ValueError("mode must be 0 .. 4")
+        n = ngroups * P
+        src = None
+        if mode != 0:
+            if values_in is None:
+                raise ValueError("modes 1 to 4 need values_in")
+            src = self.asdevice(values_in, np.float64)
+            if src.size != ncomp * n:
+                raise ValueError("values_in must hold one value per component and node")
+        shape = (ncomp,) + tuple(pts.shape[:-1])
+        if out is None:
+            out = self.empty(shape, np.float64)
+        else:
+            out = self.asdevice(out, np.float64)
+            if out.size != ncomp * n:
+                raise ValueError("out must hold one value per component and node")
+        rc = self.lib.mm_radial_model_apply(self.handle, pts.ptr, ngroups, P, r.ptr, v.ptr, r.shape[0], ncomp, int(mode),
+                                            src.ptr if src else None, out.ptr)
+        if rc == -1:   # MM_ERR_ARG
+            raise ValueError(self.lib.mm_last_error().decode())
+        check(rc, "mm_radial_model_apply")
+        return out
+
     # ---- diffusion: the stiffness operator and the smoothing it gives -------------------------------
     def diffusion(self, shape_order, gll_points, kappa_h=1.0, kappa_r=None):
         """A :class:`Diffusion` over gll_points f64[E, (order+1)^dim, dim], orders 1, 2, 4: ``apply(u)`` is the bare

@@ -54,6 +54,7 @@ EXPORTED_SYMBOLS = (
     "mm_gll_diffusion_apply", "mm_pcg_combine", "mm_pcg_scalars", "mm_pcg_direction", "mm_pcg_advance",
     "mm_gll_gradient",
     "mm_gll_tensor_apply", "mm_element_deviation",
+    "mm_radial_bins", "mm_binned_weighted_sum", "mm_radial_model_apply",
 )
 
 
@@ -188,6 +189,12 @@ def load_lib():
     lib.mm_weighted_sum.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, vp]
     lib.mm_divide_rows.restype = C.c_int
     lib.mm_divide_rows.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, vp]
+    lib.mm_radial_bins.restype = C.c_int64
+    lib.mm_radial_bins.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, vp, vp]
+    lib.mm_binned_weighted_sum.restype = C.c_int
+    lib.mm_binned_weighted_sum.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, vp, vp]
+    lib.mm_radial_model_apply.restype = C.c_int
+    lib.mm_radial_model_apply.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int, vp, vp]
     lib.mm_gll_diffusion_apply.restype = C.c_int
     lib.mm_gll_diffusion_apply.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int64, vp, vp, vp, C.c_int64, C.c_double, vp, C.c_int,
                                            C.c_double, vp, vp]

@@ -337,7 +337,7 @@ def map_to_ellipse(base_mesh, mesh, nelem_to_search=25, tolerance=1.05, context=
     ratio = ctx.sphere_ratio(gp_d, z_en, r_ref=R_EARTH)
     base_sphere = ctx.map_to_sphere(gp_d, z_en, r_ref=R_EARTH)
     targets = _sphere_mapped(mesh, ctx)
-    flat = DeviceArray(ctx, targets.ptr, (targets.size // 3, 3), np.float64, owner=False, keepalive=targets)
+    flat = targets.reshape(targets.size // 3, 3)
     values, missing = ctx.interpolate_gll(order, base_sphere, flat, ratio, nelem_to_search=nelem_to_search,
                                           tolerance=tolerance)
     if missing:
@@ -482,7 +482,7 @@ def _hex8_mass(mesh: HexMesh, ctx):
         lumped = op.apply(np.ones(mesh.nelem))                                       # [1, npoint]
     finally:
         op.free()
-    return DeviceArray(ctx, lumped.ptr, (mesh.npoint,), np.float64, owner=False, keepalive=lumped)
+    return lumped.reshape(mesh.npoint)
 
 
 def hex8_mass_matrix(mesh: HexMesh, context=None):
@@ -528,9 +528,8 @@ def _assembler(ctx, gll_points):
     """(transposed scatter-sum operator, inverse int64[N, 1]) over the unique nodes of element-nodal points."""
     pts = ctx.asdevice(np.ascontiguousarray(gll_points, dtype=np.float64), np.float64)
     n = pts.size // pts.shape[-1]
-    flat = DeviceArray(ctx, pts.ptr, (n, pts.shape[-1]), np.float64, owner=False, keepalive=pts)
-    uniq, inv = ctx.unique_points(flat, ordered=False)
-    inverse = DeviceArray(ctx, inv.ptr, (n, 1), np.int64, owner=False, keepalive=inv)
+    uniq, inv = ctx.unique_points(pts.reshape(n, pts.shape[-1]), ordered=False)
+    inverse = inv.reshape(n, 1)
     return ctx.transpose_nodes(inverse, np.ones((n, 1)), uniq.shape[0]), inverse
 
 
@@ -590,11 +589,8 @@ def apply_gll_operator_adjoint(elements, coeffs, values, target_mass, source_mes
         n = pts.shape[0] * pts.shape[1]
         sum_op, inverse = _assembler(ctx, pts)
         try:
-            rhs = _assemble(ctx, DeviceArray(ctx, rhs.ptr, (rhs.shape[0], n), np.float64, owner=False, keepalive=rhs),
-                            sum_op, inverse)
-            mass = _assemble(ctx, DeviceArray(ctx, mass.ptr, (1, n), np.float64, owner=False, keepalive=mass), sum_op,
-                             inverse)
-            mass = DeviceArray(ctx, mass.ptr, (n,), np.float64, owner=False, keepalive=mass)
+            rhs = _assemble(ctx, rhs.reshape(rhs.shape[0], n), sum_op, inverse)
+            mass = _assemble(ctx, mass.reshape(1, n), sum_op, inverse).reshape(n)
         finally:
             sum_op.free()
     return ctx.divide_rows(rhs, mass, out=rhs).numpy().reshape((-1,) + pts.shape[:2])
@@ -767,8 +763,8 @@ def _gradient(mesh, params, assemble, ctx, wanted):
     if assemble:
         op = ctx.diffusion(order, gp)                                             # (its smooth(steps=0) IS the node average)
         try:
-            planes = tuple(op.smooth(DeviceArray(ctx, v.ptr, (int(np.prod(v.shape[:-2])),) + pts.shape[:2], np.float64,
-                                                 owner=False, keepalive=v), steps=0) if v.size else v for v in planes)
+            planes = tuple(op.smooth(v.reshape(int(np.prod(v.shape[:-2])), *pts.shape[:2]), steps=0) if v.size else v
+                           for v in planes)
         finally:
             op.free()
     return pts, u.shape[0], [v.numpy() for v in planes]
@@ -2005,7 +2001,7 @@ def radial_profile(mesh, params=None, edges=None, nbins=None, context=None):
     mean, rms = {}, {}
     if names:
         f = ctx.to_device(fields.reshape(len(names), -1))
-        m_flat = DeviceArray(ctx, mass.ptr, (mass.size,), np.float64, owner=False, keepalive=mass)
+        m_flat = mass.reshape(mass.size)
         s1 = ctx.binned_weighted_sum(m_flat, bins, nb, f)
         s2 = ctx.binned_weighted_sum(m_flat, bins, nb, f, square=True)
         with np.errstate(divide="ignore", invalid="ignore"):

@@ -16,6 +16,7 @@ import numpy as np
 
 from . import helpers as H
 from .helpers import MM_FP_EXACT, MM_FP_TOL, MM_KNN_MAX_K, STAGES, MultiMeshHipError, check, load_lib
+from .synth import gll_derivative_matrix, gll_order_table, gll_weights_1d   # (ValueError for an order without tables)
 
 # MM_KNN_RAN_* in bit order
 KNN_KERNELS = ("lane", "strip", "cell", "list", "generic", "levels", "tree", "one_pass")
@@ -23,7 +24,61 @@ KNN_KERNELS = ("lane", "strip", "cell", "list", "generic", "levels", "tree", "on
 _NP2ITEM = {np.dtype(np.float64): 8, np.dtype(np.int64): 8, np.dtype(np.int32): 4, np.dtype(np.uint8): 1}
 
 
-class DeviceArray:
+class _Released:
+    """Whatever holds device memory or a library handle is released when it is collected: ``__del__`` runs ``free()`` (or
+    the method ``_release`` names), which may have run before, and never raises."""
+    _release = "free"
+
+    def __del__(self):
+        try:
+            getattr(self, self._release)()
+        except Exception:
+            pass
+
+
+class _Handle(_Released):
+    """A library handle on a context; the subclass names the symbol that destroys it.  After ``free()`` it is None."""
+    _destroy = None
+
+    def free(self):
+        if self.handle and self.ctx.handle:
+            getattr(self.ctx.lib, self._destroy)(self.ctx.handle, self.handle)
+        self.handle = None
+
+
+def _components(x, ndim):
+    """A single component given without its leading axis ([M], [E, P], [D, LA, LO]: ``ndim`` axes) as [1, ...]."""
+    return x.reshape(1, *x.shape) if len(x.shape) == ndim else x
+
+
+def _element_nodal(ctx, values, nelem, P, name):
+    """``values`` as f64[C, E, P] on the device over the nodes of a GLL mesh."""
+    v = _components(ctx.asdevice(values, np.float64), 2)
+    if len(v.shape) != 3 or v.shape[1:] != (nelem, P):
+        raise ValueError(f"{name} must be [C, E, P] (or [E, P]) over gll_points [E, P, dim]")
+    return v
+
+
+def _hex8_arrays(ctx, nnodes, points, fields, want_operator, out):
+    """What interpolate_hex8 and Source.interpolate hand to their call besides the mesh: (points, fields f64[C, M], values
+    f64[N, C], enc, weights), the last two None unless the operator is wanted.  ``out`` is taken at the caller's word."""
+    pts = ctx.asdevice(points, np.float64)
+    f = _components(ctx.asdevice(fields, np.float64), 1)
+    if f.shape[1] != nnodes:
+        raise ValueError("fields must be [C, number of nodes]")
+    n = pts.shape[0]
+    out = ctx._out(out, (n, f.shape[0]))
+    enc = ctx.empty((n, 8), np.int64) if want_operator else None
+    w = ctx.empty((n, 8), np.float64) if want_operator else None
+    return pts, f, out, enc, w
+
+
+def _with_operator(want_operator, values, index, weights, count):
+    """(values, count) or, with the operator, (values, index, weights, count)."""
+    return (values, index, weights, int(count)) if want_operator else (values, int(count))
+
+
+class DeviceArray(_Released):
     """A C-contiguous array resident in HBM, owned (or merely viewed) by a Context."""
 
     def __init__(self, ctx, ptr, shape, dtype, owner=True, keepalive=None):
@@ -57,21 +112,23 @@ class DeviceArray:
         return DeviceArray(self.ctx, self.ptr + start * row_bytes, (stop - start,) + self.shape[1:], self.dtype,
                            owner=False, keepalive=self)
 
+    def reshape(self, *shape):
+        """A non-owning view of the same bytes in another shape of the same size; it keeps this array alive."""
+        view = DeviceArray(self.ctx, self.ptr, shape, self.dtype, owner=False, keepalive=self)
+        if view.size != self.size:
+            raise ValueError(f"cannot reshape {self.shape} to {view.shape}")
+        return view
+
     def free(self):
         if self._owner and self.ptr and self.ctx.handle:
             self.ctx.lib.mm_device_free(self.ctx.handle, self.ptr)
         self.ptr = 0
         self._owner = False
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
-
-class KnnIndex:
+class KnnIndex(_Handle):
     """Device-resident search structure over source points (the cKDTree stand-in)."""
+    _destroy = "mm_knn_destroy"
 
     def __init__(self, ctx, handle, nsrc, ndim, keepalive):
         self.ctx, self.handle, self.nsrc, self.ndim = ctx, handle, nsrc, ndim
@@ -92,21 +149,11 @@ class KnnIndex:
               "mm_knn_query")
         return (idx, dist) if want_dist else idx
 
-    def free(self):
-        if self.handle and self.ctx.handle:
-            self.ctx.lib.mm_knn_destroy(self.ctx.handle, self.handle)
-        self.handle = None
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class Source:
+class Source(_Handle):
     """A hex8 source mesh kept resident for repeated calls (mm_source_create): nodes, connectivity, element centroids and
     the search grid over them -- built once, like the reference's cKDTree (scripts/cli.py:66, queried at :141-195)."""
+    _destroy = "mm_source_destroy"
 
     def __init__(self, ctx, handle, nodes, conn):
         self.ctx, self.handle = ctx, handle
@@ -115,37 +162,17 @@ class Source:
     def interpolate(self, points, fields, nelem_to_search=20, want_operator=False, out=None):
         """:meth:`Context.interpolate_hex8` without the centroid and grid-build stages; identical results."""
         ctx = self.ctx
-        pts = ctx.asdevice(points, np.float64)
-        f = ctx.asdevice(fields, np.float64)
-        if len(f.shape) == 1:
-            f = DeviceArray(ctx, f.ptr, (1, f.shape[0]), f.dtype, owner=False, keepalive=f)
-        if f.shape[1] != self.nodes.shape[0]:
-            raise ValueError("fields must be [C, number of nodes]")
-        n, ncomp = pts.shape[0], f.shape[0]
-        out = ctx.empty((n, ncomp), np.float64) if out is None else ctx.asdevice(out, np.float64)
-        enc = ctx.empty((n, 8), np.int64) if want_operator else None
-        w = ctx.empty((n, 8), np.float64) if want_operator else None
-        nf = check(ctx.lib.mm_interpolate_hex8_on(ctx.handle, self.handle, pts.ptr, n, f.ptr, ncomp, nelem_to_search, out.ptr,
-                                                  enc.ptr if enc else None, w.ptr if w else None), "mm_interpolate_hex8_on")
-        if want_operator:
-            return out, enc, w, int(nf)
-        return out, int(nf)
-
-    def free(self):
-        if self.handle and self.ctx.handle:
-            self.ctx.lib.mm_source_destroy(self.ctx.handle, self.handle)
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+        pts, f, out, enc, w = _hex8_arrays(ctx, self.nodes.shape[0], points, fields, want_operator, out)
+        nf = check(ctx.lib.mm_interpolate_hex8_on(ctx.handle, self.handle, pts.ptr, pts.shape[0], f.ptr, f.shape[0],
+                                                  nelem_to_search, out.ptr, enc.ptr if enc else None,
+                                                  w.ptr if w else None), "mm_interpolate_hex8_on")
+        return _with_operator(want_operator, out, enc, w, nf)
 
 
-class TransposedOperator:
+class TransposedOperator(_Handle):
     """The transpose of an interpolation operator, grouped by destination once (mm_transpose_create_nodes / _elem) and
     applied to any number of value sets: bit for bit ``np.add.at`` on zeros (include/multimesh_hip.h)."""
+    _destroy = "mm_transpose_destroy"
 
     def __init__(self, ctx, handle, npoints, out_shape, keepalive):
         self.ctx, self.handle, self.npoints = ctx, handle, int(npoints)
@@ -159,35 +186,22 @@ class TransposedOperator:
             raise ValueError("the operator has been freed")
         v = ctx.asdevice(values, np.float64)
         if len(v.shape) == 1:
-            v = DeviceArray(ctx, v.ptr, (v.shape[0], 1) if point_major else (1, v.shape[0]), v.dtype, owner=False, keepalive=v)
+            v = v.reshape(v.shape[0], 1) if point_major else v.reshape(1, v.shape[0])
         if len(v.shape) != 2 or v.shape[0 if point_major else 1] != self.npoints:
             raise ValueError("values must be [N, C] (point_major) or [C, N]")
         ncomp = v.shape[1 if point_major else 0]
         shape = (ncomp,) + self.out_shape
-        if out is None:
-            out = ctx.empty(shape, np.float64)
-        else:
-            out = ctx.asdevice(out, np.float64)
-            if out.shape != shape:
-                raise ValueError(f"out must be {shape}")
+        out = ctx._out(out, shape, f"out must be {shape}")
         check(ctx.lib.mm_transpose_apply(ctx.handle, self.handle, v.ptr, ncomp, 1 if point_major else 0, out.ptr),
               "mm_transpose_apply")
         return out
 
     def free(self):
-        if self.handle and self.ctx.handle:
-            self.ctx.lib.mm_transpose_destroy(self.ctx.handle, self.handle)
-        self.handle = None
+        super().free()
         self._keepalive = None
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
-
-class Diffusion:
+class Diffusion(_Released):
     """The stiffness operator ``K`` of an element-nodal GLL mesh with its diffusivity (``mm_gll_diffusion_apply``), and the
     backward-Euler diffusion steps ``(M + tau K) u_new = M u_old`` on the assembled space that smooth a field with it.
     What depends on the mesh alone -- the tables, the scatter-sum over shared nodes, the inverse index, the assembled mass
@@ -213,24 +227,16 @@ class Diffusion:
               "mm_gll_diffusion_apply")
 
     def _fields(self, values):
-        v = self.ctx.asdevice(values, np.float64)
-        if v.shape == (self.nelem, self.P):
-            v = DeviceArray(self.ctx, v.ptr, (1,) + v.shape, v.dtype, owner=False, keepalive=v)
-        if len(v.shape) != 3 or v.shape[1:] != (self.nelem, self.P):
-            raise ValueError("values must be [C, E, P] (or [E, P]) over gll_points [E, P, dim]")
-        return v
+        return _element_nodal(self.ctx, values, self.nelem, self.P, "values")
 
     def apply(self, u, out=None):
         """``K_e u`` per element, not assembled: u f64[C, E, P] (or [E, P]) -> f64[C, E, P]."""
         if self.gp is None:
             raise ValueError("the operator has been freed")
         v = self._fields(u)
-        if out is None:
-            out = self.ctx.empty(v.shape, np.float64)
-        else:
-            out = self.ctx.asdevice(out, np.float64)
-            if out.shape != v.shape or out.ptr == v.ptr:
-                raise ValueError("out must be another array of the shape of u")
+        out = self.ctx._out(out, v.shape, "out must be another array of the shape of u")
+        if out.ptr == v.ptr:
+            raise ValueError("out must be another array of the shape of u")
         self._apply(v.ptr, v.shape[0], out.ptr)
         return out
 
@@ -252,15 +258,13 @@ class Diffusion:
         if self._asm is None:
             ctx = self.ctx
             n = self.nelem * self.P
-            flat = DeviceArray(ctx, self.gp.ptr, (n, self.dim), np.float64, owner=False, keepalive=self.gp)
-            uniq, inv = ctx.unique_points(flat, ordered=False)
+            uniq, inv = ctx.unique_points(self.gp.reshape(n, self.dim), ordered=False)
             nu = uniq.shape[0]
-            inverse = DeviceArray(ctx, inv.ptr, (n, 1), np.int64, owner=False, keepalive=inv)
+            inverse = inv.reshape(n, 1)
             ones = ctx.to_device(np.ones((n, 1)))
             op = ctx.transpose_nodes(inverse, ones, nu)
             elem_mass, _ = ctx.gll_mass(self.order, self.gp)
-            mass = op.apply(DeviceArray(ctx, elem_mass.ptr, (1, n), np.float64, owner=False, keepalive=elem_mass),
-                            point_major=False)                  # [1, U]: the assembled mass
+            mass = op.apply(elem_mass.reshape(1, n), point_major=False)   # [1, U]: the assembled mass
             self._asm = dict(op=op, inverse=inverse, ones=ones, elem_mass=elem_mass, mass=mass, n=n, nu=nu)
         return self._asm
 
@@ -363,16 +367,11 @@ class Diffusion:
         self.gp = None
         self.kappa_h, self.kappa_r = (1.0, None), None
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
-
-class Context:
+class Context(_Released):
     """One GPU + one HIP stream.  ``stream`` is a raw hipStream_t value (e.g.
     ``torch.cuda.current_stream().cuda_stream``); None = the device's default stream."""
+    _release = "close"
 
     def __init__(self, device=0, stream=None):
         self.lib = load_lib()
@@ -422,6 +421,49 @@ class Context:
 
     def synchronize(self):
         check(self.lib.mm_synchronize(self.handle), "mm_synchronize")
+
+    # ---- checks that many methods share ------------------------------------------------------
+    def _out(self, out, shape, message=None, size_only=False):
+        """The f64 output of a call: a new array of ``shape`` or the caller's ``out``, which must have that shape (with
+        ``size_only``: that many values in any shape) or ``message`` is raised; no message: the caller's word."""
+        if out is None:
+            return self.empty(shape, np.float64)
+        out = self.asdevice(out, np.float64)
+        if message and (out.size != int(np.prod(shape, dtype=np.int64)) if size_only else out.shape != tuple(shape)):
+            raise ValueError(message)
+        return out
+
+    def _check_args(self, rc, what):
+        """Status -1 (MM_ERR_ARG) is the caller's mistake: ``ValueError`` with the library's message; else :func:`check`."""
+        if rc == -1:
+            raise ValueError(self.lib.mm_last_error().decode(errors="replace"))
+        return check(rc, what)
+
+    def _pairs(self, ids, weights):
+        """(ids int64[N, P], weights f64[N, P], N, P) of an operator on the device."""
+        idv = self.asdevice(ids, np.int64)
+        w = self.asdevice(weights, np.float64)
+        if idv.shape != w.shape or len(idv.shape) != 2:
+            raise ValueError("ids and weights must both be [N, P]")
+        return (idv, w) + idv.shape
+
+    def _gll_points(self, shape_order, gll_points):
+        """(gll_points f64[nelem, P, dim] on the device, nelem, P, dim) of a 2-D or 3-D GLL mesh of ``shape_order``."""
+        gp = self.asdevice(gll_points, np.float64)
+        if len(gp.shape) != 3 or gp.shape[2] not in (2, 3) or gp.shape[1] != (shape_order + 1) ** gp.shape[2]:
+            raise ValueError("gll_points must be [nelem, (order+1)^dim, dim] with dim 2 or 3")
+        return (gp,) + gp.shape
+
+    def _fields_over(self, m, fields):
+        """(fields on the device or None, number of components) for fields over the values of ``m``."""
+        if fields is None:
+            return None, 1
+        f = self.asdevice(fields, np.float64)
+        if f.shape == m.shape:
+            return f, 1
+        if f.shape[1:] == m.shape:
+            return f, f.shape[0]
+        raise ValueError("fields must be [C, ...] over the shape of mass, or the shape of mass")
 
     # ---- timers -------------------------------------------------------------------------
     def set_profiling(self, on=True):
@@ -506,14 +548,8 @@ class Context:
     # ---- A9 -----------------------------------------------------------------------------
     def gather(self, fields, ids, weights, point_major=True):
         """fields f64[C,M] (or [M]) -> f64[N,C] (point_major) or f64[C,N]."""
-        f = self.asdevice(fields, np.float64)
-        if len(f.shape) == 1:
-            f = DeviceArray(self, f.ptr, (1, f.shape[0]), f.dtype, owner=False, keepalive=f)
-        idv = self.asdevice(ids, np.int64)
-        w = self.asdevice(weights, np.float64)
-        if idv.shape != w.shape or len(idv.shape) != 2:
-            raise ValueError("ids and weights must both be [N, P]")
-        n, p = idv.shape
+        f = _components(self.asdevice(fields, np.float64), 1)
+        idv, w, n, p = self._pairs(ids, weights)
         ncomp, nsrc = f.shape
         out = self.empty((n, ncomp) if point_major else (ncomp, n), np.float64)
         check(self.lib.mm_gather(self.handle, f.ptr, nsrc, ncomp, idv.ptr, w.ptr, n, p, out.ptr,
@@ -521,10 +557,7 @@ class Context:
         return out
 
     # ---- A10 (GLL) ------------------------------------------------------------------------
-    def locate_gll(self, shape_order, nearest_element_indices, gll_points, points, tolerance=1.05,
-                   snap_to_nearest=False):
-        """``get_element_weights`` core (reference interpolator.py:1181-1233) for
-        gll_points f64[E, (order+1)^dim, dim].  Returns (elem int64[N], coeffs f64[N,P], nmissing)."""
+    def _locate_gll(self, symbol, shape_order, nearest_element_indices, gll_points, points, *options):
         nn = self.asdevice(nearest_element_indices, np.int64)
         gp = self.asdevice(gll_points, np.float64)
         pts = self.asdevice(points, np.float64)
@@ -535,35 +568,27 @@ class Context:
         k = nn.shape[1] if len(nn.shape) == 2 else 0
         elem = self.empty((n,), np.int64)
         coeffs = self.empty((n, P), np.float64)
-        miss = check(self.lib.mm_locate_gll(self.handle, shape_order, dim, k, n, nn.ptr, gp.ptr, nelem, pts.ptr,
-                                            float(tolerance), 1 if snap_to_nearest else 0, elem.ptr, coeffs.ptr),
-                     "mm_locate_gll")
-        return elem, coeffs, int(miss)
+        count = check(getattr(self.lib, symbol)(self.handle, shape_order, dim, k, n, nn.ptr, gp.ptr, nelem, pts.ptr,
+                                                *options, elem.ptr, coeffs.ptr), symbol)
+        return elem, coeffs, int(count)
+
+    def locate_gll(self, shape_order, nearest_element_indices, gll_points, points, tolerance=1.05,
+                   snap_to_nearest=False):
+        """``get_element_weights`` core (reference interpolator.py:1181-1233) for
+        gll_points f64[E, (order+1)^dim, dim].  Returns (elem int64[N], coeffs f64[N,P], nmissing)."""
+        return self._locate_gll("mm_locate_gll", shape_order, nearest_element_indices, gll_points, points,
+                                float(tolerance), 1 if snap_to_nearest else 0)
 
     def locate_gll_bbox(self, shape_order, nearest_element_indices, gll_points, points):
         """The bounding-box variant ``_check_if_inside_element`` (reference interpolator.py:1409-1473)
         for gll_points f64[E, (order+1)^dim, dim].  Returns (elem int64[N], coeffs f64[N,P], number
         of points whose final inverse transform failed)."""
-        nn = self.asdevice(nearest_element_indices, np.int64)
-        gp = self.asdevice(gll_points, np.float64)
-        pts = self.asdevice(points, np.float64)
-        nelem, P, dim = gp.shape
-        if P != (shape_order + 1) ** dim or pts.shape[1] != dim:
-            raise ValueError("gll_points must be [nelem, (order+1)^dim, dim] and points [N, dim]")
-        n = pts.shape[0]
-        k = nn.shape[1] if len(nn.shape) == 2 else 0
-        elem = self.empty((n,), np.int64)
-        coeffs = self.empty((n, P), np.float64)
-        hard = check(self.lib.mm_locate_gll_bbox(self.handle, shape_order, dim, k, n, nn.ptr, gp.ptr, nelem, pts.ptr,
-                                                 elem.ptr, coeffs.ptr), "mm_locate_gll_bbox")
-        return elem, coeffs, int(hard)
+        return self._locate_gll("mm_locate_gll_bbox", shape_order, nearest_element_indices, gll_points, points)
 
     def gather_elem(self, element_nodal_fields, elem, coeffs, point_major=True):
         """``np.sum(coeffs * field[elem], axis=1)`` (reference interpolator.py:976);
         element_nodal_fields f64[C, E, P] (or [E, P]) -> f64[N, C]."""
-        f = self.asdevice(element_nodal_fields, np.float64)
-        if len(f.shape) == 2:
-            f = DeviceArray(self, f.ptr, (1,) + f.shape, f.dtype, owner=False, keepalive=f)
+        f = _components(self.asdevice(element_nodal_fields, np.float64), 2)
         el = self.asdevice(elem, np.int64)
         co = self.asdevice(coeffs, np.float64)
         ncomp, nelem, P = f.shape
@@ -579,11 +604,7 @@ class Context:
     def transpose_nodes(self, ids, weights, nsrc):
         """Group the operator (ids int64[N, P], weights f64[N, P]) by source node: a :class:`TransposedOperator` whose
         ``apply(values)`` is ``np.add.at(out[c], ids, weights * values[:, c, None])`` -> f64[C, nsrc]."""
-        idv = self.asdevice(ids, np.int64)
-        w = self.asdevice(weights, np.float64)
-        if idv.shape != w.shape or len(idv.shape) != 2:
-            raise ValueError("ids and weights must both be [N, P]")
-        n, p = idv.shape
+        idv, w, n, p = self._pairs(ids, weights)
         h = C.c_void_p()
         check(self.lib.mm_transpose_create_nodes(self.handle, idv.ptr, w.ptr, n, p, int(nsrc), C.byref(h)),
               "mm_transpose_create_nodes")
@@ -607,13 +628,8 @@ class Context:
         """The diagonal GLL mass matrix ``w_p |det J_e(xi_p)|`` of gll_points f64[E, (order+1)^dim, dim], orders 1, 2, 4
         (``mm_gll_mass``: bit for bit the NumPy statement of include/multimesh_hip.h).  Returns (mass f64[E, P], n_bad)
         or, with ``want_det``, (mass, n_bad, det f64[E, P]); ``n_bad`` counts the nodes whose determinant is not > 0."""
-        from .synth import gll_derivative_matrix, gll_weights_1d   # (ValueError for an order without tables)
-
         deriv, weights = gll_derivative_matrix(shape_order), gll_weights_1d(shape_order)
-        gp = self.asdevice(gll_points, np.float64)
-        if len(gp.shape) != 3 or gp.shape[2] not in (2, 3) or gp.shape[1] != (shape_order + 1) ** gp.shape[2]:
-            raise ValueError("gll_points must be [nelem, (order+1)^dim, dim] with dim 2 or 3")
-        nelem, P, dim = gp.shape
+        gp, nelem, P, dim = self._gll_points(shape_order, gll_points)
         mass = self.empty((nelem, P), np.float64)
         det = self.empty((nelem, P), np.float64) if want_det else None
         d_d, w_d = self.to_device(deriv), self.to_device(weights)
@@ -626,15 +642,7 @@ class Context:
         f64[1], the sum of ``mass``.  mass f64[E, P] (any shape), fields f64[C, E, P] or the shape of ``mass`` (one
         field).  Deterministic, in the fixed order ``mm_weighted_sum`` states."""
         m = self.asdevice(mass, np.float64)
-        ncomp, f = 1, None
-        if fields is not None:
-            f = self.asdevice(fields, np.float64)
-            if f.shape == m.shape:
-                ncomp = 1
-            elif f.shape[1:] == m.shape:
-                ncomp = f.shape[0]
-            else:
-                raise ValueError("fields must be [C, ...] over the shape of mass, or the shape of mass")
+        f, ncomp = self._fields_over(m, fields)
         out = self.empty((ncomp,), np.float64)
         check(self.lib.mm_weighted_sum(self.handle, m.ptr, f.ptr if f else None, m.size, ncomp, out.ptr), "mm_weighted_sum")
         return out.numpy()
@@ -645,12 +653,7 @@ class Context:
         d = self.asdevice(den, np.float64)
         if a.shape != d.shape and a.shape[1:] != d.shape:
             raise ValueError("num must be [C, ...] over the shape of den, or the shape of den")
-        if out is None:
-            out = self.empty(a.shape, np.float64)
-        else:
-            out = self.asdevice(out, np.float64)
-            if out.shape != a.shape:
-                raise ValueError("out must have the shape of num")
+        out = self._out(out, a.shape, "out must have the shape of num")
         check(self.lib.mm_divide_rows(self.handle, a.ptr, d.ptr, d.size, a.size // max(d.size, 1), out.ptr), "mm_divide_rows")
         return out
 
@@ -667,9 +670,7 @@ class Context:
         bins = self.empty((n,), np.int32)
         radius = self.empty((n,), np.float64) if want_radius else None
         rc = self.lib.mm_radial_bins(self.handle, pts.ptr, n, e.ptr, e.shape[0] - 1, bins.ptr, radius.ptr if radius else None)
-        if rc == -1:   # MM_ERR_ARG
-            raise ValueError(self.lib.mm_last_error().decode())
-        check(rc, "mm_radial_bins")
+        self._check_args(rc, "mm_radial_bins")
         return (bins, int(rc), radius) if want_radius else (bins, int(rc))
 
     def binned_weighted_sum(self, mass, bins, nbins, fields=None, square=False, want_count=False):
@@ -685,15 +686,7 @@ class Context:
         nbins = int(nbins)
         if nbins < 1:
             raise ValueError("nbins must be at least 1")
-        ncomp, f = 1, None
-        if fields is not None:
-            f = self.asdevice(fields, np.float64)
-            if f.shape == m.shape:
-                ncomp = 1
-            elif f.shape[1:] == m.shape:
-                ncomp = f.shape[0]
-            else:
-                raise ValueError("fields must be [C, ...] over the shape of mass, or the shape of mass")
+        f, ncomp = self._fields_over(m, fields)
         out = self.empty((ncomp, nbins), np.float64)
         count = self.empty((nbins,), np.int64) if want_count else None
         check(self.lib.mm_binned_weighted_sum(self.handle, m.ptr, f.ptr if f else None, b.ptr, m.size, ncomp, nbins,
@@ -729,18 +722,10 @@ class Context:
             src = self.asdevice(values_in, np.float64)
             if src.size != ncomp * n:
                 raise ValueError("values_in must hold one value per component and node")
-        shape = (ncomp,) + tuple(pts.shape[:-1])
-        if out is None:
-            out = self.empty(shape, np.float64)
-        else:
-            out = self.asdevice(out, np.float64)
-            if out.size != ncomp * n:
-                raise ValueError("out must hold one value per component and node")
+        out = self._out(out, (ncomp,) + pts.shape[:-1], "out must hold one value per component and node", size_only=True)
         rc = self.lib.mm_radial_model_apply(self.handle, pts.ptr, ngroups, P, r.ptr, v.ptr, r.shape[0], ncomp, int(mode),
                                             src.ptr if src else None, out.ptr)
-        if rc == -1:   # MM_ERR_ARG
-            raise ValueError(self.lib.mm_last_error().decode())
-        check(rc, "mm_radial_model_apply")
+        self._check_args(rc, "mm_radial_model_apply")
         return out
 
     # ---- diffusion: the stiffness operator and the smoothing it gives -------------------------------
@@ -749,13 +734,9 @@ class Context:
         ``K u``, ``smooth(values, ...)`` the diffusion steps.  ``kappa_h`` / ``kappa_r``: the lateral and the radial
         diffusivity, each a number or an element-nodal array f64[E, P]; ``kappa_r=None``: isotropic (``kappa_h`` in every
         direction; the only choice in 2-D).  A scalar is passed to the kernel as a scalar, never made an array."""
-        from .synth import gll_derivative_matrix, gll_weights_1d   # (ValueError for an order without tables)
-
         deriv, weights = gll_derivative_matrix(shape_order), gll_weights_1d(shape_order)
-        gp = self.asdevice(gll_points, np.float64)
-        if len(gp.shape) != 3 or gp.shape[2] not in (2, 3) or gp.shape[1] != (shape_order + 1) ** gp.shape[2]:
-            raise ValueError("gll_points must be [nelem, (order+1)^dim, dim] with dim 2 or 3")
-        if kappa_r is not None and gp.shape[2] != 3:
+        gp, _, _, dim = self._gll_points(shape_order, gll_points)
+        if kappa_r is not None and dim != 3:
             raise ValueError("a radial diffusivity needs a 3-D mesh")
 
         def kappa(k, name):
@@ -784,22 +765,13 @@ class Context:
         Returns the requested device arrays in the order of the flags -- ``grad`` f64[C, dim, E, P], ``radial`` (the
         derivative along x / |x|), ``lateral`` (the norm of what is left of the gradient) and ``norm``, each f64[C, E, P] --
         as a tuple, or the array itself when one is asked for.  ``radial`` and ``lateral`` need a 3-D mesh."""
-        from .synth import gll_derivative_matrix   # (ValueError for an order without tables)
-
         deriv = gll_derivative_matrix(shape_order)
-        gp = self.asdevice(gll_points, np.float64)
-        if len(gp.shape) != 3 or gp.shape[2] not in (2, 3) or gp.shape[1] != (shape_order + 1) ** gp.shape[2]:
-            raise ValueError("gll_points must be [nelem, (order+1)^dim, dim] with dim 2 or 3")
-        nelem, P, dim = gp.shape
+        gp, nelem, P, dim = self._gll_points(shape_order, gll_points)
         if not (grad or radial or lateral or norm):
             raise ValueError("ask for at least one of grad, radial, lateral and norm")
         if (radial or lateral) and dim != 3:
             raise ValueError("the radial / lateral split needs a 3-D mesh")
-        v = self.asdevice(u, np.float64)
-        if v.shape == (nelem, P):
-            v = DeviceArray(self, v.ptr, (1,) + v.shape, v.dtype, owner=False, keepalive=v)
-        if len(v.shape) != 3 or v.shape[1:] != (nelem, P):
-            raise ValueError("u must be [C, E, P] (or [E, P]) over gll_points [E, P, dim]")
+        v = _element_nodal(self, u, nelem, P, "u")
         ncomp = v.shape[0]
         outs = [self.empty((ncomp, dim, nelem, P) if full else (ncomp, nelem, P), np.float64) if want else None
                 for want, full in ((grad, True), (radial, False), (lateral, False), (norm, False))]
@@ -819,8 +791,6 @@ class Context:
         :func:`multimesh_amd.synth.gll_order_table` or, with ``transpose``, the transpose of the interpolation
         ``order_out -> order_in``.  ``scale_in`` f64[E, P_in] multiplies the input, ``div_out`` f64[E, P_out] divides the
         output (both nullable, shared by the components)."""
-        from .synth import gll_order_table   # (ValueError for an order without tables)
-
         order_in, order_out, dim, layout = int(order_in), int(order_out), int(dim), int(layout)
         table = (np.ascontiguousarray(gll_order_table(order_out, order_in).T) if transpose
                  else gll_order_table(order_in, order_out))
@@ -830,8 +800,8 @@ class Context:
             raise ValueError("dim must be 2 or 3 and layout 0 ([C, E, P]), 1 ([E, P, C]) or 2 ([E, C, P])")
         pin, pout = (order_in + 1) ** dim, (order_out + 1) ** dim
         v = self.asdevice(values, np.float64)
-        if layout == 0 and len(v.shape) == 2:
-            v = DeviceArray(self, v.ptr, (1,) + v.shape, v.dtype, owner=False, keepalive=v)
+        if layout == 0:
+            v = _components(v, 2)
         if len(v.shape) != 3 or v.shape[(2, 1, 2)[layout]] != pin:
             raise ValueError(f"values must hold {pin} nodes per element in layout {layout}, got shape {v.shape}")
         ncomp, nelem = ((v.shape[0], v.shape[1]), (v.shape[2], v.shape[0]), (v.shape[1], v.shape[0]))[layout]
@@ -845,12 +815,7 @@ class Context:
             div = self.asdevice(div_out, np.float64)
             if div.shape != (nelem, pout):
                 raise ValueError(f"div_out must be [{nelem}, {pout}]")
-        if out is None:
-            out = self.empty(shape, np.float64)
-        else:
-            out = self.asdevice(out, np.float64)
-            if out.shape != shape:
-                raise ValueError(f"out must be {shape}")
+        out = self._out(out, shape, f"out must be {shape}")
         t_d = self.to_device(table)
         check(self.lib.mm_gll_tensor_apply(self.handle, dim, order_in, order_out, t_d.ptr, layout, v.ptr, out.ptr, nelem,
                                            ncomp, scale.ptr if scale else None, div.ptr if div else None),
@@ -878,30 +843,21 @@ class Context:
         Returns (values f64[N, C], nmissing) or (values, elem int64[N], coeffs f64[N, P], nmissing)."""
         gp = self.asdevice(gll_points, np.float64)
         pts = self.asdevice(points, np.float64)
-        f = self.asdevice(element_nodal_fields, np.float64)
-        if len(f.shape) == 2:
-            f = DeviceArray(self, f.ptr, (1,) + f.shape, f.dtype, owner=False, keepalive=f)
+        f = _components(self.asdevice(element_nodal_fields, np.float64), 2)
         nelem, P, dim = gp.shape
         if P != (shape_order + 1) ** dim or len(pts.shape) != 2 or pts.shape[1] != dim:
             raise ValueError("gll_points must be [nelem, (order+1)^dim, dim] and points [N, dim]")
         if f.shape[1:] != (nelem, P):
             raise ValueError("element_nodal_fields must be [C, nelem, P]")
         n, ncomp = pts.shape[0], f.shape[0]
-        if out is None:
-            out = self.empty((n, ncomp), np.float64)
-        else:
-            out = self.asdevice(out, np.float64)
-            if out.shape != (n, ncomp):
-                raise ValueError("out must be [N, C]")
+        out = self._out(out, (n, ncomp), "out must be [N, C]")
         elem = self.empty((n,), np.int64) if want_operator else None
         coeffs = self.empty((n, P), np.float64) if want_operator else None
         miss = check(self.lib.mm_interpolate_gll(self.handle, shape_order, dim, gp.ptr, nelem, pts.ptr, n, f.ptr, ncomp,
                                                  nelem_to_search, float(tolerance), 1 if snap_to_nearest else 0,
                                                  out.ptr, elem.ptr if elem else None, coeffs.ptr if coeffs else None),
                      "mm_interpolate_gll")
-        if want_operator:
-            return out, elem, coeffs, int(miss)
-        return out, int(miss)
+        return _with_operator(want_operator, out, elem, coeffs, miss)
 
     def sample_columns_gll(self, shape_order, gll_points, element_nodal_fields, lat_table, lon_table, radius,
                            paired=False, nelem_to_search=25, tolerance=1.05, fill_value=np.nan, chunk_points=None,
@@ -914,9 +870,7 @@ class Context:
         chunk (None: the library's byte budget).
         Returns (values f64[C, D, H], nmissing) or, with ``want_points``, (values, nmissing, points f64[D, H, 3])."""
         gp = self.asdevice(gll_points, np.float64)
-        f = self.asdevice(element_nodal_fields, np.float64)
-        if len(f.shape) == 2:
-            f = DeviceArray(self, f.ptr, (1,) + f.shape, f.dtype, owner=False, keepalive=f)
+        f = _components(self.asdevice(element_nodal_fields, np.float64), 2)
         lat = self.asdevice(lat_table, np.float64)
         lon = self.asdevice(lon_table, np.float64)
         rad = self.asdevice(radius, np.float64)
@@ -934,12 +888,7 @@ class Context:
             raise ValueError("chunk_points must be >= 1 (or None)")
         ncol = nlat if paired else nlat * nlon
         ncomp = f.shape[0]
-        if out is None:
-            out = self.empty((ncomp, nd, ncol), np.float64)
-        else:
-            out = self.asdevice(out, np.float64)
-            if tuple(out.shape) != (ncomp, nd, ncol):
-                raise ValueError("out must be [C, D, H]")
+        out = self._out(out, (ncomp, nd, ncol), "out must be [C, D, H]")
         pts = self.empty((nd, ncol, 3), np.float64) if want_points else None
         miss = check(self.lib.mm_sample_columns_gll(self.handle, int(shape_order), gp.ptr, nelem, f.ptr, ncomp, lat.ptr,
                                                     nlat, lon.ptr, nlon, 1 if paired else 0, rad.ptr, nd,
@@ -965,9 +914,7 @@ class Context:
         if outside not in modes:
             raise ValueError(f"outside must be one of {sorted(modes)}, got {outside!r}")
         pts, n = self._points3(points)
-        g = self.asdevice(grid_values, np.float64)
-        if len(g.shape) == 3:
-            g = DeviceArray(self, g.ptr, (1,) + g.shape, g.dtype, owner=False, keepalive=g)
+        g = _components(self.asdevice(grid_values, np.float64), 3)
         axes = []
         for name, a in (("depth", depth), ("lat", lat), ("lon", lon)):
             if isinstance(a, np.ndarray) or not hasattr(a, "data_ptr"):
@@ -1007,24 +954,12 @@ class Context:
         Returns (values f64[N,C], nfailed) or (values, enc, weights, nfailed)."""
         nod = self.asdevice(nodes, np.float64)
         conn = self.asdevice(connectivity, np.int64)
-        pts = self.asdevice(points, np.float64)
-        f = self.asdevice(fields, np.float64)
-        if len(f.shape) == 1:
-            f = DeviceArray(self, f.ptr, (1, f.shape[0]), f.dtype, owner=False, keepalive=f)
-        n = pts.shape[0]
-        ncomp = f.shape[0]
-        if f.shape[1] != nod.shape[0]:
-            raise ValueError("fields must be [C, number of nodes]")
-        out = self.empty((n, ncomp), np.float64) if out is None else self.asdevice(out, np.float64)
-        enc = self.empty((n, 8), np.int64) if want_operator else None
-        w = self.empty((n, 8), np.float64) if want_operator else None
+        pts, f, out, enc, w = _hex8_arrays(self, nod.shape[0], points, fields, want_operator, out)
         nf = check(self.lib.mm_interpolate_hex8(self.handle, nod.ptr, nod.shape[0], conn.ptr, conn.shape[0],
-                                                pts.ptr, n, f.ptr, ncomp, nelem_to_search, out.ptr,
+                                                pts.ptr, pts.shape[0], f.ptr, f.shape[0], nelem_to_search, out.ptr,
                                                 enc.ptr if enc else None, w.ptr if w else None),
                    "mm_interpolate_hex8")
-        if want_operator:
-            return out, enc, w, int(nf)
-        return out, int(nf)
+        return _with_operator(want_operator, out, enc, w, nf)
 
     def source(self, nodes, connectivity):
         """Keep a hex8 source mesh resident (centroids + search grid built once): :class:`Source`."""
@@ -1062,9 +997,7 @@ class Context:
                                                      enc.ctypes.data if want_operator else None,
                                                      w.ctypes.data if want_operator else None),
                    "mm_interpolate_hex8_host")
-        if want_operator:
-            return out, enc, w, int(nf)
-        return out, int(nf)
+        return _with_operator(want_operator, out, enc, w, nf)
 
     # ---- section 8f-4: device passes of the layer-aware drivers ------------------------------------
     def scatter_elements(self, values, inverse, elem_ids, out):
@@ -1109,9 +1042,7 @@ class Context:
         conn = self.asdevice(connectivity, np.int64)
         first = self.empty((int(nnodes),), np.int64)
         rc = self.lib.mm_first_occurrence(self.handle, conn.ptr, conn.size, int(nnodes), first.ptr)
-        if rc == -1:
-            raise ValueError(self.lib.mm_last_error().decode(errors="replace"))
-        unreferenced = check(rc, "mm_first_occurrence")
+        unreferenced = self._check_args(rc, "mm_first_occurrence")
         if unreferenced:
             raise ValueError(f"{unreferenced} nodes are not referenced by the connectivity: z_node_1D has no value "
                              "for them")
@@ -1152,12 +1083,7 @@ class Context:
             if host_out.shape != pts.shape or host_out.dtype != np.float64 or not host_out.flags.c_contiguous:
                 raise ValueError("out must be a C-contiguous f64 array of the shape of points")
             out = pts if host_out is points else None
-        if out is None:
-            out = self.empty(pts.shape, np.float64)
-        else:
-            out = self.asdevice(out, np.float64)
-            if out.size != pts.size:
-                raise ValueError("out must have the shape of points")
+        out = self._out(out, pts.shape, "out must have the shape of points", size_only=True)
         check(self.lib.mm_map_to_sphere(self.handle, pts.ptr, n, r.ptr, r.size, first.ptr if first else None,
                                         float(r_ref), out.ptr), "mm_map_to_sphere")
         if host_out is not None:      # a NumPy ``out`` (``points`` itself for the in-place map) receives the result
@@ -1181,12 +1107,7 @@ class Context:
         f = self.asdevice(factor, np.float64)
         if f.size != n:
             raise ValueError("factor needs one value per point")
-        if out is None:
-            out = self.empty(pts.shape, np.float64)
-        else:
-            out = self.asdevice(out, np.float64)
-            if out.size != pts.size:
-                raise ValueError("out must have the shape of points")
+        out = self._out(out, pts.shape, "out must have the shape of points", size_only=True)
         check(self.lib.mm_scale_points(self.handle, pts.ptr, n, f.ptr, out.ptr), "mm_scale_points")
         return out
 
@@ -1205,8 +1126,7 @@ class Context:
             raise ValueError("unique_out / inverse_out too small: need [N, dim] and [N]")
         fn = self.lib.mm_unique_points if ordered else self.lib.mm_unique_points_any_order
         nu = check(fn(self.handle, pts.ptr, n, dim, uniq.ptr, inv.ptr), "mm_unique_points")
-        return (DeviceArray(self, uniq.ptr, (int(nu), dim), np.float64, owner=False, keepalive=uniq),
-                DeviceArray(self, inv.ptr, (n,), np.int64, owner=False, keepalive=inv))
+        return uniq.rows(0, int(nu)), inv.rows(0, n)
 
     def close(self):
         if self.handle:
@@ -1219,12 +1139,6 @@ class Context:
     def __exit__(self, *exc):
         self.close()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 _default = {}
 
@@ -1236,4 +1150,5 @@ def default_context(device=0):
     return _default[device]
 
 
-__all__ = ["Context", "DeviceArray", "Diffusion", "KnnIndex", "TransposedOperator", "default_context", "MultiMeshHipError"]
+__all__ = ["Context", "DeviceArray", "Diffusion", "KnnIndex", "Source", "TransposedOperator", "default_context",
+           "MultiMeshHipError"]

@@ -36,38 +36,88 @@ MM_PCG_RZ, MM_PCG_RZ_OLD, MM_PCG_PAP, MM_PCG_BB, MM_PCG_ALPHA, MM_PCG_BETA, MM_P
 MM_PCG_PHASE_START, MM_PCG_PHASE_BETA, MM_PCG_PHASE_ALPHA = range(3)
 STAGES = ("centroid", "knn_build", "knn_query", "locate", "gather", "knn_cell", "locate_pass0")
 
-#: every symbol include/multimesh_hip.h declares (tests check the library exports all of them)
-EXPORTED_SYMBOLS = (
-    "centroid", "triLinearInterpolator",
-    "mm_device_count", "mm_last_error", "mm_last_status",
-    "mm_context_create", "mm_context_destroy", "mm_synchronize",
-    "mm_device_alloc", "mm_device_free", "mm_copy_h2d", "mm_copy_d2h", "mm_memset",
-    "mm_centroid", "mm_knn_build", "mm_knn_query", "mm_knn_destroy",
-    "mm_locate_hex8", "mm_gather", "mm_interpolate_hex8", "mm_interpolate_hex8_host", "mm_locate_gll", "mm_gather_elem",
-    "mm_scatter_elements", "mm_fluid_solid_fix", "mm_set_profiling", "mm_last_timings", "mm_set_lazy_lists", "mm_unique_points", "mm_locate_gll_bbox", "mm_interpolate_gll",
-    "mm_set_fp_mode", "mm_get_fp_mode", "mm_last_locate_stats", "mm_last_knn_kernels",
-    "mm_source_create", "mm_source_destroy", "mm_interpolate_hex8_on", "mm_points_to_elements", "mm_unique_points_any_order",
-    "mm_map_to_sphere", "mm_first_occurrence", "mm_sphere_ratio", "mm_scale_points", "mm_sample_columns_gll",
-    "mm_sample_grid",
-    "mm_transpose_create_nodes", "mm_transpose_create_elem", "mm_transpose_apply", "mm_transpose_destroy",
-    "mm_gll_mass", "mm_weighted_sum", "mm_divide_rows",
-    "mm_gll_diffusion_apply", "mm_pcg_combine", "mm_pcg_scalars", "mm_pcg_direction", "mm_pcg_advance",
-    "mm_gll_gradient",
-    "mm_gll_tensor_apply", "mm_element_deviation",
-    "mm_radial_bins", "mm_binned_weighted_sum", "mm_radial_model_apply",
-)
-
 
 class MultiMeshHipError(RuntimeError):
     """A negative MM_ERR_* code came back from multi_mesh_hip.so."""
 
 
-def _i64_2d():
-    return np.ctypeslib.ndpointer(dtype=np.int64, ndim=2, flags=["C_CONTIGUOUS"])
+i32, i64, usize, f64, vp = C.c_int, C.c_int64, C.c_size_t, C.c_double, C.c_void_p
+# the two legacy symbols take NumPy arrays (reference helpers.py:43-81); their scalars are long long
+_I64_2D = np.ctypeslib.ndpointer(dtype=np.int64, ndim=2, flags=["C_CONTIGUOUS"])
+_F64_2D = np.ctypeslib.ndpointer(dtype=np.float64, ndim=2, flags=["C_CONTIGUOUS"])
 
+#: name -> (restype, argtypes) of every function include/multimesh_hip.h declares, in the header's order; load_lib applies
+#: it and tests/test_abi.py compares it with the header argument by argument.  vp stands for any pointer.
+SIGNATURES = {
+    "centroid": (None, (i64, i64, i64, _I64_2D, _F64_2D, _F64_2D)),
+    "triLinearInterpolator": (i64, (i64, i64, _I64_2D, _I64_2D, _I64_2D, _F64_2D, _F64_2D, _F64_2D)),
+    "mm_device_count": (i32, ()),
+    "mm_last_error": (C.c_char_p, ()),
+    "mm_last_status": (i32, ()),
+    "mm_context_create": (i32, (i32, vp, C.POINTER(vp))),
+    "mm_context_destroy": (None, (vp,)),
+    "mm_synchronize": (i32, (vp,)),
+    "mm_device_alloc": (i32, (vp, usize, C.POINTER(vp))),
+    "mm_device_free": (i32, (vp, vp)),
+    "mm_copy_h2d": (i32, (vp, vp, vp, usize)),
+    "mm_copy_d2h": (i32, (vp, vp, vp, usize)),
+    "mm_memset": (i32, (vp, vp, i32, usize)),
+    "mm_centroid": (i32, (vp, i64, i64, i64, vp, vp, vp)),
+    "mm_knn_build": (i32, (vp, vp, i64, i64, C.POINTER(vp))),
+    "mm_knn_query": (i32, (vp, vp, vp, i64, i64, vp, vp)),
+    "mm_knn_destroy": (None, (vp, vp)),
+    "mm_locate_hex8": (i64, (vp, i64, i64, vp, vp, i64, i32, vp, vp, vp, vp)),
+    "mm_gather": (i32, (vp, vp, i64, i64, vp, vp, i64, i64, vp, i32)),
+    "mm_locate_gll": (i64, (vp, i32, i32, i64, i64, vp, vp, i64, vp, f64, i32, vp, vp)),
+    "mm_locate_gll_bbox": (i64, (vp, i32, i32, i64, i64, vp, vp, i64, vp, vp, vp)),
+    "mm_gather_elem": (i32, (vp, vp, i64, i64, vp, vp, i64, i64, vp, i32)),
+    "mm_interpolate_gll": (i64, (vp, i32, i32, vp, i64, vp, i64, vp, i64, i64, f64, i32, vp, vp, vp)),
+    "mm_sample_columns_gll": (i64, (vp, i32, vp, i64, vp, i64, vp, i64, vp, i64, i32, vp, i64, i64, f64, f64, i64, vp,
+                                  vp)),
+    "mm_sample_grid": (i64, (vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i32, i32, f64, vp, vp)),
+    "mm_transpose_create_nodes": (i32, (vp, vp, vp, i64, i64, i64, C.POINTER(vp))),
+    "mm_transpose_create_elem": (i32, (vp, vp, vp, i64, i64, i64, C.POINTER(vp))),
+    "mm_transpose_apply": (i32, (vp, vp, vp, i64, i32, vp)),
+    "mm_transpose_destroy": (None, (vp, vp)),
+    "mm_gll_mass": (i64, (vp, i32, i32, vp, i64, vp, vp, vp, vp)),
+    "mm_weighted_sum": (i32, (vp, vp, vp, i64, i64, vp)),
+    "mm_divide_rows": (i32, (vp, vp, vp, i64, i64, vp)),
+    "mm_gll_diffusion_apply": (i32, (vp, i32, i32, vp, i64, vp, vp, vp, i64, f64, vp, i32, f64, vp, vp)),
+    "mm_gll_gradient": (i32, (vp, i32, i32, vp, i64, vp, vp, i64, vp, vp, vp, vp)),
+    "mm_gll_tensor_apply": (i32, (vp, i32, i32, i32, vp, i32, vp, vp, i64, i64, vp, vp)),
+    "mm_element_deviation": (i32, (vp, i32, i64, vp, vp, i64, vp, vp)),
+    "mm_radial_bins": (i64, (vp, vp, i64, vp, i64, vp, vp)),
+    "mm_binned_weighted_sum": (i32, (vp, vp, vp, vp, i64, i64, i64, i32, vp, vp)),
+    "mm_radial_model_apply": (i32, (vp, vp, i64, i64, vp, vp, i64, i64, i32, vp, vp)),
+    "mm_pcg_combine": (i32, (vp, vp, vp, f64, vp, i64, i64, vp)),
+    "mm_pcg_scalars": (i32, (vp, vp, i64, i32, f64, vp)),
+    "mm_pcg_direction": (i32, (vp, vp, vp, i64, i64, vp)),
+    "mm_pcg_advance": (i32, (vp, vp, vp, vp, i64, i64, vp, vp)),
+    "mm_unique_points": (i64, (vp, vp, i64, i64, vp, vp)),
+    "mm_unique_points_any_order": (i64, (vp, vp, i64, i64, vp, vp)),
+    "mm_scatter_elements": (i32, (vp, vp, i64, i64, vp, vp, i64, i64, i64, vp)),
+    "mm_map_to_sphere": (i32, (vp, vp, i64, vp, i64, vp, f64, vp)),
+    "mm_first_occurrence": (i64, (vp, vp, i64, i64, vp)),
+    "mm_sphere_ratio": (i32, (vp, vp, i64, vp, i64, vp, f64, vp)),
+    "mm_scale_points": (i32, (vp, vp, i64, vp, vp)),
+    "mm_points_to_elements": (i32, (vp, vp, i64, i64)),
+    "mm_fluid_solid_fix": (i64, (vp, vp, vp, vp, i64, i64, i64, i64)),
+    "mm_interpolate_hex8": (i64, (vp, vp, i64, vp, i64, vp, i64, vp, i64, i64, vp, vp, vp)),
+    "mm_source_create": (i32, (vp, vp, i64, vp, i64, C.POINTER(vp))),
+    "mm_source_destroy": (None, (vp, vp)),
+    "mm_interpolate_hex8_on": (i64, (vp, vp, vp, i64, vp, i64, i64, vp, vp, vp)),
+    "mm_interpolate_hex8_host": (i64, (vp, vp, i64, vp, i64, vp, i64, vp, i64, i64, vp, vp, vp)),
+    "mm_set_lazy_lists": (i32, (vp, i32)),
+    "mm_set_fp_mode": (i32, (vp, i32)),
+    "mm_get_fp_mode": (i32, (vp,)),
+    "mm_last_locate_stats": (i32, (vp, C.POINTER(C.c_longlong))),
+    "mm_last_knn_kernels": (i32, (vp, C.POINTER(i32))),
+    "mm_set_profiling": (i32, (vp, i32)),
+    "mm_last_timings": (i32, (vp, C.POINTER(f64), i32)),
+}
 
-def _f64_2d():
-    return np.ctypeslib.ndpointer(dtype=np.float64, ndim=2, flags=["C_CONTIGUOUS"])
+#: every symbol include/multimesh_hip.h declares (tests check the library exports all of them)
+EXPORTED_SYMBOLS = tuple(SIGNATURES)
 
 
 def load_lib():
@@ -82,149 +132,9 @@ def load_lib():
             "or `python -c 'import __graft_entry__ as g; g.build()'`"
         )
     lib = C.CDLL(candidates[0])
-
-    # ---- legacy symbols (reference helpers.py:43-81) ----
-    lib.centroid.restype = None
-    lib.centroid.argtypes = [C.c_int64, C.c_int64, C.c_int64, _i64_2d(), _f64_2d(), _f64_2d()]
-    lib.triLinearInterpolator.restype = C.c_int64
-    lib.triLinearInterpolator.argtypes = [
-        C.c_int64, C.c_int64, _i64_2d(), _i64_2d(), _i64_2d(), _f64_2d(), _f64_2d(), _f64_2d(),
-    ]
-
-    # ---- device-pointer API (include/multimesh_hip.h) ----
-    vp = C.c_void_p
-    lib.mm_device_count.restype = C.c_int
-    lib.mm_device_count.argtypes = []
-    lib.mm_last_error.restype = C.c_char_p
-    lib.mm_last_error.argtypes = []
-    lib.mm_last_status.restype = C.c_int
-    lib.mm_last_status.argtypes = []
-    lib.mm_context_create.restype = C.c_int
-    lib.mm_context_create.argtypes = [C.c_int, vp, C.POINTER(vp)]
-    lib.mm_context_destroy.restype = None
-    lib.mm_context_destroy.argtypes = [vp]
-    lib.mm_synchronize.restype = C.c_int
-    lib.mm_synchronize.argtypes = [vp]
-    lib.mm_device_alloc.restype = C.c_int
-    lib.mm_device_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
-    lib.mm_device_free.restype = C.c_int
-    lib.mm_device_free.argtypes = [vp, vp]
-    lib.mm_copy_h2d.restype = C.c_int
-    lib.mm_copy_h2d.argtypes = [vp, vp, vp, C.c_size_t]
-    lib.mm_copy_d2h.restype = C.c_int
-    lib.mm_copy_d2h.argtypes = [vp, vp, vp, C.c_size_t]
-    lib.mm_memset.restype = C.c_int
-    lib.mm_memset.argtypes = [vp, vp, C.c_int, C.c_size_t]
-    lib.mm_centroid.restype = C.c_int
-    lib.mm_centroid.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp]
-    lib.mm_knn_build.restype = C.c_int
-    lib.mm_knn_build.argtypes = [vp, vp, C.c_int64, C.c_int64, C.POINTER(vp)]
-    lib.mm_knn_query.restype = C.c_int
-    lib.mm_knn_query.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, vp, vp]
-    lib.mm_knn_destroy.restype = None
-    lib.mm_knn_destroy.argtypes = [vp, vp]
-    lib.mm_locate_hex8.restype = C.c_int64
-    lib.mm_locate_hex8.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, C.c_int, vp, vp, vp, vp]
-    lib.mm_gather.restype = C.c_int
-    lib.mm_gather.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, C.c_int64, vp, C.c_int]
-    lib.mm_scatter_elements.restype = C.c_int
-    lib.mm_scatter_elements.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp]
-    lib.mm_fluid_solid_fix.restype = C.c_int64
-    lib.mm_fluid_solid_fix.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64]
-    lib.mm_interpolate_hex8.restype = C.c_int64
-    lib.mm_interpolate_hex8.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64,
-                                        C.c_int64, vp, vp, vp]
-    lib.mm_interpolate_hex8_host.restype = C.c_int64
-    lib.mm_interpolate_hex8_host.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64,
-                                        C.c_int64, vp, vp, vp]
-    lib.mm_locate_gll.restype = C.c_int64
-    lib.mm_locate_gll.argtypes = [vp, C.c_int, C.c_int, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp, C.c_double,
-                                  C.c_int, vp, vp]
-    lib.mm_gather_elem.restype = C.c_int
-    lib.mm_gather_elem.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, C.c_int64, vp, C.c_int]
-    lib.mm_interpolate_gll.restype = C.c_int64
-    lib.mm_interpolate_gll.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, C.c_int64,
-                                       C.c_double, C.c_int, vp, vp, vp]
-    lib.mm_sample_columns_gll.restype = C.c_int64
-    lib.mm_sample_columns_gll.argtypes = [vp, C.c_int, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, C.c_int,
-                                          vp, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int64, vp, vp]
-    lib.mm_sample_grid.restype = C.c_int64
-    lib.mm_sample_grid.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int,
-                                   C.c_double, vp, vp]
-    lib.mm_locate_gll_bbox.restype = C.c_int64
-    lib.mm_locate_gll_bbox.argtypes = [vp, C.c_int, C.c_int, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp, vp, vp]
-    lib.mm_unique_points.restype = C.c_int64
-    lib.mm_unique_points.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp]
-    lib.mm_set_lazy_lists.restype = C.c_int
-    lib.mm_set_lazy_lists.argtypes = [vp, C.c_int]
-    lib.mm_unique_points_any_order.restype = C.c_int64
-    lib.mm_unique_points_any_order.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp]
-    lib.mm_points_to_elements.restype = C.c_int
-    lib.mm_points_to_elements.argtypes = [vp, vp, C.c_int64, C.c_int64]
-    lib.mm_source_create.restype = C.c_int
-    lib.mm_source_create.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.POINTER(vp)]
-    lib.mm_source_destroy.restype = None
-    lib.mm_source_destroy.argtypes = [vp, vp]
-    lib.mm_interpolate_hex8_on.restype = C.c_int64
-    lib.mm_interpolate_hex8_on.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp, vp]
-    lib.mm_map_to_sphere.restype = C.c_int
-    lib.mm_map_to_sphere.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_double, vp]
-    lib.mm_first_occurrence.restype = C.c_int64
-    lib.mm_first_occurrence.argtypes = [vp, vp, C.c_int64, C.c_int64, vp]
-    lib.mm_sphere_ratio.restype = C.c_int
-    lib.mm_sphere_ratio.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_double, vp]
-    lib.mm_scale_points.restype = C.c_int
-    lib.mm_scale_points.argtypes = [vp, vp, C.c_int64, vp, vp]
-    lib.mm_transpose_create_nodes.restype = C.c_int
-    lib.mm_transpose_create_nodes.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.POINTER(vp)]
-    lib.mm_transpose_create_elem.restype = C.c_int
-    lib.mm_transpose_create_elem.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.POINTER(vp)]
-    lib.mm_transpose_apply.restype = C.c_int
-    lib.mm_transpose_apply.argtypes = [vp, vp, vp, C.c_int64, C.c_int, vp]
-    lib.mm_transpose_destroy.restype = None
-    lib.mm_transpose_destroy.argtypes = [vp, vp]
-    lib.mm_gll_mass.restype = C.c_int64
-    lib.mm_gll_mass.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int64, vp, vp, vp, vp]
-    lib.mm_weighted_sum.restype = C.c_int
-    lib.mm_weighted_sum.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, vp]
-    lib.mm_divide_rows.restype = C.c_int
-    lib.mm_divide_rows.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, vp]
-    lib.mm_radial_bins.restype = C.c_int64
-    lib.mm_radial_bins.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, vp, vp]
-    lib.mm_binned_weighted_sum.restype = C.c_int
-    lib.mm_binned_weighted_sum.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, vp, vp]
-    lib.mm_radial_model_apply.restype = C.c_int
-    lib.mm_radial_model_apply.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int, vp, vp]
-    lib.mm_gll_diffusion_apply.restype = C.c_int
-    lib.mm_gll_diffusion_apply.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int64, vp, vp, vp, C.c_int64, C.c_double, vp, C.c_int,
-                                           C.c_double, vp, vp]
-    lib.mm_gll_gradient.restype = C.c_int
-    lib.mm_gll_gradient.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, vp, vp]
-    lib.mm_gll_tensor_apply.restype = C.c_int
-    lib.mm_gll_tensor_apply.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int64, C.c_int64, vp, vp]
-    lib.mm_element_deviation.restype = C.c_int
-    lib.mm_element_deviation.argtypes = [vp, C.c_int, C.c_int64, vp, vp, C.c_int64, vp, vp]
-    lib.mm_pcg_combine.restype = C.c_int
-    lib.mm_pcg_combine.argtypes = [vp, vp, vp, C.c_double, vp, C.c_int64, C.c_int64, vp]
-    lib.mm_pcg_scalars.restype = C.c_int
-    lib.mm_pcg_scalars.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_double, vp]
-    lib.mm_pcg_direction.restype = C.c_int
-    lib.mm_pcg_direction.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, vp]
-    lib.mm_pcg_advance.restype = C.c_int
-    lib.mm_pcg_advance.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, vp, vp]
-    lib.mm_set_fp_mode.restype = C.c_int
-    lib.mm_set_fp_mode.argtypes = [vp, C.c_int]
-    lib.mm_get_fp_mode.restype = C.c_int
-    lib.mm_get_fp_mode.argtypes = [vp]
-    lib.mm_last_locate_stats.restype = C.c_int
-    lib.mm_last_locate_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
-    lib.mm_last_knn_kernels.restype = C.c_int
-    lib.mm_last_knn_kernels.argtypes = [vp, C.POINTER(C.c_int)]
-    lib.mm_set_profiling.restype = C.c_int
-    lib.mm_set_profiling.argtypes = [vp, C.c_int]
-    lib.mm_last_timings.restype = C.c_int
-    lib.mm_last_timings.argtypes = [vp, C.POINTER(C.c_double), C.c_int]
-
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, list(argtypes)
     lib._filename = candidates[0]
     cache.append(lib)
     return lib

@@ -1,0 +1,157 @@
+"""The GLL array cores (the reference's salvus.fem numerics restated) under the file-level drivers."""
+from __future__ import annotations
+
+import numpy as np
+
+from ..device import default_context
+from ..helpers import check
+from ..mesh import HexMesh
+from ._common import GllMesh, _components_first, _order_from_point_count, _report_not_found, _scatter_back
+from .earth import _sphere_mapped
+
+
+def get_element_weights(gll_points, shape_order, centroid_tree, points, nelem_to_search=25, tolerance=1.05,
+                        snap_to_nearest=False, context=None):
+    """Enclosing element and interpolation coefficients of every point
+    (reference interpolator.py:1147-1255).  ``centroid_tree``: a :class:`multimesh_amd.device.KnnIndex`
+    over the element centroids, or the centroid array itself.  Returns ``(elems int64[N] with -1 for
+    "not found", coeffs f64[N, P])``."""
+    ctx = context or default_context()
+    tree = centroid_tree if hasattr(centroid_tree, "query") else ctx.knn_build(centroid_tree)
+    nn = tree.query(points, nelem_to_search)
+    elem, coeffs, _ = ctx.locate_gll(shape_order, nn, gll_points, points, tolerance, snap_to_nearest)
+    return elem.numpy(), coeffs.numpy()
+
+
+def check_if_inside_element(gll_model, nearest_elements, points, shape_order, context=None):
+    """Array form of the reference's ``_check_if_inside_element`` (interpolator.py:1409-1473, called
+    per point by gll_2_exodus and the layered drivers): bounding-box pre-test, acceptance at
+    |xi| <= 1.04, best-candidate fallback.  ``gll_model`` f64[E, P, dim], ``nearest_elements``
+    int64[N, k], ``points`` f64[N, dim] -> (element int64[N], coefficients f64[N, P])."""
+    ctx = context or default_context()
+    elem, coeffs, _ = ctx.locate_gll_bbox(shape_order, nearest_elements, gll_model, points)
+    return elem.numpy(), coeffs.numpy()
+
+
+def interpolate_gll_to_points(mesh: GllMesh, points, params_to_interp, nelem_to_search=25, tolerance=1.05,
+                              context=None, make_spherical=False):
+    """The GLL form of ``interpolate_to_points`` (reference interpolator.py:931-977): centroid tree,
+    element weights, then ``np.sum(coeffs * field[elem], axis=1)`` per parameter -> f64[N, C].
+    ``make_spherical``: the mesh's GLL points are mapped onto the sphere of its 1-D model first (:943-944), on
+    the device and as a copy (``mesh`` is not changed); the points are taken as they are."""
+    ctx = context or default_context()
+    points = np.ascontiguousarray(points, dtype=np.float64)
+    fields = np.stack([mesh.element_nodal_fields[p] for p in params_to_interp])
+    gll_points = _sphere_mapped(mesh, ctx) if make_spherical else mesh.gll_points
+    vals, num_failed = ctx.interpolate_gll(mesh.shape_order, gll_points, points, fields,
+                                           nelem_to_search=nelem_to_search, tolerance=tolerance)
+    _report_not_found(num_failed)
+    return vals.numpy()
+
+
+def get_unique_points(points, context=None):
+    """Array form of the reference's ``utils.get_unique_points`` (utils.py:484-488):
+    ``np.unique(points.reshape(-1, dim), axis=0, return_inverse=True)`` on the device.
+    ``points`` f64[E, P, dim] (element-nodal) or f64[N, dim] -> (unique f64[U, dim], inverse int64[N])."""
+    ctx = context or default_context()
+    pts = np.ascontiguousarray(points, dtype=np.float64)
+    uniq, inv = ctx.unique_points(pts.reshape(-1, pts.shape[-1]))
+    return uniq.numpy(), inv.numpy()
+
+
+def interpolate_gll_to_gll(mesh_a: GllMesh, target_gll_points, params_to_interp, nelem_to_search=20,
+                           tolerance=1.05, context=None):
+    """The array core of ``gll_2_gll`` (reference interpolator.py:700-830): the target mesh's
+    element-nodal points are reduced to their unique set (shared faces/edges/corners repeat),
+    interpolated once each, and scattered back with the inverse index (``values[recon]``,
+    interpolator.py:823).  ``target_gll_points`` f64[E_t, P_t, dim] -> f64[C, E_t, P_t]."""
+    ctx = context or default_context()
+    tgt = np.ascontiguousarray(target_gll_points, dtype=np.float64)
+    # (the unique rows are only interpolated and scattered back: their order never reaches the result)
+    uniq, inv = ctx.unique_points(tgt.reshape(-1, tgt.shape[-1]), ordered=False)
+    fields = np.stack([mesh_a.element_nodal_fields[p] for p in params_to_interp])
+    vals, num_failed = ctx.interpolate_gll(mesh_a.shape_order, mesh_a.gll_points, uniq, fields,
+                                           nelem_to_search=nelem_to_search, tolerance=tolerance)
+    _report_not_found(num_failed)
+    return _scatter_back(vals.numpy(), inv.numpy(), (len(params_to_interp),) + tgt.shape[:2])
+
+
+def interpolate_hex8_to_gll(mesh_a: HexMesh, target_gll_points, params, nelem_to_search=20, context=None,
+                            return_nfailed=False):
+    """The array core of ``exodus_2_gll`` (reference cli.py:128-257, interpolator.py:60-150): the
+    reference runs its hex8 path once per GLL slot (125 times at order 4) over points that repeat on
+    shared faces, edges and corners; here the target mesh's element-nodal points are reduced to
+    their unique set on the device, interpolated once each through the hex8 pipeline, and scattered
+    back with the inverse index.  ``target_gll_points`` f64[E_t, P_t, 3] -> f64[C, E_t, P_t]; points
+    that are not found get zero."""
+    ctx = context or default_context()
+    tgt = np.ascontiguousarray(target_gll_points, dtype=np.float64)
+    uniq, inv = ctx.unique_points(tgt.reshape(-1, tgt.shape[-1]), ordered=False)
+    vals, nfailed = ctx.interpolate_hex8(mesh_a.points, mesh_a.connectivity, uniq, mesh_a.fields_matrix(list(params)),
+                                         nelem_to_search=nelem_to_search)
+    _report_not_found(nfailed)
+    out = _scatter_back(vals.numpy(), inv.numpy(), (len(list(params)),) + tgt.shape[:2])
+    return (out, nfailed) if return_nfailed else out
+
+
+def find_gll_centroids(gll_coordinates, dimensions=3):
+    """The reference's ``_find_gll_centroids`` (interpolator.py:1389-1406): per-dimension
+    ``np.mean(gll_coordinates[:, :, d], axis=1)`` -- NumPy's pairwise row sum over the strided view,
+    not the node-order sum of ``mean(axis=1)`` on the 3-D array that the mesh reader uses; kept on the
+    host in NumPy so that the tree is built over bit-identical centroids (an O(E P) pass)."""
+    gll_coordinates = np.asarray(gll_coordinates, dtype=np.float64)
+    if dimensions != gll_coordinates.shape[2]:
+        raise ValueError("Dimensions of GLL model not the same as input")
+    centroids = np.zeros(shape=[gll_coordinates.shape[0], dimensions])
+    for d in range(dimensions):
+        centroids[:, d] = np.mean(gll_coordinates[:, :, d], axis=1, dtype=np.float64)
+    return centroids
+
+
+def interpolate_gll_to_nodes(gll_points, gll_data, points, shape_order=4, nelem_to_search=20, context=None):
+    """The array core of ``gll_2_exodus`` (reference interpolator.py:227-285): centroid tree over the
+    GLL elements, ``nelem_to_search`` nearest per mesh node, the bounding-box acceptance loop
+    ``_check_if_inside_element`` (:1409-1473) and ``np.sum(gll_data[element, :, :] * coeffs, axis=1)``.
+    ``gll_points`` f64[E, P, dim], ``gll_data`` f64[E, C, P] (the layout of the HDF5 ``MODEL/data``),
+    ``points`` f64[N, dim] -> values f64[N, C]."""
+    ctx = context or default_context()
+    gll_points = np.ascontiguousarray(gll_points, dtype=np.float64)
+    dim = gll_points.shape[2]
+    tree = ctx.knn_build(find_gll_centroids(gll_points, dim))
+    pts = ctx.asdevice(np.ascontiguousarray(points, dtype=np.float64), np.float64)
+    nn = tree.query(pts, nelem_to_search)
+    elem, coeffs, _ = ctx.locate_gll_bbox(shape_order, nn, gll_points, pts)
+    return ctx.gather_elem(_components_first(gll_data), elem, coeffs).numpy()
+
+
+def _gll_operator_over_all_points(ctx, gll_points, points, nelem_to_search, ignore_hard_elements):
+    """``find_gll_coeffs`` as ``query_model`` and ``gll_2_gll`` drive it (reference interpolator.py:91-126,
+    :742-786): a tree over ALL GLL points (not the centroids), the ``nelem_to_search`` nearest points per
+    coordinate mapped to their elements by ``floor(index / P)`` (an element can appear several times in a
+    list), then the bounding-box acceptance loop (:1409-1473).  Returns device arrays ``(element, coeffs)``."""
+    nelem, P, dim = gll_points.shape
+    gll_order = _order_from_point_count(P, dim)
+    tree = ctx.knn_build(gll_points.reshape(nelem * P, dim))
+    pts = ctx.asdevice(points if hasattr(points, "numpy") else np.ascontiguousarray(points, dtype=np.float64),
+                       np.float64)
+    nearest = tree.query(pts, nelem_to_search)
+    check(ctx.lib.mm_points_to_elements(ctx.handle, nearest.ptr, nearest.size, P), "mm_points_to_elements")   # floor(index / P), on the device
+    elem, coeffs, hard = ctx.locate_gll_bbox(gll_order, nearest, gll_points, pts)
+    if hard and not ignore_hard_elements:
+        raise ValueError("Can't find an appropriate element.")
+    return elem, coeffs
+
+
+def query_gll_model(gll_points, gll_data, coordinates, nelem_to_search=20, ignore_hard_elements=False, context=None):
+    """The array core of ``query_model`` (reference interpolator.py:60-139) after its file read and
+    ``latlondepth_to_xyz``: :func:`_gll_operator_over_all_points`, then
+    ``np.sum(original_data[elements] * coeffs, axis=2)``.
+    ``gll_points`` f64[E, P, dim], ``gll_data`` f64[E, C, P], ``coordinates`` f64[N, dim] (Cartesian)
+    -> values f64[N, C].  Like the reference it raises ``ValueError`` when no candidate element
+    admits an inverse transform, unless ``ignore_hard_elements``.  Equidistant points (the copies of
+    a node shared by several elements) are ordered by index here; cKDTree's order among them is
+    unspecified."""
+    ctx = context or default_context()
+    gll_points = np.ascontiguousarray(gll_points, dtype=np.float64)
+    elem, coeffs = _gll_operator_over_all_points(ctx, gll_points, coordinates, nelem_to_search, ignore_hard_elements)
+    return ctx.gather_elem(_components_first(gll_data), elem, coeffs).numpy()

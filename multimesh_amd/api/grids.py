@@ -1,0 +1,417 @@
+"""Sampling on latitude x longitude x depth columns: extract_regular_grid (reference api.py:600-642,
+interpolator.py:1600-1646), the depth slice plot_depth_slice samples (plotter.py:89-110, :159-187) and the radius x path
+section of plot_cross_section (plotter.py:360-391).  The targets are generated on the device
+(Context.sample_columns_gll); the host only computes the 1-D factors below.  Plotting is not part of this."""
+import numpy as np
+
+from .. import io as mio
+from ..device import DeviceArray, default_context
+from ..mesh import HexMesh
+from ._common import GllMesh, _mesh_points, _order_from_point_count
+from .earth import _sphere_mapped
+
+DIMS = ("depth", "latitude", "longitude")
+UNITS = {"depth": "m", "latitude": "deg", "longitude": "deg"}
+
+
+def _extent(extent, name):
+    """``np.linspace(min, max, num)`` of an extent ``(min, max, num)``, as the reference forms its axes."""
+    try:
+        lo, hi, num = extent
+        lo, hi = float(lo), float(hi)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be (min, max, num), got {extent!r}") from None
+    if not (np.isfinite(lo) and np.isfinite(hi)):
+        raise ValueError(f"{name}: the bounds must be finite, got {extent!r}")
+    if isinstance(num, (bool, np.bool_)) or not float(num).is_integer() or int(num) < 1:
+        raise ValueError(f"{name}: num must be an integer >= 1, got {num!r}")
+    return np.linspace(lo, hi, int(num))
+
+
+def column_tables(lat, lon, depth):
+    """``(lat_table f64[nlat, 2], lon_table f64[nlon, 2], radius f64[D])`` as :meth:`Context.sample_columns_gll`
+    reads them: (sin colat, cos colat), (cos lon, sin lon) and 6371000 - depth, computed with the expressions of
+    :func:`latlondepth_to_xyz` on columns of [n, 3] arrays like its own (so that NumPy runs the same loops).  The
+    device forms ``((r * sin colat) * cos lon, (r * sin colat) * sin lon, r * cos colat)`` from them: that
+    function's rows bit for bit."""
+    def rows(values, col):
+        a = np.zeros((len(values), 3))
+        a[:, col] = np.asarray(values, dtype=np.float64)
+        return a
+
+    la, lo, de = rows(lat, 0), rows(lon, 1), rows(depth, 2)
+    colat = np.deg2rad(90.0 - la[:, 0])
+    lonr = np.deg2rad(lo[:, 1])
+    lat_table = np.ascontiguousarray(np.stack([np.sin(colat), np.cos(colat)], axis=1))
+    lon_table = np.ascontiguousarray(np.stack([np.cos(lonr), np.sin(lonr)], axis=1))
+    return lat_table, lon_table, np.ascontiguousarray(6371000.0 - de[:, 2])
+
+
+def _gll_model(mesh, parameters, make_spherical, ctx):
+    """(gll_points f64[E, P, 3] (host or device), shape_order, fields f64[C, E, P]) of a :class:`GllMesh` or of a Salvus
+    model (a file, or an h5py-like object read through :func:`multimesh_amd.io.load_hdf5_params_to_memory`, whose
+    parameters are picked by name from ``DIMENSION_LABELS``).  ``make_spherical`` maps a copy onto the mesh's 1-D sphere."""
+    parameters = mio.pick_parameters(parameters)
+    if not isinstance(mesh, GllMesh):
+        points, data, names = mio.load_hdf5_params_to_memory(mesh)
+        missing = [p for p in parameters if p not in names]
+        if missing:
+            raise ValueError(f"parameters {missing} are not in the model (it holds {names})")
+        P = points.shape[1]
+        order = _order_from_point_count(P, 3)
+        if points.ndim != 3 or points.shape[2] != 3 or (order + 1) ** 3 != P:
+            raise ValueError(f"MODEL/coordinates must be [nelem, (order+1)^3, 3], got {points.shape}")
+        wanted = set(parameters) | ({"z_node_1D"} if make_spherical and "z_node_1D" in names else set())
+        mesh = GllMesh(points, order, {p: data[:, names.index(p), :] for p in wanted})
+    fields = np.stack([np.asarray(mesh.element_nodal_fields[p], dtype=np.float64) for p in parameters])
+    gll_points = _sphere_mapped(mesh, ctx) if make_spherical else mesh.gll_points
+    return gll_points, mesh.shape_order, fields
+
+
+def _sample(mesh, parameters, lat, lon, depth, paired, make_spherical, nelem_to_search, tolerance, fill_value,
+            chunk_points, context):
+    """values f64[C, D, H] (host) and the number of targets without an element."""
+    ctx = context or default_context()
+    gll_points, order, fields = _gll_model(mesh, parameters, make_spherical, ctx)
+    lat_t, lon_t, radius = column_tables(lat, lon, depth)
+    values, nmissing = ctx.sample_columns_gll(order, gll_points, fields, lat_t, lon_t, radius, paired=paired,
+                                              nelem_to_search=nelem_to_search, tolerance=tolerance,
+                                              fill_value=fill_value, chunk_points=chunk_points)
+    return values.numpy(), nmissing
+
+
+class RegularGrid:
+    """What reference ``extract_regular_grid`` returns as an xarray Dataset (``utils.create_xarray_dataset``,
+    utils.py:619-646), without xarray: ``coords`` depth (m), latitude and longitude (deg); ``data_vars`` one f64
+    array per parameter with dims (depth, latitude, longitude); ``attrs`` {"radius_in_meters": 6371000.0};
+    ``nmissing`` targets outside the mesh, which hold ``fill_value``.  ``grid[name]`` returns a variable or a
+    coordinate."""
+
+    dims = DIMS
+
+    def __init__(self, depth, latitude, longitude, data_vars, nmissing=0, fill_value=np.nan):
+        self.coords = {"depth": np.asarray(depth, dtype=np.float64), "latitude": np.asarray(latitude, dtype=np.float64),
+                       "longitude": np.asarray(longitude, dtype=np.float64)}
+        shape = tuple(len(self.coords[d]) for d in DIMS)
+        self.data_vars = {}
+        for name, v in data_vars.items():
+            v = np.asarray(v, dtype=np.float64)
+            if v.shape != shape:
+                raise ValueError(f"{name}: shape {v.shape}, the grid is {shape}")
+            self.data_vars[name] = v
+        self.attrs = {"radius_in_meters": 6371000.0}
+        self.nmissing = int(nmissing)
+        self.fill_value = float(fill_value)
+
+    def __getitem__(self, name):
+        return self.data_vars[name] if name in self.data_vars else self.coords[name]
+
+    def to_netcdf(self, path):
+        """Classic netCDF with 64-bit offsets (``scipy.io.netcdf_file(version=2)``): dimensions and coordinate
+        variables depth / latitude / longitude with their ``units``, the global ``radius_in_meters``, one f64 variable
+        per parameter over (depth, latitude, longitude) with ``_FillValue`` = the fill value (NaN stays NaN).  A
+        variable the format cannot hold (4 GiB - 4 bytes at most) raises ``ValueError`` before anything is written."""
+        from scipy.io import netcdf_file
+
+        limit = 2 ** 32 - 4
+        for name, v in list(self.coords.items()) + list(self.data_vars.items()):
+            if v.nbytes > limit:
+                raise ValueError(f"variable {name!r} needs {v.nbytes} bytes; the 64-bit-offset netCDF format holds "
+                                 f"at most {limit} per variable: write a smaller grid (or fewer depths) per file")
+        clash = set(self.data_vars) & set(DIMS)
+        if clash:
+            raise ValueError(f"parameter names {sorted(clash)} clash with the coordinates")
+        with netcdf_file(path, "w", version=2) as f:
+            f.radius_in_meters = self.attrs["radius_in_meters"]
+            for d in DIMS:
+                f.createDimension(d, len(self.coords[d]))
+                c = f.createVariable(d, "d", (d,))
+                c[:] = self.coords[d]
+                c.units = UNITS[d]
+            for name, v in self.data_vars.items():
+                var = f.createVariable(name, "d", DIMS)
+                var._FillValue = self.fill_value
+                var[:] = v
+
+    @classmethod
+    def from_netcdf(cls, path):
+        """The inverse of :meth:`to_netcdf`, for any classic netCDF cube (``scipy.io.netcdf_file``): the coordinate
+        variables ``depth``, ``latitude`` and ``longitude``, and every other variable over exactly those three
+        dimensions, in any order -- transposed to (depth, latitude, longitude).  Values equal to a variable's
+        ``_FillValue`` or ``missing_value`` become NaN (``fill_value`` of the result is NaN); the global
+        ``radius_in_meters`` is kept when the file has one.  Other variables are ignored."""
+        from scipy.io import netcdf_file
+
+        with netcdf_file(path, "r", mmap=False) as f:
+            missing = [d for d in DIMS if d not in f.variables]
+            if missing:
+                raise ValueError(f"{path}: no coordinate variable(s) {missing}")
+            coords = {d: np.array(f.variables[d][:], dtype=np.float64).reshape(-1) for d in DIMS}
+            data_vars = {}
+            for name, var in f.variables.items():
+                if name in DIMS or sorted(var.dimensions) != sorted(DIMS):
+                    continue
+                v = np.array(var[:], dtype=np.float64)
+                for attr in ("_FillValue", "missing_value"):
+                    flag = getattr(var, attr, None)
+                    if flag is not None:
+                        flag = np.asarray(flag, dtype=np.float64).reshape(-1)
+                        v[np.isin(v, flag[~np.isnan(flag)])] = np.nan
+                data_vars[name] = np.ascontiguousarray(np.transpose(v, [var.dimensions.index(d) for d in DIMS]))
+            radius = getattr(f, "radius_in_meters", None)
+        grid = cls(coords["depth"], coords["latitude"], coords["longitude"], data_vars)
+        if radius is not None:
+            grid.attrs["radius_in_meters"] = float(np.asarray(radius).reshape(-1)[0])
+        return grid
+
+    def __repr__(self):
+        shape = ", ".join(f"{d}: {len(self.coords[d])}" for d in DIMS)
+        return f"<RegularGrid ({shape}) {list(self.data_vars)} nmissing={self.nmissing}>"
+
+
+def extract_regular_grid(mesh, parameters, lat_extent, lon_extent, depth_extent, save_to_netcdf=False, netcdf_path=None,
+                         *, make_spherical=False, nelem_to_search=25, tolerance=1.05, fill_value=np.nan,
+                         chunk_points=None, context=None):
+    """A GLL model on a regular latitude x longitude x depth grid (reference api.py:600-642, interpolator.py:1600-1646).
+
+    ``mesh``: a :class:`GllMesh`, a Salvus model file, or an h5py-like object (parameters picked by name from
+    ``MODEL/data``'s ``DIMENSION_LABELS``).  Extents are ``(min, max, num)`` through ``np.linspace``; latitudes are
+    geocentric degrees and depths metres below 6371 km (:func:`latlondepth_to_xyz`).  Every grid point is
+    interpolated as :meth:`Context.interpolate_gll` interpolates it (centroid kNN over ``nelem_to_search``,
+    acceptance at ``tolerance``); points outside the mesh hold ``fill_value``.  The points are generated on the
+    device in chunks (``chunk_points``; None: a fixed scratch budget).  ``make_spherical`` samples a copy of the mesh
+    mapped onto its 1-D sphere (:func:`map_to_sphere`); the caller's arrays are not changed.
+
+    Returns a :class:`RegularGrid` (the reference returns an xarray Dataset; xarray is not used here), or, with
+    ``save_to_netcdf``, writes it to ``netcdf_path`` (:meth:`RegularGrid.to_netcdf`) and returns None."""
+    lat = _extent(lat_extent, "lat_extent")
+    lon = _extent(lon_extent, "lon_extent")
+    depth = _extent(depth_extent, "depth_extent")
+    if save_to_netcdf and netcdf_path is None:
+        raise ValueError("save_to_netcdf needs a netcdf_path")
+    parameters = mio.pick_parameters(parameters)
+    values, nmissing = _sample(mesh, parameters, lat, lon, depth, False, make_spherical, nelem_to_search, tolerance,
+                               fill_value, chunk_points, context)
+    shape = (len(depth), len(lat), len(lon))
+    grid = RegularGrid(depth, lat, lon, {p: values[c].reshape(shape) for c, p in enumerate(parameters)}, nmissing,
+                       fill_value)
+    if save_to_netcdf:
+        grid.to_netcdf(netcdf_path)
+        return None
+    return grid
+
+
+def extract_depth_slice(mesh, depth_in_km, num, lat_extent=(-90.0, 90.0), lon_extent=(-180.0, 180.0), parameter="VSV",
+                        diff_percentage=False, *, make_spherical=False, nelem_to_search=25, tolerance=1.05,
+                        fill_value=np.nan, chunk_points=None, context=None):
+    """The ``num x num`` array reference ``plot_depth_slice`` plots (plotter.py:89-110): ``parameter`` at
+    ``depth_in_km`` on ``np.linspace`` latitudes and longitudes, in the reference's layout -- the points of
+    ``_create_depthslice`` (``np.meshgrid(lat, lon)``, raveled) reshaped to (num, num), i.e. ``[longitude, latitude]``.
+    ``diff_percentage``: ``(v - mean) / mean * 100`` with the mean over the points inside the mesh, and all zeros
+    when the largest deviation is below 0.1 % (a 1-D model), as the reference does.  Points outside the mesh hold
+    ``fill_value``."""
+    lat = _extent((lat_extent[0], lat_extent[1], num), "lat_extent")
+    lon = _extent((lon_extent[0], lon_extent[1], num), "lon_extent")
+    depth = np.array([depth_in_km * 1000.0])
+    values, _ = _sample(mesh, [parameter], lat, lon, depth, False, make_spherical, nelem_to_search, tolerance, np.nan,
+                        chunk_points, context)
+    vals = np.ascontiguousarray(values[0, 0].reshape(len(lat), len(lon)).T)   # [lat, lon] -> the reference's [lon, lat]
+    found = ~np.isnan(vals)
+    if diff_percentage and found.any():
+        mean = np.mean(vals[found])
+        vals = (vals - mean) / mean * 100.0
+        if np.max(np.abs(vals[found])) < 0.1:   # (reference plotter.py:108-109)
+            vals[found] = 0.0
+    vals[~found] = fill_value
+    return vals
+
+
+def extract_cross_section(mesh, parameters, lats, lons, depths, make_spherical=True, *, nelem_to_search=25,
+                          tolerance=1.05, fill_value=np.nan, chunk_points=None, context=None):
+    """A radius x path section, what reference ``plot_cross_section`` samples (plotter.py:360-391):
+    values f64[C, ndepth, npath] at the points (``lats[h]``, ``lons[h]``, ``depths[d]``) -> :func:`latlondepth_to_xyz`.
+
+    The reference builds its path as a WGS84 geodesic between two points (``greatcircle_points`` through
+    geographiclib) and converts it to geocentric latitudes; that library is not used here, so the caller passes the
+    path itself: ``lats`` (geocentric degrees) and ``lons`` of equal length, and ``depths`` in metres.
+    ``make_spherical`` (default True, as plotter.py:385-390) samples a copy of the mesh mapped onto its 1-D sphere.
+    Points outside the mesh hold ``fill_value``; the reference's per-radius percentage is plotting and not done."""
+    lats = np.atleast_1d(np.asarray(lats, dtype=np.float64))
+    lons = np.atleast_1d(np.asarray(lons, dtype=np.float64))
+    depths = np.atleast_1d(np.asarray(depths, dtype=np.float64))
+    if lats.ndim != 1 or lons.ndim != 1 or depths.ndim != 1 or len(lats) != len(lons):
+        raise ValueError("lats and lons must be 1-D of the same length, depths 1-D")
+    if not (np.isfinite(lats).all() and np.isfinite(lons).all() and np.isfinite(depths).all()):
+        raise ValueError("the path and the depths must be finite")
+    values, _ = _sample(mesh, parameters, lats, lons, depths, True, make_spherical, nelem_to_search, tolerance,
+                        fill_value, chunk_points, context)
+    return values
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# The other direction: a regular latitude x longitude x depth grid onto the points of a mesh (Context.sample_grid).  The
+# host only prepares the grid-sized arrays below; the mesh-sized work -- xyz -> lat/lon/depth, the cell search and the
+# trilinear values -- runs on the device.
+def _ascending_axis(name, values):
+    """(axis ascending, flipped?) of a coordinate; ``ValueError`` unless it is 1-D, finite and strictly monotone."""
+    a = np.array(values, dtype=np.float64)
+    if a.ndim != 1 or a.size < 1 or not np.isfinite(a).all():
+        raise ValueError(f"the {name} axis must be 1-D, finite and not empty")
+    d = np.diff(a)
+    if (d > 0).all():
+        return a, False
+    if (d < 0).all():
+        return np.ascontiguousarray(a[::-1]), True
+    raise ValueError(f"the {name} axis is not strictly monotone")
+
+
+def _is_global_longitude(lon, data):
+    """A longitude axis that goes once round: its span plus one mean spacing is 360 (within 1e-6 of a spacing), or its
+    span is 360 and the first and the last column hold the same data."""
+    if len(lon) < 2:
+        return False
+    span = lon[-1] - lon[0]
+    spacing = span / (len(lon) - 1)
+    if abs(span + spacing - 360.0) <= 1e-6 * spacing:
+        return True
+    return abs(span - 360.0) <= 1e-6 * spacing and np.array_equal(data[..., 0], data[..., -1], equal_nan=True)
+
+
+def prepare_regular_grid(grid, parameters=None, lon_periodic=None):
+    """``(depth, lat, lon, data f64[C, D, LA, LO], parameters, periodic)`` as :meth:`Context.sample_grid` takes them, from
+    a :class:`RegularGrid`: descending axes are flipped to ascending with their data, an axis that is not strictly
+    monotone or not finite raises ``ValueError``.  ``lon_periodic=None`` detects a global longitude axis
+    (:func:`_is_global_longitude`).  A periodic axis is shifted by a multiple of 360 to start in [-180, 180) when it
+    starts outside [-360, 180], and closed: when it ends before ``lon[0] + 360``, the column ``lon[0] + 360`` with the
+    data of column 0 is appended; an end within rounding of it becomes exactly that."""
+    parameters = list(grid.data_vars) if parameters is None else mio.pick_parameters(parameters)
+    unknown = [p for p in parameters if p not in grid.data_vars]
+    if unknown:
+        raise ValueError(f"parameters {unknown} are not in the grid (it holds {list(grid.data_vars)})")
+    axes, flipped = {}, {}
+    for d in DIMS:
+        axes[d], flipped[d] = _ascending_axis(d, grid.coords[d])
+    shape = tuple(len(axes[d]) for d in DIMS)
+    fields = []
+    for p in parameters:
+        v = np.asarray(grid.data_vars[p], dtype=np.float64)
+        if v.shape != shape:
+            raise ValueError(f"{p}: shape {v.shape}, the grid is {shape}")
+        fields.append(v)
+    data = np.stack(fields) if fields else np.zeros((0,) + shape)
+    for ax, d in enumerate(DIMS):
+        if flipped[d]:
+            data = np.flip(data, axis=ax + 1)
+    lon = axes["longitude"]
+    periodic = _is_global_longitude(lon, data) if lon_periodic is None else bool(lon_periodic)
+    if periodic:
+        if not -360.0 <= lon[0] <= 180.0:
+            lon = lon - 360.0 * np.floor((lon[0] + 180.0) / 360.0)
+        end = lon[0] + 360.0
+        spacing = (lon[-1] - lon[0]) / max(len(lon) - 1, 1)
+        if lon[-1] > end + 1e-6 * spacing:
+            raise ValueError("a periodic longitude axis must not span more than 360 degrees")
+        if len(lon) > 1 and abs(lon[-1] - end) <= 1e-6 * spacing:
+            lon = np.concatenate([lon[:-1], [end]])
+        else:
+            lon = np.concatenate([lon, [end]])
+            data = np.concatenate([data, data[..., :1]], axis=-1)
+        if not (np.diff(lon) > 0).all():
+            raise ValueError("the longitude axis cannot be closed at lon[0] + 360")
+    return axes["depth"], axes["latitude"], lon, np.ascontiguousarray(data), parameters, periodic
+
+
+def sample_regular_grid(grid, points, parameters=None, outside="fill", fill_value=np.nan, lon_periodic=None, context=None):
+    """A :class:`RegularGrid` sampled at ``points`` f64[N, 3] (metres, Earth-centred): trilinear in (depth, geocentric
+    latitude, longitude), with ``depth = 6371000 - |p|`` -- the inverse of :func:`latlondepth_to_xyz`, evaluated on the
+    device (:meth:`Context.sample_grid`, where the arithmetic is stated).  ``parameters``: names of ``grid.data_vars``
+    (None: all).  ``outside``: "fill" (points outside the grid get ``fill_value``) or "clamp" (the edge value extends).
+    ``lon_periodic``: None detects a global longitude axis (``0 ... 357.5``, or ``-180 ... 180`` with the first column
+    repeated), which then wraps; see :func:`prepare_regular_grid` for what is done to the axes.  A NaN node makes the
+    values of its eight cells NaN.  Returns (values f64[C, N], number of points outside the grid)."""
+    depth, lat, lon, data, _, periodic = prepare_regular_grid(grid, parameters, lon_periodic)
+    if outside == "keep":
+        raise ValueError('outside="keep" needs values to keep: use import_regular_grid, or Context.sample_grid with out')
+    ctx = context or default_context()
+    values, nmissing = ctx.sample_grid(points, data, depth, lat, lon, outside=outside, fill_value=fill_value,
+                                       lon_periodic=periodic)
+    return values.numpy(), nmissing
+
+
+def import_regular_grid(grid, mesh, parameters=None, outside="keep", fill_value=np.nan, lon_periodic=None,
+                        make_spherical=False, context=None):
+    """A gridded model onto a mesh: every node of ``mesh`` gets the value of ``grid`` at its (geocentric latitude,
+    longitude, depth = 6371000 - |p|), as :func:`sample_regular_grid` gives it.
+
+    ``grid``: a :class:`RegularGrid` or the path of a netCDF file (:meth:`RegularGrid.from_netcdf`).  ``mesh``:
+
+    * a :class:`GllMesh`: ``element_nodal_fields[p]`` becomes a new f64[E, P] array;
+    * a :class:`HexMesh`: nodal fields through ``attach_field``;
+    * a writable Salvus model -- an h5py-like object (:class:`multimesh_amd.io.MemoryH5`) or, with h5py, a path: the
+      columns of ``MODEL/data`` that ``DIMENSION_LABELS`` names are overwritten in place, every other column stays as it
+      is.  A parameter the labels do not hold raises ``ValueError`` before anything is written.
+
+    ``parameters``: None = every variable of the grid.  ``outside``: "keep" (default: nodes outside the grid keep the
+    mesh's value; the field must exist, else ``ValueError``), "fill" or "clamp".  ``make_spherical`` evaluates the
+    coordinates on a copy of the mesh mapped onto its 1-D sphere (:func:`map_to_sphere`), as the extract drivers do; the
+    mesh's own coordinates never change.  Returns the number of nodes outside the grid."""
+    if outside not in ("keep", "fill", "clamp"):
+        raise ValueError(f'outside must be "keep", "fill" or "clamp", got {outside!r}')
+    if not isinstance(grid, RegularGrid):
+        grid = RegularGrid.from_netcdf(grid)
+    depth, lat, lon, data, parameters, periodic = prepare_regular_grid(grid, parameters, lon_periodic)
+
+    def ctx():   # (asked for when the first kernel runs: what is wrong with the arguments is said without a device)
+        return context or default_context()
+
+    def run(points, existing):
+        """existing: name -> array of the points' leading shape (keep mode reads it) -> values f64[C, ...] (host)"""
+        lead = tuple(np.shape(points)[:-1]) if not isinstance(points, DeviceArray) else points.shape[:-1]
+        out = None
+        if outside == "keep":
+            out = np.ascontiguousarray(np.stack([np.asarray(existing[p], dtype=np.float64).reshape(lead)
+                                                 for p in parameters]) if parameters else np.zeros((0,) + lead))
+        values, nmissing = ctx().sample_grid(points, data, depth, lat, lon, outside=outside, fill_value=fill_value,
+                                             lon_periodic=periodic, out=out)
+        return values.numpy().reshape((len(parameters),) + lead), nmissing
+
+    if isinstance(mesh, (GllMesh, HexMesh)):
+        pts = np.asarray(_mesh_points(mesh))
+        if pts.shape[-1] != 3:
+            raise ValueError(f"import_regular_grid needs a 3-D mesh (points of shape {pts.shape})")
+        fields = mesh.element_nodal_fields if isinstance(mesh, GllMesh) else mesh.nodal_fields
+        if outside == "keep":
+            absent = [p for p in parameters if p not in fields]
+            if absent:
+                raise ValueError(f'outside="keep" keeps the mesh\'s values, but it has no field(s) {absent}')
+        values, nmissing = run(_sphere_mapped(mesh, ctx()) if make_spherical else pts, fields)
+        for c, p in enumerate(parameters):
+            if isinstance(mesh, GllMesh):
+                mesh.element_nodal_fields[p] = np.ascontiguousarray(values[c])
+            else:
+                mesh.attach_field(p, values[c])
+        return nmissing
+
+    with mio.open_h5(mesh, "r+") as f:
+        model = f["MODEL/data"]
+        names = mio.dimension_labels(model, 1)
+        unknown = [p for p in parameters if p not in names]
+        if unknown:
+            raise ValueError(f"parameters {unknown} are not in MODEL/data (it holds {names})")
+        points = np.array(f["MODEL/coordinates"][()], dtype=np.float64)
+        if points.ndim != 3 or points.shape[2] != 3:
+            raise ValueError(f"MODEL/coordinates must be [nelem, P, 3], got {points.shape}")
+        columns = {p: names.index(p) for p in parameters}
+        existing = {p: np.array(model[:, columns[p], :], dtype=np.float64) for p in parameters} if outside == "keep" else {}
+        if make_spherical:
+            if "z_node_1D" not in names:
+                raise ValueError("make_spherical needs the model's z_node_1D, which MODEL/data does not hold")
+            order = _order_from_point_count(points.shape[1], 3)
+            z = np.array(model[:, names.index("z_node_1D"), :], dtype=np.float64)
+            sample_at = _sphere_mapped(GllMesh(points, order, {"z_node_1D": z}), ctx())
+        else:
+            sample_at = points
+        values, nmissing = run(sample_at, existing)
+        for c, p in enumerate(parameters):
+            model[:, columns[p], :] = values[c]
+    return nmissing

@@ -35,6 +35,12 @@ class _Released:
         except Exception:
             pass
 
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        getattr(self, self._release)()
+
 
 class _Handle(_Released):
     """A library handle on a context; the subclass names the symbol that destroys it.  After ``free()`` it is None."""

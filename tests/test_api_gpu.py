@@ -680,3 +680,68 @@ def test_query_model_and_layered_driver_on_model_files(tmp_path):
     got_multi = to_multi["MODEL/data"][()]
     assert np.array_equal(got_multi[layer_b == 1], want_bbox.transpose(1, 0, 2)[layer_b == 1])
     assert np.array_equal(got_multi[layer_b == 0], before[layer_b == 0])
+
+
+def _printed(capsys):
+    """The lines printed since the last call, the wall-clock of the closing line replaced."""
+    import re
+
+    lines = [re.sub(r"^Finished in time: \S+ (seconds|minutes)$", r"Finished in time: <t> \1", line)
+             for line in capsys.readouterr().out.splitlines()]
+    with capsys.disabled():
+        print(lines)
+    return lines
+
+
+@pytest.mark.gpu
+def test_what_the_layered_drivers_print(tmp_path, capsys):
+    # the files of test_query_model_and_layered_driver_on_model_files; what each of the three drivers prints, line by
+    # line, without a stored operator, and for gll_2_gll_layered_multi_two with one: written, then re-applied
+    from multimesh_amd import api
+
+    src = synth.gll_mesh(5, 2, seed=1, dim=3)
+    tgt = synth.gll_mesh(6, 2, seed=7, dim=3)
+    layer_a = (src.mean(axis=1)[:, 2] > 0.5) * 1.0
+    layer_b = (tgt.mean(axis=1)[:, 2] > 0.5) * 1.0
+    fields = np.stack([synth.field_linear(src), synth.field_smooth(src.reshape(-1, 3)).reshape(src.shape[:2])], axis=1)
+    before = np.random.default_rng(2).normal(size=(tgt.shape[0], 2, tgt.shape[1]))
+    from_model = _gll_model(src, fields, ["VP", "VS"], fluid=1.0 - layer_a, layer=layer_a)
+    mesh_a = api.GllMesh(src, 2, {"VP": fields[:, 0], "VS": fields[:, 1]})
+    want = api.interpolate_gll_to_gll_layered(mesh_a, layer_a, tgt, layer_b, ["VP", "VS"], layers=[1], nelem_to_search=20,
+                                              existing=before.transpose(1, 0, 2)).transpose(1, 0, 2)
+    want_bbox = api.interpolate_gll_to_gll_layered(mesh_a, layer_a, tgt, layer_b, ["VP", "VS"], layers=[1],
+                                                   nelem_to_search=20, acceptance="bbox").transpose(1, 0, 2)
+    capsys.readouterr()
+
+    def receiver():
+        return _gll_model(tgt, before, ["VP", "VS"], layer=layer_b)
+
+    to_old = receiver()
+    api.gll_2_gll_layered(from_model, to_old, layers="nocore", parameters=["VP", "VS"])
+    lines = _printed(capsys)
+    assert lines == ["Initialization stage", "Interpolating layer: 1", "Finished in time: <t> seconds"]
+    assert np.array_equal(to_old["MODEL/data"][()], want_bbox)
+
+    to_multi = receiver()
+    api.gll_2_gll_layered_multi(from_model, to_multi, parameters=["VP", "VS"], threads=4)
+    lines = _printed(capsys)
+    assert lines == ["Initialization stage", "Interpolating layer: 1", "Finished in time: <t> seconds"]
+    assert np.array_equal(to_multi["MODEL/data"][()][layer_b == 1], want_bbox[layer_b == 1])
+    assert np.array_equal(to_multi["MODEL/data"][()][layer_b == 0], before[layer_b == 0])
+
+    to_two = receiver()
+    api.gll_2_gll_layered_multi_two(from_model, to_two, layers=[1], nelem_to_search=20, parameters="all")
+    lines = _printed(capsys)
+    assert lines == ["interpolating layer 1 ...", "Finished in time: <t> seconds"]
+    assert np.array_equal(to_two["MODEL/data"][()], want)
+
+    store = str(tmp_path / "interp_info")
+    expected = (["interpolating layer 1 ...", "Saving interpolation matrices", "Finished in time: <t> seconds"],
+                ["No need for looping, we have the matrices", "Finished in time: <t> seconds"])
+    for expected_lines in expected:                       # the first run writes the operator, the second re-applies it
+        to_stored = receiver()
+        api.gll_2_gll_layered_multi_two(from_model, to_stored, layers=[1], nelem_to_search=20, parameters="all",
+                                        stored_array=store)
+        lines = _printed(capsys)
+        assert lines == expected_lines
+        assert np.array_equal(to_stored["MODEL/data"][()], want)

@@ -296,6 +296,36 @@ def test_handles_may_be_freed_twice(ctx, d):
     assert other.handle is None
 
 
+def test_handles_are_released_at_the_end_of_a_with_block(ctx):
+    # a 2 x 2 x 2-element hex8 mesh: the transposed operator over its connectivity, the stiffness operator of its elements
+    nodes, conn = synth.hex_mesh(3, jitter=0.0)
+    weights = np.full(conn.shape, 0.125)
+    gll = np.ascontiguousarray(nodes[conn[:, [0, 1, 3, 2, 4, 5, 7, 6]]])             # exodus -> tensor order, order 1
+    with ctx.transpose_nodes(conn, weights, len(nodes)) as op:
+        assert op.handle and op.apply(np.ones(len(conn))).numpy().sum() == len(conn)
+    assert op.handle is None and op._keepalive is None
+    op.free()                                                                        # (a second release is harmless)
+    assert op.handle is None
+    with pytest.raises(ValueError, match="inside the block"):
+        with ctx.transpose_nodes(conn, weights, len(nodes)) as op:
+            raise ValueError("inside the block")
+    assert op.handle is None
+
+    with ctx.diffusion(1, gll) as dif:
+        assert np.abs(dif.smooth(np.ones(gll.shape[:2]), steps=0).numpy() - 1.0).max() < 1e-14     # (the node average of 1)
+        inner = dif._asm["op"]
+        assert inner.handle
+    assert dif._asm is None and dif.gp is None and inner.handle is None
+    dif.free()
+    assert dif.gp is None
+    with pytest.raises(ValueError, match="inside the block"):
+        with ctx.diffusion(1, gll) as dif:
+            dif.smooth(np.ones(gll.shape[:2]), steps=0)
+            inner = dif._asm["op"]
+            raise ValueError("inside the block")
+    assert dif._asm is None and dif.gp is None and inner.handle is None
+
+
 # -------------------------------------------------------------------------------------------------------- caller errors
 def test_a_callers_mistake_raises_value_error_with_the_librarys_text(ctx, d):
     with pytest.raises(ValueError, match="mm_radial_bins: the edges are not finite and strictly ascending"):

@@ -152,7 +152,7 @@ def test_depth_slice_follows_the_references_point_order(monkeypatch, num):
         seen.update(lat=lat, lon=lon, depth=depth, paired=paired, parameters=parameters)
         return np.arange(len(lat) * len(lon), dtype=np.float64).reshape(1, 1, -1), 0
 
-    monkeypatch.setattr(api, "_sample", fake_sample)
+    monkeypatch.setattr(api.grids, "_sample", fake_sample)
     vals = api.extract_depth_slice(object(), 35.5, num, lat_extent, lon_extent, parameter="VPV")
     assert vals.shape == (num, num) and not seen["paired"] and seen["parameters"] == ["VPV"]
     assert np.array_equal(seen["depth"], [35_500.0])
@@ -167,13 +167,13 @@ def test_depth_slice_follows_the_references_point_order(monkeypatch, num):
 def test_depth_slice_percentages_use_the_points_inside(monkeypatch):
     v = np.array([[1.0, 2.0], [np.nan, 3.0]])   # [lat, lon]; one point outside the mesh
 
-    monkeypatch.setattr(api, "_sample", lambda *a: (v.reshape(1, 1, -1).copy(), 1))
+    monkeypatch.setattr(api.grids, "_sample", lambda *a: (v.reshape(1, 1, -1).copy(), 1))
     got = api.extract_depth_slice(object(), 10.0, 2, diff_percentage=True, fill_value=-1.0)
     want = (v.T - 2.0) / 2.0 * 100.0
     want[np.isnan(want)] = -1.0
     assert np.array_equal(got, want)
     flat = np.array([[5.0, 5.0], [5.0, np.nan]])
-    monkeypatch.setattr(api, "_sample", lambda *a: (flat.reshape(1, 1, -1).copy(), 1))
+    monkeypatch.setattr(api.grids, "_sample", lambda *a: (flat.reshape(1, 1, -1).copy(), 1))
     got = api.extract_depth_slice(object(), 10.0, 2, diff_percentage=True)
     assert np.array_equal(np.isnan(got), np.isnan(flat.T)) and np.all(got[~np.isnan(got)] == 0.0)
 

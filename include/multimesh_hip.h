@@ -452,6 +452,55 @@ int mm_binned_weighted_sum(mm_context *ctx, const double *mass_d, const double *
 int mm_radial_model_apply(mm_context *ctx, const double *points_d, int64_t ngroups, int64_t P, const double *radius_d,
                           const double *values_d, int64_t m, int64_t ncomp, int mode, const double *in_d, double *out_d);
 
+/* KERNEL PRECONDITIONING: the cut-out around sources and receivers, exact order statistics of a field and clipping at bounds
+ * that are already on the device -- what stands between "sum the event kernels" and "smooth".  The reference has no counterpart.
+ *
+ * mm_point_taper: points_d f64[ngroups][P][3], 1 <= P <= 256 (P = 1: a point cloud, hex8 nodes); centres_d f64[K][3], inner_d
+ * and outer_d f64[K], 0 <= K <= 2^20; in_d and out_d f64[ncomp][ngroups * P], out_d may be in_d; weight_out_d f64[ngroups * P]
+ * or NULL; ncomp == 0 with weight_out_d is valid.  Per node x and centre k, every product, quotient and sum rounded on its own:
+ *   dx = x0 - c0, dy = x1 - c1, dz = x2 - c2;   d = sqrt((dx*dx + dy*dy) + dz*dz)
+ *   t_k = 0.0                      if d <= inner_k
+ *         1.0                      else if d >= outer_k
+ *         (s*s) * (3.0 - 2.0*s)    else, with s = (d - inner_k) / (outer_k - inner_k)
+ *   w = 1.0;  for k ascending:  if (t_k < w) w = t_k      (a NaN t_k never wins: a node with a NaN coordinate keeps w = 1.0)
+ *   out[c][i] = w * in[c][i]
+ * outer == inner is a hard cut: the order of the tests makes it well defined, nothing is divided.  A minimum of values <= 1
+ * does not depend on its order and a centre with d >= outer_k at every node of an element contributes exactly 1.0, so the
+ * kernel skips such centres per element by a bounding-box test that goes through the statement's own roundings (margin zero:
+ * mm_precondition.hip) -- bit for bit this statement.  An element that no centre reaches gets out = in and weight 1.0, and
+ * nothing at all is written for it when out_d == in_d and weight_out_d == NULL.
+ * Returns the number of nodes with w < 1 (an integer sum, the same on every run) or a negative MM_ERR_*: MM_ERR_ARG, with
+ * nothing written, for a null ctx or array, P outside [1, 256], a negative size, K > 2^20, a centre that is not finite, an
+ * inner or outer that is not finite, inner < 0 or outer < inner (the centres are checked on the device).  ngroups == 0 is
+ * valid.  Synchronises. */
+int64_t mm_point_taper(mm_context *ctx, const double *points_d, int64_t ngroups, int64_t P, const double *centres_d,
+                       const double *inner_d, const double *outer_d, int64_t K, int64_t ncomp, const double *in_d,
+                       double *out_d, double *weight_out_d);
+
+/* Exact order statistics of ncomp rows of n values: values_d f64[ncomp][n]; q_d f64[m], every q in [0, 1], 1 <= m <= 16;
+ * method 0 = lower, 1 = higher; out_d f64[ncomp][m]; nvalid_d int64[ncomp].  Per row:
+ *   NaNs are excluded; nvalid = the number of the others, which are ordered by the key of their bits u (absolute: of the bits
+ *   with the sign cleared):  key = sign(u) ? ~u : u | 2^63  as unsigned 64-bit integers -- the numeric order, -0.0 before +0.0;
+ *   pos = q * (double)(nvalid - 1), one rounded product;  rank = floor(pos) (lower) or ceil(pos) (higher);
+ *   out = the value whose key has that rank (absolute: |v|);  nvalid == 0: NaN.
+ * The result is defined by the order alone and exact for every input: a most-significant-digit radix select over the keys, one
+ * byte per pass, eight passes over the values for all m ranks and all rows together, integer histograms only.
+ * Scratch: 32 KiB of histograms and 0.6 KiB of state per row, whatever n is.
+ * MM_ERR_ARG (nothing is written) for a null ctx or array, a negative size, n >= 2^42, m outside [1, 16], an unknown method, a q
+ * that is NaN or outside [0, 1].  n == 0 gives NaN and nvalid 0; ncomp == 0 is valid.  Synchronises once before its kernels are
+ * queued (q is read back and checked on the host), not after: the results are on the device. */
+int mm_order_statistics(mm_context *ctx, const double *values_d, int64_t n, int64_t ncomp, int absolute, const double *q_d,
+                        int64_t m, int method, double *out_d, int64_t *nvalid_d);
+
+/* Clipping: out[c][i] = v < lo[c] ? lo[c] : (v > hi[c] ? hi[c] : v) for in_d, out_d f64[ncomp][n], out_d may be in_d.  lower_d
+ * and upper_d f64[ncomp] ON THE DEVICE (the output of mm_order_statistics with m = 1 as it stands), NULL: no bound on that
+ * side; symmetric = 1 takes lower_d == NULL and uses lo[c] = -upper_d[c].  A NaN passes through (both comparisons are false),
+ * -0.0 is kept against a bound of 0.0, a NaN bound bounds nothing.  changed_d int64[ncomp] or NULL: the number of values
+ * replaced (integer atomics, one per workgroup).  MM_ERR_ARG (nothing is written) for a null ctx or array, a negative size,
+ * symmetric other than 0 / 1, symmetric with lower_d or without upper_d.  n == 0 and ncomp == 0 are valid.  Not synchronising. */
+int mm_clamp(mm_context *ctx, const double *in_d, int64_t n, int64_t ncomp, const double *lower_d, const double *upper_d,
+             int symmetric, double *out_d, int64_t *changed_d);
+
 /* The streaming kernels of a preconditioned conjugate-gradient loop over ncomp independent systems of n unknowns each
  * (vectors f64[ncomp][n]), whose scalars never leave the device.  state_d f64[ncomp][8] holds, per system, the slots below:
  * the dots are written into MM_PCG_RZ, MM_PCG_PAP and MM_PCG_BB by mm_weighted_sum (one call per system with ncomp = 1).

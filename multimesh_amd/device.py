@@ -20,6 +20,8 @@ from .synth import gll_derivative_matrix, gll_order_table, gll_weights_1d   # (V
 
 # MM_KNN_RAN_* in bit order
 KNN_KERNELS = ("lane", "strip", "cell", "list", "generic", "levels", "tree", "one_pass")
+#: centres per LDS batch of the taper kernel (kBatch in csrc/mm_precondition.hip)
+POINT_TAPER_BATCH = 256
 
 _NP2ITEM = {np.dtype(np.float64): 8, np.dtype(np.int64): 8, np.dtype(np.int32): 4, np.dtype(np.uint8): 1}
 
@@ -733,6 +735,95 @@ class Context(_Released):
                                             src.ptr if src else None, out.ptr)
         self._check_args(rc, "mm_radial_model_apply")
         return out
+
+    # ---- kernel preconditioning: the cut-out weight, order statistics, clipping -------------------------
+    def point_taper(self, points, centres, inner, outer, values_in=None, out=None, want_weight=False):
+        """The cut-out around ``centres`` (``mm_point_taper``): per node the least, over the centres, of a smoothstep of the
+        distance -- 0 within ``inner[k]``, 1 beyond ``outer[k]`` -- times the values.  points f64[G, P, 3] (P nodes per
+        element, at most 256) or f64[N, 3]; centres f64[K, 3], inner and outer f64[K] (K may be 0); ``values_in``
+        f64[C, G * P] (any shape of that size per component, or one component of the points' shape) or None; ``out`` may
+        be ``values_in``: elements that no centre reaches are then not written at all.  Returns (values f64[C, G, P] or
+        [C, N] on the device, or None without ``values_in``; the number of nodes with weight < 1) and, with
+        ``want_weight``, the weight f64[G, P] / [N] as a third entry.  Centres or radii that are not finite, a negative
+        inner, an outer below its inner raise ``ValueError`` and nothing is written."""
+        pts = self.asdevice(points, np.float64)
+        if len(pts.shape) not in (2, 3) or pts.shape[-1] != 3:
+            raise ValueError("points must be [G, P, 3] or [N, 3]")
+        ngroups, P = (pts.shape[0], pts.shape[1]) if len(pts.shape) == 3 else (pts.shape[0], 1)
+        if not 1 <= P <= 256:
+            raise ValueError("P must lie in [1, 256]")
+        c = self.asdevice(centres, np.float64)
+        ri, ro = self.asdevice(inner, np.float64), self.asdevice(outer, np.float64)
+        if len(c.shape) != 2 or c.shape[1] != 3 or ri.shape != (c.shape[0],) or ro.shape != (c.shape[0],):
+            raise ValueError("centres must be [K, 3], inner and outer [K]")
+        n = ngroups * P
+        src, ncomp = None, 0
+        if values_in is not None:
+            src = self.asdevice(values_in, np.float64)
+            ncomp = 1 if src.shape == pts.shape[:-1] else src.shape[0]
+            if src.size != ncomp * n:
+                raise ValueError("values_in must hold one value per component and node")
+            out = self._out(out, (ncomp,) + pts.shape[:-1], "out must hold one value per component and node", size_only=True)
+        elif out is not None:
+            raise ValueError("out without values_in")
+        elif not want_weight:
+            raise ValueError("ask for the weight or pass values_in")
+        weight = self.empty(pts.shape[:-1], np.float64) if want_weight else None
+        rc = self.lib.mm_point_taper(self.handle, pts.ptr, ngroups, P, c.ptr, ri.ptr, ro.ptr, c.shape[0], ncomp,
+                                     src.ptr if src else None, out.ptr if src else None, weight.ptr if weight else None)
+        self._check_args(rc, "mm_point_taper")
+        return (out, int(rc), weight) if want_weight else (out, int(rc))
+
+    def order_statistics(self, values, q, absolute=False, method="lower"):
+        """Exact order statistics (``mm_order_statistics``): values f64[C, ...] (every row read flat) or f64[n] (one row),
+        q f64[m] in [0, 1], 1 <= m <= 16.  NaNs are left out; of the ``nvalid`` others (``absolute``: of their absolute
+        values) the one of rank ``floor(q * (nvalid - 1))`` (``method="lower"``) or ``ceil`` (``"higher"``) in the numeric
+        order, -0.0 before +0.0; NaN for a row without a valid value.  Returns (out f64[C, m], nvalid int64[C]), both on
+        the device: nothing is read back."""
+        v = self.asdevice(values, np.float64)
+        if len(v.shape) == 0:
+            raise ValueError("values must be [C, ...] or [n]")
+        ncomp = v.shape[0] if len(v.shape) > 1 else 1
+        n = v.size // ncomp if ncomp else 0
+        if method not in ("lower", "higher"):
+            raise ValueError('method must be "lower" or "higher"')
+        if not isinstance(q, DeviceArray):
+            q = np.atleast_1d(np.asarray(q, dtype=np.float64))
+            if q.ndim != 1 or not 1 <= q.size <= 16 or not ((q >= 0.0) & (q <= 1.0)).all():
+                raise ValueError("q must hold between 1 and 16 values in [0, 1]")
+        qd = self.asdevice(q, np.float64)
+        m = qd.size
+        out = self.empty((ncomp, m), np.float64)
+        nvalid = self.empty((ncomp,), np.int64)
+        rc = self.lib.mm_order_statistics(self.handle, v.ptr, n, ncomp, 1 if absolute else 0, qd.ptr, m,
+                                          0 if method == "lower" else 1, out.ptr, nvalid.ptr)
+        self._check_args(rc, "mm_order_statistics")
+        return out, nvalid
+
+    def clamp(self, values, lower=None, upper=None, symmetric=False, out=None, want_count=True):
+        """``v < lo ? lo : (v > hi ? hi : v)`` (``mm_clamp``) for values f64[C, ...] (every row read flat) or f64[n] with
+        bounds f64[C] that are on the device already (a :class:`DeviceArray`, such as a column of
+        :meth:`order_statistics`) or are copied there; None: no bound on that side; ``symmetric``: ``lower`` must be None
+        and is ``-upper``.  A NaN passes through, -0.0 is kept.  ``out`` may be ``values``.  Returns (out on the device,
+        changed int64[C] on the device -- the number of values replaced -- or None without ``want_count``)."""
+        v = self.asdevice(values, np.float64)
+        if len(v.shape) == 0:
+            raise ValueError("values must be [C, ...] or [n]")
+        ncomp = v.shape[0] if len(v.shape) > 1 else 1
+        n = v.size // ncomp if ncomp else 0
+        if symmetric and (lower is not None or upper is None):
+            raise ValueError("symmetric takes upper alone")
+        lo = None if lower is None else self.asdevice(lower, np.float64)
+        hi = None if upper is None else self.asdevice(upper, np.float64)
+        for b in (lo, hi):
+            if b is not None and b.size != ncomp:
+                raise ValueError("a bound per component")
+        out = self._out(out, v.shape, "out must hold one value per value", size_only=True)
+        changed = self.empty((ncomp,), np.int64) if want_count else None
+        rc = self.lib.mm_clamp(self.handle, v.ptr, n, ncomp, lo.ptr if lo else None, hi.ptr if hi else None,
+                               1 if symmetric else 0, out.ptr, changed.ptr if changed else None)
+        self._check_args(rc, "mm_clamp")
+        return out, changed
 
     # ---- diffusion: the stiffness operator and the smoothing it gives -------------------------------
     def diffusion(self, shape_order, gll_points, kappa_h=1.0, kappa_r=None):

@@ -89,6 +89,9 @@ SIGNATURES = {
     "mm_radial_bins": (i64, (vp, vp, i64, vp, i64, vp, vp)),
     "mm_binned_weighted_sum": (i32, (vp, vp, vp, vp, i64, i64, i64, i32, vp, vp)),
     "mm_radial_model_apply": (i32, (vp, vp, i64, i64, vp, vp, i64, i64, i32, vp, vp)),
+    "mm_point_taper": (i64, (vp, vp, i64, i64, vp, vp, vp, i64, i64, vp, vp, vp)),
+    "mm_order_statistics": (i32, (vp, vp, i64, i64, i32, vp, i64, i32, vp, vp)),
+    "mm_clamp": (i32, (vp, vp, i64, i64, vp, vp, i32, vp, vp)),
     "mm_pcg_combine": (i32, (vp, vp, vp, f64, vp, i64, i64, vp)),
     "mm_pcg_scalars": (i32, (vp, vp, i64, i32, f64, vp)),
     "mm_pcg_direction": (i32, (vp, vp, vp, i64, i64, vp)),

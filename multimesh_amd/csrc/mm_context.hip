@@ -148,7 +148,8 @@ extern "C" int mm_context_create(int device, void *hip_stream, mm_context **out)
         if (fp && (fp[0] == 't' || fp[0] == 'T' || fp[0] == '1')) ctx->fp_mode = MM_FP_TOL;
     }
     hipError_t e = mm_raw_alloc(device, (void **)&ctx->d_counters, 64 * sizeof(i64));
-    if (e == hipSuccess) e = hipMemset(ctx->d_counters, 0, 64 * sizeof(i64));
+    if (e == hipSuccess) e = hipMemsetAsync(ctx->d_counters, 0, 64 * sizeof(i64), ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e == hipSuccess) e = hipHostMalloc((void **)&ctx->h_counters, 64 * sizeof(i64), 0);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_misc, hipEventDisableTiming);
     if (e != hipSuccess) {

@@ -411,14 +411,25 @@ class Context(_Released):
             check(self.lib.mm_copy_h2d(self.handle, d.ptr, a.ctypes.data, a.nbytes), "mm_copy_h2d")
         return d
 
+    @staticmethod
+    def _on_host(x):
+        """Whether ``x`` names a ``device`` that is not a GPU (a CPU tensor); no ``device`` at all: not on the host."""
+        device = getattr(x, "device", None)
+        return device is not None and getattr(device, "type", "cuda") != "cuda"
+
     def asdevice(self, x, dtype):
-        """NumPy -> copy to HBM; DeviceArray / torch-like -> wrap without copying."""
+        """NumPy -> copy to HBM; DeviceArray / torch-like on this GPU -> wrap without copying.  A torch-like object whose
+        ``device`` is not a GPU is copied like NumPy; one on another GPU raises ``ValueError``; one without a ``device``
+        is device memory at the caller's word."""
         dtype = np.dtype(dtype)
         if isinstance(x, DeviceArray):
             if x.dtype != dtype:
                 raise TypeError(f"expected {dtype}, got {x.dtype}")
             return x
-        if hasattr(x, "data_ptr") and hasattr(x, "shape"):
+        if hasattr(x, "data_ptr") and hasattr(x, "shape") and not self._on_host(x):
+            index = getattr(getattr(x, "device", None), "index", None)
+            if index is not None and index != self.device:
+                raise ValueError(f"tensor lives on GPU {index}, this context on GPU {self.device}")
             name = str(getattr(x, "dtype", "")).replace("torch.", "")
             if name and np.dtype(name) != dtype:
                 raise TypeError(f"expected {dtype}, got {name}")
@@ -436,6 +447,11 @@ class Context(_Released):
         ``size_only``: that many values in any shape) or ``message`` is raised; no message: the caller's word."""
         if out is None:
             return self.empty(shape, np.float64)
+        if not isinstance(out, DeviceArray):             # (a copy of it would receive the result and be lost)
+            index = getattr(getattr(out, "device", None), "index", None)
+            if not (hasattr(out, "data_ptr") and hasattr(out, "shape")) or self._on_host(out) or \
+                    (index is not None and index != self.device):
+                raise ValueError(f"out must live on GPU {self.device}")
         out = self.asdevice(out, np.float64)
         if message and (out.size != int(np.prod(shape, dtype=np.int64)) if size_only else out.shape != tuple(shape)):
             raise ValueError(message)

@@ -13,6 +13,8 @@ group), the computation is the C-ABI library.
 """
 from __future__ import annotations
 
+import contextlib
+
 import numpy as np
 
 
@@ -71,6 +73,25 @@ def interpolate_sharded(points, local_interpolate, group=None):
     return gathered, int(nf.item())
 
 
+@contextlib.contextmanager
+def _on_captured_stream(handle, device):
+    """The library call inside runs on the stream ``handle`` that a context captured when it was built.  Entered under
+    another current stream, the captured one first waits for what the current one holds (the points may still be in
+    production there), and the current one afterwards waits for the call; the same stream: nothing is added."""
+    import torch
+
+    current = torch.cuda.current_stream(device)
+    if current.cuda_stream == handle:
+        yield
+        return
+    captured = torch.cuda.ExternalStream(handle, device=device) if handle else torch.cuda.default_stream(device)
+    captured.wait_stream(current)
+    try:
+        yield
+    finally:
+        current.wait_stream(captured)
+
+
 class HipShardInterpolator:
     """``local_interpolate`` for :func:`interpolate_sharded` backed by the HIP library: keeps the
     replicated source mesh resident on this rank's GPU and runs the fused hot path per shard."""
@@ -83,7 +104,8 @@ class HipShardInterpolator:
         if device_index is None:
             device_index = torch.cuda.current_device()
         self.device = torch.device("cuda", device_index)
-        self.ctx = Context(device_index, stream=torch.cuda.current_stream(self.device).cuda_stream)
+        self.stream = torch.cuda.current_stream(self.device).cuda_stream
+        self.ctx = Context(device_index, stream=self.stream)
         self.k = nelem_to_search
         as_dev = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a, dtype=dt)).to(self.device)  # noqa: E731
         self.nodes = as_dev(nodes, np.float64)
@@ -98,8 +120,9 @@ class HipShardInterpolator:
         out = torch.empty((pts.shape[0], self.fields.shape[0]), dtype=torch.float64, device=self.device)
         if pts.shape[0] == 0:
             return out, 0
-        _, nfailed = self.ctx.interpolate_hex8(self.nodes, self.conn, pts, self.fields,
-                                               nelem_to_search=self.k, out=out)
+        with _on_captured_stream(self.stream, self.device):
+            _, nfailed = self.ctx.interpolate_hex8(self.nodes, self.conn, pts, self.fields,
+                                                   nelem_to_search=self.k, out=out)
         return out, nfailed
 
 
@@ -117,7 +140,8 @@ class HipShardGllInterpolator:
         if device_index is None:
             device_index = torch.cuda.current_device()
         self.device = torch.device("cuda", device_index)
-        self.ctx = Context(device_index, stream=torch.cuda.current_stream(self.device).cuda_stream)
+        self.stream = torch.cuda.current_stream(self.device).cuda_stream
+        self.ctx = Context(device_index, stream=self.stream)
         self.order, self.k, self.tolerance = int(shape_order), nelem_to_search, float(tolerance)
         as_dev = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(self.device)  # noqa: E731
         self.gll_points = as_dev(gll_points)                       # [E, P, dim]
@@ -132,6 +156,7 @@ class HipShardGllInterpolator:
         out = torch.empty((pts.shape[0], self.fields.shape[0]), dtype=torch.float64, device=self.device)
         if pts.shape[0] == 0:
             return out, 0
-        _, missing = self.ctx.interpolate_gll(self.order, self.gll_points, pts, self.fields,
-                                              nelem_to_search=self.k, tolerance=self.tolerance, out=out)
+        with _on_captured_stream(self.stream, self.device):
+            _, missing = self.ctx.interpolate_gll(self.order, self.gll_points, pts, self.fields,
+                                                  nelem_to_search=self.k, tolerance=self.tolerance, out=out)
         return out, missing

@@ -520,6 +520,14 @@ def test_fluid_solid_fix_equals_the_reference_statements():
         if solid_elements[elem]:
             want[elem, :, :] = new_values[elem, :, :]
     assert np.array_equal(got, want)
+    # the count the device pass returns: the solid elements restored under those statements
+    from multimesh_amd.device import Context
+
+    restored = sum(1 for elem in np.unique(zero_vs[0]) if solid_elements[elem])
+    with Context(0) as ctx:
+        fixed = ctx.to_device(values)
+        assert ctx.fluid_solid_fix(fixed, new_values, solid_elements, vs_index) == restored > 0
+        assert np.array_equal(fixed.numpy(), want)
 
 
 # ------------------------------------------------------------------------------- section 8f-2: file-level drivers

@@ -153,6 +153,13 @@ int mm_zero_async(mm_context *ctx, void *dst_d, size_t bytes);
 // n (<= 64) 64-bit words of device memory into the context's pinned mirror, by a kernel on ctx->stream.
 int mm_mirror_async(mm_context *ctx, long long *dst_pinned, const long long *src_d, int n);
 
+// The small counter readback of a call, words [slot, slot + n) of d_counters (the table of slots is below).  begin: their
+// device address, zeroed by mm_zero_async.  end: hipGetLastError for the launches in between, mm_mirror_async, one
+// hipStreamSynchronize (after a failure too: the caller may free what its kernels used); the n words in the pinned mirror.
+// Both return null after a failure, with the error set.
+unsigned long long *mm_counters_begin(mm_context *ctx, int slot, int n);
+const i64 *mm_counters_end(mm_context *ctx, int slot, int n);
+
 // Cached buffer of at least `bytes` for `slot` (grows by reallocation, after a stream sync).
 int mm_buffer_get(mm_context *ctx, int slot, size_t bytes, void **out);
 

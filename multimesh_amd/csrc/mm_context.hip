@@ -268,7 +268,8 @@ __global__ __launch_bounds__(256) void zero_fill_kernel(unsigned char *__restric
 int mm_zero_async(mm_context *ctx, void *dst_d, size_t bytes)
 {
     if (bytes == 0) return MM_OK;
-    if ((reinterpret_cast<uintptr_t>(dst_d) & 15) != 0) {   // (never on the hot path)
+    if (bytes >= 16 && (reinterpret_cast<uintptr_t>(dst_d) & 15) != 0) {   // (never on the hot path; a span below 16 bytes
+                                                                            // is written byte by byte wherever it starts)
         MM_HIP_CHECK(hipMemsetAsync(dst_d, 0, bytes, ctx->stream));
         return MM_OK;
     }
@@ -292,6 +293,26 @@ int mm_mirror_async(mm_context *ctx, long long *dst_pinned, const long long *src
     hipLaunchKernelGGL(mirror_words_kernel, dim3(1), dim3(64), 0, ctx->stream, src_d, dst_pinned, n < 64 ? n : 64);
     MM_HIP_CHECK(hipGetLastError());
     return MM_OK;
+}
+
+unsigned long long *mm_counters_begin(mm_context *ctx, int slot, int n)
+{
+    i64 *words = ctx->d_counters + slot;
+    return mm_zero_async(ctx, words, (size_t)n * sizeof(i64)) == MM_OK ? (unsigned long long *)words : nullptr;
+}
+
+const i64 *mm_counters_end(mm_context *ctx, int slot, int n)
+{
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) mm_set_error(MM_ERR_HIP, "a kernel launch failed: %s", hipGetErrorString(e));
+    bool ok = e == hipSuccess && mm_mirror_async(ctx, (long long *)ctx->h_counters + slot,
+                                                 (const long long *)ctx->d_counters + slot, n) == MM_OK;
+    const hipError_t s = hipStreamSynchronize(ctx->stream);   // (after a failure too)
+    if (ok && s != hipSuccess) {
+        mm_set_error(MM_ERR_HIP, "hipStreamSynchronize -> %s", hipGetErrorString(s));
+        ok = false;
+    }
+    return ok ? ctx->h_counters + slot : nullptr;
 }
 
 // ---- scratch -----------------------------------------------------------------------

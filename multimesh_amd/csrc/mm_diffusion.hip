@@ -20,13 +20,12 @@
 // LDS (one array per direction), a barrier, the transposed derivative from LDS, one store.  Every buffer is single: two
 // barriers per tile and component; the next step's loads are issued before the current one is computed.
 // HBM bytes per node: 24 + 16 C, plus 8 per kappa array.
-#include "mm_common.h"
 #include "mm_gll_tile.h"
 
 namespace {
 
 using gll::ipow;
-using gll::kThreads;
+using mm_stream::kThreads;
 constexpr int kStateStride = 8;    // doubles per component of the PCG state block (MM_PCG_* in the header)
 
 template <int ORDER, int DIM, bool ANISO>
@@ -268,11 +267,7 @@ __global__ __launch_bounds__(kThreads) void pcg_advance_kernel(const double *__r
     }
 }
 
-unsigned stream_blocks(i64 n)
-{
-    const i64 blocks = (n + kThreads - 1) / kThreads;
-    return (unsigned)(blocks < 8192 ? blocks : 8192);
-}
+unsigned stream_blocks(i64 n) { return mm_blocks(n, kThreads, 8192); }
 
 }  // namespace
 

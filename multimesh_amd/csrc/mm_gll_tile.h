@@ -2,7 +2,9 @@
 // of that geometry: J, det, G = J^-1, the unit radius, the reference gradient g and the physical gradient gr = G g.
 // Who uses what: gll_mass_kernel (mm_mass.hip) and gll_gradient_kernel (mm_gradient.hip) use all of it; the stiffness
 // kernel gll_diffusion_kernel (mm_diffusion.hip) uses the constants and the geometry functions and keeps its own lane
-// set-up, loads and stores (see its header comment); mm_order.hip uses kThreads, kMaxBlocks, ipow and grid_size.
+// set-up, loads and stores (see its header comment); mm_order.hip uses kThreads, kMaxBlocks, ipow and grid_size;
+// radial_apply_kernel (mm_radial.hip) and point_taper_kernel (mm_precondition.hip) use RunTile, the bookkeeping of the
+// same tile for a P known only at run time.
 // Every expression here is under a bit-parity contract with a NumPy statement (tests/mass_cases.py, diffusion_cases.py,
 // gradient_cases.py) and its order of operations is published in include/multimesh_hip.h: every product is rounded on
 // its own (-ffp-contract=off), every sum starts from its first term and adds in ascending a.
@@ -24,21 +26,35 @@
 // stride 3 doubles between nodes, odd, so the banks of 32 consecutive nodes are distinct as well.
 #pragma once
 
-#include "mm_common.h"
+#include "mm_stream.h"
 
 namespace gll {
 
-constexpr int kThreads = 256;
+using mm_stream::kThreads;
 constexpr i64 kMaxBlocks = 2048;   // 256 CUs x 8 resident blocks; blocks stride over the rest
 
 constexpr int ipow(int b, int e) { return e == 0 ? 1 : b * ipow(b, e - 1); }
 
 // blocks of a launch over nelem elements, `tile` of them per block and step
-inline unsigned grid_size(i64 nelem, int tile)
-{
-    const i64 ntiles = (nelem + tile - 1) / tile;
-    return (unsigned)(ntiles < kMaxBlocks ? ntiles : kMaxBlocks);
-}
+inline unsigned grid_size(i64 nelem, int tile) { return mm_blocks(nelem, tile, kMaxBlocks); }
+
+// The tile for a run-time P: 256 / P whole elements (groups of P points) per block and step.  Bookkeeping only -- as for
+// the compile-time tile below, the load into LDS (a loop, or registers staged a step ahead) is each kernel's own.
+struct RunTile {
+    i64 ngroups;
+    int P;
+    int tile;     // whole elements per block and step
+    int el;       // this lane's element of the tile: the same one in every tile
+    i64 ntiles;
+
+    __device__ __forceinline__ RunTile(i64 ngroups_, int P_)
+        : ngroups(ngroups_), P(P_), tile(kThreads / P_), el((int)threadIdx.x / P_), ntiles((ngroups_ + tile - 1) / tile) {}
+    // elements and nodes of tile t (the last one may hold fewer elements), its first node, its coordinates in points[.][3]
+    __device__ __forceinline__ int nel(i64 t) const { return (int)(ngroups - t * tile < tile ? ngroups - t * tile : tile); }
+    __device__ __forceinline__ int nnodes(i64 t) const { return nel(t) * P; }
+    __device__ __forceinline__ i64 first_node(i64 t) const { return t * (i64)tile * P; }
+    __device__ __forceinline__ const double *coords(const double *points, i64 t) const { return points + first_node(t) * 3; }
+};
 
 template <int ORDER, int DIM>
 struct Tile {
@@ -207,7 +223,7 @@ struct Tile {
     {
         const int tid = threadIdx.x;
         const double x0 = xs[tid * DIM], x1 = xs[tid * DIM + 1], x2 = xs[tid * DIM + 2];
-        const double rn = sqrt((x0 * x0 + x1 * x1) + x2 * x2);
+        const double rn = mm_norm3(x0, x1, x2);
         const bool off_centre = rn > 0.0;
         rh[0] = off_centre ? x0 / rn : 0.0;
         rh[1] = off_centre ? x1 / rn : 0.0;

@@ -1,10 +1,10 @@
 // A regular latitude x longitude x depth grid sampled at arbitrary points: the import direction of the regular-grid
 // drivers (mm_sample_columns_gll is the extract direction).  One lane per point in a grid-stride loop:
 //
-//   r = sqrt((x*x + y*y) + z*z)    depth = 6371000 - r    lat = 90 - acos(r > 0 ? z / r : 0) * (180 / pi)
+//   r = mm_norm3(x, y, z)    depth = 6371000 - r    lat = 90 - acos(r > 0 ? z / r : 0) * (180 / pi)
 //   lon = atan2(y, x) * (180 / pi), wrapped once into [lon[0], lon[0] + 360) on a periodic axis
 //   per axis: i = clip(upper_bound(a, v) - 1, 0, n - 2), t = (v - a[i]) / (a[i + 1] - a[i]); a length-1 axis is constant
-//   value = lerp over longitude (4), then latitude (2), then depth (1), lerp(t, p, q) = (1 - t) * p + t * q
+//   value = lerp over longitude (4), then latitude (2), then depth (1), by mm_lerp(t, p, q)
 //
 // Every product, quotient and sum is rounded on its own (the library is built with -ffp-contract=off), so the values are
 // bit for bit the NumPy statement of include/multimesh_hip.h evaluated on the (lat, lon, depth) this kernel computed;
@@ -13,15 +13,15 @@
 // Traffic: 24 B read + 8 B per component written per point, plus the eight corners per component, which neighbouring
 // points share (mesh points are ordered in space, so a wave's corners sit in a few cache lines of a cube that is small
 // beside the points).  The axes are staged in LDS when the three together fit kAxisLds doubles and bisected there;
-// longer axes are bisected in global memory.  The outside count is an integer: summed per workgroup, then one atomic per
-// workgroup, so it does not depend on the order of arrival.
-#include "mm_common.h"
+// longer axes are bisected in global memory.  The outside count is an integer sum (mm_count_to): it does not depend on the
+// order of arrival.
+#include "mm_stream.h"
 
 #include <limits.h>
 
 namespace {
 
-constexpr int kThreads = 256;
+using mm_stream::kThreads;
 constexpr i64 kMaxBlocks = 2048;    // 256 CUs x 8 workgroups; the grid-stride loop takes the rest
 constexpr int kAxisLds = 2048;      // doubles of LDS for the three axes together (16 KiB: eight workgroups per CU)
 constexpr double kEarthRadius = 6371000.0;
@@ -62,15 +62,7 @@ __device__ __forceinline__ Cell find_cell(const double *a, int n, double v, bool
         c.inside = v >= lo && v <= hi;
         if (!c.inside) return c;
     }
-    int b = 0, e = n;   // first index whose node is greater than v
-    while (b < e) {
-        const int mid = (b + e) >> 1;
-        if (!(v < a[mid]))
-            b = mid + 1;
-        else
-            e = mid;
-    }
-    int i = b - 1;
+    int i = mm_upper_bound(a, 0, n, v) - 1;
     i = i < 0 ? 0 : i;
     i = i > n - 2 ? n - 2 : i;
     c.i = i;
@@ -79,18 +71,16 @@ __device__ __forceinline__ Cell find_cell(const double *a, int n, double v, bool
     return c;
 }
 
-__device__ __forceinline__ double lerp(double t, double p, double q) { return (1.0 - t) * p + t * q; }
-
 __device__ __forceinline__ double sample_one(const double *__restrict__ g, i64 row, i64 plane, const Cell &cd,
                                              const Cell &ca, const Cell &co)
 {
     const double *g0 = g + (i64)cd.i * plane, *g1 = g + (i64)cd.i1 * plane;
     const i64 r0 = (i64)ca.i * row, r1 = (i64)ca.i1 * row;
-    const double a00 = lerp(co.t, g0[r0 + co.i], g0[r0 + co.i1]);
-    const double a01 = lerp(co.t, g0[r1 + co.i], g0[r1 + co.i1]);
-    const double a10 = lerp(co.t, g1[r0 + co.i], g1[r0 + co.i1]);
-    const double a11 = lerp(co.t, g1[r1 + co.i], g1[r1 + co.i1]);
-    return lerp(cd.t, lerp(ca.t, a00, a01), lerp(ca.t, a10, a11));
+    const double a00 = mm_lerp(co.t, g0[r0 + co.i], g0[r0 + co.i1]);
+    const double a01 = mm_lerp(co.t, g0[r1 + co.i], g0[r1 + co.i1]);
+    const double a10 = mm_lerp(co.t, g1[r0 + co.i], g1[r0 + co.i1]);
+    const double a11 = mm_lerp(co.t, g1[r1 + co.i], g1[r1 + co.i1]);
+    return mm_lerp(cd.t, mm_lerp(ca.t, a00, a01), mm_lerp(ca.t, a10, a11));
 }
 
 // NC: components unrolled (1..4), 0: a loop over args.ncomp.  LDS_AXES: the axes are copied to LDS first.
@@ -98,7 +88,6 @@ template <int NC, bool LDS_AXES>
 __global__ __launch_bounds__(kThreads) void grid_sample_kernel(const GridArgs args)
 {
     __shared__ double s_axes[LDS_AXES ? kAxisLds : 1];
-    __shared__ unsigned s_count[kThreads / 64];
 
     const int nd = args.ndepth, nla = args.nlat, nlo = args.nlon;
     const double *depth_a = args.depth, *lat_a = args.lat, *lon_a = args.lon;
@@ -119,7 +108,7 @@ __global__ __launch_bounds__(kThreads) void grid_sample_kernel(const GridArgs ar
     const i64 stride = (i64)gridDim.x * blockDim.x;
     for (i64 p = (i64)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += stride) {
         const double x = args.points[3 * p], y = args.points[3 * p + 1], z = args.points[3 * p + 2];
-        const double r = sqrt((x * x + y * y) + z * z);
+        const double r = mm_norm3(x, y, z);
         const double depth = kEarthRadius - r;
         const double c = r > 0.0 ? z / r : 0.0;
         const double lat = 90.0 - acos(c) * kRadToDeg;
@@ -149,16 +138,7 @@ __global__ __launch_bounds__(kThreads) void grid_sample_kernel(const GridArgs ar
                 for (int q = 0; q < ncomp; ++q) args.out[q * n + p] = args.fill;
         }
     }
-
-    // workgroup sum of the outside counts, then one atomic
-    for (int off = 32; off > 0; off >>= 1) outside += __shfl_down(outside, off, 64);
-    if ((threadIdx.x & 63) == 0) s_count[threadIdx.x >> 6] = outside;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned total = 0;
-        for (int w = 0; w < kThreads / 64; ++w) total += s_count[w];
-        if (total) atomicAdd(args.outside, (unsigned long long)total);
-    }
+    mm_count_to(args.outside, outside);
 }
 
 template <bool LDS_AXES>
@@ -194,8 +174,8 @@ extern "C" int64_t mm_sample_grid(mm_context *ctx, const double *points_d, int64
     }
     if (npoints == 0) return 0;
     MM_HIP_CHECK(hipSetDevice(ctx->device));
-    unsigned long long *counter = (unsigned long long *)ctx->d_counters;
-    if (mm_zero_async(ctx, counter, sizeof(i64)) != MM_OK) return MM_ERR_HIP;
+    unsigned long long *counter = mm_counters_begin(ctx, 0, 1);
+    if (!counter) return MM_ERR_HIP;
     GridArgs a;
     a.points = points_d;
     a.npoints = npoints;
@@ -213,14 +193,11 @@ extern "C" int64_t mm_sample_grid(mm_context *ctx, const double *points_d, int64
     a.out = out_d;
     a.lld = latlondepth_out_d;
     a.outside = counter;
-    const i64 blocks = (npoints + kThreads - 1) / kThreads;
-    const unsigned grid = (unsigned)(blocks < kMaxBlocks ? blocks : kMaxBlocks);
+    const unsigned grid = mm_blocks(npoints, kThreads, kMaxBlocks);
     if (ndepth + nlat + nlon <= kAxisLds)
         launch<true>(ctx, a, grid);
     else
         launch<false>(ctx, a, grid);
-    MM_HIP_CHECK(hipGetLastError());
-    if (mm_mirror_async(ctx, (long long *)ctx->h_counters, (const long long *)counter, 1) != MM_OK) return MM_ERR_HIP;
-    MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return ctx->h_counters[0];
+    const i64 *count = mm_counters_end(ctx, 0, 1);
+    return count ? count[0] : MM_ERR_HIP;
 }

@@ -102,11 +102,10 @@ extern "C" int64_t mm_fluid_solid_fix(mm_context *ctx, double *values_d, const d
     if (nelem == 0) return 0;
     MM_REQUIRE(values_d && previous_d && solid_d, "null array");
     MM_HIP_CHECK(hipSetDevice(ctx->device));
-    MM_HIP_CHECK(hipMemsetAsync(ctx->d_counters + 1, 0, sizeof(i64), ctx->stream));
+    unsigned long long *restored = mm_counters_begin(ctx, 1, 1);
+    if (!restored) return MM_ERR_HIP;
     hipLaunchKernelGGL(fluid_solid_fix_kernel, dim3((unsigned)nelem), dim3(64), 0, ctx->stream, values_d, previous_d,
-                       solid_d, nelem, (int)ncomp, (int)P, (int)vs_index, (unsigned long long *)(ctx->d_counters + 1));
-    MM_HIP_CHECK(hipGetLastError());
-    MM_HIP_CHECK(hipMemcpyAsync(ctx->h_counters + 1, ctx->d_counters + 1, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
-    MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return ctx->h_counters[1];
+                       solid_d, nelem, (int)ncomp, (int)P, (int)vs_index, restored);
+    const i64 *count = mm_counters_end(ctx, 1, 1);
+    return count ? count[0] : MM_ERR_HIP;
 }

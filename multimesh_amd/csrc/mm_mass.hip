@@ -13,14 +13,11 @@
 // mm_gll_mass is a streaming kernel on the element tile of mm_gll_tile.h: 24 B read and 8 B written per node, ~110 flops.
 // Only the coordinates go into LDS, in one buffer: a barrier before it is overwritten and one after, the next tile's loads
 // issued before the current one is computed.
-#include "mm_common.h"
 #include "mm_gll_tile.h"
 
 namespace {
 
-using gll::kThreads;
-constexpr int kWave = 64;
-constexpr int kChunk = 4096;       // mm_weighted_sum: values per chunk (fixed by the definition, not a launch shape)
+using namespace mm_stream;   // kThreads, kChunk
 
 template <int ORDER, int DIM>
 __global__ __launch_bounds__(kThreads) void gll_mass_kernel(const double *__restrict__ gp, i64 nelem,
@@ -58,11 +55,7 @@ __global__ __launch_bounds__(kThreads) void gll_mass_kernel(const double *__rest
             if (!(det > 0.0)) ++bad;
         }
     }
-    // integer counts: the order of the atomics does not reach the result
-    unsigned total = bad;
-#pragma unroll
-    for (int off = kWave / 2; off >= 1; off >>= 1) total += __shfl_down(total, off);
-    if ((tid & (kWave - 1)) == 0 && total != 0) atomicAdd(nbad, (unsigned long long)total);
+    mm_count_to(nbad, bad);
 }
 
 template <int ORDER, int DIM>
@@ -73,35 +66,20 @@ void launch_mass(mm_context *ctx, const double *gp, i64 nelem, const double *der
                        dim3(kThreads), 0, ctx->stream, gp, nelem, deriv, weights, mass, det, nbad);
 }
 
-// ---- the weighted sum.  One block per chunk of kChunk values and component: lane l adds its 16 terms l, l + 256, ... in
-// that order, then the 256 lane sums are halved eight times (s[l] + s[l + h], h = 128 .. 1).  a: the weights (component
-// stride sa, 0 for a shared mass); f: the fields (nullable; component stride n).  partial[c * nchunks + chunk].
+// ---- the weighted sum.  One block per chunk of kChunk values and component: mm_chunk_sum from the lane's first term.
+// a: the weights (component stride sa, 0 for a shared mass); f: the fields (nullable; component stride n).
+// partial[c * nchunks + chunk].
 __global__ __launch_bounds__(kThreads) void weighted_sum_kernel(const double *__restrict__ a, i64 sa,
                                                                 const double *__restrict__ f, i64 n,
                                                                 double *__restrict__ partial)
 {
     __shared__ double s[kThreads];
-    const int tid = threadIdx.x;
     const i64 c = blockIdx.y;
-    const i64 first = (i64)blockIdx.x * kChunk;
     const double *ac = a + c * sa;
     const double *fc = f ? f + c * n : nullptr;
-    double acc = 0.0;
-#pragma unroll
-    for (int r = 0; r < kChunk / kThreads; ++r) {
-        const i64 idx = first + r * kThreads + tid;
-        double t = 0.0;   // (the padding of the last chunk)
-        if (idx < n) t = fc ? ac[idx] * fc[idx] : ac[idx];
-        acc = r == 0 ? t : acc + t;
-    }
-    s[tid] = acc;
-    __syncthreads();
-#pragma unroll
-    for (int h = kThreads / 2; h >= 1; h >>= 1) {
-        if (tid < h) s[tid] = s[tid] + s[tid + h];
-        __syncthreads();
-    }
-    if (tid == 0) partial[c * gridDim.x + blockIdx.x] = s[0];
+    const double sum = mm_chunk_sum<true>(s, (i64)blockIdx.x * kChunk, n,
+                                          [&](i64 idx) { return fc ? ac[idx] * fc[idx] : ac[idx]; });
+    if (threadIdx.x == 0) partial[c * gridDim.x + blockIdx.x] = sum;
 }
 
 __global__ __launch_bounds__(kThreads) void divide_rows_kernel(const double *num, const double *__restrict__ den, i64 n,
@@ -114,8 +92,6 @@ __global__ __launch_bounds__(kThreads) void divide_rows_kernel(const double *num
         for (i64 c = 0; c < ncomp; ++c) out[c * n + idx] = num[c * n + idx] / d;
     }
 }
-
-i64 chunks_of(i64 n) { return n <= kChunk ? 1 : (n + kChunk - 1) / kChunk; }
 
 }  // namespace
 
@@ -130,8 +106,8 @@ extern "C" int64_t mm_gll_mass(mm_context *ctx, int order, int dim, const double
     if (nelem == 0) return 0;
     MM_REQUIRE(gll_points_d != nullptr && mass_d != nullptr, "null array");
     MM_HIP_CHECK(hipSetDevice(ctx->device));
-    unsigned long long *nbad = (unsigned long long *)(ctx->d_counters + 2);
-    MM_HIP_CHECK(hipMemsetAsync(nbad, 0, sizeof(i64), ctx->stream));
+    unsigned long long *nbad = mm_counters_begin(ctx, 2, 1);
+    if (!nbad) return MM_ERR_HIP;
 #define MM_MASS_CASE(O, D)                                                                              \
     if (order == O && dim == D) launch_mass<O, D>(ctx, gll_points_d, nelem, deriv_d, weights_d, mass_d, det_d, nbad)
     MM_MASS_CASE(1, 2);
@@ -141,10 +117,8 @@ extern "C" int64_t mm_gll_mass(mm_context *ctx, int order, int dim, const double
     MM_MASS_CASE(2, 3);
     MM_MASS_CASE(4, 3);
 #undef MM_MASS_CASE
-    MM_HIP_CHECK(hipGetLastError());
-    MM_HIP_CHECK(hipMemcpyAsync(ctx->h_counters + 2, nbad, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
-    MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return ctx->h_counters[2];
+    const i64 *count = mm_counters_end(ctx, 2, 1);
+    return count ? count[0] : MM_ERR_HIP;
 }
 
 extern "C" int mm_weighted_sum(mm_context *ctx, const double *mass_d, const double *fields_d, int64_t n, int64_t ncomp,
@@ -157,24 +131,20 @@ extern "C" int mm_weighted_sum(mm_context *ctx, const double *mass_d, const doub
     if (ncomp == 0) return MM_OK;
     MM_REQUIRE(out_d != nullptr && (mass_d != nullptr || n == 0), "null array");
     MM_HIP_CHECK(hipSetDevice(ctx->device));
-    // the partial sums of every level but the last: level 0 has chunks_of(n) per component, level 1 chunks_of(that) ...
-    // (n < 2^42 and 4096 values per chunk: at most three such levels)
-    double *partial[4] = {nullptr, nullptr, nullptr, nullptr};
-    mm_scratch_layout lay;
-    int nlevels = 0;
-    for (i64 m = chunks_of(n); m > 1; m = chunks_of(m)) lay.add(&partial[nlevels++], (size_t)(m * ncomp));
-    if (nlevels) {
+    mm_sum_levels levels(n);   // one row of chunk sums per component
+    if (levels.n) {
+        mm_scratch_layout lay;
+        levels.add_to(lay, ncomp);
         const int rc = lay.commit(ctx, __func__);
         if (rc != MM_OK) return rc;
     }
     const double *a = mass_d, *f = fields_d;
     i64 sa = 0, count = n;
-    for (int level = 0;; ++level) {
-        const i64 nchunks = chunks_of(count);
-        double *dst = nchunks == 1 ? out_d : partial[level];
+    for (int level = 0; level <= levels.n; ++level) {
+        const i64 nchunks = levels.chunks_at(level);
+        double *dst = level == levels.n ? out_d : levels.partial[level];
         hipLaunchKernelGGL(weighted_sum_kernel, dim3((unsigned)nchunks, (unsigned)ncomp), dim3(kThreads), 0, ctx->stream, a,
                            sa, f, count, dst);
-        if (nchunks == 1) break;
         a = dst;          // the next level sums the chunk sums: no fields, one row per component
         f = nullptr;
         sa = nchunks;
@@ -193,9 +163,8 @@ extern "C" int mm_divide_rows(mm_context *ctx, const double *num_d, const double
     if (n == 0 || ncomp == 0) return MM_OK;
     MM_REQUIRE(num_d && den_d && out_d, "null array");
     MM_HIP_CHECK(hipSetDevice(ctx->device));
-    const i64 blocks = (n + kThreads - 1) / kThreads;
-    hipLaunchKernelGGL(divide_rows_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(kThreads), 0, ctx->stream,
-                       num_d, den_d, n, ncomp, out_d);
+    hipLaunchKernelGGL(divide_rows_kernel, dim3(mm_blocks(n, kThreads, 8192)), dim3(kThreads), 0, ctx->stream, num_d, den_d,
+                       n, ncomp, out_d);
     MM_HIP_CHECK(hipGetLastError());
     return MM_OK;
 }

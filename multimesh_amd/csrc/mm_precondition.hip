@@ -9,7 +9,7 @@
 //
 // The taper.  w is a minimum of values <= 1, so its order does not show, and a centre with d >= outer for every node of
 // an element contributes exactly 1.0 to all of them: such a centre may be SKIPPED for that element.  A workgroup takes a
-// tile of 256 / P whole elements (the tile of mm_gll_tile.h with a run-time P, as mm_radial.hip uses it): the coordinates
+// tile of 256 / P whole elements (gll::RunTile of mm_gll_tile.h, as mm_radial.hip uses it): the coordinates
 // go to LDS coalesced, up to eight lanes form an element's bounding box, the boxes are joined into the tile's box.  The centres
 // pass by in batches of kBatch: lane j of the workgroup holds centre j of the batch in registers, tests it against the
 // tile's box and, if that does not exclude it, against every element's box; the centres that hit an element are compacted
@@ -38,14 +38,13 @@
 // share a histogram (repeated q, close ranks); up to 16 prefixes are carried.  Counts are exact in any order, so the
 // result is a function of the values alone.  When all candidates of a wave fall into one bin (all values equal; the top
 // bytes of any smooth field) the wave adds their number once instead of serialising on one LDS address.
-#include "mm_common.h"
+#include "mm_gll_tile.h"
 
 #include <math.h>
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWave = 64;
+using namespace mm_stream;   // kThreads, kWave
 constexpr int kWaves = kThreads / kWave;
 constexpr i64 kMaxBlocks = 2048;    // 256 CUs x 8 workgroups; grid-stride beyond
 constexpr int kBatch = kThreads;    // centres per batch: one per lane (multimesh_amd.device.POINT_TAPER_BATCH)
@@ -57,19 +56,6 @@ constexpr int kPasses = 8;
 constexpr int kSelectLoads = 4;     // values per lane and step of the histogram kernel
 typedef unsigned long long u64;
 
-// workgroup sum of an integer count, then one atomic (the order of the atomics does not reach the result)
-__device__ __forceinline__ void count_to(u64 *counter, unsigned mine, unsigned *s_count)
-{
-    for (int off = kWave / 2; off > 0; off >>= 1) mine += __shfl_down(mine, off, kWave);
-    if ((threadIdx.x & (kWave - 1)) == 0) s_count[threadIdx.x / kWave] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned total = 0;
-        for (int w = 0; w < kWaves; ++w) total += s_count[w];
-        if (total) atomicAdd(counter, (u64)total);
-    }
-}
-
 __device__ __forceinline__ bool is_finite(double v) { return fabs(v) < __builtin_inf(); }
 
 // ---------------------------------------------------------------------------------------------------- mm_point_taper
@@ -78,7 +64,6 @@ __global__ __launch_bounds__(kThreads) void centres_check_kernel(const double *_
                                                                  const double *__restrict__ inner,
                                                                  const double *__restrict__ outer, int K, u64 *bad)
 {
-    __shared__ unsigned s_count[kWaves];
     unsigned mine = 0;
     const int stride = gridDim.x * blockDim.x;
     for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < K; k += stride) {
@@ -87,7 +72,7 @@ __global__ __launch_bounds__(kThreads) void centres_check_kernel(const double *_
                         is_finite(a) && is_finite(b) && a >= 0.0 && b >= a;
         if (!ok) ++mine;
     }
-    count_to(bad, mine, s_count);
+    mm_count_to(bad, mine);
 }
 
 // the distance of a centre from a box in the statement's arithmetic (see the derivation above): d of a node >= this
@@ -97,7 +82,7 @@ __device__ __forceinline__ double box_distance(double lo0, double hi0, double lo
     const double g0 = fmax(fmax(lo0 - c0, c0 - hi0), 0.0);
     const double g1 = fmax(fmax(lo1 - c1, c1 - hi1), 0.0);
     const double g2 = fmax(fmax(lo2 - c2, c2 - hi2), 0.0);
-    return sqrt((g0 * g0 + g1 * g1) + g2 * g2);
+    return mm_norm3(g0, g1, g2);
 }
 
 struct TaperArgs {
@@ -120,17 +105,14 @@ __global__ __launch_bounds__(kThreads) void point_taper_kernel(const TaperArgs a
     __shared__ double s_hitc[5][kBatch];         // the batch's centres that hit an element: c0, c1, c2, inner, outer
     __shared__ int s_hit[kThreads];              // element e of the tile has been hit by a centre
     __shared__ int s_wcount[kWaves];
-    __shared__ unsigned s_count[kWaves];
     if (*args.bad != 0) return;   // (a refused call: nothing is written)
 
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
     const int P = args.P, K = args.K, ncomp = args.ncomp;
-    const int tile = kThreads / P;            // whole elements per block and step
-    const int el = tid / P;                   // (this lane's element of the tile: the same one in every tile)
+    const gll::RunTile T(args.ngroups, P);
     const int sub = P >= kSub ? kSub : 1;     // lanes per element while the boxes are formed (tile * kSub <= 256)
     const int be = tid / sub, bs = tid - be * sub;
     const i64 n = args.ngroups * P;
-    const i64 ntiles = (args.ngroups + tile - 1) / tile;
     const bool copy = args.out != args.in;
     const double inf = __builtin_inf();
     unsigned mine = 0;
@@ -138,17 +120,15 @@ __global__ __launch_bounds__(kThreads) void point_taper_kernel(const TaperArgs a
     // the coordinates of a tile are fetched into registers one step ahead and copied to LDS when its step comes
     double stage[3];
     auto fetch = [&](i64 t) {
-        if (t >= ntiles) return;
-        const i64 left = args.ngroups - t * tile;
-        const int nd = 3 * (int)(left < tile ? left : tile) * P;
-        const double *src = args.points + t * (i64)tile * P * 3;
+        if (t >= T.ntiles) return;
+        const int nd = 3 * T.nnodes(t);
+        const double *src = T.coords(args.points, t);
 #pragma unroll
         for (int r = 0; r < 3; ++r) stage[r] = r * kThreads + tid < nd ? src[r * kThreads + tid] : 0.0;
     };
     fetch(blockIdx.x);
-    for (i64 t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const i64 left = args.ngroups - t * tile;
-        const int nel = (int)(left < tile ? left : tile), nnodes = nel * P;
+    for (i64 t = blockIdx.x; t < T.ntiles; t += gridDim.x) {
+        const int nel = T.nel(t), nnodes = T.nnodes(t);
         __syncthreads();   // (the previous step's reads of xs, s_box, s_hit and the lists are done)
 #pragma unroll
         for (int r = 0; r < 3; ++r) xs[r * kThreads + tid] = stage[r];
@@ -235,11 +215,11 @@ __global__ __launch_bounds__(kThreads) void point_taper_kernel(const TaperArgs a
                 s_hitc[0][pos] = c0, s_hitc[1][pos] = c1, s_hitc[2][pos] = c2, s_hitc[3][pos] = ri, s_hitc[4][pos] = ro;
             }
             __syncthreads();
-            if (tid < nnodes && s_hit[el]) {
+            if (tid < nnodes && s_hit[T.el]) {
                 for (int j = 0; j < total; ++j) {
                     const double dx = x0 - s_hitc[0][j], dy = x1 - s_hitc[1][j], dz = x2 - s_hitc[2][j];
                     const double in_k = s_hitc[3][j], out_k = s_hitc[4][j];
-                    const double d = sqrt((dx * dx + dy * dy) + dz * dz);
+                    const double d = mm_norm3(dx, dy, dz);
                     double tk;
                     if (d <= in_k) {
                         tk = 0.0;
@@ -255,8 +235,8 @@ __global__ __launch_bounds__(kThreads) void point_taper_kernel(const TaperArgs a
         }
         __syncthreads();   // (s_hit is complete: K == 0 or a last batch without a list ends without a barrier of its own)
         if (tid < nnodes) {
-            const bool touched = s_hit[el] != 0;
-            const i64 node = t * (i64)tile * P + tid;
+            const bool touched = s_hit[T.el] != 0;
+            const i64 node = T.first_node(t) + tid;
             if (w < 1.0) ++mine;
             if (args.weight) args.weight[node] = w;
             if (touched || copy) {
@@ -267,7 +247,7 @@ __global__ __launch_bounds__(kThreads) void point_taper_kernel(const TaperArgs a
             }
         }
     }
-    count_to(args.count, mine, s_count);
+    mm_count_to(args.count, mine);
 }
 
 // ----------------------------------------------------------------------------------------------- mm_order_statistics
@@ -417,7 +397,6 @@ __global__ __launch_bounds__(kThreads) void clamp_kernel(const double *in, i64 n
                                                          const double *__restrict__ upper, int symmetric, double *out,
                                                          u64 *changed)
 {
-    __shared__ unsigned s_count[kWaves];
     const i64 c = blockIdx.y;
     const double inf = __builtin_inf();
     const double hi = upper ? upper[c] : inf;
@@ -432,14 +411,10 @@ __global__ __launch_bounds__(kThreads) void clamp_kernel(const double *in, i64 n
         dst[i] = below ? lo : (above ? hi : v);
         if (below || above) ++mine;
     }
-    if (changed) count_to(changed + c, mine, s_count);
+    if (changed) mm_count_to(changed + c, mine);
 }
 
-unsigned stream_grid(i64 n, i64 per_block)
-{
-    const i64 b = (n + per_block - 1) / per_block;
-    return (unsigned)(b < kMaxBlocks ? (b > 0 ? b : 1) : kMaxBlocks);
-}
+unsigned stream_grid(i64 n, i64 per_block) { return mm_blocks(n, per_block, kMaxBlocks); }
 
 }  // namespace
 
@@ -456,8 +431,8 @@ extern "C" int64_t mm_point_taper(mm_context *ctx, const double *points_d, int64
     MM_REQUIRE(ngroups == 0 || points_d != nullptr, "null points");
     MM_REQUIRE(ngroups == 0 || ncomp == 0 || (in_d != nullptr && out_d != nullptr), "null values");
     MM_HIP_CHECK(hipSetDevice(ctx->device));
-    u64 *counters = (u64 *)(ctx->d_counters + 2);   // [2] nodes with w < 1, [3] bad centres
-    if (mm_zero_async(ctx, counters, 2 * sizeof(i64)) != MM_OK) return MM_ERR_HIP;
+    u64 *counters = mm_counters_begin(ctx, 2, 2);   // [0] nodes with w < 1, [1] bad centres
+    if (!counters) return MM_ERR_HIP;
     if (K > 0)
         hipLaunchKernelGGL(centres_check_kernel, dim3(stream_grid(K, kThreads)), dim3(kThreads), 0, ctx->stream, centres_d,
                            inner_d, outer_d, (int)K, counters + 1);
@@ -478,16 +453,15 @@ extern "C" int64_t mm_point_taper(mm_context *ctx, const double *points_d, int64
         a.count = counters;
         hipLaunchKernelGGL(point_taper_kernel, dim3(stream_grid(ngroups, kThreads / P)), dim3(kThreads), 0, ctx->stream, a);
     }
-    MM_HIP_CHECK(hipGetLastError());
-    if (mm_mirror_async(ctx, (long long *)ctx->h_counters + 2, (const long long *)counters, 2) != MM_OK) return MM_ERR_HIP;
-    MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (ctx->h_counters[3] != 0) {
+    const i64 *count = mm_counters_end(ctx, 2, 2);
+    if (!count) return MM_ERR_HIP;
+    if (count[1] != 0) {
         mm_set_error(MM_ERR_ARG,
                      "mm_point_taper: %lld centres are not finite or have radii that are not finite with 0 <= inner <= outer",
-                     (long long)ctx->h_counters[3]);
+                     (long long)count[1]);
         return MM_ERR_ARG;
     }
-    return ctx->h_counters[2];
+    return count[0];
 }
 
 extern "C" int mm_order_statistics(mm_context *ctx, const double *values_d, int64_t n, int64_t ncomp, int absolute,

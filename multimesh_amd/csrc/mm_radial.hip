@@ -4,8 +4,8 @@
 //   mm_binned_weighted_sum  : out[c][b] = sum over bin[i] == b of mass[i] * f[c][i], all bins in one pass per component
 //   mm_radial_model_apply   : ref = the table's layer of the element's centre, lerped at the node's radius; five modes
 //
-// Bit parity with the NumPy statements (tests/radial_cases.py): |p| = sqrt((x*x + y*y) + z*z) as in mm_sphere.hip, the
-// lerp of mm_grid_sample.hip, every product, quotient and sum rounded on its own (-ffp-contract=off).
+// Bit parity with the NumPy statements (tests/radial_cases.py): |p|, the bisection and the lerp are those of mm_stream.h,
+// every product, quotient and sum rounded on its own (-ffp-contract=off).
 //
 // The binned sum.  The definition (include/multimesh_hip.h) is mm_weighted_sum's rule applied to every bin on its own,
 // with +0.0 for the values of other bins and every lane sum started from +0.0.  Such a partial sum is never -0.0
@@ -15,12 +15,12 @@
 // tab[kWindow][256] in LDS of which lane l touches only column l while it adds its terms in ascending order (no
 // conflicts: consecutive lanes, consecutive doubles; no atomics), then the rows are halved across lanes, all rows of the
 // window in one step per barrier.  The chunk sums go to a zero-filled dst[bin][chunk]; the levels above are dense
-// (binned_level_kernel).  On a layered mesh a chunk (about 33 order-4 elements) spans a few bins: one window.  A chunk of
+// (binned_level_kernel: mm_chunk_sum from +0.0).  On a layered mesh a chunk (about 33 order-4 elements) spans a few bins: one window.  A chunk of
 // a shuffled cloud takes ceil(span / kWindow) windows over the same registers.
 //
-// The table evaluation works on tiles of 256 / P whole elements (the tile of mm_gll_tile.h with a run-time P): the
+// The table evaluation works on tiles of 256 / P whole elements (gll::RunTile of mm_gll_tile.h): the
 // coordinates go to LDS coalesced, lane e < tile forms element e's centre and finds its layer, then lane t is node t.
-#include "mm_common.h"
+#include "mm_gll_tile.h"
 
 #include <limits.h>
 
@@ -28,63 +28,27 @@
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWave = 64;
-constexpr int kChunk = 4096;        // values per chunk (fixed by the definition, not a launch shape)
-constexpr int kTerms = kChunk / kThreads;
+using namespace mm_stream;   // kThreads, kWave, kChunk, kTerms
 constexpr int kWindow = 8;          // bins per LDS window: 16 KiB of doubles (+ 8 KiB of counts when asked for)
 constexpr i64 kMaxBlocks = 2048;    // 256 CUs x 8 workgroups; grid-stride beyond
 constexpr int kEdgeLds = 2048;      // doubles of LDS for the edges (16 KiB)
 constexpr int kTableLds = 4096;     // doubles of LDS for the table, radii and values together (32 KiB)
 constexpr i64 kMaxBins = (i64)1 << 20;
 
-unsigned grid_for(i64 n)
-{
-    const i64 b = (n + kThreads - 1) / kThreads;
-    return (unsigned)(b < kMaxBlocks ? (b > 0 ? b : 1) : kMaxBlocks);
-}
-
-i64 chunks_of(i64 n) { return n <= kChunk ? 1 : (n + kChunk - 1) / kChunk; }
-
-// first index in [b, e) whose value is greater than v (np.searchsorted(a, v, side="right"))
-__device__ __forceinline__ int upper_bound(const double *a, int b, int e, double v)
-{
-    while (b < e) {
-        const int mid = (b + e) >> 1;
-        if (!(v < a[mid]))
-            b = mid + 1;
-        else
-            e = mid;
-    }
-    return b;
-}
-
-// workgroup sum of an integer count, then one atomic (the order of the atomics does not reach the result)
-__device__ __forceinline__ void count_to(unsigned long long *counter, unsigned mine, unsigned *s_count)
-{
-    for (int off = kWave / 2; off > 0; off >>= 1) mine += __shfl_down(mine, off, kWave);
-    if ((threadIdx.x & (kWave - 1)) == 0) s_count[threadIdx.x / kWave] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned total = 0;
-        for (int w = 0; w < kThreads / kWave; ++w) total += s_count[w];
-        if (total) atomicAdd(counter, (unsigned long long)total);
-    }
-}
+unsigned grid_for(i64 n) { return mm_blocks(n, kThreads, kMaxBlocks); }
 
 // ---------------------------------------------------------------------------------------------------- mm_radial_bins
 // *bad = the number of i in [0, nbins] with a non-finite edges[i] or (i > 0) edges[i] <= edges[i - 1]
 __global__ __launch_bounds__(kThreads) void edges_check_kernel(const double *__restrict__ edges, int nbins,
                                                                unsigned long long *bad)
 {
-    __shared__ unsigned s_count[kThreads / kWave];
     unsigned mine = 0;
     const int stride = gridDim.x * blockDim.x;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i <= nbins; i += stride) {
         const double e = edges[i];
         if (!(fabs(e) < __builtin_inf()) || (i > 0 && !(e > edges[i - 1]))) ++mine;
     }
-    count_to(bad, mine, s_count);
+    mm_count_to(bad, mine);
 }
 
 template <bool LDS_EDGES>
@@ -95,7 +59,6 @@ __global__ __launch_bounds__(kThreads) void radial_bins_kernel(const double *__r
                                                                unsigned long long *outside)
 {
     __shared__ double s_edges[LDS_EDGES ? kEdgeLds : 1];
-    __shared__ unsigned s_count[kThreads / kWave];
     if (*bad != 0) return;   // (the edges are not a valid axis: nothing is written)
     const double *e = edges;
     if (LDS_EDGES) {
@@ -108,10 +71,10 @@ __global__ __launch_bounds__(kThreads) void radial_bins_kernel(const double *__r
     const i64 stride = (i64)gridDim.x * blockDim.x;
     for (i64 p = (i64)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += stride) {
         const double x = points[3 * p], y = points[3 * p + 1], z = points[3 * p + 2];
-        const double r = sqrt((x * x + y * y) + z * z);
+        const double r = mm_norm3(x, y, z);
         int b = -1;
         if (r >= lo && r <= hi) {   // (false for a NaN)
-            b = upper_bound(e, 0, nbins + 1, r) - 1;
+            b = mm_upper_bound(e, 0, nbins + 1, r) - 1;
             b = b > nbins - 1 ? nbins - 1 : b;   // r == edges[nbins]
         } else {
             ++mine;
@@ -119,7 +82,7 @@ __global__ __launch_bounds__(kThreads) void radial_bins_kernel(const double *__r
         bin[p] = b;
         if (radius) radius[p] = r;
     }
-    count_to(outside, mine, s_count);
+    mm_count_to(outside, mine);
 }
 
 // -------------------------------------------------------------------------------------------- mm_binned_weighted_sum
@@ -217,24 +180,10 @@ __global__ __launch_bounds__(kThreads) void binned_level_kernel(const double *__
                                                                 double *__restrict__ dst)
 {
     __shared__ double s[kThreads];
-    const int tid = threadIdx.x;
     const i64 row = blockIdx.x / nch, chunk = blockIdx.x - row * nch;
     const double *a = src + row * count;
-    const i64 first = chunk * kChunk;
-    double acc = 0.0;
-#pragma unroll
-    for (int r = 0; r < kTerms; ++r) {
-        const i64 idx = first + r * kThreads + tid;
-        if (idx < count) acc = acc + a[idx];
-    }
-    s[tid] = acc;
-    __syncthreads();
-#pragma unroll
-    for (int h = kThreads / 2; h >= 1; h >>= 1) {
-        if (tid < h) s[tid] = s[tid] + s[tid + h];
-        __syncthreads();
-    }
-    if (tid == 0) dst[blockIdx.x] = s[0];
+    const double sum = mm_chunk_sum<false>(s, chunk * kChunk, count, [&](i64 idx) { return a[idx]; });
+    if (threadIdx.x == 0) dst[blockIdx.x] = sum;
 }
 
 // --------------------------------------------------------------------------------------------- mm_radial_model_apply
@@ -248,6 +197,13 @@ struct ApplyArgs {
     int nlayers;
     const double *in;
     double *out;
+};
+
+// the first radius of every layer, as an axis to bisect
+struct LayerFloor {
+    const double *R;
+    const int *lstart;
+    __device__ __forceinline__ double operator[](int k) const { return R[lstart[k]]; }
 };
 
 // LDS_TABLE: radii and values are copied to (dynamic) LDS first and read there.
@@ -265,17 +221,14 @@ __global__ __launch_bounds__(kThreads) void radial_apply_kernel(const ApplyArgs 
         R = s_table;
         V = s_table + m;
     }
-    const int tile = kThreads / P;            // whole elements per block and step
-    const int el = tid / P;                   // (this lane's element of the tile: the same one in every tile)
+    const gll::RunTile T(args.ngroups, P);
     const i64 n = args.ngroups * P;
-    const i64 ntiles = (args.ngroups + tile - 1) / tile;
     const double *in = args.in;               // (out may be in: no __restrict__, every lane reads its value before writing)
     double *out = args.out;
 
-    for (i64 t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const i64 left = args.ngroups - t * tile;
-        const int nel = (int)(left < tile ? left : tile), nnodes = nel * P;
-        const double *src = args.points + t * (i64)tile * P * 3;
+    for (i64 t = blockIdx.x; t < T.ntiles; t += gridDim.x) {
+        const int nel = T.nel(t), nnodes = T.nnodes(t);
+        const double *src = T.coords(args.points, t);
         __syncthreads();   // (the previous step's reads of xs, s_a and s_b are done; the table is in place)
         for (int q = tid; q < 3 * nnodes; q += kThreads) xs[q] = src[q];
         __syncthreads();
@@ -289,19 +242,11 @@ __global__ __launch_bounds__(kThreads) void radial_apply_kernel(const ApplyArgs 
             }
             const double dp = (double)P;
             cx = cx / dp, cy = cy / dp, cz = cz / dp;
-            const double rc = sqrt((cx * cx + cy * cy) + cz * cz);
+            const double rc = mm_norm3(cx, cy, cz);
             int a = -1, b = -1;
             if (rc == rc) {
                 // the last layer whose first radius is <= rc, clipped: the layer with r_lo <= rc < r_hi
-                int lb = 0, le = args.nlayers;
-                while (lb < le) {
-                    const int mid = (lb + le) >> 1;
-                    if (!(rc < R[args.lstart[mid]]))
-                        lb = mid + 1;
-                    else
-                        le = mid;
-                }
-                int k = lb - 1;
+                int k = mm_upper_bound(LayerFloor{R, args.lstart}, 0, args.nlayers, rc) - 1;
                 k = k < 0 ? 0 : k;
                 a = args.lstart[k];
                 b = args.lstart[k + 1] - 1;
@@ -312,22 +257,22 @@ __global__ __launch_bounds__(kThreads) void radial_apply_kernel(const ApplyArgs 
         __syncthreads();
         if (tid < nnodes) {
             const double x = xs[3 * tid], y = xs[3 * tid + 1], z = xs[3 * tid + 2];
-            const int a = s_a[el], b = s_b[el];
-            const i64 node = t * (i64)tile * P + tid;
+            const int a = s_a[T.el], b = s_b[T.el];
+            const i64 node = T.first_node(t) + tid;
             int i = 0;
             double w = __builtin_nan("");
             if (a >= 0) {
-                double r = sqrt((x * x + y * y) + z * z);
+                double r = mm_norm3(x, y, z);
                 r = r < R[a] ? R[a] : r;
                 r = r > R[b] ? R[b] : r;
-                i = upper_bound(R, a, b + 1, r) - 1;
+                i = mm_upper_bound(R, a, b + 1, r) - 1;
                 i = i < a ? a : i;
                 i = i > b - 1 ? b - 1 : i;
                 w = (r - R[i]) / (R[i + 1] - R[i]);
             }
             for (int c = 0; c < ncomp; ++c) {
                 const double *Vc = V + (i64)c * m;
-                const double ref = a >= 0 ? (1.0 - w) * Vc[i] + w * Vc[i + 1] : w;
+                const double ref = a >= 0 ? mm_lerp(w, Vc[i], Vc[i + 1]) : w;
                 double o = ref;
                 if (args.mode != 0) {
                     const double v = in[c * n + node];
@@ -355,8 +300,8 @@ extern "C" int64_t mm_radial_bins(mm_context *ctx, const double *points_d, int64
     MM_REQUIRE(edges_d != nullptr, "null edges");
     MM_REQUIRE((points_d != nullptr && bin_d != nullptr) || n == 0, "null array");
     MM_HIP_CHECK(hipSetDevice(ctx->device));
-    unsigned long long *counters = (unsigned long long *)(ctx->d_counters + 2);   // [2] outside, [3] bad edges
-    if (mm_zero_async(ctx, counters, 2 * sizeof(i64)) != MM_OK) return MM_ERR_HIP;
+    unsigned long long *counters = mm_counters_begin(ctx, 2, 2);   // [0] outside, [1] bad edges
+    if (!counters) return MM_ERR_HIP;
     hipLaunchKernelGGL(edges_check_kernel, dim3(grid_for(nbins + 1)), dim3(kThreads), 0, ctx->stream, edges_d, (int)nbins,
                        counters + 1);
     if (n > 0) {
@@ -367,15 +312,14 @@ extern "C" int64_t mm_radial_bins(mm_context *ctx, const double *points_d, int64
             hipLaunchKernelGGL(radial_bins_kernel<false>, dim3(grid_for(n)), dim3(kThreads), 0, ctx->stream, points_d, n,
                                edges_d, (int)nbins, (int *)bin_d, radius_out_d, counters + 1, counters);
     }
-    MM_HIP_CHECK(hipGetLastError());
-    if (mm_mirror_async(ctx, (long long *)ctx->h_counters + 2, (const long long *)counters, 2) != MM_OK) return MM_ERR_HIP;
-    MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (ctx->h_counters[3] != 0) {
+    const i64 *count = mm_counters_end(ctx, 2, 2);
+    if (!count) return MM_ERR_HIP;
+    if (count[1] != 0) {
         mm_set_error(MM_ERR_ARG, "mm_radial_bins: the edges are not finite and strictly ascending (%lld of them)",
-                     (long long)ctx->h_counters[3]);
+                     (long long)count[1]);
         return MM_ERR_ARG;
     }
-    return ctx->h_counters[2];
+    return count[0];
 }
 
 extern "C" int mm_binned_weighted_sum(mm_context *ctx, const double *mass_d, const double *fields_d, const int32_t *bin_d,
@@ -388,20 +332,17 @@ extern "C" int mm_binned_weighted_sum(mm_context *ctx, const double *mass_d, con
     MM_REQUIRE(fields_d != nullptr || ncomp <= 1, "without fields there is one sum");
     MM_REQUIRE(out_d != nullptr || ncomp == 0, "null output");
     MM_REQUIRE((mass_d != nullptr && bin_d != nullptr) || n == 0, "null array");
-    // the chunk sums of every level but the last: level 0 has nbins * chunks_of(n), level 1 nbins * chunks_of(that) ...
-    i64 level_chunks[4] = {0, 0, 0, 0};
-    int nlevels = 0;
-    for (i64 c = chunks_of(n); c > 1; c = chunks_of(c)) level_chunks[nlevels++] = c;
-    if (nlevels > 1 && nbins * level_chunks[1] >= ((i64)1 << 31)) {
+    mm_sum_levels levels(n);   // one row of chunk sums per bin
+    const int nlevels = levels.n;
+    if (nlevels > 1 && nbins * levels.chunks[1] >= ((i64)1 << 31)) {
         mm_set_error(MM_ERR_UNSUPPORTED, "mm_binned_weighted_sum: nbins * ceil(n / 4096^2) is out of range");
         return MM_ERR_UNSUPPORTED;
     }
     if (ncomp == 0 && count_d == nullptr) return MM_OK;
     MM_HIP_CHECK(hipSetDevice(ctx->device));
-    double *partial[4] = {nullptr, nullptr, nullptr, nullptr};
     if (nlevels) {
         mm_scratch_layout lay;
-        for (int l = 0; l < nlevels; ++l) lay.add(&partial[l], (size_t)(nbins * level_chunks[l]));
+        levels.add_to(lay, nbins);
         const int rc = lay.commit(ctx, __func__);
         if (rc != MM_OK) return rc;
     }
@@ -410,7 +351,7 @@ extern "C" int mm_binned_weighted_sum(mm_context *ctx, const double *mass_d, con
     if (n == 0) return MM_OK;
     // (ncomp == 0 with count_d: one pass for the counts alone, its sums go nowhere but the scratch -- or nowhere at all)
     const i64 passes = ncomp > 0 ? ncomp : 1;
-    const i64 nchunks = chunks_of(n);
+    const i64 nchunks = levels.chunks_at(0);
     double *sink = nullptr;
     if (ncomp == 0 && nlevels == 0) {
         mm_scratch_layout lay;
@@ -420,7 +361,7 @@ extern "C" int mm_binned_weighted_sum(mm_context *ctx, const double *mass_d, con
     }
     for (i64 c = 0; c < passes; ++c) {
         double *out_c = ncomp > 0 ? out_d + c * nbins : sink;
-        double *dst = nlevels ? partial[0] : out_c;
+        double *dst = nlevels ? levels.partial[0] : out_c;
         if (nlevels && mm_zero_async(ctx, dst, (size_t)(nbins * nchunks) * sizeof(double)) != MM_OK) return MM_ERR_HIP;
         const double *f = fields_d ? fields_d + c * n : nullptr;
         const i64 stride = nlevels ? nchunks : 1;
@@ -434,10 +375,10 @@ extern "C" int mm_binned_weighted_sum(mm_context *ctx, const double *mass_d, con
                                (unsigned long long *)nullptr);
         if (ncomp == 0) break;
         for (int l = 0; l < nlevels; ++l) {
-            const i64 nch = l + 1 < nlevels ? level_chunks[l + 1] : 1;
-            double *next = l + 1 < nlevels ? partial[l + 1] : out_c;
+            const i64 nch = levels.chunks_at(l + 1);
+            double *next = l + 1 < nlevels ? levels.partial[l + 1] : out_c;
             hipLaunchKernelGGL(binned_level_kernel, dim3((unsigned)(nbins * nch)), dim3(kThreads), 0, ctx->stream,
-                               (const double *)partial[l], level_chunks[l], nch, next);
+                               (const double *)levels.partial[l], levels.chunks[l], nch, next);
         }
     }
     MM_HIP_CHECK(hipGetLastError());
@@ -498,9 +439,7 @@ extern "C" int mm_radial_model_apply(mm_context *ctx, const double *points_d, in
     a.nlayers = nlayers;
     a.in = in_d;
     a.out = out_d;
-    const i64 tile = kThreads / P;
-    const i64 ntiles = (ngroups + tile - 1) / tile;
-    const unsigned grid = (unsigned)(ntiles < kMaxBlocks ? ntiles : kMaxBlocks);
+    const unsigned grid = mm_blocks(ngroups, kThreads / P, kMaxBlocks);
     const i64 table = m * (1 + ncomp);
     if (table <= kTableLds)
         hipLaunchKernelGGL(radial_apply_kernel<true>, dim3(grid), dim3(kThreads), (size_t)table * sizeof(double), ctx->stream,

@@ -12,20 +12,15 @@
 // (the centre, NaN) are left alone, like the reference's r > 0 mask.
 //
 // HBM-bound: 24 B read + 8 B radius (+ 8 B index in the node layout) + 24 B written per point, no reuse.
-#include "mm_common.h"
+#include "mm_stream.h"
 
 #include <limits.h>
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr i64 kMaxBlocks = 8192;   // grid-stride beyond 2 M threads
+using mm_stream::kThreads;
 
-unsigned grid_for(i64 n)
-{
-    const i64 b = (n + kThreads - 1) / kThreads;
-    return (unsigned)(b < kMaxBlocks ? b : kMaxBlocks);
-}
+unsigned grid_for(i64 n) { return mm_blocks(n, kThreads, 8192); }   // grid-stride beyond 2 M threads
 
 // radius index of point i: itself (element-nodal layout) or the first occurrence of the node (node layout);
 // -1 when that index is not a valid one of rad[nrad]
@@ -43,7 +38,7 @@ __global__ __launch_bounds__(kThreads) void map_to_sphere_kernel(const double *i
     const i64 stride = (i64)gridDim.x * blockDim.x;
     for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < npoints; i += stride) {
         const double x = in[3 * i], y = in[3 * i + 1], z = in[3 * i + 2];
-        const double r = sqrt((x * x + y * y) + z * z);
+        const double r = mm_norm3(x, y, z);
         const i64 j = rad_index(first, i, nrad);
         if (r > 0.0 && j >= 0) {
             const double rr = rad[j];
@@ -67,7 +62,7 @@ __global__ __launch_bounds__(kThreads) void sphere_ratio_kernel(const double *__
     for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < npoints; i += stride) {
         const double x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
         const i64 j = rad_index(first, i, nrad);
-        ratio[i] = j >= 0 ? (sqrt((x * x + y * y) + z * z) / r_ref) / rad[j] : __builtin_nan("");
+        ratio[i] = j >= 0 ? (mm_norm3(x, y, z) / r_ref) / rad[j] : __builtin_nan("");
     }
 }
 
@@ -153,8 +148,8 @@ extern "C" int64_t mm_first_occurrence(mm_context *ctx, const int64_t *connectiv
     MM_REQUIRE(first_d != nullptr || nnodes == 0, "null array");
     MM_REQUIRE(connectivity_d != nullptr || nentries == 0, "null array");
     MM_HIP_CHECK(hipSetDevice(ctx->device));
-    unsigned long long *counters = (unsigned long long *)(ctx->d_counters + 2);   // [2] unreferenced, [3] out of range
-    MM_HIP_CHECK(hipMemsetAsync(counters, 0, 2 * sizeof(i64), ctx->stream));
+    unsigned long long *counters = mm_counters_begin(ctx, 2, 2);   // [0] unreferenced, [1] out of range
+    if (!counters) return MM_ERR_HIP;
     unsigned long long *first = (unsigned long long *)first_d;
     if (nnodes > 0)
         hipLaunchKernelGGL(first_init_kernel, dim3(grid_for(nnodes)), dim3(kThreads), 0, ctx->stream, first, nnodes);
@@ -164,15 +159,14 @@ extern "C" int64_t mm_first_occurrence(mm_context *ctx, const int64_t *connectiv
     if (nnodes > 0)
         hipLaunchKernelGGL(first_finish_kernel, dim3(grid_for(nnodes)), dim3(kThreads), 0, ctx->stream, first, nnodes,
                            counters);
-    MM_HIP_CHECK(hipGetLastError());
-    MM_HIP_CHECK(hipMemcpyAsync(ctx->h_counters + 2, counters, 2 * sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
-    MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (ctx->h_counters[3] != 0) {
-        mm_set_error(MM_ERR_ARG, "mm_first_occurrence: %lld connectivity entries outside [0, %lld)",
-                     (long long)ctx->h_counters[3], (long long)nnodes);
+    const i64 *count = mm_counters_end(ctx, 2, 2);
+    if (!count) return MM_ERR_HIP;
+    if (count[1] != 0) {
+        mm_set_error(MM_ERR_ARG, "mm_first_occurrence: %lld connectivity entries outside [0, %lld)", (long long)count[1],
+                     (long long)nnodes);
         return MM_ERR_ARG;
     }
-    return ctx->h_counters[2];
+    return count[0];
 }
 
 extern "C" int mm_sphere_ratio(mm_context *ctx, const double *points_d, int64_t npoints, const double *rad_d,

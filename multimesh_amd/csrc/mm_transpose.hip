@@ -32,7 +32,7 @@
 // All components go through in one pass over the operator, four at a time (accumulators in registers).
 #include <new>
 
-#include "mm_common.h"
+#include "mm_stream.h"
 
 // (public handle: global namespace)
 struct mm_transpose {
@@ -52,14 +52,14 @@ namespace {
 
 typedef unsigned long long u64;
 
-constexpr int kThreads = 256;
-constexpr int kWave = 64;
+using namespace mm_stream;   // kThreads, kWave
 constexpr int kLongRow = 32;    // node form: rows longer than this are served by a wave each
 constexpr int kCompBlock = 4;   // components per pass over the operator
 // the sort's tile offsets and mm_exclusive_scan_int are int, and so are the handle's row offsets
 constexpr i64 kMaxContrib = 0x7fffffff;
 
-unsigned blocks_for(i64 n) { return (unsigned)((n + kThreads - 1) / kThreads); }
+// (no kernel here strides: the cap is the largest grid)
+unsigned blocks_for(i64 n) { return mm_blocks(n, kThreads, kMaxContrib); }
 
 // key = the destination, payload = the flat index; ids outside [lo, ndst) are counted (the key is then 0: the handle is
 // never built).  minus_one_key: the key of id -1 (element form: ndst, behind every element; node form: unused)
@@ -75,8 +75,7 @@ __global__ __launch_bounds__(kThreads) void transpose_keys_kernel(const i64 *__r
         key[i] = bad ? 0ull : (id < 0 ? (u64)ndst : (u64)id);
         val[i] = (unsigned)i;
     }
-    const u64 votes = __ballot(bad);
-    if (votes != 0 && (threadIdx.x & (kWave - 1)) == 0) atomicAdd(nbad, (u64)__popcll(votes));
+    mm_count_to(nbad, bad ? 1u : 0u);
 }
 
 // offsets[d] = the number of sorted keys below d, d in [0, ndst]
@@ -287,7 +286,7 @@ int build_handle(mm_context *ctx, mm_transpose *t, const i64 *ids, const double 
     u64 *ka = nullptr, *kb = nullptr;
     unsigned *va = nullptr, *vb = nullptr;
     void *sort_scratch = nullptr;
-    u64 *counters = (u64 *)(ctx->d_counters + 2);   // [2] ids out of range, [3] long rows
+    u64 *counters = nullptr;   // [0] ids out of range, [1] long rows
     bool ok = mm_raw_alloc(ctx->device, (void **)&t->offsets, (size_t)(ndst + 1) * sizeof(unsigned)) == hipSuccess;
     if (n > 0) {
         ok = ok && mm_raw_alloc(ctx->device, (void **)&t->target, n_sz * sizeof(unsigned)) == hipSuccess;
@@ -307,7 +306,8 @@ int build_handle(mm_context *ctx, mm_transpose *t, const i64 *ids, const double 
     }
     const u64 *key = ka;
     const unsigned *val = va;
-    if (rc == MM_OK && hipMemsetAsync(counters, 0, 2 * sizeof(i64), ctx->stream) != hipSuccess) rc = MM_ERR_HIP;
+    const i64 *count = nullptr;
+    if (rc == MM_OK && (counters = mm_counters_begin(ctx, 2, 2)) == nullptr) rc = MM_ERR_HIP;
     if (rc == MM_OK && n > 0) {
         hipLaunchKernelGGL(transpose_keys_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, ctx->stream, ids, n, lo, ndst, ka, va,
                            counters);
@@ -329,12 +329,11 @@ int build_handle(mm_context *ctx, mm_transpose *t, const i64 *ids, const double 
         if (n > 0 && w && ndst > 0)
             hipLaunchKernelGGL(transpose_long_rows_kernel, dim3(blocks_for(ndst)), dim3(kThreads), 0, ctx->stream, t->offsets,
                                ndst, t->long_rows, counters + 1);
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpyAsync(ctx->h_counters + 2, counters, 2 * sizeof(i64), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-            rc = MM_ERR_HIP;
+        if ((count = mm_counters_end(ctx, 2, 2)) == nullptr) rc = MM_ERR_HIP;
+    } else {
+        // (on failure too: the temporaries below must not be freed under a running kernel; mm_counters_end has synchronised)
+        (void)hipStreamSynchronize(ctx->stream);
     }
-    // (also on failure: the temporaries below must not be freed under a running kernel)
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == MM_OK) rc = MM_ERR_HIP;
     if (rc == MM_ERR_HIP) mm_set_error(MM_ERR_HIP, "%s: a HIP call failed: %s", what, hipGetErrorString(hipGetLastError()));
     if (ka) (void)mm_raw_free(ka);
     if (kb) (void)mm_raw_free(kb);
@@ -342,12 +341,11 @@ int build_handle(mm_context *ctx, mm_transpose *t, const i64 *ids, const double 
     if (vb) (void)mm_raw_free(vb);
     if (sort_scratch) (void)mm_raw_free(sort_scratch);
     if (rc != MM_OK) return rc;
-    if (ctx->h_counters[2] != 0) {
-        mm_set_error(MM_ERR_ARG, "%s: %lld ids outside [%lld, %lld)", what, (long long)ctx->h_counters[2], (long long)lo,
-                     (long long)ndst);
+    if (count[0] != 0) {
+        mm_set_error(MM_ERR_ARG, "%s: %lld ids outside [%lld, %lld)", what, (long long)count[0], (long long)lo, (long long)ndst);
         return MM_ERR_ARG;
     }
-    t->nlong = ctx->h_counters[3];
+    t->nlong = count[1];
     return MM_OK;
 }
 

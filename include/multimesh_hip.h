@@ -675,6 +675,7 @@ int mm_last_locate_stats(mm_context *ctx, long long *out4);
 #define MM_KNN_RAN_LEVELS 32   /* k > 32: knn_query_levels_kernel over density levels */
 #define MM_KNN_RAN_TREE 64     /* the density-adaptive tree */
 #define MM_KNN_RAN_ONE_PASS 128 /* build: mm_interpolate_hex8 sorted the centroids as it computed them (centroid_sort_kernel) */
+#define MM_KNN_RAN_TARGET_REPLAY 256 /* query: mm_interpolate_hex8 put the targets where the previous call's sort put them (target_replay_kernel) */
 int mm_last_knn_kernels(mm_context *ctx, int *mask);
 
 /* Stage timers (hipEvents on the context's stream).  With profiling on, every kernel

@@ -89,6 +89,9 @@ enum mm_buffer_slot {
     MM_BUF_TREE_LEVEL,
     MM_BUF_TREE_COARSE,
     MM_BUF_TREE_DOWN,                     //   ... targets of a query whose first window overflowed the tile (second pass)
+    MM_BUF_TPOS,                          // the fused hex8 pipeline's target sort, kept for the next call's replay
+    MM_BUF_TSTART,                        //   (mm_context::target_replay): every target's position in MM_BUF_TSORTED, the
+    MM_BUF_LANE_ITEMS,                    //   targets' cell starts, the lane kernel's work-item slots
     MM_BUF_LEVELS,                        // density levels of the kNN grid: {cell_start, sorted_xyz} per level
     MM_BUF_SAMPLE_POINTS = MM_BUF_LEVELS + 2 * 8,   // mm_sample_columns_gll: the chunk's generated targets
     MM_BUF_COUNT
@@ -127,6 +130,27 @@ struct mm_context {
         int misses = 0;
         long long calls_guessed = 0;   // (mm_debug_grid_guess: what the tests look at)
     } grid_guess;
+    // mm_interpolate_hex8: the target sort of the previous fused call (knn_query_typed).  The guess is the grid guess's
+    // -- this call's meshes are the previous call's --: then every target lies in the cell it lay in and its record belongs
+    // where it went last time, MM_BUF_TPOS[i].  A replayed sort computes the cell from THIS call's coordinates, stores
+    // the record at that position if it lies inside the cell's range of MM_BUF_TSTART, and raises the eighth mismatch
+    // word (mm_aborted) and the pinned word kMmCountsBadSlot otherwise: no count, no scan, no atomic; the lane kernel's work
+    // items (MM_BUF_LANE_ITEMS), a function of the cell starts alone, are last call's too.
+    // The pipeline asks its query to keep the sort while guessing is on (mm_knn_query_sorted_impl).  ok: the three
+    // buffers and MM_BUF_TSORTED hold the completed sort of npts targets on the grid {dims, geom} with the lane kernel's
+    // launch shape {Z, nstrips_total, max_items}; cleared by whatever else takes MM_BUF_TSORTED, by a replay that
+    // missed and by a failed call.
+    struct {
+        bool ok = false;
+        bool replayed = false;   // this attempt's sort was a replay
+        i64 npts = 0;
+        int dims[3] = {0, 0, 0};
+        double geom[6] = {0, 0, 0, 0, 0, 0};   // lo, inv_h: what cell_of_point reads
+        int Z = 0;
+        i64 nstrips_total = 0, max_items = 0;
+        long long replays = 0, records = 0, item_lists = 0;   // (mm_debug_target_replay: replayed sorts, recorded sorts, work
+                                                              // lists built for a kept sort)
+    } target_replay;
     // kNN queries whose targets fill only part of the grid (knn_query_typed): the verdict of the occupied-strip statistic
     struct {
         bool valid = false;
@@ -175,14 +199,16 @@ void mm_stage_end(mm_context *ctx, int stage);
 // measured: on this multi-XCD part the device-scope fence every workgroup needs before it takes its ticket writes
 // its XCD's L2 back -- the centroid kernel went from 0.26 to 0.72 ms, a scan's first kernel from 5 to 80 us.)
 //   24..27 (eight ints) mismatch flags of a guessed grid (mm_aborted)   2..3 scratch of small readbacks
-//   54 (h_counters) the one-pass build's per-cell counts differ from the guess (cursor_check_kernel)
+//   54 (h_counters) the one-pass build's per-cell counts differ from the guess (cursor_check_kernel), or a replayed
+//      target sort found a target outside last call's cell (target_replay_kernel)
 constexpr int kMmStatSlot = 32, kMmBoxSlot = 48, kMmAbortSlot = 24;   // (slots 0..15 are cleared by every locate stage)
 constexpr int kMmCountsBadSlot = 54;
 
 // A call over a GUESSED search grid (mm_interpolate_hex8): abort6 = eight ints; the first six are non-zero when this
 // call's bounding box is not the one the grid was laid out from, the seventh when a one-pass build found other per-cell
-// counts than the ones it placed its records by (the eighth is spare and zero).  The kernels that would be ruinously
-// slow on a foreign grid -- or read stale records -- ask first.
+// counts than the ones it placed its records by, the eighth when a replayed target sort found a target outside the cell
+// it lay in last call (a call on a resident source has only that one: the pipeline clears the block itself).  The
+// kernels that would be ruinously slow on a foreign grid -- or read stale records -- ask first.
 __device__ __forceinline__ bool mm_aborted(const int *__restrict__ abort6)
 {
     if (!abort6) return false;
@@ -242,8 +268,9 @@ int mm_knn_build_one_pass(mm_context *ctx, const i64 *conn, const double *nodes,
 bool mm_knn_guess_confirmed(mm_context *ctx);
 int mm_knn_query_impl(mm_context *ctx, const mm_knn_index *ix, const double *pts_d, i64 npts, i64 k, void *idx_d,
                       double *dist_d, bool idx_is_int32);
+// keep_sort: the targets' sort is kept for the next call, or replayed from the last one (mm_context::target_replay)
 int mm_knn_query_sorted_impl(mm_context *ctx, const mm_knn_index *ix, const double *pts_d, i64 npts, i64 k, int *idx_d,
-                             const double **tsorted_out);
+                             const double **tsorted_out, bool keep_sort);
 
 // The density-adaptive part of a kNN index (mm_knn_tree.inc.h): the sources in Morton order.
 struct mm_knn_tree {

@@ -41,14 +41,47 @@ __global__ __launch_bounds__(kBlock) void target_scatter_kernel(const int *__res
                                                                 const int *__restrict__ start,
                                                                 double *__restrict__ tsorted,
                                                                 const int *__restrict__ list,
-                                                                const int *__restrict__ list_count)
+                                                                const int *__restrict__ list_count,
+                                                                int *__restrict__ pos_out)
 {
+    // pos_out (nullable; no list): every target's position in the sorted order, for the next call's replay
     const i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= (list ? (i64)*list_count : npts)) return;
     const i64 p = list ? (i64)list[t] : t;   // the record carries the target's own index
     const double x = pts[p * ndim], y = ndim > 1 ? pts[p * ndim + 1] : 0.0, z = ndim > 2 ? pts[p * ndim + 2] : 0.0;
     const i64 pos = (i64)start[cell_of_point(x, y, z, g)] + rank_of[t];
     store_record(tsorted + pos * kRec, x, y, z, (int)p);
+    if (pos_out) pos_out[t] = (int)pos;
+}
+
+// The target sort of a call whose targets are the previous call's (mm_context::target_replay): the record of target t,
+// built from THIS call's coordinates, goes where last call's sort put it, pos_prev[t] -- if that lies inside the range
+// its cell of this call has in last call's cell starts.  When that holds for every target, every target is in the cell
+// it was in, and the placement is last call's permutation with this call's coordinates: this call's sort (the order
+// inside a cell is whatever the atomics gave last time, as ever).  A target for which it does not hold stores nothing
+// and raises the eighth mismatch word (mm_aborted) and the pinned word the host reads at the end of the call, which is
+// then run again with an ordinary sort.  Stale records are last call's: in their cells, ids in [0, npts).
+// zero[0 .. nzero): the query's counters, cleared on the way (nzero <= kBlock; nothing before this kernel reads them).
+__global__ __launch_bounds__(kBlock) void target_replay_kernel(const double *__restrict__ pts, i64 npts, int ndim, GridParams g,
+                                                               const int *__restrict__ pos_prev,
+                                                               const int *__restrict__ start, double *__restrict__ tsorted,
+                                                               int *__restrict__ mismatch8, long long *__restrict__ bad_h,
+                                                               int *__restrict__ zero, int nzero)
+{
+    if (blockIdx.x == 0 && (int)threadIdx.x < nzero) zero[threadIdx.x] = 0;
+    const i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    bool miss = false;
+    if (t < npts) {
+        const double x = pts[t * ndim], y = ndim > 1 ? pts[t * ndim + 1] : 0.0, z = ndim > 2 ? pts[t * ndim + 2] : 0.0;
+        const int c = cell_of_point(x, y, z, g);
+        const int pos = pos_prev[t];
+        miss = !(pos >= start[c] && pos < start[c + 1] && pos >= 0 && (i64)pos < npts);
+        if (!miss) store_record(tsorted + (i64)pos * kRec, x, y, z, (int)t);
+    }
+    if (__any(miss) && (threadIdx.x & 63) == 0) {
+        mismatch8[7] = 1;
+        *bad_h = 1;
+    }
 }
 
 // What serves level 0 of a query (choose_lane) and, for the lane kernel, the scratch of its work-item prepass
@@ -64,6 +97,7 @@ struct LaneWork {
     i64 max_items;       // upper bound on the work items: strips + targets / (64 * kLaneRounds)
     int *tile_sums;      // [tiles of strips + 1]: exclusive item offsets per tile, then the number of items
     int2 *items;         // [max_items]
+    bool items_kept;     // the items are in place: a replayed target sort (same cell starts, same list)
 };
 
 // Kernels are instantiated for a few list lengths k; a query runs the smallest instance that holds its k.
@@ -185,11 +219,13 @@ void launch_fast(mm_context *ctx, const mm_knn_index *ix, const GridParams &g, c
         constexpr int KL = K <= kLaneMaxK ? K : 1;   // (the strip-only list lengths are never instantiated)
         const int per_item = kWave * kLaneRounds;
         const int ntiles = (int)((lane->nstrips_total + kScanTile - 1) / kScanTile);
-        hipLaunchKernelGGL(lane_items_sums_kernel, dim3(ntiles), dim3(kBlock), 0, ctx->stream, g, tstart, lane->Z, per_item,
-                           lane->nstrips_total, lane->tile_sums, lane->items, lane->max_items);
-        hipLaunchKernelGGL(lane_items_offsets_kernel, dim3(1), dim3(kBlock), 0, ctx->stream, lane->tile_sums, ntiles);
-        hipLaunchKernelGGL(lane_items_place_kernel, dim3(ntiles), dim3(kBlock), 0, ctx->stream, g, tstart, lane->Z, per_item,
-                           lane->nstrips_total, lane->tile_sums, ntiles, lane->items);
+        if (!lane->items_kept) {
+            hipLaunchKernelGGL(lane_items_sums_kernel, dim3(ntiles), dim3(kBlock), 0, ctx->stream, g, tstart, lane->Z, per_item,
+                               lane->nstrips_total, lane->tile_sums, lane->items, lane->max_items);
+            hipLaunchKernelGGL(lane_items_offsets_kernel, dim3(1), dim3(kBlock), 0, ctx->stream, lane->tile_sums, ntiles);
+            hipLaunchKernelGGL(lane_items_place_kernel, dim3(ntiles), dim3(kBlock), 0, ctx->stream, g, tstart, lane->Z, per_item,
+                               lane->nstrips_total, lane->tile_sums, ntiles, lane->items);
+        }
         ctx->knn_kernels |= MM_KNN_RAN_LANE;
         const i64 wgs = lane->max_items;   // one workgroup per slot (a multiple of 8; < 2^31: npts and the strip count are)
         if (record_stage) mm_stage_begin(ctx, MM_STAGE_KNN_CELL);
@@ -399,7 +435,7 @@ static void grid_layout(const double *box, i64 nsrc, int ndim, double per_cell, 
 // 32-byte records), on ctx->stream.  counts must be zero.
 static int sort_targets(mm_context *ctx, const GridParams &gl, i64 ncells, int ndim, const double *pts_d, i64 npts,
                         const int *list, const int *list_count, int *cell_of, int *counts, int *start, int *tile_sums,
-                        double *tsorted)
+                        double *tsorted, int *pos_out = nullptr)
 {
     const unsigned gpts = (unsigned)((npts + kBlock - 1) / kBlock);
     const int ntiles = (int)((ncells + kScanTile - 1) / kScanTile);
@@ -413,7 +449,7 @@ static int sort_targets(mm_context *ctx, const GridParams &gl, i64 ncells, int n
                        (unsigned long long *)nullptr, 0);
     launch_scan_tail(ctx, counts, ncells, tile_sums, ntiles, start);
     hipLaunchKernelGGL(target_scatter_kernel, dim3(gpts), dim3(kBlock), 0, ctx->stream, cell_of, npts, pts_d, ndim, gl,
-                       start, tsorted, list, list_count);
+                       start, tsorted, list, list_count, list ? (int *)nullptr : pos_out);
     MM_HIP_CHECK(hipGetLastError());
     return MM_OK;
 }
@@ -1003,6 +1039,7 @@ static int tree_query(mm_context *ctx, const mm_knn_index *ix, const double *pts
     double *tsorted = ts.tsorted;
     if (sorted_rows) {
         // (outlives this call's scratch: the locate stage reads it)
+        ctx->target_replay.ok = false;   // (another order of the targets in there)
         rc = mm_buffer_get(ctx, MM_BUF_TSORTED, (size_t)npts * kRec * sizeof(double), (void **)&tsorted);
         if (rc != MM_OK) return rc;
     }
@@ -1159,18 +1196,38 @@ struct LevelScratch {
     double *tsorted = nullptr;      // cell-sorted target records (MM_BUF_TSORTED instead when the rows go by sorted position)
 
     // (level 0's counts are in the layout already: right behind the counters, see knn_query_typed)
-    void add(mm_scratch_layout &lay, const mm_knn_index *l, int level, i64 npts, bool have_list, bool sorted_rows)
+    // kept: `start` lives in a context buffer (mm_context::target_replay); replay: nothing is counted or scanned
+    void add(mm_scratch_layout &lay, const mm_knn_index *l, int level, i64 npts, bool have_list, bool sorted_rows, bool kept,
+             bool replay)
     {
-        lay.add(&cell_of, (size_t)npts);
+        if (!replay) lay.add(&cell_of, (size_t)npts);
         if (l->fine) lay.add(&down_list, (size_t)npts);
         if (level > 0) lay.add(&counts, (size_t)(l->ncells + 1));
-        lay.add(&start, (size_t)(l->ncells + 1));
-        lay.add(&tile_sums, (size_t)((l->ncells + kScanTile - 1) / kScanTile));
+        if (!kept) lay.add(&start, (size_t)(l->ncells + 1));
+        if (!replay) lay.add(&tile_sums, (size_t)((l->ncells + kScanTile - 1) / kScanTile));
         if (level > 0 || have_list) lay.add(&strip_list, (size_t)npts);
         if (!sorted_rows) lay.add(&tsorted, (size_t)npts * kRec);
     }
 };
 }  // namespace
+
+// The fused hex8 pipeline's target sort is kept for its next call (mm_context::target_replay): level 0's cell starts and the
+// lane kernel's work items live in context buffers instead of the scratch pool, the scatter records every target's position
+// (tpos) -- or, replay, the kept ones place this call's records.
+struct TargetKeep {
+    int *tpos;
+    bool replay;
+    int ncounters;   // ints of the query's counter block, which a replay clears itself
+};
+
+// Does the context hold the sort of these targets on this grid, with the lane kernel's launch shape of this query?
+static bool target_replay_holds(const mm_context *ctx, const mm_knn_index *ix, i64 npts, const LaneWork &lane)
+{
+    const auto &r = ctx->target_replay;
+    bool same = r.ok && r.npts == npts && r.Z == lane.Z && r.nstrips_total == lane.nstrips_total && r.max_items == lane.max_items;
+    for (int a = 0; a < 3 && same; ++a) same = r.dims[a] == ix->dims[a] && r.geom[a] == ix->lo[a] && r.geom[3 + a] == ix->inv_h[a];
+    return same;
+}
 
 // One density level of a query: its share of the targets (`list`; null: all of them) is counting-sorted by the level's
 // cells and visited strip by strip.  counts_zeroed: level 0's counts were cleared with the counters.
@@ -1178,7 +1235,7 @@ template <typename IDX>
 static int query_level(mm_context *ctx, const mm_knn_index *ix, const mm_knn_index *l, int level, int nlevels, const LevelScratch &s,
                        const double *pts_d, i64 npts, int kout, IDX *idx_d, double *dist_d, const double **tsorted_out,
                        const int *list, const int *list_count, int *fb_list, int *fb_count, bool counts_zeroed,
-                       LaneWork *lane, const QueryKnobs &kn)
+                       LaneWork *lane, const QueryKnobs &kn, const TargetKeep *keep = nullptr)
 {
     const GridParams gl = params_of(l);
     const i64 ncells = l->ncells;
@@ -1187,10 +1244,20 @@ static int query_level(mm_context *ctx, const mm_knn_index *ix, const mm_knn_ind
     // the targets' counting sort.  (Round 4 also ran it AHEAD of a guessed call -- its grid is known before the centroids
     // exist -- on a second stream beside the centroid kernel and the source sort: no gain, 3.51 vs 3.48 ms per step; they
     // are all bandwidth-bound and simply share the HBM.)
-    if (!counts_zeroed)
-        if (mm_zero_async(ctx, s.counts, mm_fill_span((size_t)(ncells + 1) * sizeof(int))) != MM_OK) return MM_ERR_HIP;
-    int rc = sort_targets(ctx, gl, ncells, l->ndim, pts_d, npts, list, list_count, s.cell_of, s.counts, s.start, s.tile_sums, s.tsorted);
-    if (rc != MM_OK) return rc;
+    int rc = MM_OK;
+    if (keep && keep->replay) {
+        // last call's sort with this call's coordinates (target_replay_kernel, which also clears the counters)
+        hipLaunchKernelGGL(target_replay_kernel, dim3((unsigned)((npts + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, pts_d,
+                           npts, l->ndim, gl, (const int *)keep->tpos, (const int *)s.start, s.tsorted, ctx->abort_flags,
+                           reinterpret_cast<long long *>(ctx->h_counters + kMmCountsBadSlot), fb_count, keep->ncounters);
+        ctx->knn_kernels |= MM_KNN_RAN_TARGET_REPLAY;
+    } else {
+        if (!counts_zeroed)
+            if (mm_zero_async(ctx, s.counts, mm_fill_span((size_t)(ncells + 1) * sizeof(int))) != MM_OK) return MM_ERR_HIP;
+        rc = sort_targets(ctx, gl, ncells, l->ndim, pts_d, npts, list, list_count, s.cell_of, s.counts, s.start, s.tile_sums, s.tsorted,
+                          keep ? keep->tpos : nullptr);
+        if (rc != MM_OK) return rc;
+    }
     if (lane->probe && level == 0) {
         if ((rc = lane_probe_readback(ctx, ix, gl, npts, s.start, lane)) != MM_OK) return rc;
         if (lane->sorted_rows) *tsorted_out = s.tsorted;
@@ -1218,7 +1285,7 @@ static int query_level(mm_context *ctx, const mm_knn_index *ix, const mm_knn_ind
 template <typename IDX>
 static int knn_query_typed(mm_context *ctx, const mm_knn_index *ix, const double *pts_d, i64 npts, i64 k, IDX *idx_d,
                            double *dist_d, const double **tsorted_out, const int *list0 = nullptr,
-                           const int *list0_count = nullptr, i64 list0_len = -1)
+                           const int *list0_count = nullptr, i64 list0_len = -1, bool keep_wanted = false)
 {
     // list0 (device): only the targets list0[0 .. *list0_count) are served (rows by the targets' own indices as ever);
     // the tiled kernels then walk just the strips that hold any of them (k <= 32)
@@ -1235,6 +1302,10 @@ static int knn_query_typed(mm_context *ctx, const mm_knn_index *ix, const double
     // visited strip by strip; targets whose strip is too full for the tile go down to the next level
     // (a device-side list), everything else the level cannot place goes to its generic kernel.
     LaneWork lane = choose_lane(ctx, ix, npts, k, list0, tsorted_out != nullptr, kn);
+    // the pipeline's sort, kept for its next call -- the plain case only: one grid, the lane kernel, rows by sorted position
+    const bool keep_sort = keep_wanted && lane.use_lane && lane.sorted_rows && !lane.probe && !ix->fine && !list0 &&
+                           !kn.force_list;
+    TargetKeep keep = {nullptr, keep_sort && ctx->abort_flags && target_replay_holds(ctx, ix, npts, lane), 0};
     int nlevels = 0;
     for (const mm_knn_index *l = ix; l; l = l->fine) ++nlevels;
     MM_REQUIRE(nlevels <= kMaxLevels, "more density levels than the build lays out");
@@ -1247,25 +1318,38 @@ static int knn_query_typed(mm_context *ctx, const mm_knn_index *ix, const double
     mm_scratch_layout lay;
     lay.add(&fb_list, (size_t)npts);
     lay.add(&fb_count, counter_ints);
-    lay.add(&lvs[0].counts, (size_t)(ix->ncells + 1));
+    if (!keep.replay) lay.add(&lvs[0].counts, (size_t)(ix->ncells + 1));
     if (lane.use_lane) {
-        lay.add(&lane.tile_sums, (size_t)((lane.nstrips_total + kScanTile) / kScanTile + 2));
-        lay.add(&lane.items, (size_t)lane.max_items);
+        if (!keep.replay) lay.add(&lane.tile_sums, (size_t)((lane.nstrips_total + kScanTile) / kScanTile + 2));
+        if (!keep_sort) lay.add(&lane.items, (size_t)lane.max_items);
     }
     if (!kn.force_list) {
         int level = 0;
-        for (const mm_knn_index *l = ix; l; l = l->fine, ++level) lvs[level].add(lay, l, level, npts, list0 != nullptr, lane.sorted_rows != 0);
+        for (const mm_knn_index *l = ix; l; l = l->fine, ++level) lvs[level].add(lay, l, level, npts, list0 != nullptr, lane.sorted_rows != 0, keep_sort && level == 0, keep.replay && level == 0);
     }
     int rc = lay.commit(ctx, __func__);
     if (rc != MM_OK) return rc;
     if (lane.sorted_rows) {
         // (outlives this call's scratch: the locate stage reads it)
+        if (!keep.replay) ctx->target_replay.ok = false;   // (rewritten below; set again once the kept sort is queued)
         rc = mm_buffer_get(ctx, MM_BUF_TSORTED, (size_t)npts * kRec * sizeof(double), (void **)&lvs[0].tsorted);
         if (rc != MM_OK) return rc;
         if (!lane.probe) *tsorted_out = lvs[0].tsorted;
     }
-    const bool one_fill = !kn.force_list && mm_scratch_adjacent(fb_count, counter_ints * sizeof(int), lvs[0].counts);   // (not so under MM_GUARD_ALLOC)
-    rc = mm_zero_async(ctx, fb_count, counter_ints * sizeof(int) + (one_fill ? mm_round256((size_t)(ix->ncells + 1) * sizeof(int)) : 0));
+    if (keep_sort) {
+        // (the same sizes as the call that left them: no reallocation, the contents stay)
+        rc = mm_buffer_get(ctx, MM_BUF_TPOS, (size_t)npts * sizeof(int), (void **)&keep.tpos);
+        if (rc == MM_OK) rc = mm_buffer_get(ctx, MM_BUF_TSTART, (size_t)(ix->ncells + 1) * sizeof(int), (void **)&lvs[0].start);
+        if (rc == MM_OK) rc = mm_buffer_get(ctx, MM_BUF_LANE_ITEMS, (size_t)lane.max_items * sizeof(int2), (void **)&lane.items);
+        if (rc != MM_OK) return rc;
+        keep.ncounters = (int)counter_ints;
+        lane.items_kept = keep.replay;
+        static_assert(64 * 2 <= kBlock, "one workgroup of the replay kernel clears a single level's counters");
+    }
+    const bool one_fill = !kn.force_list && !keep.replay &&
+                          mm_scratch_adjacent(fb_count, counter_ints * sizeof(int), lvs[0].counts);   // (not so under MM_GUARD_ALLOC)
+    if (!keep.replay)
+        rc = mm_zero_async(ctx, fb_count, counter_ints * sizeof(int) + (one_fill ? mm_round256((size_t)(ix->ncells + 1) * sizeof(int)) : 0));
     if (rc != MM_OK) return rc;
     if (kn.force_list)
         hipLaunchKernelGGL(list_all_kernel, dim3((unsigned)((npts + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, fb_list, fb_count, npts);
@@ -1273,7 +1357,7 @@ static int knn_query_typed(mm_context *ctx, const mm_knn_index *ix, const double
     int level = 0;
     for (const mm_knn_index *l = ix; l && !kn.force_list; l = l->fine, ++level) {
         rc = query_level<IDX>(ctx, ix, l, level, nlevels, lvs[level], pts_d, npts, kout, idx_d, dist_d, tsorted_out, list, list_count,
-                              fb_list, fb_count, level == 0 && one_fill, &lane, kn);
+                              fb_list, fb_count, level == 0 && one_fill, &lane, kn, keep_sort ? &keep : nullptr);
         if (rc != MM_OK) return rc;
         list = lvs[level].down_list;
         list_count = fb_count + 64 * (1 + level);
@@ -1285,6 +1369,22 @@ static int knn_query_typed(mm_context *ctx, const mm_knn_index *ix, const double
                                               kout, idx_d, dist_d, fb_list, fb_count, kListKeepMax);
     });
     MM_HIP_CHECK(hipGetLastError());
+    if (keep_sort) {
+        auto &r = ctx->target_replay;
+        r.replayed = keep.replay;
+        ++(keep.replay ? r.replays : r.records);
+        if (!lane.items_kept) ++r.item_lists;
+        r.ok = true;   // (a replay that missed: the pipeline clears it after the call's last synchronisation)
+        r.npts = npts;
+        r.Z = lane.Z;
+        r.nstrips_total = lane.nstrips_total;
+        r.max_items = lane.max_items;
+        for (int a = 0; a < 3; ++a) {
+            r.dims[a] = ix->dims[a];
+            r.geom[a] = ix->lo[a];
+            r.geom[3 + a] = ix->inv_h[a];
+        }
+    }
     return MM_OK;
 }
 
@@ -1320,9 +1420,9 @@ int mm_knn_query_impl(mm_context *ctx, const mm_knn_index *ix, const double *pts
 
 // int32 rows, in the cell-sorted order of the targets when the lane kernel serves the query (see knn_query_typed)
 int mm_knn_query_sorted_impl(mm_context *ctx, const mm_knn_index *ix, const double *pts_d, i64 npts, i64 k, int *idx_d,
-                             const double **tsorted_out)
+                             const double **tsorted_out, bool keep_sort)
 {
-    return knn_query_typed<int>(ctx, ix, pts_d, npts, k, idx_d, nullptr, tsorted_out);
+    return knn_query_typed<int>(ctx, ix, pts_d, npts, k, idx_d, nullptr, tsorted_out, nullptr, nullptr, -1, keep_sort);
 }
 
 extern "C" int mm_knn_build(mm_context *ctx, const double *src_d, int64_t nsrc, int64_t ndim, mm_knn_index **out)

@@ -151,25 +151,43 @@ static int describe_call(mm_context *ctx, const double *nodes_d, int64_t nnodes,
 // switches it off.  A guessed call whose context also still holds the cell_start of that grid's sort
 // (grid_guess.cells_ok) guesses the per-cell counts as well and sorts the centroids as it computes them
 // (mm_knn_build_one_pass); other counts are a miss like another box.
-static bool may_guess(const mm_context *ctx, const hex8_call &call)
+// The same guess covers the targets: a call keeps its target sort for the next one (mm_context::target_replay), which puts
+// its records where that sort put them and checks every one; a target that has left its cell is a miss like another box.
+static bool guessing_on(const mm_context *ctx)
 {
     static const bool guess_on = !(getenv("MM_GRID_GUESS") && atoi(getenv("MM_GRID_GUESS")) == 0);
     // (MM_KNN_LEVELS is read per call by the ordinary build -- tests switch it inside one process -- and a guessed build
     // would ignore it)
-    return guess_on && ctx->grid_guess.valid && ctx->grid_guess.nsrc == call.nelem && ctx->grid_guess.misses < 2 &&
-           !getenv("MM_KNN_LEVELS") && !call.resident;
+    return guess_on && ctx->grid_guess.misses < 2 && !getenv("MM_KNN_LEVELS");
+}
+
+static bool may_guess(const mm_context *ctx, const hex8_call &call)
+{
+    return guessing_on(ctx) && ctx->grid_guess.valid && ctx->grid_guess.nsrc == call.nelem && !call.resident;
+}
+
+// A call on a resident source has no box to guess, but its targets may be the previous call's: the mismatch words the
+// replayed sort reports to are cleared here (a guessed build's bbox_final_kernel does it otherwise).
+static int begin_resident_replay(mm_context *ctx)
+{
+    ctx->h_counters[kMmCountsBadSlot] = 0;   // (pinned; the stream is idle: every call that writes it ends with a wait)
+    ctx->abort_flags = reinterpret_cast<int *>(ctx->d_counters + kMmAbortSlot);
+    return mm_zero_async(ctx, ctx->abort_flags, 8 * sizeof(int));
 }
 
 // What a guessed call that ran to its end leaves in the context.
-static void settle_guess(mm_context *ctx, bool confirmed)
+static void settle_guess(mm_context *ctx, bool guessed, bool confirmed)
 {
     if (!confirmed) {
-        // not this mesh's grid (the call is run again the ordinary way, which also leaves the right box for the next call)
-        ctx->grid_guess.valid = false;
-        ctx->grid_guess.cells_ok = false;
+        // not this mesh's grid, or not these targets (the call is run again the ordinary way, which also leaves the right
+        // box and the right target sort for the next call)
+        if (guessed) ctx->grid_guess.valid = false;
+        if (guessed) ctx->grid_guess.cells_ok = false;
+        ctx->target_replay.ok = false;
         ++ctx->grid_guess.misses;
         return;
     }
+    if (!guessed) return;
     ctx->grid_guess.cells_ok = true;   // (the buffers hold this grid's complete sort)
     // (a long-lived context forgives old misses: every 64 calls that confirmed their guess take one back)
     if (ctx->grid_guess.misses > 0 && (ctx->grid_guess.calls_guessed & 63) == 0) --ctx->grid_guess.misses;
@@ -218,7 +236,8 @@ static int index_for_attempt(mm_context *ctx, const hex8_call &call, bool guesse
 
 // The stages of one attempt, each host upload just before the stage that needs it (feed may be null); ends with the
 // synchronisation after which the failed-point count is in the pinned mirror.
-static int64_t run_stages(mm_context *ctx, const hex8_call &call, const mm_host_feed *feed, bool guessed, IndexOwner *built)
+static int64_t run_stages(mm_context *ctx, const hex8_call &call, const mm_host_feed *feed, bool guessed, bool replay,
+                          IndexOwner *built)
 {
     const bool lazily = call.kq < call.k;
     int rc = MM_OK;
@@ -233,7 +252,10 @@ static int64_t run_stages(mm_context *ctx, const hex8_call &call, const mm_host_
     // (only with lazily evaluated lists: the reference-order kernel then reads the FULL lists, which are rows
     // by the targets' own indices; with eager lists it reads these rows and needs them in that order)
     const double *tsorted = nullptr;
-    rc = mm_knn_query_sorted_impl(ctx, lazy.index, call.points, call.npoints, call.kq, call.nn, lazily ? &tsorted : nullptr);
+    if (replay && call.resident && ctx->target_replay.ok && (rc = begin_resident_replay(ctx)) != MM_OK) return rc;
+    // (the sort is kept while guessing is on; it is replayed where abort_flags is set: a guessed or a resident call)
+    rc = mm_knn_query_sorted_impl(ctx, lazy.index, call.points, call.npoints, call.kq, call.nn, lazily ? &tsorted : nullptr,
+                                  guessing_on(ctx));
     mm_stage_end(ctx, MM_STAGE_KNN_QUERY);
     if (rc != MM_OK) return rc;
 
@@ -269,13 +291,17 @@ static int64_t run_stages(mm_context *ctx, const hex8_call &call, const mm_host_
 
 // One attempt at the call: the number of failed points, or a negative status after synchronising the stream.  The index
 // the attempt built lives until here (its arrays are borrowed from the context cache and stay).
-static int64_t attempt(mm_context *ctx, const hex8_call &call, const mm_host_feed *feed, bool guessed)
+static int64_t attempt(mm_context *ctx, const hex8_call &call, const mm_host_feed *feed, bool guessed, bool replay)
 {
     IndexOwner built;
     ctx->abort_flags = nullptr;
-    const int64_t result = run_stages(ctx, call, feed, guessed, &built);
+    ctx->target_replay.replayed = false;
+    const int64_t result = run_stages(ctx, call, feed, guessed, replay, &built);
     ctx->abort_flags = nullptr;
-    if (result < 0) (void)hipStreamSynchronize(ctx->stream);
+    if (result < 0) {
+        (void)hipStreamSynchronize(ctx->stream);
+        ctx->target_replay.ok = false;
+    }
     return result;
 }
 
@@ -291,14 +317,15 @@ static int64_t interpolate_hex8_impl(mm_context *ctx, const double *nodes_d, int
     if (rc != MM_OK) return rc;
     if (npoints == 0) return 0;
     const bool guessed = may_guess(ctx, call);
-    int64_t result = attempt(ctx, call, feed, guessed);
-    if (guessed && result >= 0) {
-        const bool confirmed = mm_knn_guess_confirmed(ctx);
-        settle_guess(ctx, confirmed);
+    int64_t result = attempt(ctx, call, feed, guessed, /*replay=*/true);
+    if ((guessed || ctx->target_replay.replayed) && result >= 0) {
+        // (a resident source's call guessed its targets alone: the one word the replayed sort raises)
+        const bool confirmed = guessed ? mm_knn_guess_confirmed(ctx) : ctx->h_counters[kMmCountsBadSlot] == 0;
+        settle_guess(ctx, guessed, confirmed);
         if (!confirmed) {
             // everything again without the guess -- and without the feed: the device copies of host arrays are in place
             mm_stage_reset(ctx);
-            result = attempt(ctx, call, nullptr, false);
+            result = attempt(ctx, call, nullptr, false, false);
         }
     }
     return result;
@@ -313,6 +340,19 @@ extern "C" int mm_debug_grid_guess(mm_context *ctx, long long *out4)
     out4[1] = ctx->grid_guess.misses;
     out4[2] = ctx->grid_guess.calls_guessed;
     out4[3] = ctx->grid_guess.nsrc;
+    return MM_OK;
+}
+
+// Debugging aid like mm_debug_grid_guess: out5 = {a target sort is held, fused calls that replayed it, fused calls that
+// recorded one, targets of the held sort, lane work lists built for kept sorts (a replay builds none)}.
+extern "C" int mm_debug_target_replay(mm_context *ctx, long long *out5)
+{
+    MM_REQUIRE(ctx != nullptr && out5 != nullptr, "null argument");
+    out5[0] = ctx->target_replay.ok ? 1 : 0;
+    out5[1] = ctx->target_replay.replays;
+    out5[2] = ctx->target_replay.records;
+    out5[3] = ctx->target_replay.npts;
+    out5[4] = ctx->target_replay.item_lists;
     return MM_OK;
 }
 

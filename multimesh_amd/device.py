@@ -19,7 +19,7 @@ from .helpers import MM_FP_EXACT, MM_FP_TOL, MM_KNN_MAX_K, STAGES, MultiMeshHipE
 from .synth import gll_derivative_matrix, gll_order_table, gll_weights_1d   # (ValueError for an order without tables)
 
 # MM_KNN_RAN_* in bit order
-KNN_KERNELS = ("lane", "strip", "cell", "list", "generic", "levels", "tree", "one_pass")
+KNN_KERNELS = ("lane", "strip", "cell", "list", "generic", "levels", "tree", "one_pass", "target_replay")
 #: centres per LDS batch of the taper kernel (kBatch in csrc/mm_precondition.hip)
 POINT_TAPER_BATCH = 256
 

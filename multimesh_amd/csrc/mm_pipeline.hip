@@ -189,7 +189,8 @@ static void settle_guess(mm_context *ctx, bool guessed, bool confirmed)
     }
     if (!guessed) return;
     ctx->grid_guess.cells_ok = true;   // (the buffers hold this grid's complete sort)
-    // (a long-lived context forgives old misses: every 64 calls that confirmed their guess take one back)
+    // (a long-lived context forgives old misses: a confirmed guess that is the context's 64th, 128th, ... guessed call,
+    // the missed ones counted, takes one back; with two misses nothing is guessed any more and nothing is taken back)
     if (ctx->grid_guess.misses > 0 && (ctx->grid_guess.calls_guessed & 63) == 0) --ctx->grid_guess.misses;
 }
 

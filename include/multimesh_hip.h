@@ -501,6 +501,86 @@ int mm_order_statistics(mm_context *ctx, const double *values_d, int64_t n, int6
 int mm_clamp(mm_context *ctx, const double *in_d, int64_t n, int64_t ncomp, const double *lower_d, const double *upper_d,
              int symmetric, double *out_d, int64_t *changed_d);
 
+/* BOUNDARIES: where a hexahedral mesh ends, which side of the domain each boundary face is, the distance of any point to
+ * the nearest boundary node up to a cutoff, and a taper or blend of fields driven by that distance (a regional model put
+ * inside a larger one without a step along its outline; a kernel damped towards absorbing sides).  3-D only.  The reference
+ * has no counterpart.  Integer atomics only; every result is the same on every run.
+ *
+ * Conventions.  Tensor corner c = i + 2 j + 4 k with i, j, k in {0, 1}; for a GLL element of order n, m = n + 1, corner c is
+ * node p = n i + m n j + m m n k; a hex8 connectivity in exodus order gives tensor order by its columns [0,1,3,2,4,5,7,6].
+ * Local faces f = 0 .. 5 are i = 0, i = 1, j = 0, j = 1, k = 0, k = 1, with the corners
+ *   (0,2,4,6) (1,3,5,7) (0,1,4,5) (2,3,6,7) (0,1,2,3) (4,5,6,7)      and, in cyclic order for the normal,
+ *   (0,2,6,4) (1,3,7,5) (0,1,5,4) (2,3,7,6) (0,1,3,2) (4,5,7,6).
+ * A face's nodes are the m m nodes with that index fixed, in ascending p.  The code of face f of element e is 6 e + f.
+ *
+ * mm_boundary_faces: corner_ids_d int64[nelem][8] in tensor order, every id in [0, nnodes), nnodes < 2^31, nelem < 2^27;
+ * faces_d int64[6 * nelem] (room for the worst case); info_d int64[1] or NULL.
+ *   keys = np.sort(corner_ids[:, FACE_CORNERS], axis=2).reshape(6 * nelem, 4)
+ *   _, inverse, counts = np.unique(keys, axis=0, return_inverse=True, return_counts=True)
+ *   faces = np.flatnonzero(counts[inverse] == 1);   info[0] = (counts[inverse] > 2).sum()
+ * faces_d receives the codes ascending; the return value is their number.  Faces whose key occurs more than twice count as
+ * interior: the mesh is then not a manifold.  A hash table of face indices claimed by compare-and-swap, matches found by
+ * comparing the claimant's sorted ids, a count per class, flags, a prefix sum.  Scratch: 8 bytes per slot of a table of
+ * 12 * nelem slots rounded up to a power of two, and 12 bytes per face.  MM_ERR_ARG, with nothing written to faces_d, for a
+ * null ctx or array, a size out of range or an id outside [0, nnodes) (checked on the device).  nelem == 0 is valid.
+ * Synchronises. */
+int64_t mm_boundary_faces(mm_context *ctx, const int64_t *corner_ids_d, int64_t nelem, int64_t nnodes, int64_t *faces_d,
+                          int64_t *info_d);
+
+/* The side of every boundary face: corners_d f64[nelem][8][3] in tensor order, faces_d int64[nb] codes in [0, 6 * nelem)
+ * (checked on the device: MM_ERR_ARG, nothing is read through a bad code), side_d int[nb].  Every product, sum and quotient
+ * rounded on its own; with q0 .. q3 the face's corners in cyclic order and c0 .. c7 the element's:
+ *   a = q2 - q0;  b = q3 - q1;  n = (a1*b2 - a2*b1, a2*b0 - a0*b2, a0*b1 - a1*b0)
+ *   fc = ((q0 + q1) + (q2 + q3)) * 0.25;  ec = (((((((c0 + c1) + c2) + c3) + c4) + c5) + c6) + c7) * 0.125;  g = fc - ec
+ *   if ((n0*g0 + n1*g1) + n2*g2 < 0) n = -n                                  (outward)
+ *   u = fc if radial (Earth-centred coordinates) else (upx, upy, upz)
+ *   t = (n0*u0 + n1*u1) + n2*u2;  lim = cos_min * sqrt(((n0*n0 + n1*n1) + n2*n2) * ((u0*u0 + u1*u1) + u2*u2))
+ *   side = 1 (top) if t >= lim, else 2 (bottom) if t <= -lim, else 0 (lateral side); a NaN gives 0.
+ * MM_ERR_ARG also for a null ctx or array, a size out of range, nb > 6 * nelem, radial other than 0 / 1, cos_min outside
+ * (0, 1], and without radial an up that is zero or not finite.  nb == 0 is valid.  Synchronises. */
+int mm_boundary_classify(mm_context *ctx, const double *corners_d, int64_t nelem, const int64_t *faces_d, int64_t nb,
+                         int radial, double upx, double upy, double upz, double cos_min, int *side_d);
+
+/* The nodes of the selected boundary faces: points_d f64[nelem][P][3], P = (order + 1)^3, order 1, 2 or 4 (hex8: order 1 with
+ * the gathered tensor-order corners); faces_d int64[nb], side_d int[nb] (NULL: every face is selected); a face is selected
+ * when bit (1 << side) of side_mask is set; out_d f64[nb * (order + 1)^2][3] (room for the worst case).
+ *   out = np.concatenate([points[e, FACE_NODES[f]] for (e, f) of the selected faces, in faces_d's order])
+ * face by face, ascending p within a face; a node shared by two faces appears twice, which is harmless for a minimum.
+ * Returns the number of points written, (order + 1)^2 per selected face.  MM_ERR_ARG, with nothing written, for a null ctx
+ * or array, another order, a size out of range, nb > 6 * nelem, side_mask outside [0, 7], a code outside [0, 6 * nelem) or a
+ * side outside [0, 2] (both checked on the device).  Synchronises. */
+int64_t mm_boundary_nodes(mm_context *ctx, const double *points_d, int64_t nelem, int order, const int64_t *faces_d,
+                          const int *side_d, int64_t nb, int side_mask, double *out_d);
+
+/* The distance to the nearest source up to a cutoff: points_d f64[n][3], sources_d f64[K][3], dist_d f64[n].
+ *   d_i = cutoff
+ *   for every source j:  dx, dy, dz = the differences;  r = sqrt((dx*dx + dy*dy) + dz*dz);  if (r < d_i) d_i = r
+ * A minimum does not depend on its order: the result is defined by the SET of sources alone, bit for bit.  A point with a
+ * NaN coordinate keeps cutoff.  Returns the number of points with d < cutoff.  A cell grid over the sources' bounding box,
+ * built by a counting sort (integer histogram, prefix sum, scatter), with an edge of cutoff * (1 + 2^-30) -- enlarged until
+ * there are at most 1024 cells per axis and 2^22 in all --; a point scans the 27 cells around its own and a point outside
+ * the box grown by one cell is done at once.  The margin covers the rounding of the cell index and of r itself (DESIGN.md
+ * section 5): a source whose rounded r is below cutoff never sits outside the 27 cells.  The distance is to the nearest
+ * NODE given, not to the surface they sample: its resolution is the node spacing.
+ * Scratch: 28 bytes per source and 8 per cell.  MM_ERR_ARG (nothing is written) for a null ctx or array, a negative size,
+ * K >= 2^30, a cutoff that is not finite, not positive or below 2^-500 (the margin's derivation needs the squares of the
+ * offsets not to underflow), a source that is not finite (checked on the device), an extent of the sources that overflows.
+ * K == 0 (every d is cutoff) and n == 0 are valid.  Synchronises. */
+int64_t mm_cutoff_distance(mm_context *ctx, const double *points_d, int64_t n, const double *sources_d, int64_t K, double cutoff,
+                           double *dist_d);
+
+/* Taper or blend by a distance: dist_d f64[n]; a_d, b_d (or NULL), out_d f64[ncomp][n]; elem_d int64[n] or NULL;
+ * weight_out_d f64[n] or NULL.  w is mm_point_taper's smoothstep of d, formula and order of the tests unchanged:
+ *   w = 0.0 if d <= inner, else 1.0 if d >= outer, else (s*s) * (3.0 - 2.0*s) with s = (d - inner) / (outer - inner)
+ *   with elem_d: w = 0.0 where elem < 0 (a point that was not located)
+ *   b_d == NULL (taper):  out = w * a
+ *   otherwise (blend):    out = b if w == 0, a if w == 1, else (w * a) + ((1.0 - w) * b)
+ * so a garbage or NaN a where w == 0 never leaks into a blend.  inner == outer is a hard cut.  out_d may be a_d or b_d.
+ * Returns the number of nodes with w < 1.  MM_ERR_ARG (nothing is written) for a null ctx or array, a negative size,
+ * ncomp >= 65536, radii that are not finite with 0 <= inner <= outer.  n == 0 and ncomp == 0 are valid.  Synchronises. */
+int64_t mm_distance_taper(mm_context *ctx, const double *dist_d, int64_t n, double inner, double outer, int64_t ncomp,
+                          const double *a_d, const double *b_d, const int64_t *elem_d, double *out_d, double *weight_out_d);
+
 /* The streaming kernels of a preconditioned conjugate-gradient loop over ncomp independent systems of n unknowns each
  * (vectors f64[ncomp][n]), whose scalars never leave the device.  state_d f64[ncomp][8] holds, per system, the slots below:
  * the dots are written into MM_PCG_RZ, MM_PCG_PAP and MM_PCG_BB by mm_weighted_sum (one call per system with ncomp = 1).

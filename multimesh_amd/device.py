@@ -841,6 +841,131 @@ class Context(_Released):
         self._check_args(rc, "mm_clamp")
         return out, changed
 
+    # ---- boundaries: faces, their side and nodes, the distance to them, the taper and blend it drives ------
+    def _faces(self, faces, nelem, side=None):
+        """(faces int64[nb] on the device, side int32[nb] or None, nb), checked against ``nelem`` elements."""
+        fd = self.asdevice(faces, np.int64)
+        if len(fd.shape) != 1 or fd.shape[0] > 6 * nelem:
+            raise ValueError("faces must be 1-D with at most 6 * nelem codes")
+        sd = None if side is None else self.asdevice(side, np.int32)
+        if sd is not None and sd.shape != fd.shape:
+            raise ValueError("side must hold one entry per face")
+        return fd, sd, fd.shape[0]
+
+    def boundary_faces(self, corner_ids, nnodes):
+        """The boundary faces of a hexahedral mesh (``mm_boundary_faces``): corner_ids int64[E, 8] in tensor order
+        (corner ``i + 2 j + 4 k``), every id in [0, nnodes).  A face is a boundary face when its four sorted ids occur once
+        among all 6 E faces.  Returns (codes ``6 e + f`` int64[nb] ascending, on the device; the number of faces whose ids
+        occur more than twice -- not zero: the mesh is not a manifold).  An id out of range raises ``ValueError``."""
+        ids = self.asdevice(corner_ids, np.int64)
+        if len(ids.shape) != 2 or ids.shape[1] != 8:
+            raise ValueError("corner_ids must be [E, 8]")
+        nnodes = int(nnodes)
+        if not 0 <= nnodes < 1 << 31 or ids.shape[0] >= 1 << 27:
+            raise ValueError("nnodes must lie in [0, 2^31) and E below 2^27")
+        faces = self.empty((6 * ids.shape[0],), np.int64)
+        info = self.empty((1,), np.int64)
+        rc = self.lib.mm_boundary_faces(self.handle, ids.ptr, ids.shape[0], nnodes, faces.ptr, info.ptr)
+        self._check_args(rc, "mm_boundary_faces")
+        return faces.rows(0, int(rc)), int(info.numpy()[0])
+
+    def boundary_classify(self, corners, faces, up=None, cos_min=0.5):
+        """Top (1), bottom (2) or lateral side (0) of every boundary face (``mm_boundary_classify``): corners f64[E, 8, 3]
+        in tensor order, faces int64[nb] codes.  ``up=None``: radial, the direction of the face's centre in Earth-centred
+        coordinates; else a vector (x, y, z).  A face is top when the cosine between its outward normal and up is at least
+        ``cos_min`` (in (0, 1]), bottom when it is at most ``-cos_min``.  Returns int32[nb] on the device."""
+        c = self.asdevice(corners, np.float64)
+        if len(c.shape) != 3 or c.shape[1:] != (8, 3):
+            raise ValueError("corners must be [E, 8, 3]")
+        fd, _, nb = self._faces(faces, c.shape[0])
+        if not 0.0 < float(cos_min) <= 1.0:
+            raise ValueError("cos_min must lie in (0, 1]")
+        u = (0.0, 0.0, 0.0)
+        if up is not None:
+            u = tuple(float(v) for v in np.asarray(up, dtype=np.float64).reshape(-1))
+            if len(u) != 3 or not np.isfinite(u).all() or not any(u):
+                raise ValueError("up must be three finite numbers, not all zero")
+        side = self.empty((nb,), np.int32)
+        rc = self.lib.mm_boundary_classify(self.handle, c.ptr, c.shape[0], fd.ptr, nb, 1 if up is None else 0, u[0], u[1],
+                                           u[2], float(cos_min), side.ptr)
+        self._check_args(rc, "mm_boundary_classify")
+        return side
+
+    def boundary_nodes(self, points, shape_order, faces, side=None, side_mask=7):
+        """The nodes of the boundary faces whose side is in ``side_mask`` (bit ``1 << side``; ``mm_boundary_nodes``):
+        points f64[E, (order+1)^3, 3], order 1, 2 or 4; faces int64[nb], side int32[nb] (None: every face).  Face by face in
+        the order of ``faces``, ascending node index within a face; a node shared by two faces appears twice.  Returns
+        f64[K, 3] on the device, K = (order+1)^2 per selected face."""
+        pts = self.asdevice(points, np.float64)
+        order = int(shape_order)
+        if order not in (1, 2, 4):
+            raise ValueError("shape_order must be 1, 2 or 4")
+        if len(pts.shape) != 3 or pts.shape[1:] != ((order + 1) ** 3, 3):
+            raise ValueError("points must be [E, (order+1)^3, 3]")
+        fd, sd, nb = self._faces(faces, pts.shape[0], side)
+        if not 0 <= int(side_mask) <= 7:
+            raise ValueError("side_mask must lie in [0, 7]")
+        out = self.empty((nb * (order + 1) ** 2, 3), np.float64)
+        rc = self.lib.mm_boundary_nodes(self.handle, pts.ptr, pts.shape[0], order, fd.ptr, sd.ptr if sd else None, nb,
+                                        int(side_mask), out.ptr)
+        self._check_args(rc, "mm_boundary_nodes")
+        return out.rows(0, int(rc))
+
+    def cutoff_distance(self, points, sources, cutoff):
+        """``min(cutoff, min over the sources of |x - s|)`` for points f64[..., 3] and sources f64[K, 3]
+        (``mm_cutoff_distance``): bit for bit the brute-force minimum, by a cell grid whose edge is just above ``cutoff``;
+        points far from every source cost O(1).  A point with a NaN coordinate keeps ``cutoff``.  Returns (distance f64 of
+        the points' leading shape, on the device; the number of points with distance < cutoff).  A cutoff that is not
+        positive and finite, or a source that is not finite, raises ``ValueError``."""
+        pts, n = self._points3(points)
+        s = self.asdevice(sources, np.float64)
+        if len(s.shape) != 2 or s.shape[1] != 3:
+            raise ValueError("sources must be [K, 3]")
+        cutoff = float(cutoff)
+        if not (np.isfinite(cutoff) and cutoff > 0.0):
+            raise ValueError("cutoff must be positive and finite")
+        dist = self.empty(pts.shape[:-1], np.float64)
+        rc = self.lib.mm_cutoff_distance(self.handle, pts.ptr, n, s.ptr, s.shape[0], cutoff, dist.ptr)
+        self._check_args(rc, "mm_cutoff_distance")
+        return dist, int(rc)
+
+    def distance_taper(self, dist, inner, outer, a, b=None, elem=None, out=None, want_weight=False):
+        """Taper or blend by a distance (``mm_distance_taper``): ``w`` = 0 for ``dist <= inner``, 1 for ``dist >= outer``,
+        the smoothstep ``s*s*(3 - 2*s)`` between them, and 0 where ``elem`` (int64, one per node) is negative.  ``a``
+        f64[C, ...] over the shape of ``dist`` (or that shape: one component), or None with ``want_weight``; ``b`` None:
+        ``out = w * a``; else ``out = b`` where w == 0, ``a`` where w == 1, ``(w * a) + ((1 - w) * b)`` between.  ``out`` may be
+        ``a`` or ``b``.  Returns (out on the device or None, the number of nodes with w < 1) and, with ``want_weight``, the
+        weight as a third entry.  ``0 <= inner <= outer``, finite (``ValueError`` otherwise)."""
+        d = self.asdevice(dist, np.float64)
+        inner, outer = float(inner), float(outer)
+        if not (np.isfinite(inner) and np.isfinite(outer) and 0.0 <= inner <= outer):
+            raise ValueError("the radii need 0 <= inner <= outer, both finite")
+        n = d.size
+        av, bv, ncomp = None, None, 0
+        if a is not None:
+            av = self.asdevice(a, np.float64)
+            ncomp = 1 if av.shape == d.shape else av.shape[0]
+            if av.size != ncomp * n:
+                raise ValueError("a must hold one value per component and node")
+            if b is not None:
+                bv = self.asdevice(b, np.float64)
+                if bv.size != av.size:
+                    raise ValueError("b must hold one value per value of a")
+            out = self._out(out, (ncomp,) + d.shape, "out must hold one value per component and node", size_only=True)
+        elif b is not None or out is not None:
+            raise ValueError("b or out without a")
+        elif not want_weight:
+            raise ValueError("ask for the weight or pass a")
+        ev = None if elem is None else self.asdevice(elem, np.int64)
+        if ev is not None and ev.size != n:
+            raise ValueError("elem must hold one entry per node")
+        weight = self.empty(d.shape, np.float64) if want_weight else None
+        rc = self.lib.mm_distance_taper(self.handle, d.ptr, n, inner, outer, ncomp, av.ptr if av else None,
+                                        bv.ptr if bv else None, ev.ptr if ev else None, out.ptr if av else None,
+                                        weight.ptr if weight else None)
+        self._check_args(rc, "mm_distance_taper")
+        return (out if av else None, int(rc), weight) if want_weight else (out, int(rc))
+
     # ---- diffusion: the stiffness operator and the smoothing it gives -------------------------------
     def diffusion(self, shape_order, gll_points, kappa_h=1.0, kappa_r=None):
         """A :class:`Diffusion` over gll_points f64[E, (order+1)^dim, dim], orders 1, 2, 4: ``apply(u)`` is the bare

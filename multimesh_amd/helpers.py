@@ -92,6 +92,11 @@ SIGNATURES = {
     "mm_point_taper": (i64, (vp, vp, i64, i64, vp, vp, vp, i64, i64, vp, vp, vp)),
     "mm_order_statistics": (i32, (vp, vp, i64, i64, i32, vp, i64, i32, vp, vp)),
     "mm_clamp": (i32, (vp, vp, i64, i64, vp, vp, i32, vp, vp)),
+    "mm_boundary_faces": (i64, (vp, vp, i64, i64, vp, vp)),
+    "mm_boundary_classify": (i32, (vp, vp, i64, vp, i64, i32, f64, f64, f64, f64, vp)),
+    "mm_boundary_nodes": (i64, (vp, vp, i64, i32, vp, vp, i64, i32, vp)),
+    "mm_cutoff_distance": (i64, (vp, vp, i64, vp, i64, f64, vp)),
+    "mm_distance_taper": (i64, (vp, vp, i64, f64, f64, i64, vp, vp, vp, vp, vp)),
     "mm_pcg_combine": (i32, (vp, vp, vp, f64, vp, i64, i64, vp)),
     "mm_pcg_scalars": (i32, (vp, vp, i64, i32, f64, vp)),
     "mm_pcg_direction": (i32, (vp, vp, vp, i64, i64, vp)),

@@ -581,6 +581,54 @@ int64_t mm_cutoff_distance(mm_context *ctx, const double *points_d, int64_t n, c
 int64_t mm_distance_taper(mm_context *ctx, const double *dist_d, int64_t n, double inner, double outer, int64_t ncomp,
                           const double *a_d, const double *b_d, const int64_t *elem_d, double *out_d, double *weight_out_d);
 
+/* RESOLUTION: what a model asks of the mesh it sits on -- the time step the model forces and the shortest period the mesh
+ * still resolves with it -- from the node spacing and the edge lengths of every element.  The reference has no counterpart
+ * (it leaves this to Salvus).
+ *   gll_points_d f64[nelem][P][dim], P = m^dim, m = order + 1, order 1, 2 or 4, dim 2 or 3, node p = i + m j + m^2 k; fields
+ *   f64[C][nelem][P] (the layouts of mm_gll_mass).  Every difference, product, sum, root and quotient is rounded on its own
+ *   (no fused multiply-add).  The distance of two nodes is sqrt((dx*dx + dy*dy) + dz*dz) with d = later - earlier (2-D:
+ *   sqrt(dx*dx + dy*dy)).
+ *   h[e][p]     = the least distance from node p to its tensor-line neighbours: the predecessor and the successor along
+ *                 each of the dim directions, where they exist (a node at the end of a line has one neighbour along it)
+ *   spacing[e]  = min_p h[e][p]
+ *   edge_min[e], edge_max[e] = the least and greatest of the straight corner-to-corner edge lengths, 12 in 3-D and 4 in
+ *                 2-D: corner c = i + 2 j + 4 k is node p = n i + m n j + m m n k (n = order), the edges join the corners
+ *                 (c, c | 1 << d) with bit d of c clear.  On a curved element the edge is the CHORD, not the arc.
+ *   With fast_d f64[nfast][nelem][P], nfast >= 1, and slow_d f64[nslow][nelem][P], nslow >= 0:
+ *   vfast[e][p] = max_c fast[c][e][p];      step[e] = min_p (h[e][p] / vfast[e][p])
+ *   vslow[e][p] = the least of the slow[c][e][p] that are > 0; if none is, min_c fast[c][e][p] (a fluid element, where
+ *                 VS = 0, is resolved by its P wavelength)
+ *   period[e]   = edge_max[e] / (min_p vslow[e][p])                      (one division per element)
+ * A time step is courant * min_e step[e], a resolved period elements_per_wavelength * max_e period[e]: the two factors are
+ * the caller's conventions, not part of this definition.  All minima and maxima are taken over exact values, so their order
+ * cannot change a bit.  (The kernel takes them of the squared distances and then one root: a correctly rounded root is
+ * monotone, so the bits are those of the statement.)
+ * Validity.  An element is geometry-invalid when any of its coordinates is not finite; model-invalid when it is
+ * geometry-invalid, when any of its fast or slow values is not finite, when any fast value is <= 0 or any slow value < 0.
+ * A geometry-invalid element's entries of all five rows (and its row of node_h_d) are NaN; a model-invalid element's entries
+ * of step and period are NaN.  Coincident nodes (h = 0) are valid and give step = 0.
+ *   node_h_d f64[nelem][P] or NULL: h;  out_d f64[5][nelem]: spacing, edge_min, edge_max, step, period -- with nfast == 0
+ *   rows 3 and 4 are not written (out_d may then be f64[3][nelem]) and slow_d must be NULL with nslow == 0;
+ *   info_d int64[2]: the geometry-invalid and the model-invalid elements (equal with nfast == 0).
+ * One streaming pass: 24 B read per node (8 more per node and velocity component), 24 or 40 B written per element.
+ * MM_ERR_ARG (nothing is written) for a null ctx or array, another order or dim, a size out of range, nfast or nslow outside
+ * [0, 1024], slow velocities without a fast one.  nelem == 0 is valid (info_d is zeroed).  Not synchronising: everything
+ * stays on the device. */
+int mm_gll_resolution(mm_context *ctx, int order, int dim, const double *gll_points_d, int64_t nelem, const double *fast_d,
+                      int64_t nfast, const double *slow_d, int64_t nslow, double *node_h_d, double *out_d, int64_t *info_d);
+
+/* The least (want_max == 0) or greatest (1) value of every row of values_d f64[nrows][n] that is not a NaN, and where it
+ * stands: value_d f64[nrows], index_d int64[nrows], nvalid_d int64[nrows] (the values that are not NaN).  Among equal values
+ * the LOWEST index wins; -0.0 and +0.0 compare equal; the value returned is the one stored at that index (so it may be
+ * -0.0).  A row without a valid value gives NaN and -1.  In NumPy, per row:
+ *   valid = np.flatnonzero(~np.isnan(row));  i = valid[np.argmax(row[valid])]   (np.argmin for the least)
+ * Integer atomics only -- a 64-bit atomicMax on the order-preserving integer image of the double, then one on the complement
+ * of the index of the values equal to it -- so the result is the same on every run.  No scratch, and nothing is read back:
+ * not synchronising.  MM_ERR_ARG for a null ctx or array, nrows outside [0, 65536), n outside [0, 2^48), want_max other
+ * than 0 or 1.  nrows == 0 and n == 0 are valid. */
+int mm_arg_extreme(mm_context *ctx, const double *values_d, int64_t nrows, int64_t n, int want_max, double *value_d,
+                   int64_t *index_d, int64_t *nvalid_d);
+
 /* The streaming kernels of a preconditioned conjugate-gradient loop over ncomp independent systems of n unknowns each
  * (vectors f64[ncomp][n]), whose scalars never leave the device.  state_d f64[ncomp][8] holds, per system, the slots below:
  * the dots are written into MM_PCG_RZ, MM_PCG_PAP and MM_PCG_BB by mm_weighted_sum (one call per system with ncomp = 1).

@@ -2,7 +2,8 @@
 // of that geometry: J, det, G = J^-1, the unit radius, the reference gradient g and the physical gradient gr = G g.
 // Who uses what: gll_mass_kernel (mm_mass.hip) and gll_gradient_kernel (mm_gradient.hip) use all of it; the stiffness
 // kernel gll_diffusion_kernel (mm_diffusion.hip) uses the constants and the geometry functions and keeps its own lane
-// set-up, loads and stores (see its header comment); mm_order.hip uses kThreads, kMaxBlocks, ipow and grid_size;
+// set-up, loads and stores (see its header comment); gll_resolution_kernel (mm_resolution.hip) uses the tile, its fetch and
+// the lanes' bookkeeping (Node) but no table and no Jacobian; mm_order.hip uses kThreads, kMaxBlocks, ipow and grid_size;
 // radial_apply_kernel (mm_radial.hip) and point_taper_kernel (mm_precondition.hip) use RunTile, the bookkeeping of the
 // same tile for a P known only at run time.
 // Every expression here is under a bit-parity contract with a NumPy statement (tests/mass_cases.py, diffusion_cases.py,
@@ -83,38 +84,46 @@ struct Tile {
     }
 
     // ---- this lane's node of the tile: p = i[0] + M i[1] + M^2 i[2] of element el; direction d is the line of the
-    // nodes that differ from it in i[d] alone, line[d] its first node (an offset in nodes of the tile), M^d its stride
-    struct Lane {
+    // nodes that differ from it in i[d] alone, line[d] its first node (an offset in nodes of the tile), M^d its stride.
+    // Node is the bookkeeping alone (mm_resolution.hip needs no table); Lane adds the lane's rows of D.
+    struct Node {
         bool node_lane;   // 256 / P leaves lanes over: they hold no node (and are clamped to node 0)
+        int el, p;        // the lane's element of the tile and its node of that element
         int i[DIM];
         int line[DIM];
-        double row[DIM][M];   // rows of D: D[i[d]][a]
 
-        __device__ __forceinline__ explicit Lane(const double *tab)
+        __device__ __forceinline__ Node()
         {
             const int tid = threadIdx.x;
             const bool has_node = tid < TILE_NODES;
-            const int el = has_node ? tid / P : 0;
-            const int p = has_node ? tid - el * P : 0;
+            el = has_node ? tid / P : 0;
+            p = has_node ? tid - el * P : 0;
             node_lane = has_node;
             const int pi = p % M, pj = (p / M) % M, pk = DIM == 3 ? p / (M * M) : 0;
             const int nbase = el * P;
             i[0] = pi, i[1] = pj;
             line[0] = nbase + (p - pi), line[1] = nbase + (p - pj * M);
             if constexpr (DIM == 3) i[2] = pk, line[2] = nbase + (p - pk * M * M);
+        }
+    };
+    struct Lane : Node {
+        double row[DIM][M];   // rows of D: D[i[d]][a]
+
+        __device__ __forceinline__ explicit Lane(const double *tab) : Node()
+        {
 #pragma unroll
             for (int a = 0; a < M; ++a) {
-                row[0][a] = tab[pi * M + a];
-                row[1][a] = tab[pj * M + a];
-                if constexpr (DIM == 3) row[2][a] = tab[pk * M + a];
+                row[0][a] = tab[this->i[0] * M + a];
+                row[1][a] = tab[this->i[1] * M + a];
+                if constexpr (DIM == 3) row[2][a] = tab[this->i[2] * M + a];
             }
         }
         // (w_k * w_j) * w_i from the weights behind D in tab
         __device__ __forceinline__ double wprod(const double *tab) const
         {
             const double *w = tab + TABLE;
-            if constexpr (DIM == 3) return (w[i[2]] * w[i[1]]) * w[i[0]];
-            else return w[i[1]] * w[i[0]];
+            if constexpr (DIM == 3) return (w[this->i[2]] * w[this->i[1]]) * w[this->i[0]];
+            else return w[this->i[1]] * w[this->i[0]];
         }
     };
 

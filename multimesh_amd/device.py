@@ -966,6 +966,43 @@ class Context(_Released):
         self._check_args(rc, "mm_distance_taper")
         return (out if av else None, int(rc), weight) if want_weight else (out, int(rc))
 
+    # ---- resolution: node spacing, edge lengths, the time step and the resolved period of a model ------
+    def gll_resolution(self, shape_order, gll_points, fast=None, slow=None, want_node_spacing=False):
+        """The sizes of every element of gll_points f64[E, (order+1)^dim, dim], orders 1, 2, 4, and what a model makes of
+        them (``mm_gll_resolution``: bit for bit the NumPy statement of include/multimesh_hip.h).  ``fast`` f64[nfast, E, P]
+        (or [E, P]) and ``slow`` f64[nslow, E, P] are the velocities; ``slow`` needs ``fast``.  Returns (out, info), both on
+        the device and nothing read back: out f64[5, E] = spacing, edge_min, edge_max, step, period -- f64[3, E] without
+        ``fast`` --, info int64[2] = the geometry-invalid and the model-invalid elements, whose entries are NaN.  The edges
+        are corner-to-corner chords, not arcs.  With ``want_node_spacing`` a third entry: h f64[E, P], every node's least
+        distance to its tensor-line neighbours."""
+        gp, nelem, P, dim = self._gll_points(shape_order, gll_points)
+        f = None if fast is None else _element_nodal(self, fast, nelem, P, "fast")
+        s = None if slow is None else _element_nodal(self, slow, nelem, P, "slow")
+        out = self.empty((5 if f else 3, nelem), np.float64)
+        info = self.empty((2,), np.int64)
+        node_h = self.empty((nelem, P), np.float64) if want_node_spacing else None
+        rc = self.lib.mm_gll_resolution(self.handle, int(shape_order), dim, gp.ptr, nelem, f.ptr if f else None,
+                                        f.shape[0] if f else 0, s.ptr if s else None, s.shape[0] if s else 0,
+                                        node_h.ptr if node_h else None, out.ptr, info.ptr)
+        self._check_args(rc, "mm_gll_resolution")
+        return (out, info, node_h) if want_node_spacing else (out, info)
+
+    def arg_extreme(self, values, want_max=False):
+        """The least (``want_max``: greatest) value of every row of values f64[R, ...] (every row read flat) or f64[n] (one
+        row) that is not a NaN, and its place (``mm_arg_extreme``): the lowest index among equal values, -0.0 equal to
+        +0.0, NaN and -1 for a row without a valid value.  Returns (value f64[R], index int64[R], nvalid int64[R]), all on
+        the device: nothing is read back.  Deterministic (integer atomics only)."""
+        v = self.asdevice(values, np.float64)
+        if len(v.shape) == 0:
+            raise ValueError("values must be [R, ...] or [n]")
+        nrows = v.shape[0] if len(v.shape) > 1 else 1
+        n = v.size // nrows if nrows else 0
+        value = self.empty((nrows,), np.float64)
+        index, nvalid = self.empty((nrows,), np.int64), self.empty((nrows,), np.int64)
+        rc = self.lib.mm_arg_extreme(self.handle, v.ptr, nrows, n, 1 if want_max else 0, value.ptr, index.ptr, nvalid.ptr)
+        self._check_args(rc, "mm_arg_extreme")
+        return value, index, nvalid
+
     # ---- diffusion: the stiffness operator and the smoothing it gives -------------------------------
     def diffusion(self, shape_order, gll_points, kappa_h=1.0, kappa_r=None):
         """A :class:`Diffusion` over gll_points f64[E, (order+1)^dim, dim], orders 1, 2, 4: ``apply(u)`` is the bare

@@ -97,6 +97,8 @@ SIGNATURES = {
     "mm_boundary_nodes": (i64, (vp, vp, i64, i32, vp, vp, i64, i32, vp)),
     "mm_cutoff_distance": (i64, (vp, vp, i64, vp, i64, f64, vp)),
     "mm_distance_taper": (i64, (vp, vp, i64, f64, f64, i64, vp, vp, vp, vp, vp)),
+    "mm_gll_resolution": (i32, (vp, i32, i32, vp, i64, vp, i64, vp, i64, vp, vp, vp)),
+    "mm_arg_extreme": (i32, (vp, vp, i64, i64, i32, vp, vp, vp)),
     "mm_pcg_combine": (i32, (vp, vp, vp, f64, vp, i64, i64, vp)),
     "mm_pcg_scalars": (i32, (vp, vp, i64, i32, f64, vp)),
     "mm_pcg_direction": (i32, (vp, vp, vp, i64, i64, vp)),

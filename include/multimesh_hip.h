@@ -69,6 +69,14 @@ long long triLinearInterpolator(long long nelem_to_search, long long npoints,
  * (2) Device-pointer API.
  * ---------------------------------------------------------------------------------- */
 
+/* Alignment: a device array needs the alignment of its element type and no more (8 bytes for f64 / int64, 4 for int32,
+ * 1 for unsigned char), so a view that starts part-way into a larger buffer is a valid argument everywhere.  The hex8
+ * locate and kNN kernels move connectivity rows, operator rows and rows of an even k 16 bytes at a time: mm_knn_query
+ * (idx_d, dist_d), mm_locate_hex8 (connectivity_d -- which then needs nelem > 0, else MM_ERR_ARG --,
+ * enclosing_elem_indices_d, weights_d), mm_interpolate_hex8 (connectivity_d, enc_d, w_d), mm_source_create
+ * (connectivity_d) and mm_interpolate_hex8_on (enc_d, w_d) serve such an array that starts off 16 bytes through a copy of
+ * their own (an allocation, device-to-device copies and a wait per call; the source keeps its copy): same results, slower.
+ * Arrays on 16 bytes -- anything from mm_device_alloc, hipMalloc or a whole torch tensor -- take the direct path. */
 typedef struct mm_context mm_context;     /* device, stream, scratch pool, stage timers */
 typedef struct mm_knn_index mm_knn_index; /* device-resident search grid over source points */
 
@@ -122,6 +130,8 @@ void mm_knn_destroy(mm_context *ctx, mm_knn_index *index);
  * point coordinates are not special cases: the stage is the reference's arithmetic on whatever it is given, and every
  * row -- a NaN weight included -- is what the reference computes from the same arrays (MM_FP_EXACT: bit for bit;
  * MM_FP_TOL: see there).  A target no candidate accepts, a non-finite one among them, counts as failed and keeps its row. */
+/* A connectivity_d that starts off 16 bytes (a view into a larger buffer) is copied by the call, which must then know its
+ * size: with nelem == 0 (no bounds guard) such an array is refused with MM_ERR_ARG; on 16 bytes nelem == 0 is served. */
 int64_t mm_locate_hex8(mm_context *ctx, int64_t nelem_to_search, int64_t npoints,
                        const int64_t *nearest_element_indices_d, const int64_t *connectivity_d,
                        int64_t nelem, int conn_is_exodus, int64_t *enclosing_elem_indices_d,

@@ -177,6 +177,32 @@ int mm_zero_async(mm_context *ctx, void *dst_d, size_t bytes);
 // n (<= 64) 64-bit words of device memory into the context's pinned mirror, by a kernel on ctx->stream.
 int mm_mirror_async(mm_context *ctx, long long *dst_pinned, const long long *src_d, int n);
 
+// A caller's array that kernels read or write 16 bytes at a time (longlong2 / double2: connectivity rows, operator rows,
+// kNN rows).  The header promises such an array the alignment of its elements only, so the entry point takes it through
+// this: an array that starts on 16 bytes is used as it is -- the kernels and the aligned caller's path are what they were
+// --, any other is replaced by a copy of the library's own for the call (an allocation, a copy in on ctx->stream, for an
+// output a copy back, a wait and a free: correct, not fast).  DESIGN.md section 1, "Caller pointers and alignment".
+class mm_aligned16 {
+public:
+    mm_aligned16() = default;
+    mm_aligned16(const mm_aligned16 &) = delete;
+    mm_aligned16 &operator=(const mm_aligned16 &) = delete;
+    ~mm_aligned16();   // waits for the stream before it frees a copy
+    // bytes: a multiple of 16 (a guarded allocation ends with its array); a null array stays null; copy_in false: an
+    // output of which the call writes every byte
+    int take(mm_context *ctx, const void *caller, size_t bytes, bool copy_in = true);
+    int give_back();   // the copy's bytes into the caller's array, on the stream (nothing to do without a copy)
+    void *release();   // the copy (or null), which is now the caller's to free with mm_raw_free after a wait
+    template <typename T>
+    T *as() const { return static_cast<T *>(copy_ ? copy_ : const_cast<void *>(caller_)); }
+
+private:
+    mm_context *ctx_ = nullptr;
+    const void *caller_ = nullptr;
+    void *copy_ = nullptr;
+    size_t bytes_ = 0;
+};
+
 // The small counter readback of a call, words [slot, slot + n) of d_counters (the table of slots is below).  begin: their
 // device address, zeroed by mm_zero_async.  end: hipGetLastError for the launches in between, mm_mirror_async, one
 // hipStreamSynchronize (after a failure too: the caller may free what its kernels used); the n words in the pinned mirror.

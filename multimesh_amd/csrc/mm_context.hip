@@ -281,6 +281,43 @@ int mm_zero_async(mm_context *ctx, void *dst_d, size_t bytes)
     return MM_OK;
 }
 
+// ---- caller arrays off 16 bytes ---------------------------------------------------------
+int mm_aligned16::take(mm_context *ctx, const void *caller, size_t bytes, bool copy_in)
+{
+    ctx_ = ctx;
+    caller_ = caller;
+    bytes_ = bytes;
+    if (!caller || bytes == 0 || (reinterpret_cast<uintptr_t>(caller) & 15) == 0) return MM_OK;
+    if (mm_raw_alloc(ctx->device, &copy_, bytes) != hipSuccess) {
+        copy_ = nullptr;
+        mm_set_error(MM_ERR_ALLOC, "device allocation of %zu bytes for an array off 16-byte alignment failed", bytes);
+        return MM_ERR_ALLOC;
+    }
+    if (copy_in) MM_HIP_CHECK(hipMemcpyAsync(copy_, caller, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    return MM_OK;
+}
+
+int mm_aligned16::give_back()
+{
+    if (!copy_) return MM_OK;
+    MM_HIP_CHECK(hipMemcpyAsync(const_cast<void *>(caller_), copy_, bytes_, hipMemcpyDeviceToDevice, ctx_->stream));
+    return MM_OK;
+}
+
+void *mm_aligned16::release()
+{
+    void *p = copy_;
+    copy_ = nullptr;
+    return p;
+}
+
+mm_aligned16::~mm_aligned16()
+{
+    if (!copy_) return;
+    (void)hipStreamSynchronize(ctx_->stream);
+    (void)mm_raw_free(copy_);
+}
+
 // n 64-bit words from device memory to the context's pinned host mirror, by a kernel (a copy command of the runtime's
 // is a dispatch of 4 us behind a 6 us gap; this is 4 us and no gap).  The host reads them after synchronising.
 __global__ void mirror_words_kernel(const long long *__restrict__ src, long long *__restrict__ dst, int n)

@@ -1448,9 +1448,18 @@ extern "C" int mm_knn_query(mm_context *ctx, const mm_knn_index *index, const do
     MM_REQUIRE(npts == 0 || k == 0 || (pts_d && idx_d), "null array");
     MM_HIP_CHECK(hipSetDevice(ctx->device));
     mm_stage_reset(ctx);
+    // rows of an even k are written two entries at a time: a caller's array off 16 bytes is served through a copy
+    mm_aligned16 idx, dist;
+    const size_t row_bytes = (k & 1) == 0 ? (size_t)npts * (size_t)k * 8 : 0;
+    int rc = idx.take(ctx, row_bytes ? idx_d : nullptr, row_bytes, /*copy_in=*/false);   // (every row is written)
+    if (rc == MM_OK) rc = dist.take(ctx, row_bytes ? dist_d : nullptr, row_bytes, /*copy_in=*/false);
+    if (rc != MM_OK) return rc;
     mm_stage_begin(ctx, MM_STAGE_KNN_QUERY);
-    int rc = mm_knn_query_impl(ctx, index, pts_d, npts, k, idx_d, dist_d, false);
+    rc = mm_knn_query_impl(ctx, index, pts_d, npts, k, row_bytes ? idx.as<int64_t>() : idx_d,
+                           row_bytes ? dist.as<double>() : dist_d, false);
     mm_stage_end(ctx, MM_STAGE_KNN_QUERY);
+    if (rc == MM_OK) rc = idx.give_back();
+    if (rc == MM_OK) rc = dist.give_back();
     return rc;
 }
 

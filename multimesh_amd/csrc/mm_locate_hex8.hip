@@ -1054,10 +1054,23 @@ extern "C" int64_t mm_locate_hex8(mm_context *ctx, int64_t k, int64_t npoints, c
                "null array");
     MM_HIP_CHECK(hipSetDevice(ctx->device));
     mm_stage_reset(ctx);
+    // connectivity and operator rows are read and written 16 bytes at a time: arrays off 16 bytes go through a copy
+    // (nelem == 0: the number of elements is not known here, and such an array is refused)
+    mm_aligned16 conn, enc, w;
+    const bool rows = npoints > 0 && k > 0;
+    MM_REQUIRE(!rows || nelem > 0 || (reinterpret_cast<uintptr_t>(conn_d) & 15) == 0,
+               "connectivity_d off 16-byte alignment needs nelem");
+    int rc = conn.take(ctx, rows ? conn_d : nullptr, (size_t)(nelem > 0 ? nelem : 0) * 8 * sizeof(i64));
+    if (rc == MM_OK) rc = enc.take(ctx, rows ? enc_d : nullptr, (size_t)npoints * 8 * sizeof(i64));
+    if (rc == MM_OK) rc = w.take(ctx, rows ? w_d : nullptr, (size_t)npoints * 8 * sizeof(double));
+    if (rc != MM_OK) return rc;
     mm_stage_begin(ctx, MM_STAGE_LOCATE);
-    int rc = mm_launch_locate_hex8(ctx, k, npoints, nn_d, false, (const i64 *)conn_d, nelem, conn_is_exodus,
-                                   (i64 *)enc_d, nodes_d, w_d, pts_d, ctx->d_counters, 0, nullptr, 0, 0, nullptr, nullptr);
+    rc = mm_launch_locate_hex8(ctx, k, npoints, nn_d, false, rows ? conn.as<const i64>() : (const i64 *)conn_d, nelem,
+                               conn_is_exodus, rows ? enc.as<i64>() : (i64 *)enc_d, nodes_d, rows ? w.as<double>() : w_d,
+                               pts_d, ctx->d_counters, 0, nullptr, 0, 0, nullptr, nullptr);
     mm_stage_end(ctx, MM_STAGE_LOCATE);
+    if (rc == MM_OK) rc = enc.give_back();
+    if (rc == MM_OK) rc = w.give_back();
     if (rc != MM_OK) return rc;
     rc = mm_mirror_async(ctx, (long long *)ctx->h_counters, (const long long *)ctx->d_counters, 1);
     if (rc != MM_OK) return rc;

@@ -50,6 +50,7 @@ struct mm_source {
     i64 nnodes = 0;
     const i64 *conn = nullptr;
     i64 nelem = 0;
+    i64 *conn_copy = nullptr;      // owned: what conn points to when the caller's array starts off 16 bytes (mm_aligned16)
     double *centroids = nullptr;   // owned
     mm_knn_index *index = nullptr; // owned (its arrays are its own, not the context's buffer cache)
     int device = 0;
@@ -61,6 +62,7 @@ static int require_sizes(const char *who, const mm_context *ctx, int64_t nnodes,
 {
     MM_REQUIRE_AS(who, ctx != nullptr, "ctx is null");
     MM_REQUIRE_AS(who, nnodes >= 1 && nelem >= 1, "empty source mesh");
+    MM_REQUIRE_AS(who, nelem < (int64_t)0x7fffffff, "too many elements");
     MM_REQUIRE_AS(who, npoints >= 0 && ncomp >= 0, "negative size");
     return MM_OK;
 }
@@ -115,7 +117,6 @@ static int describe_call(mm_context *ctx, const double *nodes_d, int64_t nnodes,
     if (!host_checked && (rc = require_sizes(who, ctx, nnodes, nelem, npoints, ncomp)) != MM_OK) return rc;
     MM_REQUIRE_AS(who, k >= 1 && k <= MM_KNN_MAX_K, "nelem_to_search must be in 1..MM_KNN_MAX_K");
     if (!host_checked && (rc = require_arrays(who, npoints, ncomp, nodes_d, conn_d, points_d, fields_d, out_d)) != MM_OK) return rc;
-    MM_REQUIRE_AS(who, nelem < (int64_t)0x7fffffff, "too many elements");
     MM_HIP_CHECK(hipSetDevice(ctx->device));
     mm_stage_reset(ctx);
     *call = hex8_call{nodes_d, nnodes, (const i64 *)conn_d, nelem, points_d, npoints, fields_d, ncomp, k, out_d, resident};
@@ -310,11 +311,38 @@ static int64_t interpolate_hex8_impl(mm_context *ctx, const double *nodes_d, int
                                      const int64_t *conn_d, int64_t nelem, const double *points_d,
                                      int64_t npoints, const double *fields_d, int64_t ncomp, int64_t k,
                                      double *out_d, int64_t *enc_d, double *w_d, const mm_host_feed *feed,
-                                     const mm_source *resident = nullptr)
+                                     const mm_source *resident, bool checked);
+
+// The device-pointer entries' way in: the caller's operator rows, which the kernels write 16 bytes at a time, go through
+// copies when they start off 16 bytes (mm_aligned16; every row is written, so nothing is copied in).  checked: the caller
+// has made the shared argument checks.
+static int64_t interpolate_hex8_with_rows(mm_context *ctx, const double *nodes_d, int64_t nnodes, const int64_t *conn_d,
+                                          int64_t nelem, const double *points_d, int64_t npoints, const double *fields_d,
+                                          int64_t ncomp, int64_t k, double *out_d, int64_t *enc_d, double *w_d,
+                                          const mm_source *resident, bool checked)
+{
+    mm_aligned16 enc, w;
+    const bool rows = ctx && enc_d && w_d && npoints > 0;
+    int rc = rows ? hipSetDevice(ctx->device) == hipSuccess ? MM_OK : MM_ERR_HIP : MM_OK;
+    if (rc == MM_OK) rc = enc.take(ctx, rows ? enc_d : nullptr, (size_t)(rows ? npoints : 0) * 8 * sizeof(i64), /*copy_in=*/false);
+    if (rc == MM_OK) rc = w.take(ctx, rows ? w_d : nullptr, (size_t)(rows ? npoints : 0) * 8 * sizeof(double), /*copy_in=*/false);
+    if (rc != MM_OK) return rc;
+    const int64_t result = interpolate_hex8_impl(ctx, nodes_d, nnodes, conn_d, nelem, points_d, npoints, fields_d, ncomp, k, out_d,
+                                                 rows ? enc.as<int64_t>() : enc_d, rows ? w.as<double>() : w_d, nullptr, resident, checked);
+    if (result < 0) return result;
+    if ((rc = enc.give_back()) != MM_OK || (rc = w.give_back()) != MM_OK) return rc;
+    return result;
+}
+
+static int64_t interpolate_hex8_impl(mm_context *ctx, const double *nodes_d, int64_t nnodes,
+                                     const int64_t *conn_d, int64_t nelem, const double *points_d,
+                                     int64_t npoints, const double *fields_d, int64_t ncomp, int64_t k,
+                                     double *out_d, int64_t *enc_d, double *w_d, const mm_host_feed *feed,
+                                     const mm_source *resident, bool checked)
 {
     hex8_call call;
     const int rc = describe_call(ctx, nodes_d, nnodes, conn_d, nelem, points_d, npoints, fields_d, ncomp, k, out_d, enc_d, w_d,
-                                 resident, /*host_checked=*/feed != nullptr, &call);
+                                 resident, /*host_checked=*/checked, &call);
     if (rc != MM_OK) return rc;
     if (npoints == 0) return 0;
     const bool guessed = may_guess(ctx, call);
@@ -362,8 +390,17 @@ extern "C" int64_t mm_interpolate_hex8(mm_context *ctx, const double *nodes_d, i
                                        int64_t npoints, const double *fields_d, int64_t ncomp, int64_t k,
                                        double *out_d, int64_t *enc_d, double *w_d)
 {
-    return interpolate_hex8_impl(ctx, nodes_d, nnodes, conn_d, nelem, points_d, npoints, fields_d, ncomp, k, out_d,
-                                 enc_d, w_d, nullptr);
+    // the shared argument checks, here and not in the pipeline: the connectivity rows are read 16 bytes at a time, and an
+    // array off 16 bytes is copied (mm_aligned16) once its size is known to be sound
+    static const char *const who = "interpolate_hex8_impl";
+    int rc = require_sizes(who, ctx, nnodes, nelem, npoints, ncomp);
+    if (rc == MM_OK) rc = require_arrays(who, npoints, ncomp, nodes_d, conn_d, points_d, fields_d, out_d);
+    if (rc != MM_OK) return rc;
+    MM_HIP_CHECK(hipSetDevice(ctx->device));
+    mm_aligned16 conn;
+    if ((rc = conn.take(ctx, npoints > 0 ? conn_d : nullptr, (size_t)nelem * 8 * sizeof(i64))) != MM_OK) return rc;
+    return interpolate_hex8_with_rows(ctx, nodes_d, nnodes, npoints > 0 ? conn.as<const int64_t>() : conn_d, nelem, points_d,
+                                      npoints, fields_d, ncomp, k, out_d, enc_d, w_d, nullptr, /*checked=*/true);
 }
 
 extern "C" int mm_source_create(mm_context *ctx, const double *nodes_d, int64_t nnodes, const int64_t *conn_d, int64_t nelem,
@@ -381,18 +418,21 @@ extern "C" int mm_source_create(mm_context *ctx, const double *nodes_d, int64_t 
     }
     s->nodes = nodes_d;
     s->nnodes = nnodes;
-    s->conn = (const i64 *)conn_d;
     s->nelem = nelem;
     s->device = ctx->device;
-    int rc = MM_OK;
-    if (mm_raw_alloc(ctx->device, (void **)&s->centroids, (size_t)nelem * 3 * sizeof(double)) != hipSuccess) {
+    // the locate kernels read connectivity rows 16 bytes at a time: an array off 16 bytes is kept as a copy of the source's own
+    mm_aligned16 conn;
+    int rc = conn.take(ctx, conn_d, (size_t)nelem * 8 * sizeof(i64));
+    s->conn = conn.as<const i64>();
+    s->conn_copy = static_cast<i64 *>(conn.release());   // (the wait before this function returns covers the copy)
+    if (rc == MM_OK && mm_raw_alloc(ctx->device, (void **)&s->centroids, (size_t)nelem * 3 * sizeof(double)) != hipSuccess) {
         mm_set_error(MM_ERR_ALLOC, "mm_source_create: device allocation failed");
         rc = MM_ERR_ALLOC;
     }
     mm_stage_reset(ctx);
     if (rc == MM_OK) {
         mm_stage_begin(ctx, MM_STAGE_CENTROID);
-        rc = mm_launch_centroid(ctx, 3, nelem, 8, (const i64 *)conn_d, nodes_d, s->centroids);
+        rc = mm_launch_centroid(ctx, 3, nelem, 8, s->conn, nodes_d, s->centroids);
         mm_stage_end(ctx, MM_STAGE_CENTROID);
     }
     if (rc == MM_OK) {
@@ -407,6 +447,10 @@ extern "C" int mm_source_create(mm_context *ctx, const double *nodes_d, int64_t 
     if (rc != MM_OK) {
         if (s->index) mm_knn_destroy(nullptr, s->index);
         if (s->centroids) (void)mm_raw_free(s->centroids);
+        if (s->conn_copy) {
+            (void)hipStreamSynchronize(ctx->stream);
+            (void)mm_raw_free(s->conn_copy);
+        }
         delete s;
         return rc;
     }
@@ -420,6 +464,7 @@ extern "C" void mm_source_destroy(mm_context *ctx, mm_source *source)
     if (ctx) (void)hipStreamSynchronize(ctx->stream);
     if (source->index) mm_knn_destroy(nullptr, source->index);
     if (source->centroids) (void)mm_raw_free(source->centroids);
+    if (source->conn_copy) (void)mm_raw_free(source->conn_copy);
     delete source;
 }
 
@@ -429,8 +474,8 @@ extern "C" int64_t mm_interpolate_hex8_on(mm_context *ctx, const mm_source *sour
 {
     MM_REQUIRE(ctx != nullptr && source != nullptr, "null argument");
     MM_REQUIRE(source->device == ctx->device, "the source lives on another device");
-    return interpolate_hex8_impl(ctx, source->nodes, source->nnodes, (const int64_t *)source->conn, source->nelem, points_d,
-                                 npoints, fields_d, ncomp, k, out_d, enc_d, w_d, nullptr, source);
+    return interpolate_hex8_with_rows(ctx, source->nodes, source->nnodes, (const int64_t *)source->conn, source->nelem, points_d,
+                                      npoints, fields_d, ncomp, k, out_d, enc_d, w_d, source, /*checked=*/false);
 }
 
 // The same path fed from HOST arrays (what the reference's callers hold: NumPy arrays, scripts/cli.py:62-100):
@@ -480,7 +525,7 @@ extern "C" int64_t mm_interpolate_hex8_host(mm_context *ctx, const double *nodes
     MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     const int64_t nfailed = interpolate_hex8_impl(ctx, (const double *)feed.dst[0], nnodes, (const int64_t *)feed.dst[1], nelem,
                                                   (const double *)feed.dst[2], npoints, (const double *)feed.dst[3],
-                                                  want_values ? ncomp : 0, k, out_d, (int64_t *)enc_d, w_d, &feed);
+                                                  want_values ? ncomp : 0, k, out_d, (int64_t *)enc_d, w_d, &feed, nullptr, /*checked=*/true);
     if (nfailed < 0) return nfailed;
     if (want_values) MM_HIP_CHECK(hipMemcpyAsync(out_h, out_d, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
     if (enc_h) {

@@ -65,6 +65,8 @@ __device__ __forceinline__ void store_record(double *__restrict__ rec, double x,
 }
 
 __device__ __forceinline__ int record_id(double w) { return (int)__double_as_longlong(w); }
+// the same id read from the record in memory, as ONE dword: the low word of the fourth double
+__device__ __forceinline__ int record_id_at(const double *__restrict__ rec) { return *reinterpret_cast<const int *>(rec + 3); }
 
 // hex8 centroids sorted into the cells of grid g in ONE pass (mm_centroid.hip; mm_knn_build_one_pass calls it): record of
 // element e at guess_start[cell] + rank from the zeroed per-cell cursor, per-workgroup boxes of the centroids in partial.

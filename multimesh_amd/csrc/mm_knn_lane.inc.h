@@ -575,19 +575,41 @@ __global__ __launch_bounds__(kWave, 3) void knn_lane_kernel(GridParams g, i64 ns
                     const int idx = slot < nsteps + ext_hi ? wbase + slot : wbase - ext_lo + (slot - nsteps - ext_hi);
                     pos[e] = __float_as_int(tile[min((unsigned)idx, (unsigned)nat_total)].w);   // (sentinel keys: any entry)
                 }
+                // The records of kExactChunk candidates are asked for TOGETHER, before any of them is used: one global
+                // round trip per chunk.  (Left to itself the compiler moved each record's z behind a branch on ndim, and the
+                // loads of record e + 1 behind that branch: two dependent round trips per candidate, 2 NE in a row.)
+                // Five at a time: all nine at once is 63 registers of records and the kernel spills at 3 waves per SIMD.  With five,
+                // <8, int, false> has 165 VGPRs of the 168 that 3 waves allow: a compiler update may tip it over -- check
+                // registers, spills and occupancy with tools/kernel_resources.sh mm_knn.hip knn_lane_kernel.
+                constexpr int kExactChunk = 5;
 #pragma unroll
-                for (int e = 0; e < NE; ++e) {
-                    const double2 *r2 = reinterpret_cast<const double2 *>(sorted_xyz + (i64)max(pos[e], 0) * kRec);
-                    const double2 xy = r2[0], zw = r2[1];
-                    const double dx = xy.x - px;
-                    const double dy = xy.y - py;
-                    const double dz = zw.x - pz;
-                    double d2 = dx * dx;
-                    d2 = d2 + dy * dy;
-                    if (ndim > 2) d2 = d2 + dz * dz;
-                    const bool real = d[e] < kLaneFarKey;
-                    ed[e] = real ? d2 : INFINITY;
-                    ei[e] = real ? record_id(zw.y) : 0x7fffffff - e;   // distinct ids keep sentinels apart
+                for (int e0 = 0; e0 < NE; e0 += kExactChunk) {
+                    double2 rxy[kExactChunk];
+                    double rz[kExactChunk];
+                    int rid[kExactChunk];
+#pragma unroll
+                    for (int c = 0; c < kExactChunk; ++c) {
+                        if (e0 + c >= NE) continue;
+                        const double *rec = sorted_xyz + (i64)max(pos[e0 + c], 0) * kRec;
+                        rxy[c] = *reinterpret_cast<const double2 *>(rec);
+                        rz[c] = rec[2];
+                        rid[c] = record_id_at(rec);   // (one dword: loading the whole double costs two registers per record and spills)
+                    }
+#pragma unroll
+                    for (int c = 0; c < kExactChunk; ++c) {
+                        if (e0 + c >= NE) continue;
+                        const int e = e0 + c;
+                        const double dx = rxy[c].x - px;
+                        const double dy = rxy[c].y - py;
+                        const double dz = rz[c] - pz;
+                        double d2 = dx * dx;
+                        d2 = d2 + dy * dy;
+                        const double d3 = d2 + dz * dz;
+                        d2 = ndim > 2 ? d3 : d2;
+                        const bool real = d[e] < kLaneFarKey;
+                        ed[e] = real ? d2 : INFINITY;
+                        ei[e] = real ? rid[c] : 0x7fffffff - e;   // distinct ids keep sentinels apart
+                    }
                 }
             }
 #ifdef MM_LANE_STAMPS

@@ -639,6 +639,42 @@ int mm_gll_resolution(mm_context *ctx, int order, int dim, const double *gll_poi
 int mm_arg_extreme(mm_context *ctx, const double *values_d, int64_t nrows, int64_t n, int want_max, double *value_d,
                    int64_t *index_d, int64_t *nvalid_d);
 
+/* SCATTERED MODELS: the rows of a k-nearest-neighbour query turned into values -- a model that is only points with values
+ * (no connectivity, no grid) onto any targets, by inverse-distance weights RELATIVE TO THE NEAREST SAMPLE.  The reference has
+ * no counterpart (its users go through scipy.spatial.cKDTree and NumPy on the host).
+ *   fields_d f64[ncomp][nsrc]; idx_d int64[npoints][k] and dist_d f64[npoints][k] exactly as mm_knn_query writes them (the
+ *   statement is nonetheless defined for any contents); out_d f64[npoints][ncomp] when out_point_major, else
+ *   f64[ncomp][npoints]; nearest_out_d f64[npoints] or NULL; nused_out_d int32[npoints] or NULL.
+ * Per target i, every quotient, product and sum rounded on its own (no fused multiply-add):
+ *   valid_j = (0 <= idx[i][j] < nsrc) and (dist[i][j] <= max_distance): a NaN distance is not valid, the padding index nsrc
+ *     is not valid
+ *   m = the number of valid j;  nused[i] = m
+ *   m == 0: the target is OUTSIDE: outside == 0 writes fill_value to every component, outside == 2 leaves the target's
+ *     entries of out_d as they are (1 is not defined here: the numbers are mm_sample_grid's); nearest[i] = +inf; the target
+ *     is counted in the return value
+ *   otherwise j0 = the lowest valid j, d0 = dist[i][j0], nearest[i] = d0, and
+ *     exact hit: if a valid j has dist[i][j] == 0.0, with jz the lowest such j, out[c] = fields[c][idx[i][jz]], a copy of
+ *       the bits; no weight is formed
+ *     else, for j ascending:  r_j = d0 / dist[i][j];  q_j = r_j multiplied by r_j another (power - 1) times, left to right;
+ *       w_j = q_j for a valid j and 0.0 otherwise;  s = 0.0, s = s + w_j;  per component num = 0.0,
+ *       num = num + (w_j * v_j) with v_j = fields[c][idx[i][j]] for a valid j and 0.0 otherwise (an invalid entry's field is
+ *       never read);  out[c] = num / s
+ * The weights are relative to the nearest distance on purpose: 1 / d^p overflows for close samples and underflows to an
+ * all-zero sum for far ones, while (d0 / d)^p lies in [0, 1] on sorted rows and the nearest sample always carries weight 1.
+ * power is an integer in 1..8 (a fractional power would go through pow, whose bits cannot be pinned).  Nothing else is a
+ * special case: a NaN field value under a weight of 0.0 gives NaN (under a cut neighbour it is not read); a target with a NaN
+ * coordinate has NaN distances only and is outside; k == 1 is nearest neighbour, 0.0 + (1.0 * v) over 1.0: the sample's bits
+ * (a -0.0 comes back as +0.0).
+ * The outside count is an integer sum -- per workgroup, then one integer atomic each -- and there are no float atomics: every
+ * output is the same on every run.  idx_d and dist_d are read 16 bytes at a time when k is even and both start on 16
+ * bytes, 8 bytes at a time otherwise (same results).  Returns the number of outside targets, or a negative MM_ERR_*:
+ * MM_ERR_ARG (nothing is written) for a null ctx or a null required array, a negative size, k outside 1..MM_KNN_MAX_K, power
+ * outside 1..8, a max_distance that is a NaN or negative (+inf: no limit), outside not 0 or 2, ncomp >= 65536.
+ * npoints == 0 is valid, and so is ncomp == 0 (with or without nearest_out_d / nused_out_d).  Synchronises. */
+int64_t mm_idw_gather(mm_context *ctx, const double *fields_d, int64_t nsrc, int64_t ncomp, const int64_t *idx_d,
+                      const double *dist_d, int64_t npoints, int64_t k, int power, double max_distance, int outside,
+                      double fill_value, double *out_d, int out_point_major, double *nearest_out_d, int32_t *nused_out_d);
+
 /* The streaming kernels of a preconditioned conjugate-gradient loop over ncomp independent systems of n unknowns each
  * (vectors f64[ncomp][n]), whose scalars never leave the device.  state_d f64[ncomp][8] holds, per system, the slots below:
  * the dots are written into MM_PCG_RZ, MM_PCG_PAP and MM_PCG_BB by mm_weighted_sum (one call per system with ncomp = 1).

@@ -966,6 +966,46 @@ class Context(_Released):
         self._check_args(rc, "mm_distance_taper")
         return (out if av else None, int(rc), weight) if want_weight else (out, int(rc))
 
+    # ---- scattered models: kNN rows -> inverse-distance values ------------------------------------------
+    def idw_gather(self, fields, idx, dist, power=2, max_distance=np.inf, outside="fill", fill_value=np.nan, out=None,
+                   point_major=False, want_nearest=False, want_count=False):
+        """The rows of a kNN query turned into values (``mm_idw_gather``): ``fields`` f64[C, nsrc] (or [nsrc]), ``idx``
+        int64[N, k] and ``dist`` f64[N, k] as :meth:`KnnIndex.query` gives them with ``want_dist`` (any contents are
+        served).  An entry is valid when its index lies in [0, nsrc) and its distance is ``<= max_distance``; with ``d0``
+        the first valid distance the weights are ``(d0 / d) ** power`` by repeated multiplication (``power`` an integer in
+        1..8), the value is ``sum(w * v) / sum(w)`` summed in the row's order from 0.0, and a valid entry at distance 0.0
+        (the first such) gives its sample's bits instead.  A target without a valid entry is outside: ``outside`` "fill"
+        writes ``fill_value``, "keep" leaves the entries of ``out``, which is then required.  Returns (values f64[C, N] --
+        [N, C] with ``point_major`` --, the number of outside targets) and then, as asked for, ``nearest`` f64[N] (``d0``,
+        +inf outside) and ``nused`` int32[N] (the valid entries), all on the device.  include/multimesh_hip.h states the
+        arithmetic, and the values are bit for bit that statement."""
+        modes = {"fill": 0, "keep": 2}
+        if outside not in modes:
+            raise ValueError(f"outside must be one of {sorted(modes)}, got {outside!r}")
+        if isinstance(power, bool) or not isinstance(power, (int, np.integer)) or not 1 <= power <= 8:
+            raise ValueError(f"power must be an integer in 1..8, got {power!r}")
+        max_distance = float(max_distance)
+        if not max_distance >= 0.0:
+            raise ValueError("max_distance must not be negative or a NaN (inf: no limit)")
+        f = _components(self.asdevice(fields, np.float64), 1)
+        idv, d, n, k = self._pairs(idx, dist)
+        if len(f.shape) != 2:
+            raise ValueError("fields must be [C, nsrc] (or [nsrc])")
+        if not 1 <= k <= MM_KNN_MAX_K:
+            raise ValueError(f"k must be in 1..{MM_KNN_MAX_K}")
+        ncomp, nsrc = f.shape
+        shape = (n, ncomp) if point_major else (ncomp, n)
+        if out is None and outside == "keep":
+            raise ValueError('outside="keep" keeps the entries of out: pass out')
+        out = self._out(out, shape, f"out must be {list(shape)}")
+        nearest = self.empty((n,), np.float64) if want_nearest else None
+        nused = self.empty((n,), np.int32) if want_count else None
+        rc = self.lib.mm_idw_gather(self.handle, f.ptr, nsrc, ncomp, idv.ptr, d.ptr, n, k, int(power), max_distance,
+                                    modes[outside], float(fill_value), out.ptr, 1 if point_major else 0,
+                                    nearest.ptr if nearest else None, nused.ptr if nused else None)
+        self._check_args(rc, "mm_idw_gather")
+        return (out, int(rc)) + ((nearest,) if want_nearest else ()) + ((nused,) if want_count else ())
+
     # ---- resolution: node spacing, edge lengths, the time step and the resolved period of a model ------
     def gll_resolution(self, shape_order, gll_points, fast=None, slow=None, want_node_spacing=False):
         """The sizes of every element of gll_points f64[E, (order+1)^dim, dim], orders 1, 2, 4, and what a model makes of

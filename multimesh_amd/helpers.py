@@ -99,6 +99,7 @@ SIGNATURES = {
     "mm_distance_taper": (i64, (vp, vp, i64, f64, f64, i64, vp, vp, vp, vp, vp)),
     "mm_gll_resolution": (i32, (vp, i32, i32, vp, i64, vp, i64, vp, i64, vp, vp, vp)),
     "mm_arg_extreme": (i32, (vp, vp, i64, i64, i32, vp, vp, vp)),
+    "mm_idw_gather": (i64, (vp, vp, i64, i64, vp, vp, i64, i64, i32, f64, i32, f64, vp, i32, vp, vp)),
     "mm_pcg_combine": (i32, (vp, vp, vp, f64, vp, i64, i64, vp)),
     "mm_pcg_scalars": (i32, (vp, vp, i64, i32, f64, vp)),
     "mm_pcg_direction": (i32, (vp, vp, vp, i64, i64, vp)),

@@ -251,6 +251,33 @@ int64_t mm_sample_grid(mm_context *ctx, const double *points_d, int64_t npoints,
                        int64_t ncomp, int lon_periodic, int outside_mode, double fill_value, double *out_d,
                        double *latlondepth_out_d);
 
+/* The grid import as an OPERATOR: the ids and weights that mm_sample_grid applies, written out so that they can be kept
+ * (mm_gather imports any number of cubes without a new search) and turned round (mm_transpose_create_nodes / _apply give
+ * G^T, the way back from the mesh to the cube).  points_d, the axes, lon_periodic and latlondepth_out_d as mm_sample_grid;
+ * ids_d int64[npoints][8], w_d f64[npoints][8].  Every operation is rounded on its own (no fused multiply-add):
+ *   (lat, lon, depth), the periodic wrap and per axis (i, i1, t, inside) are EXACTLY those of mm_sample_grid -- depth gives
+ *     (k, k1, tz), latitude (j, j1, ty), longitude (i, i1, tx);
+ *   corner c = 4 a + 2 b + e with a, b, e in {0, 1} selecting K = k|k1, J = j|j1, I = i|i1;
+ *   ids[n][c] = (K * nlat + J) * nlon + I, the flat index into one component's [ndepth][nlat][nlon] cube;
+ *   u(t, 0) = 1.0 - t, u(t, 1) = t;   w[n][c] = (u(tz, a) * u(ty, b)) * u(tx, e).
+ * An axis of length 1 gives i = i1 = 0 and t = 0: two corners then share an id, with the weights 1 * ... and 0 * ...; ids
+ * repeated in a row are valid input for mm_gather and mm_transpose_*.
+ * clamp == 0: a point outside the grid (a NaN coordinate is outside) gets ids 0 and weights +0.0 in all eight slots and is
+ * counted -- the all-zero row that a failed target is for mm_transpose_create_nodes.  clamp != 0: as mm_sample_grid's clamp
+ * mode, nothing is outside; a NaN coordinate yields NaN weights on the ids its cell search gives.  The clamp is
+ * v = v < a[0] ? a[0] : v, then v = v > a[n-1] ? a[n-1] : v: a coordinate of -0.0 on an axis that starts at +0.0 stays -0.0,
+ * so that t = -0.0 and the weights it multiplies are -0.0 (mm_sample_grid's values cannot tell: its t * q is added to a term).
+ * So ids_d and w_d are bit for bit this statement on latlondepth_out_d.  sum_c w[n][c] * g[ids[n][c]] in mm_gather's
+ * (NumPy's) order is NOT bit-equal to mm_sample_grid's nested lerps: for finite corners and t in [0, 1] the two differ by at
+ * most 32 eps max|corner| (ten roundings through the three lerp levels, seven through the weights, the products and the
+ * 8-term sum).
+ * Returns the number of points outside (0 with clamp; an integer sum, the same on every run), or a negative MM_ERR_*:
+ * MM_ERR_ARG for a null table or ndepth / nlat / nlon < 1 (nothing is written), MM_ERR_UNSUPPORTED when an axis exceeds
+ * INT_MAX nodes or the cube 2^63 - 1.  npoints == 0 is valid.  Synchronises. */
+int64_t mm_grid_operator(mm_context *ctx, const double *points_d, int64_t npoints, const double *depth_d, int64_t ndepth,
+                         const double *lat_d, int64_t nlat, const double *lon_d, int64_t nlon, int lon_periodic, int clamp,
+                         int64_t *ids_d, double *w_d, double *latlondepth_out_d);
+
 /* The TRANSPOSE of an interpolation operator: what comes back from the targets to the sources (a gradient on the event
  * mesh -> the inversion mesh, so that <P m, g> = <m, P^T g>; P^T 1 = the coverage map).  Deterministic: the result is bit for
  * bit np.add.at on zeros, i.e. the sequential loop, on every run (no float atomics, no reordering).

@@ -18,8 +18,11 @@ from .layers import (assess_layers, fix_fluid_solid, interpolate_gll_to_gll_laye
                      save_stored_layer_operator)
 from .drivers import (exodus_2_gll, gll_2_exodus, gll_2_gll, gll_2_gll_layered, gll_2_gll_layered_multi,
                       gll_2_gll_layered_multi_two, query_model)
-from .grids import (DIMS, RegularGrid, UNITS, column_tables, extract_cross_section, extract_depth_slice,
-                    extract_regular_grid, import_regular_grid, prepare_regular_grid, sample_regular_grid)
+from .grids import (DIMS, GridOperator, RegularGrid, UNITS, column_tables, extract_cross_section, extract_depth_slice,
+                    extract_regular_grid, fold_to_caller_layout, grid_import_operator, import_regular_grid,
+                    prepare_regular_grid, regular_grid_adjoint, sample_regular_grid, to_prepared_layout)
+# (the grid operator and its adjoint -- GridOperator, grid_import_operator, regular_grid_adjoint and the two layout
+# functions -- are reachable as api.<name>; __all__ stays the drop-in surface that tests/test_api_surface.py pins)
 from .radial import (RadialModel, RadialProfile, evaluate_radial_model, from_perturbation, radial_edges, radial_profile,
                      to_perturbation)
 

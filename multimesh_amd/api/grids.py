@@ -5,10 +5,12 @@ section of plot_cross_section (plotter.py:360-391).  The targets are generated o
 import numpy as np
 
 from .. import io as mio
-from ..device import DeviceArray, default_context
+from ..device import DeviceArray, _Released, default_context
+from ..helpers import check
 from ..mesh import HexMesh
 from ._common import GllMesh, _mesh_points, _order_from_point_count
 from .earth import _sphere_mapped
+from .mass import _device_mass, _hex8_mass
 
 DIMS = ("depth", "latitude", "longitude")
 UNITS = {"depth": "m", "latitude": "deg", "longitude": "deg"}
@@ -47,22 +49,29 @@ def column_tables(lat, lon, depth):
     return lat_table, lon_table, np.ascontiguousarray(6371000.0 - de[:, 2])
 
 
+def _as_gll_mesh(mesh, parameters, make_spherical):
+    """A :class:`GllMesh` as it is; a Salvus model (file or h5py-like object) read into one: its coordinates, the named
+    parameters and, for ``make_spherical``, its ``z_node_1D``."""
+    if isinstance(mesh, GllMesh):
+        return mesh
+    points, data, names = mio.load_hdf5_params_to_memory(mesh)
+    missing = [p for p in parameters if p not in names]
+    if missing:
+        raise ValueError(f"parameters {missing} are not in the model (it holds {names})")
+    P = points.shape[1]
+    order = _order_from_point_count(P, 3)
+    if points.ndim != 3 or points.shape[2] != 3 or (order + 1) ** 3 != P:
+        raise ValueError(f"MODEL/coordinates must be [nelem, (order+1)^3, 3], got {points.shape}")
+    wanted = set(parameters) | ({"z_node_1D"} if make_spherical and "z_node_1D" in names else set())
+    return GllMesh(points, order, {p: data[:, names.index(p), :] for p in wanted})
+
+
 def _gll_model(mesh, parameters, make_spherical, ctx):
     """(gll_points f64[E, P, 3] (host or device), shape_order, fields f64[C, E, P]) of a :class:`GllMesh` or of a Salvus
     model (a file, or an h5py-like object read through :func:`multimesh_amd.io.load_hdf5_params_to_memory`, whose
     parameters are picked by name from ``DIMENSION_LABELS``).  ``make_spherical`` maps a copy onto the mesh's 1-D sphere."""
     parameters = mio.pick_parameters(parameters)
-    if not isinstance(mesh, GllMesh):
-        points, data, names = mio.load_hdf5_params_to_memory(mesh)
-        missing = [p for p in parameters if p not in names]
-        if missing:
-            raise ValueError(f"parameters {missing} are not in the model (it holds {names})")
-        P = points.shape[1]
-        order = _order_from_point_count(P, 3)
-        if points.ndim != 3 or points.shape[2] != 3 or (order + 1) ** 3 != P:
-            raise ValueError(f"MODEL/coordinates must be [nelem, (order+1)^3, 3], got {points.shape}")
-        wanted = set(parameters) | ({"z_node_1D"} if make_spherical and "z_node_1D" in names else set())
-        mesh = GllMesh(points, order, {p: data[:, names.index(p), :] for p in wanted})
+    mesh = _as_gll_mesh(mesh, parameters, make_spherical)
     fields = np.stack([np.asarray(mesh.element_nodal_fields[p], dtype=np.float64) for p in parameters])
     gll_points = _sphere_mapped(mesh, ctx) if make_spherical else mesh.gll_points
     return gll_points, mesh.shape_order, fields
@@ -415,3 +424,306 @@ def import_regular_grid(grid, mesh, parameters=None, outside="keep", fill_value=
         for c, p in enumerate(parameters):
             model[:, columns[p], :] = values[c]
     return nmissing
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# The grid import as an operator G (Context.grid_operator: ids int64[N, 8], w f64[N, 8] into the prepared cube), and its
+# transpose.  The two functions below are the host's part of it, pure NumPy of grid size: between the caller's layout and
+# the prepared one (axes ascending, a periodic axis closed by one more column).
+TRANSPOSE_MAX_ENTRIES = 2 ** 31      # mm_transpose_create_nodes: npoints * 8 must stay below this
+
+
+def to_prepared_layout(values, flipped, appended):
+    """A cube f64[..., D, LA, LO] in the caller's layout as :func:`prepare_regular_grid` lays it out: the axes named in
+    ``flipped`` (three booleans: depth, latitude, longitude) reversed and, with ``appended``, column 0 repeated behind
+    the last longitude."""
+    v = np.asarray(values, dtype=np.float64)
+    for ax, f in zip((-3, -2, -1), flipped):
+        if f:
+            v = np.flip(v, axis=ax)
+    if appended:
+        v = np.concatenate([v, v[..., :1]], axis=-1)
+    return np.ascontiguousarray(v)
+
+
+def fold_to_caller_layout(values, flipped, appended):
+    """The transpose of :func:`to_prepared_layout`: what was scattered onto the prepared cube f64[..., D, LA, LO'] brought
+    back to the caller's layout.  An appended closing longitude column holds what belongs to column 0: it is added onto
+    column 0 (``col0 + closing``, one rounding) and dropped; flipped axes are flipped back."""
+    v = np.asarray(values, dtype=np.float64)
+    if appended:
+        closing = v[..., -1]
+        v = v[..., :-1].copy()
+        v[..., 0] = v[..., 0] + closing
+    for ax, f in zip((-3, -2, -1), flipped):
+        if f:
+            v = np.flip(v, axis=ax)
+    return np.ascontiguousarray(v)
+
+
+class GridOperator(_Released):
+    """The import of a regular grid onto fixed points, kept: ``ids`` int64[N, 8] and ``w`` f64[N, 8] on the device
+    (``mm_grid_operator``, where the arithmetic is stated), built on first use.  The ids index the PREPARED cube of
+    ``prepared_shape`` (:func:`prepare_regular_grid`); ``flipped`` (depth, latitude, longitude) and ``appended`` (a closing
+    longitude column) record what was done to the caller's axes, and every method takes and returns the caller's layout
+    ``grid_shape``.  ``noutside``: the points outside the grid (``outside="fill"``; their rows are all zero), known once
+    the operator or a chunked transpose has run.  ``lead``: the leading shape of the points ([E, P] of a GLL mesh)."""
+
+    def __init__(self, ctx, points, coords, prepared_axes, periodic, flipped, appended, clamp):
+        # the points are BORROWED: a view that keeps the array alive and never frees it (it may be the caller's own
+        # DeviceArray), as Source keeps its mesh
+        self.ctx, self.points = ctx, points.reshape(*points.shape)
+        self.lead = tuple(points.shape[:-1])
+        self.npoints = points.size // 3
+        self.coords = coords
+        self.depth, self.lat, self.lon = prepared_axes
+        self.periodic, self.flipped, self.appended, self.clamp = bool(periodic), tuple(flipped), bool(appended), bool(clamp)
+        self.grid_shape = tuple(len(coords[d]) for d in DIMS)
+        self.prepared_shape = (len(self.depth), len(self.lat), len(self.lon))
+        self.nsrc = int(np.prod(self.prepared_shape, dtype=np.int64))
+        self.ids = self.w = self.noutside = None
+        self._transposed = self._outside_rows = None
+
+    # ---- the operator itself ----------------------------------------------------------------
+    def _rows(self, start, stop):
+        """(ids, w, noutside) of the points [start, stop)"""
+        pts = self.points.reshape(self.npoints, 3).rows(start, stop)
+        return self.ctx.grid_operator(pts, self.depth, self.lat, self.lon, clamp=self.clamp, lon_periodic=self.periodic)
+
+    def build(self):
+        """Make the whole operator resident (128 B per point); the methods that need it call this."""
+        if self.points is None:
+            raise ValueError("the operator has been freed")
+        if self.ids is None:
+            self.ids, self.w, self.noutside = self._rows(0, self.npoints)
+        return self
+
+    def _cube(self, values, what):
+        """f64[C, *grid_shape] of an array f64[C, D, LA, LO] or [D, LA, LO] in the caller's layout"""
+        v = np.asarray(values, dtype=np.float64)
+        v = v[None] if v.ndim == 3 else v
+        if v.ndim != 4 or v.shape[1:] != self.grid_shape:
+            raise ValueError(f"{what} must be [C, {', '.join(map(str, self.grid_shape))}] (or one component), got {v.shape}")
+        return v
+
+    def apply(self, grid_or_values, parameters=None, fill_value=np.nan):
+        """Import a cube through the kept operator, without a new search: ``mm_gather`` of the prepared cube through
+        ``(ids, w)`` -> f64[C, *lead] (NumPy).  ``grid_or_values``: a :class:`RegularGrid` over the operator's axes
+        (``parameters``: names, None = all) or an array f64[C, D, LA, LO] / [D, LA, LO] in the caller's layout.  Points
+        outside the grid get ``fill_value`` (``outside="clamp"``: there are none).
+
+        The result is the sum ``sum_c w_c * g[id_c]`` in NumPy's order for eight terms.  It is NOT bit-equal to
+        :func:`import_regular_grid`, which nests seven lerps: for finite corners the two differ by at most
+        ``32 * eps * max|corner|`` (ten roundings through the three lerp levels, seven through the weights, the products
+        and the 8-term sum)."""
+        if isinstance(grid_or_values, RegularGrid):
+            for d in DIMS:
+                if not np.array_equal(grid_or_values.coords[d], self.coords[d]):
+                    raise ValueError(f"the grid's {d} axis is not the one this operator was built on")
+            names = list(grid_or_values.data_vars) if parameters is None else mio.pick_parameters(parameters)
+            unknown = [p for p in names if p not in grid_or_values.data_vars]
+            if unknown:
+                raise ValueError(f"parameters {unknown} are not in the grid (it holds {list(grid_or_values.data_vars)})")
+            grid_or_values = np.stack([grid_or_values.data_vars[p] for p in names]) if names else np.zeros((0,) + self.grid_shape)
+        cube = to_prepared_layout(self._cube(grid_or_values, "values"), self.flipped, self.appended)
+        self.build()
+        ncomp = cube.shape[0]
+        out = self.ctx.gather(cube.reshape(ncomp, self.nsrc), self.ids, self.w, point_major=False).numpy()
+        if not self.clamp and self.noutside:
+            if self._outside_rows is None:     # a row inside the grid sums to 1 within rounding, one outside is all zero
+                ones = np.ones((1, self.nsrc))
+                self._outside_rows = self.ctx.gather(ones, self.ids, self.w, point_major=False).numpy()[0] == 0.0
+            out[:, self._outside_rows] = fill_value
+        return out.reshape((ncomp,) + self.lead)
+
+    # ---- its transpose ------------------------------------------------------------------------
+    def _values(self, values):
+        """f64[C, N] of f64[C, N], [C, *lead], [N] or [*lead], on the host or on the device"""
+        if not hasattr(values, "data_ptr"):
+            values = np.asarray(values, dtype=np.float64)
+        shape = tuple(values.shape)
+        if shape in ((self.npoints,), self.lead):
+            shape = (1,) + shape
+        if shape[1:] not in ((self.npoints,), self.lead):
+            raise ValueError(f"values must be [C, {self.npoints}] or [C, {', '.join(map(str, self.lead))}], got {tuple(values.shape)}")
+        if isinstance(values, np.ndarray) or not hasattr(values, "data_ptr"):
+            return np.ascontiguousarray(values, dtype=np.float64).reshape(shape[0], self.npoints)
+        return self.ctx.asdevice(values, np.float64).reshape(shape[0], self.npoints)
+
+    def transpose(self, values, chunk_points=None, prepared=False):
+        """``G^T values``: values f64[C, N] or f64[C, *lead] (one component without its leading axis) at the points ->
+        f64[C, D, LA, LO] (NumPy) on the grid, deterministically.  On the prepared cube the result is bit for bit
+        ``np.add.at(zeros, ids, w * v[:, None])`` per component (``mm_transpose_create_nodes`` once per operator, kept;
+        then ``mm_transpose_apply``); ``prepared=True`` returns that, of ``prepared_shape``.  Otherwise it is brought back
+        to the caller's layout by :func:`fold_to_caller_layout`: an appended closing longitude column is added onto
+        column 0 and dropped, flipped axes are flipped back.  A grid that itself holds both ends of a global axis
+        (``-180 ... 180``) keeps each column's own sum -- the exact transpose of what the import reads, which takes a point
+        at the seam from the two columns by its weights; add the two columns for the sum over the meridian.
+
+        The grouping needs ``8 N < 2^31``.  Beyond that, or when ``chunk_points`` is given, consecutive chunks of that many
+        points are transposed on their own -- ids and weights of the chunk built, grouped, applied, freed, so that the
+        operator is never resident whole -- and added on the host in ascending chunk order, ``((c0 + c1) + c2) + ...``:
+        that sum of per-chunk ``np.add.at`` results is then the stated result."""
+        v = self._values(values)
+        ncomp = v.shape[0]
+        if self.points is None:
+            raise ValueError("the operator has been freed")
+        if chunk_points is None and 8 * self.npoints >= TRANSPOSE_MAX_ENTRIES:
+            chunk_points = TRANSPOSE_MAX_ENTRIES // 8 - 1
+        if self.npoints == 0:
+            total, self.noutside = np.zeros((ncomp, self.nsrc)), 0
+        elif chunk_points is None:
+            if self._transposed is None:
+                self.build()
+                self._transposed = self.ctx.transpose_nodes(self.ids, self.w, self.nsrc)
+            total = self._transposed.apply(v, point_major=False).numpy()
+        else:
+            chunk_points = int(chunk_points)
+            if not 1 <= chunk_points <= TRANSPOSE_MAX_ENTRIES // 8 - 1:
+                raise ValueError(f"chunk_points must be in 1 .. {TRANSPOSE_MAX_ENTRIES // 8 - 1}")
+            total, noutside = np.zeros((ncomp, self.nsrc)), 0
+            for k, start in enumerate(range(0, self.npoints, chunk_points)):
+                stop = min(start + chunk_points, self.npoints)
+                ids, w, miss = self._rows(start, stop)
+                noutside += miss
+                part = np.empty((ncomp, self.nsrc))
+                with self.ctx.transpose_nodes(ids, w, self.nsrc) as op:
+                    for c in range(ncomp):                   # (a row's columns start .. stop are contiguous)
+                        vc = v[c, start:stop] if isinstance(v, np.ndarray) else v.rows(c, c + 1).reshape(self.npoints).rows(start, stop)
+                        part[c] = op.apply(vc, point_major=False).numpy()[0]
+                ids.free()
+                w.free()
+                total = part if k == 0 else total + part
+            self.noutside = noutside
+        total = total.reshape((ncomp,) + self.prepared_shape)
+        return total if prepared else fold_to_caller_layout(total, self.flipped, self.appended)
+
+    def coverage(self, chunk_points=None):
+        """``G^T 1`` f64[D, LA, LO]: how much of the mesh's points every grid node carries (0: the node is not read by the
+        import)."""
+        return self.transpose(np.ones((1, self.npoints)), chunk_points=chunk_points)[0]
+
+    def free(self):
+        """Frees what the operator built (ids, weights, the grouped transpose) and lets go of the points, which it only
+        borrowed."""
+        for name in ("_transposed", "ids", "w"):
+            x = getattr(self, name, None)
+            if x is not None:
+                x.free()
+            setattr(self, name, None)
+        self.points = None
+
+
+def _operator_grid(grid, outside, lon_periodic):
+    """(grid, prepared axes, periodic, flipped, appended, clamp) of the grid argument of the operator drivers"""
+    if outside == "keep":
+        raise ValueError('outside="keep" keeps values of the mesh, which an operator does not have: use "fill" (rows of '
+                         'points outside are zero) or "clamp"')
+    if outside not in ("fill", "clamp"):
+        raise ValueError(f'outside must be "fill" or "clamp", got {outside!r}')
+    if not isinstance(grid, RegularGrid):
+        grid = RegularGrid.from_netcdf(grid)
+    if lon_periodic is None and grid.data_vars:
+        # the detection import_regular_grid makes for this grid, from the two end columns of its variables alone
+        ends = np.stack([np.stack([np.asarray(v, dtype=np.float64)[..., 0], np.asarray(v, dtype=np.float64)[..., -1]], axis=-1)
+                         for v in grid.data_vars.values()])
+        lon_periodic = _is_global_longitude(_ascending_axis("longitude", grid.coords["longitude"])[0], ends)
+    depth, lat, lon, _, _, periodic = prepare_regular_grid(grid, [], lon_periodic)
+    flipped = tuple(_ascending_axis(d, grid.coords[d])[1] for d in DIMS)
+    appended = len(lon) == len(grid.coords["longitude"]) + 1
+    return grid, (depth, lat, lon), periodic, flipped, appended, outside == "clamp"
+
+
+def grid_import_operator(grid, mesh_or_points, outside="fill", lon_periodic=None, make_spherical=False, context=None):
+    """The import of ``grid`` onto a mesh as a :class:`GridOperator`, to be applied to any number of cubes
+    (``.apply``) and turned round (``.transpose``, ``.coverage``).
+
+    ``grid``: a :class:`RegularGrid` or the path of a netCDF file; only its axes matter, prepared as
+    :func:`prepare_regular_grid` prepares them.  ``lon_periodic=None`` detects a global longitude axis as
+    :func:`import_regular_grid` detects it for the same grid with all its variables, so that this ``G`` is that import's:
+    an axis that spans exactly 360 degrees wraps when the first and the last column of every variable agree; a grid
+    without variables has no columns to differ, and such an axis then wraps.  ``mesh_or_points``: a
+    :class:`GllMesh`, a :class:`HexMesh`, or points f64[..., 3] on the host or on the device (a device array is
+    borrowed: it must stay alive and unchanged while the operator is used, and freeing the operator leaves it alone).
+    ``outside``: "fill" (a
+    point outside the grid gets an all-zero row: it imports nothing and sends nothing back) or "clamp" (the edge
+    extends); "keep" is refused, an operator has no values to keep.  ``make_spherical`` evaluates the coordinates on a
+    copy of the mesh mapped onto its 1-D sphere, as :func:`import_regular_grid` does."""
+    grid, axes, periodic, flipped, appended, clamp = _operator_grid(grid, outside, lon_periodic)
+    ctx = context or default_context()
+    if isinstance(mesh_or_points, (GllMesh, HexMesh)):
+        pts = np.asarray(_mesh_points(mesh_or_points))
+        if pts.shape[-1] != 3:
+            raise ValueError(f"grid_import_operator needs a 3-D mesh (points of shape {pts.shape})")
+        points = _sphere_mapped(mesh_or_points, ctx) if make_spherical else ctx.to_device(pts, np.float64)
+        points = points.reshape(*pts.shape)
+    else:
+        if make_spherical:
+            raise ValueError("make_spherical needs a mesh with z_node_1D, not bare points")
+        points, _ = ctx._points3(mesh_or_points)
+    return GridOperator(ctx, points, dict(grid.coords), axes, periodic, flipped, appended, clamp)
+
+
+def regular_grid_adjoint(grid, mesh, parameters, mass=True, normalise=False, outside="fill", lon_periodic=None,
+                         make_spherical=False, context=None):
+    """Sensitivities on a mesh brought back to the grid the model was imported from: with ``G`` the import operator of
+    ``grid`` onto ``mesh`` (:func:`grid_import_operator`) and ``K`` the mesh's fields ``parameters``, the returned
+    :class:`RegularGrid` holds ``G^T (M * K)`` per parameter -- the chain rule of a misfit through
+    :func:`import_regular_grid`, ``M`` being the diagonal mass (:func:`gll_mass_matrix` of a :class:`GllMesh` or a
+    readable Salvus model, :func:`hex8_mass_matrix` of a :class:`HexMesh`, of the mesh's own geometry) and the product
+    formed on the device.  ``mass=False``: ``G^T K``.  ``normalise=True`` divides every grid node by the ``"volume"``
+    below (``mm_divide_rows``): the volume-weighted mean of ``K`` over the node's hat function, 0 where that volume is 0.
+
+    The grid also carries ``"volume"`` = ``G^T (M * 1)`` (with ``mass=False``: ``G^T 1``, the coverage) and ``nmissing``,
+    the nodes of the mesh outside the grid, which send nothing back.  ``grid``, ``outside``, ``lon_periodic`` and
+    ``make_spherical`` as :func:`grid_import_operator` -- a global longitude axis is detected from the grid's own
+    variables as :func:`import_regular_grid` detects it, so pass the grid the model was imported from (a grid without
+    variables: an axis spanning exactly 360 degrees wraps).  The mesh must be 3-D; the sum over the grid of a parameter equals ``sum(M * K)`` over
+    the nodes inside it."""
+    grid, axes, periodic, flipped, appended, clamp = _operator_grid(grid, outside, lon_periodic)
+    parameters = mio.pick_parameters(parameters)
+    if "volume" in parameters:
+        raise ValueError('a parameter called "volume" clashes with the volume variable of the result')
+    if isinstance(mesh, (GllMesh, HexMesh)) and np.shape(_mesh_points(mesh))[-1] != 3:
+        raise ValueError(f"regular_grid_adjoint needs a 3-D mesh (points of shape {np.shape(_mesh_points(mesh))})")
+    ctx = context or default_context()
+    if isinstance(mesh, HexMesh):
+        absent = [p for p in parameters if p not in mesh.nodal_fields]
+        if absent:
+            raise ValueError(f"the mesh has no nodal field(s) {absent}")
+        fields = np.stack([np.asarray(mesh.get_nodal_field(p), dtype=np.float64) for p in parameters]) \
+            if parameters else np.zeros((0, mesh.npoint))
+        own = np.ascontiguousarray(mesh.points, dtype=np.float64)
+        points = _sphere_mapped(mesh, ctx) if make_spherical else ctx.to_device(own)
+        weight = _hex8_mass(mesh, ctx) if mass else None
+    else:
+        if isinstance(mesh, GllMesh):
+            absent = [p for p in parameters if p not in mesh.element_nodal_fields]
+            if absent:
+                raise ValueError(f"the mesh has no field(s) {absent}")
+        mesh = _as_gll_mesh(mesh, parameters, make_spherical)              # (a file is read once, here)
+        own = mesh.gll_points
+        points, order, fields = _gll_model(mesh, parameters, make_spherical, ctx)
+        points = ctx.asdevice(points, np.float64)
+        weight = _device_mass(own, order, ctx) if mass else None
+    ncomp = len(parameters)
+    n = points.size // 3
+    # rows: K per parameter, then 1 -- each multiplied by the mass on the device (mm_pcg_combine with tau = 0 is the plain
+    # product mass[i] * row[i], one rounding; M * 1.0 is M)
+    values = ctx.to_device(np.concatenate([np.asarray(fields, dtype=np.float64).reshape(ncomp, n), np.ones((1, n))]))
+    if mass and n:
+        weighted = ctx.empty(values.shape, np.float64)
+        check(ctx.lib.mm_pcg_combine(ctx.handle, weight.ptr, values.ptr, 0.0, None, n, ncomp + 1, weighted.ptr), "mm_pcg_combine")
+        values = weighted
+    with GridOperator(ctx, points.reshape(n, 3), dict(grid.coords), axes, periodic, flipped, appended, clamp) as op:
+        back = op.transpose(values)
+        nmissing = op.noutside
+    volume = back[ncomp]
+    data = back[:ncomp]
+    if normalise and ncomp:
+        data = ctx.divide_rows(data, volume).numpy()
+        data[:, volume == 0.0] = 0.0
+    out = RegularGrid(grid.coords["depth"], grid.coords["latitude"], grid.coords["longitude"],
+                      dict({p: data[c] for c, p in enumerate(parameters)}, volume=volume), nmissing)
+    out.attrs = dict(grid.attrs)
+    return out

@@ -1230,19 +1230,7 @@ class Context(_Released):
             raise ValueError(f"outside must be one of {sorted(modes)}, got {outside!r}")
         pts, n = self._points3(points)
         g = _components(self.asdevice(grid_values, np.float64), 3)
-        axes = []
-        for name, a in (("depth", depth), ("lat", lat), ("lon", lon)):
-            if isinstance(a, np.ndarray) or not hasattr(a, "data_ptr"):
-                a = np.ascontiguousarray(a, dtype=np.float64)
-                if a.ndim != 1 or a.size < 1 or not np.isfinite(a).all() or not (np.diff(a) > 0).all():
-                    raise ValueError(f"the {name} axis must be 1-D, finite and strictly ascending")
-                if name == "lon" and lon_periodic and (not -360.0 <= a[0] <= 180.0 or a[-1] != a[0] + 360.0):
-                    raise ValueError("a periodic lon axis must start in [-360, 180] and end at lon[0] + 360")
-            a = self.asdevice(a, np.float64)
-            if len(a.shape) != 1 or a.shape[0] < 1:
-                raise ValueError(f"the {name} axis must be 1-D with at least one node")
-            axes.append(a)
-        d, la, lo = axes
+        d, la, lo = self._grid_axes(depth, lat, lon, lon_periodic)
         if len(g.shape) != 4 or g.shape[1:] != (d.shape[0], la.shape[0], lo.shape[0]):
             raise ValueError(f"grid_values must be [C, {d.shape[0]}, {la.shape[0]}, {lo.shape[0]}] over the axes, got {g.shape}")
         ncomp = g.shape[0]
@@ -1261,6 +1249,48 @@ class Context(_Released):
         if want_latlondepth:
             return out, int(miss), lld
         return out, int(miss)
+
+    def _grid_axes(self, depth, lat, lon, lon_periodic):
+        """The three axes of a regular grid on the device.  Host axes are checked here (1-D, finite, strictly ascending; a
+        periodic longitude axis starts in [-360, 180] and ends at ``lon[0] + 360``), device axes are the caller's word."""
+        axes = []
+        for name, a in (("depth", depth), ("lat", lat), ("lon", lon)):
+            if isinstance(a, np.ndarray) or not hasattr(a, "data_ptr"):
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.ndim != 1 or a.size < 1 or not np.isfinite(a).all() or not (np.diff(a) > 0).all():
+                    raise ValueError(f"the {name} axis must be 1-D, finite and strictly ascending")
+                if name == "lon" and lon_periodic and (not -360.0 <= a[0] <= 180.0 or a[-1] != a[0] + 360.0):
+                    raise ValueError("a periodic lon axis must start in [-360, 180] and end at lon[0] + 360")
+            a = self.asdevice(a, np.float64)
+            if len(a.shape) != 1 or a.shape[0] < 1:
+                raise ValueError(f"the {name} axis must be 1-D with at least one node")
+            axes.append(a)
+        return axes
+
+    def grid_operator(self, points, depth, lat, lon, clamp=False, lon_periodic=False, latlondepth=False, ids_out=None,
+                      weights_out=None):
+        """The grid import of :meth:`sample_grid` as an operator (``mm_grid_operator``): for ``points`` f64[..., 3] (N
+        points, read flat) over the axes ``depth``, ``lat``, ``lon`` (checked as :meth:`sample_grid` checks them), the
+        flat indices ``(k * LA + j) * LO + i`` of the eight corners of every point's cell and their trilinear weights,
+        corner ``c = 4 a + 2 b + e`` over (depth, latitude, longitude), bit for bit the statement of
+        include/multimesh_hip.h.  ``gather(cube.reshape(C, -1), ids, w)`` imports a cube, ``transpose_nodes(ids, w,
+        D * LA * LO)`` is the way back.  ``clamp=False``: a point outside the grid gets ids 0 and weights +0.0 and is
+        counted; ``clamp=True``: the edge extends and nothing is outside.  ``ids_out`` / ``weights_out``: the caller's
+        i64[N, 8] / f64[N, 8] to write into.  Returns (ids i64[N, 8], w f64[N, 8], noutside) or, with ``latlondepth``,
+        (ids, w, noutside, latlondepth f64[N, 3])."""
+        pts, n = self._points3(points)
+        d, la, lo = self._grid_axes(depth, lat, lon, lon_periodic)
+        ids = self.empty((n, 8), np.int64) if ids_out is None else self.asdevice(ids_out, np.int64)
+        w = self.empty((n, 8), np.float64) if weights_out is None else self._out(weights_out, (n, 8))
+        if ids.shape != (n, 8) or w.shape != (n, 8):
+            raise ValueError("ids_out must be i64[N, 8] and weights_out f64[N, 8]")
+        lld = self.empty((n, 3), np.float64) if latlondepth else None
+        miss = check(self.lib.mm_grid_operator(self.handle, pts.ptr, n, d.ptr, d.shape[0], la.ptr, la.shape[0], lo.ptr,
+                                               lo.shape[0], 1 if lon_periodic else 0, 1 if clamp else 0, ids.ptr, w.ptr,
+                                               lld.ptr if lld else None), "mm_grid_operator")
+        if latlondepth:
+            return ids, w, int(miss), lld
+        return ids, w, int(miss)
 
     def interpolate_hex8(self, nodes, connectivity, points, fields, nelem_to_search=20, want_operator=False,
                          out=None):

@@ -75,6 +75,7 @@ SIGNATURES = {
     "mm_sample_columns_gll": (i64, (vp, i32, vp, i64, vp, i64, vp, i64, vp, i64, i32, vp, i64, i64, f64, f64, i64, vp,
                                   vp)),
     "mm_sample_grid": (i64, (vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i32, i32, f64, vp, vp)),
+    "mm_grid_operator": (i64, (vp, vp, i64, vp, i64, vp, i64, vp, i64, i32, i32, vp, vp, vp)),
     "mm_transpose_create_nodes": (i32, (vp, vp, vp, i64, i64, i64, C.POINTER(vp))),
     "mm_transpose_create_elem": (i32, (vp, vp, vp, i64, i64, i64, C.POINTER(vp))),
     "mm_transpose_apply": (i32, (vp, vp, vp, i64, i32, vp)),

@@ -3,7 +3,7 @@ import numpy as np
 
 from ..device import default_context
 from ..mesh import HexMesh
-from ._common import R_EARTH, GllMesh, _mesh_points
+from ._common import R_EARTH, GllMesh, _mesh_points, hex8_corners
 
 
 def _z_node_1d(mesh):
@@ -75,7 +75,7 @@ def _element_nodal_base(mesh, ctx):
     if connectivity is not None:
         z = z.reshape(-1)[ctx.first_occurrence(connectivity, pts.shape[0]).numpy()]
     if isinstance(mesh, HexMesh):        # exodus hex8 -> the tensor order of an order-1 GLL element
-        conn, order = mesh.connectivity[:, [0, 1, 3, 2, 4, 5, 7, 6]], 1
+        conn, order = hex8_corners(mesh)[0], 1
     else:                                # GLL nodes listed in tensor order (p = i + (n+1) j + (n+1)^2 k)
         conn, order = np.asarray(mesh.connectivity), int(mesh.shape_order)
     return np.ascontiguousarray(pts[conn], dtype=np.float64), np.ascontiguousarray(z[conn]), order

@@ -5,10 +5,10 @@ section of plot_cross_section (plotter.py:360-391).  The targets are generated o
 import numpy as np
 
 from .. import io as mio
-from ..device import DeviceArray, _Released, default_context
+from ..device import _Released, default_context
 from ..helpers import check
 from ..mesh import HexMesh
-from ._common import GllMesh, _mesh_points, _order_from_point_count
+from ._common import GllMesh, ImportTarget, _order_from_point_count, is_mesh, named_fields, points_of
 from .earth import _sphere_mapped
 from .mass import _device_mass, _hex8_mass
 
@@ -347,6 +347,11 @@ def sample_regular_grid(grid, points, parameters=None, outside="fill", fill_valu
     return values.numpy(), nmissing
 
 
+def _need_3d(points, who):
+    if np.shape(points)[-1] != 3:
+        raise ValueError(f"{who} needs a 3-D mesh (points of shape {np.shape(points)})")
+
+
 def import_regular_grid(grid, mesh, parameters=None, outside="keep", fill_value=np.nan, lon_periodic=None,
                         make_spherical=False, context=None):
     """A gridded model onto a mesh: every node of ``mesh`` gets the value of ``grid`` at its (geocentric latitude,
@@ -373,56 +378,14 @@ def import_regular_grid(grid, mesh, parameters=None, outside="keep", fill_value=
     def ctx():   # (asked for when the first kernel runs: what is wrong with the arguments is said without a device)
         return context or default_context()
 
-    def run(points, existing):
-        """existing: name -> array of the points' leading shape (keep mode reads it) -> values f64[C, ...] (host)"""
-        lead = tuple(np.shape(points)[:-1]) if not isinstance(points, DeviceArray) else points.shape[:-1]
-        out = None
-        if outside == "keep":
-            out = np.ascontiguousarray(np.stack([np.asarray(existing[p], dtype=np.float64).reshape(lead)
-                                                 for p in parameters]) if parameters else np.zeros((0,) + lead))
+    with ImportTarget(mesh) as target:
+        _need_3d(target.points, "import_regular_grid")
+        target.require(parameters, values=outside == "keep")
+        out = target.existing(parameters) if outside == "keep" else None
+        points = _sphere_mapped(target.sphere_mesh(), ctx()) if make_spherical else target.points
         values, nmissing = ctx().sample_grid(points, data, depth, lat, lon, outside=outside, fill_value=fill_value,
                                              lon_periodic=periodic, out=out)
-        return values.numpy().reshape((len(parameters),) + lead), nmissing
-
-    if isinstance(mesh, (GllMesh, HexMesh)):
-        pts = np.asarray(_mesh_points(mesh))
-        if pts.shape[-1] != 3:
-            raise ValueError(f"import_regular_grid needs a 3-D mesh (points of shape {pts.shape})")
-        fields = mesh.element_nodal_fields if isinstance(mesh, GllMesh) else mesh.nodal_fields
-        if outside == "keep":
-            absent = [p for p in parameters if p not in fields]
-            if absent:
-                raise ValueError(f'outside="keep" keeps the mesh\'s values, but it has no field(s) {absent}')
-        values, nmissing = run(_sphere_mapped(mesh, ctx()) if make_spherical else pts, fields)
-        for c, p in enumerate(parameters):
-            if isinstance(mesh, GllMesh):
-                mesh.element_nodal_fields[p] = np.ascontiguousarray(values[c])
-            else:
-                mesh.attach_field(p, values[c])
-        return nmissing
-
-    with mio.open_h5(mesh, "r+") as f:
-        model = f["MODEL/data"]
-        names = mio.dimension_labels(model, 1)
-        unknown = [p for p in parameters if p not in names]
-        if unknown:
-            raise ValueError(f"parameters {unknown} are not in MODEL/data (it holds {names})")
-        points = np.array(f["MODEL/coordinates"][()], dtype=np.float64)
-        if points.ndim != 3 or points.shape[2] != 3:
-            raise ValueError(f"MODEL/coordinates must be [nelem, P, 3], got {points.shape}")
-        columns = {p: names.index(p) for p in parameters}
-        existing = {p: np.array(model[:, columns[p], :], dtype=np.float64) for p in parameters} if outside == "keep" else {}
-        if make_spherical:
-            if "z_node_1D" not in names:
-                raise ValueError("make_spherical needs the model's z_node_1D, which MODEL/data does not hold")
-            order = _order_from_point_count(points.shape[1], 3)
-            z = np.array(model[:, names.index("z_node_1D"), :], dtype=np.float64)
-            sample_at = _sphere_mapped(GllMesh(points, order, {"z_node_1D": z}), ctx())
-        else:
-            sample_at = points
-        values, nmissing = run(sample_at, existing)
-        for c, p in enumerate(parameters):
-            model[:, columns[p], :] = values[c]
+        target.write(parameters, values.numpy().reshape((len(parameters),) + target.lead))
     return nmissing
 
 
@@ -651,10 +614,9 @@ def grid_import_operator(grid, mesh_or_points, outside="fill", lon_periodic=None
     copy of the mesh mapped onto its 1-D sphere, as :func:`import_regular_grid` does."""
     grid, axes, periodic, flipped, appended, clamp = _operator_grid(grid, outside, lon_periodic)
     ctx = context or default_context()
-    if isinstance(mesh_or_points, (GllMesh, HexMesh)):
-        pts = np.asarray(_mesh_points(mesh_or_points))
-        if pts.shape[-1] != 3:
-            raise ValueError(f"grid_import_operator needs a 3-D mesh (points of shape {pts.shape})")
+    if is_mesh(mesh_or_points):
+        pts = points_of(mesh_or_points)
+        _need_3d(pts, "grid_import_operator")
         points = _sphere_mapped(mesh_or_points, ctx) if make_spherical else ctx.to_device(pts, np.float64)
         points = points.reshape(*pts.shape)
     else:
@@ -684,28 +646,15 @@ def regular_grid_adjoint(grid, mesh, parameters, mass=True, normalise=False, out
     parameters = mio.pick_parameters(parameters)
     if "volume" in parameters:
         raise ValueError('a parameter called "volume" clashes with the volume variable of the result')
-    if isinstance(mesh, (GllMesh, HexMesh)) and np.shape(_mesh_points(mesh))[-1] != 3:
-        raise ValueError(f"regular_grid_adjoint needs a 3-D mesh (points of shape {np.shape(_mesh_points(mesh))})")
-    ctx = context or default_context()
-    if isinstance(mesh, HexMesh):
-        absent = [p for p in parameters if p not in mesh.nodal_fields]
-        if absent:
-            raise ValueError(f"the mesh has no nodal field(s) {absent}")
-        fields = np.stack([np.asarray(mesh.get_nodal_field(p), dtype=np.float64) for p in parameters]) \
-            if parameters else np.zeros((0, mesh.npoint))
-        own = np.ascontiguousarray(mesh.points, dtype=np.float64)
-        points = _sphere_mapped(mesh, ctx) if make_spherical else ctx.to_device(own)
-        weight = _hex8_mass(mesh, ctx) if mass else None
-    else:
-        if isinstance(mesh, GllMesh):
-            absent = [p for p in parameters if p not in mesh.element_nodal_fields]
-            if absent:
-                raise ValueError(f"the mesh has no field(s) {absent}")
+    if not is_mesh(mesh):
         mesh = _as_gll_mesh(mesh, parameters, make_spherical)              # (a file is read once, here)
-        own = mesh.gll_points
-        points, order, fields = _gll_model(mesh, parameters, make_spherical, ctx)
-        points = ctx.asdevice(points, np.float64)
-        weight = _device_mass(own, order, ctx) if mass else None
+    own = points_of(mesh)
+    _need_3d(own, "regular_grid_adjoint")
+    fields = named_fields(mesh, parameters)[1]
+    ctx = context or default_context()
+    points = ctx.asdevice(_sphere_mapped(mesh, ctx) if make_spherical else own, np.float64)
+    if mass:
+        weight = _hex8_mass(mesh, ctx) if isinstance(mesh, HexMesh) else _device_mass(own, int(mesh.shape_order), ctx)
     ncomp = len(parameters)
     n = points.size // 3
     # rows: K per parameter, then 1 -- each multiplied by the mass on the device (mm_pcg_combine with tau = 0 is the plain

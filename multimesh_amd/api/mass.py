@@ -8,7 +8,7 @@ import numpy as np
 from .. import synth
 from ..device import default_context
 from ..mesh import HexMesh
-from ._common import _gll_points_order
+from ._common import _gll_points_order, hex8_corners
 from .layers import _selected_layers
 
 
@@ -36,8 +36,8 @@ def gll_mass_matrix(mesh, context=None):
 
 
 def _hex8_mass(mesh: HexMesh, ctx):
-    conn = np.ascontiguousarray(mesh.connectivity[:, [0, 1, 3, 2, 4, 5, 7, 6]])      # exodus -> tensor order, order 1
-    mass = _device_mass(np.ascontiguousarray(mesh.points[conn]), 1, ctx)
+    conn, corners = hex8_corners(mesh)                                               # the order-1 GLL mesh it is
+    mass = _device_mass(corners, 1, ctx)
     with ctx.transpose_nodes(conn, mass, mesh.npoint) as op:
         lumped = op.apply(np.ones(mesh.nelem))                                       # [1, npoint]
     return lumped.reshape(mesh.npoint)

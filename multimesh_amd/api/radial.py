@@ -8,7 +8,7 @@ import numpy as np
 
 from ..device import default_context
 from ..mesh import HexMesh
-from ._common import _mesh_points
+from ._common import name_list, named_fields, points_of
 from .mass import _device_mass, _hex8_mass
 
 
@@ -48,7 +48,7 @@ class RadialModel:
     def from_arrays(cls, radius, values, names):
         """``values`` f64[C, m] (or [m] with one name) and the C names of its rows."""
         v = np.atleast_2d(np.asarray(values, dtype=np.float64))
-        names = [names] if isinstance(names, str) else list(names)
+        names = name_list(names, ())
         if v.shape[0] != len(names):
             raise ValueError(f"{len(names)} names for {v.shape[0]} rows of values")
         return cls(radius, dict(zip(names, v)))
@@ -59,7 +59,7 @@ class RadialModel:
 
     def table(self, params=None):
         """f64[C, m]: the rows of ``params`` (default: all, in the order given)."""
-        names = self.parameters if params is None else ([params] if isinstance(params, str) else list(params))
+        names = name_list(params, self.parameters)
         missing = [p for p in names if p not in self.values]
         if missing:
             raise ValueError(f"the radial model has no {missing} (it has {self.parameters})")
@@ -106,21 +106,13 @@ def radial_edges(points, nbins):
 
 def _radial_mesh(mesh, params):
     """(points [E, P, 3] or [N, 3], names, fields [C, ...] or None, is_hex) of a GllMesh / Salvus mesh or a HexMesh."""
-    if isinstance(mesh, HexMesh):
-        pts, store = mesh.points, mesh.nodal_fields
-    else:
-        pts = np.asarray(_mesh_points(mesh))
-        if pts.ndim != 3:
-            raise ValueError(f"need a HexMesh or element-nodal GLL points [E, P, 3] (points of shape {pts.shape})")
-        store = mesh.element_nodal_fields
+    pts = points_of(mesh)
+    if not isinstance(mesh, HexMesh) and pts.ndim != 3:
+        raise ValueError(f"need a HexMesh or element-nodal GLL points [E, P, 3] (points of shape {pts.shape})")
     if pts.shape[-1] != 3:
         raise ValueError(f"radial profiles are for 3-D meshes (points of shape {pts.shape})")
-    names = [] if params is None else ([params] if isinstance(params, str) else list(params))
-    missing = [p for p in names if p not in store]
-    if missing:
-        raise ValueError(f"the mesh has no field {missing}")
-    fields = np.stack([np.asarray(store[p], dtype=np.float64) for p in names]) if names else None
-    return np.ascontiguousarray(pts, dtype=np.float64), names, fields, isinstance(mesh, HexMesh)
+    names, fields = named_fields(mesh, params, default=())
+    return pts, names, fields, isinstance(mesh, HexMesh)
 
 
 def radial_profile(mesh, params=None, edges=None, nbins=None, context=None):
@@ -168,8 +160,7 @@ def evaluate_radial_model(model: RadialModel, mesh_or_points, params=None, conte
     :class:`HexMesh` or an [N, 3] array (a point on a discontinuity takes the upper side).  Piecewise linear within a
     layer, constant beyond the table's ends.  ``params``: names of the model (default: all)."""
     _, table = model.table(params)
-    is_mesh = hasattr(mesh_or_points, "gll_points") or hasattr(mesh_or_points, "points")
-    pts = np.ascontiguousarray(_mesh_points(mesh_or_points) if is_mesh else mesh_or_points, dtype=np.float64)
+    pts = points_of(mesh_or_points)
     if pts.ndim not in (2, 3) or pts.shape[-1] != 3:
         raise ValueError(f"points must be [E, P, 3] or [N, 3], got {pts.shape}")
     ctx = context or default_context()

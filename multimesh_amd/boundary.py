@@ -12,17 +12,15 @@ import warnings
 
 import numpy as np
 
-from .api._common import _gll_points_order, _mesh_fields, _scatter_back
+from .api._common import EXODUS_TO_TENSOR  # noqa: F401  (stated there; still reachable here, where it used to live)
+from .api._common import _gll_points_order, _mesh_fields, _scatter_back, hex8_corners, named_fields, points_of
 from .device import default_context
 from .mesh import HexMesh
-from .precondition import _is_mesh, _named_fields, _points_of
 
 __all__ = ["mesh_boundary", "distance_to_boundary", "taper_to_boundary", "blend_models"]
 
 #: the side of a boundary face as mm_boundary_classify numbers it
 SIDES = {"side": 0, "top": 1, "bottom": 2}
-#: a hex8 connectivity in exodus order -> tensor order (corner i + 2 j + 4 k)
-EXODUS_TO_TENSOR = [0, 1, 3, 2, 4, 5, 7, 6]
 _MIN_CUTOFF = 2.0 ** -500   # the least cutoff mm_cutoff_distance serves
 
 
@@ -94,8 +92,7 @@ def mesh_boundary(mesh, up=None, cos_min=0.5, context=None):
             raise ValueError("up must be three finite numbers, not all zero (None: radial)")
     hex8 = isinstance(mesh, HexMesh)
     if hex8:
-        if mesh.points.shape[1] != 3 or mesh.connectivity.shape[1] != 8:
-            raise ValueError("3-D hexahedral meshes only")
+        conn, corners = hex8_corners(mesh)
     else:
         gp, order = _gll_points_order(mesh)
         if gp.shape[2] != 3:
@@ -104,9 +101,8 @@ def mesh_boundary(mesh, up=None, cos_min=0.5, context=None):
             raise ValueError("GLL orders 1, 2 and 4 only")
     ctx = context or default_context()
     if hex8:
-        conn = np.ascontiguousarray(mesh.connectivity[:, EXODUS_TO_TENSOR])
-        corners = ctx.to_device(mesh.points[conn])
-        ids, nnodes, points, order = ctx.to_device(conn), mesh.npoint, corners, 1
+        points = corners = ctx.to_device(corners)
+        ids, nnodes, order = ctx.to_device(conn), mesh.npoint, 1
     else:
         points = ctx.to_device(gp)
         corners = points if order == 1 else ctx.to_device(gp[:, corner_nodes(order)])
@@ -136,9 +132,7 @@ def distance_to_boundary(mesh_or_points, boundary, cutoff, sides=("side", "botto
     if not isinstance(boundary, Boundary):
         raise ValueError("boundary must come from mesh_boundary")
     cutoff, mask = _cutoff(cutoff), _side_mask(sides)
-    pts = _points_of(mesh_or_points) if _is_mesh(mesh_or_points) else np.ascontiguousarray(mesh_or_points, dtype=np.float64)
-    if pts.ndim < 2 or pts.shape[-1] != 3:
-        raise ValueError(f"points must be [..., 3], got {pts.shape}")
+    pts = points_of(mesh_or_points)                       # ([..., 3]: cutoff_distance refuses anything else)
     ctx = boundary._context(context)
     return ctx.cutoff_distance(pts, boundary._nodes(mask), cutoff)[0].numpy()
 
@@ -159,8 +153,8 @@ def taper_to_boundary(mesh, params, inner, outer, sides=("side", "bottom"), boun
     free surface ("top") alone: a kernel is damped towards absorbing sides and bottom, not towards the surface."""
     inner, outer = _radii(inner, outer)
     mask = _side_mask(sides)
-    pts = _points_of(mesh)
-    _, fields = _named_fields(mesh, params)
+    pts = points_of(mesh)
+    _, fields = named_fields(mesh, params)
     if boundary is None:
         boundary = mesh_boundary(mesh, context=context)
     ctx = boundary._context(context)

@@ -6,21 +6,15 @@ from __future__ import annotations
 
 import numpy as np
 
-from .api._common import _mesh_fields, _mesh_points, latlondepth_to_xyz
+from .api._common import is_mesh, latlondepth_to_xyz, named_fields, points_of
 from .device import default_context
-from .mesh import HexMesh
 
 __all__ = ["taper_around_points", "cut_around_points", "field_quantiles", "clip_fields", "precondition_kernel"]
 
 
-def _is_mesh(x):
-    return isinstance(x, HexMesh) or hasattr(x, "gll_points") or hasattr(x, "element_nodal_fields")
-
-
 def _points_of(mesh_or_points):
     """f64[E, P, 3] of a GLL mesh, f64[N, 3] of a HexMesh or of an array of points."""
-    pts = _mesh_points(mesh_or_points) if _is_mesh(mesh_or_points) else mesh_or_points
-    pts = np.ascontiguousarray(pts, dtype=np.float64)
+    pts = points_of(mesh_or_points)
     if pts.ndim not in (2, 3) or pts.shape[-1] != 3:
         raise ValueError(f"points must be [E, P, 3] or [N, 3], got {pts.shape}")
     if pts.ndim == 3 and not 1 <= pts.shape[1] <= 256:
@@ -57,25 +51,10 @@ def _centres(centres, inner, outer, geocentric):
     return np.ascontiguousarray(c), radii[0], radii[1]
 
 
-def _named_fields(mesh, params):
-    """(names, f64[C, E, P] or [C, N]) of the fields ``params`` of a GLL mesh or a HexMesh."""
-    if isinstance(mesh, HexMesh):
-        names = mesh.nodal_parameters if params is None else ([params] if isinstance(params, str) else list(params))
-        missing = [p for p in names if p not in mesh.nodal_fields]
-        if missing:
-            raise ValueError(f"the mesh has no field {missing}")
-        return names, (mesh.fields_matrix(names) if names else np.zeros((0, mesh.npoint)))
-    names = list(mesh.element_nodal_fields) if params is None else ([params] if isinstance(params, str) else list(params))
-    missing = [p for p in names if p not in mesh.element_nodal_fields]
-    if missing:
-        raise ValueError(f"the mesh has no field {missing}")
-    return _mesh_fields(mesh, names)
-
-
 def _values_of(values_or_mesh, params):
     """f64[C, ...] from a mesh and names of its fields, or from an array [C, ...] / [n] (one component)."""
-    if _is_mesh(values_or_mesh):
-        return _named_fields(values_or_mesh, params)[1]
+    if is_mesh(values_or_mesh):
+        return named_fields(values_or_mesh, params)[1]
     if params is not None:
         raise ValueError("params name the fields of a mesh: pass a mesh, or values without params")
     v = np.ascontiguousarray(values_or_mesh, dtype=np.float64)
@@ -111,7 +90,7 @@ def cut_around_points(mesh, params, centres, inner, outer, geocentric=False, con
     values f64[C, E, P] (a :class:`HexMesh`: [C, N]) -- new arrays, the mesh's fields are untouched -- and ``ncut`` the
     number of nodes whose weight is below 1.  Arguments as :func:`taper_around_points`."""
     pts = _points_of(mesh)
-    _, fields = _named_fields(mesh, params)
+    _, fields = named_fields(mesh, params)
     c, ri, ro = _centres(centres, inner, outer, geocentric)
     ctx = context or default_context()
     out, ncut = ctx.point_taper(pts, c, ri, ro, values_in=fields.reshape(fields.shape[0], -1))
@@ -228,7 +207,7 @@ def precondition_kernel(mesh, params, sources=None, receivers=None, source_cut=N
     if clip_quantile is not None:
         clip_quantile = float(_check_q(clip_quantile).reshape(1)[0])
     pts = _points_of(mesh)
-    names, fields = _named_fields(mesh, params)
+    names, fields = named_fields(mesh, params)
     ctx = context or default_context()
     flat = ctx.to_device(fields.reshape(len(names), -1))
     out, ncut = ctx.point_taper(pts, c, ri, ro, values_in=flat, out=flat)

@@ -11,8 +11,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .api._common import _element_fields, _gll_points_order
-from .boundary import EXODUS_TO_TENSOR
+from .api._common import _element_fields, _gll_points_order, field_store, hex8_corners, name_list, named_fields
 from .device import default_context
 from .mesh import HexMesh
 
@@ -26,20 +25,13 @@ SLOW_NAMES = ("VS", "VSV", "VSH")
 def _velocities(mesh, conn, shape, given, names, what):
     """f64[C, E, P] (or None) from names of the mesh's fields, an array, or None: those of ``names`` the mesh carries."""
     hex8 = conn is not None
-    carried = mesh.nodal_fields if hex8 else getattr(mesh, "element_nodal_fields", {})
-    if given is None:
-        given = [n for n in names if n in carried]
-    elif isinstance(given, str):
-        given = [given]
+    if given is None or isinstance(given, str):
+        given = name_list(given, [n for n in names if n in field_store(mesh)])
     if isinstance(given, (list, tuple)) and all(isinstance(g, str) for g in given):
         if not given:
             return None
-        missing = [g for g in given if g not in carried]
-        if missing:
-            raise ValueError(f"the mesh has no field {missing}")
-        if hex8:
-            return np.ascontiguousarray(mesh.fields_matrix(list(given))[:, conn])
-        return _element_fields(mesh, list(given), shape)
+        fields = named_fields(mesh, given)[1]
+        return np.ascontiguousarray(fields[:, conn]) if hex8 else _element_fields(mesh, fields, shape)
     v = np.asarray(given, dtype=np.float64)
     if hex8 and v.shape[-1:] == (mesh.npoint,) and v.ndim in (1, 2):   # nodal values: gathered like the corners
         return np.ascontiguousarray(np.atleast_2d(v)[:, conn])
@@ -56,10 +48,7 @@ def _mesh_arrays(mesh, fast, slow, need_fast):
     its corners, and its nodal fields, gathered through the connectivity in tensor order."""
     conn = None
     if isinstance(mesh, HexMesh):
-        if mesh.points.shape[1] != 3 or mesh.connectivity.shape[1] != 8:
-            raise ValueError("3-D hexahedral meshes only")
-        conn = np.ascontiguousarray(mesh.connectivity[:, EXODUS_TO_TENSOR])
-        gp, order = np.ascontiguousarray(mesh.points[conn]), 1
+        (conn, gp), order = hex8_corners(mesh), 1
     else:
         gp, order = _gll_points_order(mesh)
         if gp.shape[2] not in (2, 3) or order not in (1, 2, 4) or gp.shape[1] != (order + 1) ** gp.shape[2]:

@@ -11,11 +11,9 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import io as mio
-from .api._common import GllMesh, _mesh_points, latlondepth_to_xyz
+from .api._common import ImportTarget, latlondepth_to_xyz, name_list
 from .device import default_context
 from .helpers import MM_KNN_MAX_K
-from .mesh import HexMesh
 
 __all__ = ["PointCloud", "chunk_size", "interpolate_scattered", "import_point_cloud"]
 
@@ -53,7 +51,7 @@ class PointCloud:
                 raise ValueError(f"values must be [n, C], [n] or a dict of [n] columns, got {v.shape}")
             if names is None:
                 raise ValueError("an array of values needs names for its columns")
-            names = [names] if isinstance(names, str) else list(names)
+            names = name_list(names, ())
             if len(names) != v.shape[1]:
                 raise ValueError(f"{len(names)} names for {v.shape[1]} columns of values")
             columns = [v[:, c] for c in range(v.shape[1])]
@@ -78,7 +76,7 @@ class PointCloud:
 
     def pick(self, params=None):
         """The names ``params`` asks for (None: all, a string: that one), checked against the cloud's."""
-        names = self.names if params is None else ([params] if isinstance(params, str) else list(params))
+        names = name_list(params, self.names)
         unknown = [p for p in names if p not in self.values]
         if unknown:
             raise ValueError(f"parameters {unknown} are not in the cloud (it holds {self.names})")
@@ -207,49 +205,16 @@ def import_point_cloud(cloud, mesh, params=None, k=8, power=2, max_distance=None
             raise ValueError("blend = (inner, outer) needs 0 <= inner <= outer, both finite")
     needs_mesh_values = outside == "keep" or blend is not None
 
-    def run(points, existing):
-        """existing: name -> array of the points' leading shape -> (values f64[C, ...] on the host, noutside)"""
-        pts, lead = _targets(cloud, points)
+    with ImportTarget(mesh) as target:
+        if target.points.shape[-1] != cloud.ndim:
+            raise ValueError(f"the mesh is {target.points.shape[-1]}-D, the cloud {cloud.ndim}-D")
+        target.require(names, values=needs_mesh_values)
+        pts, _ = _targets(cloud, target.points)
+        prior = target.existing(names).reshape(len(names), -1) if needs_mesh_values else None
         ctx = context or default_context()
-        prior = None
-        if needs_mesh_values:
-            prior = np.ascontiguousarray(np.stack([np.asarray(existing[p], dtype=np.float64).reshape(-1) for p in names])
-                                         if names else np.zeros((0, len(pts))))
         values, nearest, noutside = _run(cloud, ctx, pts, names, k, power, max_distance, outside, fill_value, prior, False,
                                          chunk_points)
         if blend is not None and names:
             values = ctx.distance_taper(nearest, inner, outer, prior, b=values)[0].numpy()
-        return values.reshape((len(names),) + tuple(lead)), noutside
-
-    if isinstance(mesh, (GllMesh, HexMesh)):
-        pts = np.asarray(_mesh_points(mesh))
-        if pts.shape[-1] != cloud.ndim:
-            raise ValueError(f"the mesh is {pts.shape[-1]}-D, the cloud {cloud.ndim}-D")
-        fields = mesh.element_nodal_fields if isinstance(mesh, GllMesh) else mesh.nodal_fields
-        if needs_mesh_values:
-            absent = [p for p in names if p not in fields]
-            if absent:
-                raise ValueError(f'outside="keep" and blend keep the mesh\'s values, but it has no field(s) {absent}')
-        values, noutside = run(pts, fields)
-        for c, p in enumerate(names):
-            if isinstance(mesh, GllMesh):
-                mesh.element_nodal_fields[p] = np.ascontiguousarray(values[c])
-            else:
-                mesh.attach_field(p, values[c])
-        return noutside
-
-    with mio.open_h5(mesh, "r+") as f:
-        model = f["MODEL/data"]
-        labels = mio.dimension_labels(model, 1)
-        unknown = [p for p in names if p not in labels]
-        if unknown:
-            raise ValueError(f"parameters {unknown} are not in MODEL/data (it holds {labels})")
-        points = np.array(f["MODEL/coordinates"][()], dtype=np.float64)
-        if points.ndim != 3 or points.shape[2] != cloud.ndim:
-            raise ValueError(f"MODEL/coordinates must be [nelem, P, {cloud.ndim}] like the cloud's points, got {points.shape}")
-        columns = {p: labels.index(p) for p in names}
-        existing = {p: np.array(model[:, columns[p], :], dtype=np.float64) for p in names} if needs_mesh_values else {}
-        values, noutside = run(points, existing)
-        for c, p in enumerate(names):
-            model[:, columns[p], :] = values[c]
+        target.write(names, values.reshape((len(names),) + target.lead))
     return noutside

@@ -187,17 +187,9 @@ __global__ __launch_bounds__(kBlock) void strips_with_targets_kernel(GridParams 
         xcd = (unsigned)(col / cols_per_xcd);
         m = (unsigned)(col - (int)xcd * cols_per_xcd) * (unsigned)nstrips + (unsigned)strip;
     }
-    const unsigned long long vote = __ballot(has);
-    if (!vote) return;
-    const int lane = threadIdx.x & 63;
-    const int first = __ffsll((long long)vote) - 1;
-    int base = 0;
-    if (lane == first) base = atomicAdd(count, __popcll(vote) * nsplit);
-    base = __shfl(base, first);
-    if (has) {
-        const int at = base + __popcll(vote & ((1ull << lane) - 1ull)) * nsplit;
+    const int at = wave_reserve(count, has, nsplit);
+    if (has)
         for (int p = 0; p < nsplit; ++p) list[at + p] = ((m * (unsigned)nsplit + (unsigned)p) << 3) | xcd;
-    }
 }
 
 template <int K, typename IDX>
@@ -255,24 +247,24 @@ void launch_fast(mm_context *ctx, const mm_knn_index *ix, const GridParams &g, c
             i64 walkers = (npts + kStripGroups - 1) / kStripGroups;   // no more workgroups than rounds
             if (walkers > 16384) walkers = 16384;
             hipLaunchKernelGGL((knn_strip_kernel<K, CAP, IDX, 2>), dim3((unsigned)walkers), dim3(kWave), 0, ctx->stream, g,
-                               ix->nsrc, ix->cell_start, ix->sorted_xyz, ix->ndim, kout, tstart, tsorted, idx, dist,
+                               ix->cell_start, ix->sorted_xyz, ix->ndim, kout, tstart, tsorted, idx, dist,
                                fb_list, fb_count, (int)nsplit, down_list, down_count, strip_list, strip_count);
         } else {
             strip_grid *= nsplit;
             if (down_list)
                 hipLaunchKernelGGL((knn_strip_kernel<K, CAP, IDX, 1>), dim3((unsigned)strip_grid), dim3(kWave), 0,
-                                   ctx->stream, g, ix->nsrc, ix->cell_start, ix->sorted_xyz, ix->ndim, kout, tstart,
+                                   ctx->stream, g, ix->cell_start, ix->sorted_xyz, ix->ndim, kout, tstart,
                                    tsorted, idx, dist, fb_list, fb_count, (int)nsplit, down_list, down_count,
                                    (const unsigned *)nullptr, (const int *)nullptr);
             else
                 hipLaunchKernelGGL((knn_strip_kernel<K, CAP, IDX, 0>), dim3((unsigned)strip_grid), dim3(kWave), 0,
-                                   ctx->stream, g, ix->nsrc, ix->cell_start, ix->sorted_xyz, ix->ndim, kout, tstart,
+                                   ctx->stream, g, ix->cell_start, ix->sorted_xyz, ix->ndim, kout, tstart,
                                    tsorted, idx, dist, fb_list, fb_count, (int)nsplit, (int *)nullptr,
                                    (int *)nullptr, (const unsigned *)nullptr, (const int *)nullptr);
         }
     } else {
         hipLaunchKernelGGL((knn_cell_kernel<K, CAP, IDX>), dim3((unsigned)cell_grid), dim3(kWave), 0, ctx->stream, g,
-                           ix->nsrc, ix->cell_start, ix->sorted_xyz, pts, ix->ndim, kout, tstart, tsorted, idx, dist, fb_list, fb_count);
+                           ix->cell_start, ix->sorted_xyz, ix->ndim, kout, tstart, tsorted, idx, dist, fb_list, fb_count);
     }
     if (record_stage) mm_stage_end(ctx, MM_STAGE_KNN_CELL);
 }

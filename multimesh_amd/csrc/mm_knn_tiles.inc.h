@@ -2,6 +2,37 @@
 // A part of mm_knn.hip -- ONE translation unit: the kernels of all parts are instantiated from its launchers --, included
 // inside that file's anonymous namespace in the order grid, rings, tiles, lane.  Not a header to include elsewhere.
 
+// Histogram range of both kernels: the ball holding k of a block's `count` sources has r^d = (k/count) * V_block / c_d;
+// this is its r^2 from fv = (k/count) * V_block.  Only a heuristic range, so fast exp2/log2 are fine.
+__device__ __forceinline__ float hist_r2(int dims, float fv)
+{
+    if (dims == 3) return __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(fv * (1.f / 4.18879f)) * (2.f / 3.f));
+    if (dims == 2) return fv * (1.f / 3.14159f);
+    if (dims == 1) { const float r = fv * 0.5f; return r * r; }
+    return 1.f;
+}
+
+// Append `value` of every lane with `pred` to a list on the device: one atomic per wave, the voters ranked by ballot.
+// wave_reserve: the same for `each` entries per voter; returns the index of the lane's first one (voters only).
+// Call both from wave-uniform control flow.
+__device__ __forceinline__ int wave_reserve(int *__restrict__ count, bool pred, int each)
+{
+    const unsigned long long vote = __ballot(pred);
+    if (!vote) return 0;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int first = __ffsll((long long)vote) - 1;
+    int base = 0;
+    if (lane == first) base = atomicAdd(count, __popcll(vote) * each);
+    base = __shfl(base, first);
+    return base + __popcll(vote & ((1ull << lane) - 1ull)) * each;
+}
+
+__device__ __forceinline__ void wave_append(int *__restrict__ list, int *__restrict__ count, bool pred, int value)
+{
+    const int at = wave_reserve(count, pred, 1);
+    if (pred) list[at] = value;
+}
+
 // ---- fast path: one wave per grid cell, sources staged in LDS --------------------------------
 // A wave owns one cell of the search grid and serves every target that falls into it.
 //   stage : the cell's 3x3x3 neighbourhood (9 column runs of the cell-sorted source array) is read
@@ -35,10 +66,8 @@
 // histogram range, its list overflows (many exact ties), or the exact k-th distance is not closer
 // than the nearest block face (a nearer source could sit outside the block).
 template <int K, int CAP, typename IDX>
-__global__ __launch_bounds__(kWave, 4) void knn_cell_kernel(GridParams g, i64 nsrc,
-                                                            const int *__restrict__ cell_start,
-                                                            const double *__restrict__ sorted_xyz,
-                                                             const double *__restrict__ pts, int ndim, int kout,
+__global__ __launch_bounds__(kWave, 4) void knn_cell_kernel(GridParams g, const int *__restrict__ cell_start,
+                                                            const double *__restrict__ sorted_xyz, int ndim, int kout,
                                                             const int *__restrict__ tstart,
                                                             const double *__restrict__ tsorted,
                                                             IDX *__restrict__ idx_out,
@@ -102,9 +131,8 @@ __global__ __launch_bounds__(kWave, 4) void knn_cell_kernel(GridParams g, i64 ns
     const double oy = g.loy + (double)cy * g.hy;
     const double oz = g.loz + (double)cz * g.hz;
 
-    // histogram range from the local density: the ball holding k of the block's `total` sources
-    // has r^d = (k/total) * V_block / c_d; buckets are uniform in r^2 over [0, 2.2 r^2).  Only a
-    // heuristic range, so fast exp2/log2 are fine.
+    // histogram range from the local density (hist_r2 over the block's `total` sources): buckets
+    // are uniform in r^2 over [0, 2.2 r^2)
     float scale;
     {
         const int bx = min(cx + 1, g.nx - 1) - max(cx - 1, 0) + 1;
@@ -116,12 +144,7 @@ __global__ __launch_bounds__(kWave, 4) void knn_cell_kernel(GridParams g, i64 ns
         if (g.ny > 1) { ++d; vol *= (float)by * (float)g.hy; }
         if (g.nz > 1) { ++d; vol *= (float)bz * (float)g.hz; }
         const float frac = (float)kout / (float)max(total, 1);
-        float r2;
-        if (d == 3) r2 = __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(frac * vol * (1.f / 4.18879f)) * (2.f / 3.f));
-        else if (d == 2) r2 = frac * vol * (1.f / 3.14159f);
-        else if (d == 1) { const float r = frac * vol * 0.5f; r2 = r * r; }
-        else r2 = 1.f;
-        scale = (float)kHistBuckets / (2.2f * r2);
+        scale = (float)kHistBuckets / (2.2f * hist_r2(d, frac * vol));
     }
     const bool cell_ok = runs_fit && total >= kout && total <= kTileCap && scale > 0.f && scale < INFINITY;
     if (!cell_ok) {
@@ -439,8 +462,7 @@ static_assert(kStripLayers * 9 <= kWave, "one lane stages one tile cell");
 // whose strip is too full are passed down).  2: a denser level -- the workgroups walk the list of the
 // strips that hold targets instead of being one workgroup per strip of the (mostly empty) grid.
 template <int K, int CAP, typename IDX, int MODE>
-__global__ __launch_bounds__(kWave, 4) void knn_strip_kernel(GridParams g, i64 nsrc,
-                                                             const int *__restrict__ cell_start,
+__global__ __launch_bounds__(kWave, 4) void knn_strip_kernel(GridParams g, const int *__restrict__ cell_start,
                                                              const double *__restrict__ sorted_xyz, int ndim,
                                                              int kout, const int *__restrict__ tstart,
                                                              const double *__restrict__ tsorted,
@@ -711,18 +733,13 @@ __global__ __launch_bounds__(kWave, 4) void knn_strip_kernel(GridParams g, i64 n
         const float tx = valid ? (float)(px - ox) : -1e30f, ty = (float)(py - oy), tz = (float)(pz - oz);
         const double E = 3.0 * kU * (fabs(px - ox) + fabs(py - oy) + fabs(pz - oz) + 2.0 * (g.hx + g.hy) +
                                      (double)(kStripZ + 1) * g.hz);
-        // histogram range from the density of the target's own window: the ball holding k of the
-        // window's sources has r^d = (k/count) * V_block / c_d; buckets are uniform in r^2 over
-        // [0, 2.2 r^2).  Only a heuristic range, so fast exp2/log2 are fine.
+        // histogram range from the density of the target's own window (hist_r2 over the window's
+        // sources): buckets are uniform in r^2 over [0, 2.2 r^2)
         float scale, width;
         {
             const float vol = g.nz > 1 ? vol_layer * (float)(l1 - l0) : vol_layer;
             const float frac = (float)kout / (float)max(we - ws, 1);
-            float r2;
-            if (dims == 3) r2 = __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(frac * vol * (1.f / 4.18879f)) * (2.f / 3.f));
-            else if (dims == 2) r2 = frac * vol * (1.f / 3.14159f);
-            else if (dims == 1) { const float r = frac * vol * 0.5f; r2 = r * r; }
-            else r2 = 1.f;
+            const float r2 = hist_r2(dims, frac * vol);
             // bucket width first (the division by the power-of-two bucket count is exact), the binning
             // factor is its correctly rounded reciprocal: 1/scale = width (1 +- 2u)
             width = 2.2f * r2 * (1.f / (float)kNB);
@@ -948,22 +965,8 @@ __global__ __launch_bounds__(kWave, 4) void knn_strip_kernel(GridParams g, i64 n
             // the compiler no longer combines the lanes' atomics itself)
             const bool push = valid && sl == 0 && hand_over;
             const bool push_down = push && too_dense && down_list != nullptr;
-            const unsigned long long lt = (1ull << lane) - 1ull;
-            const unsigned long long md = __ballot(push_down), mf = __ballot(push && !push_down);
-            if (md) {
-                const int first = __ffsll((long long)md) - 1;
-                int base = 0;
-                if (lane == first) base = atomicAdd(down_count, __popcll(md));
-                base = __shfl(base, first);
-                if (push_down) down_list[base + __popcll(md & lt)] = (int)i;
-            }
-            if (mf) {
-                const int first = __ffsll((long long)mf) - 1;
-                int base = 0;
-                if (lane == first) base = atomicAdd(fb_count, __popcll(mf));
-                base = __shfl(base, first);
-                if (push && !push_down) fb_list[base + __popcll(mf & lt)] = (int)i;
-            }
+            wave_append(down_list, down_count, push_down, (int)i);
+            wave_append(fb_list, fb_count, push && !push_down, (int)i);
         }
         wave_sync();  // before the next round clears the counters
     }

@@ -88,6 +88,21 @@ def list_mode_cloud(ntgt):
     return src, tgt, idx, knn_distances(src, tgt, idx)
 
 
+SPLIT_KS = (8, 25)
+STRIP_SPLIT_MIN = 192              # mm_knn.hip launch_fast: targets per strip from which nsplit = (n + 64) / 128 exceeds 1
+
+
+@functools.lru_cache(maxsize=None)
+def split_cloud():
+    """Many more targets than sources (about 800 per strip of two cells): the strip kernel shares a strip's targets
+    among several waves (nsplit > 1).  Targets reach past the sources' box; oracle for the longest k of SPLIT_KS."""
+    rng = np.random.default_rng(77)
+    src = rng.uniform(size=(2_000, 3))
+    tgt = rng.uniform(-0.1, 1.1, size=(100_000, 3))
+    idx = O.knn_ckdtree(src, tgt, max(SPLIT_KS), workers=WORKERS)[0]
+    return src, tgt, idx, knn_distances(src, tgt, idx)
+
+
 # ------------------------------------------------------------------------------------------------------------ hex8
 def no_accept_within(status, m):
     """Targets the oracle accepts in none of their first m candidates (fallback to the best one, or failed)."""

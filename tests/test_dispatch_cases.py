@@ -35,6 +35,15 @@ def test_knn_graded_and_list_mode_clouds():
     assert len(D.list_mode_cloud(5_000)[1]) < D.LIST_WAVE_MAX < len(D.list_mode_cloud(12_000)[1])
 
 
+def test_split_cloud_has_enough_targets_per_strip_for_several_waves():
+    src, tgt, idx, dist = D.split_cloud()
+    assert (np.diff(dist, axis=1) > 0).all()                 # one order: k = 8 is a slice of k = 25
+    assert (tgt < 0).any() and (tgt > 1).any()
+    # the launcher's formula at the default cell load: 8 sources per cell, two cells per strip, so nsrc / 16 strips;
+    # it shares a strip among nsplit = (targets per strip + 64) / 128 waves
+    assert 16 * len(tgt) / len(src) >= D.STRIP_SPLIT_MIN
+
+
 def test_knn_distances_are_the_in_order_sum():
     src = np.array([[0.0, 0.0, 0.0], [1.0, 2.0, 3.0]])
     tgt = np.array([[0.5, 0.5, 0.5]])

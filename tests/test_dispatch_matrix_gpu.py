@@ -102,6 +102,34 @@ def test_knn_every_k_forced_lane_strip_and_cell_kernels():
             assert set(range(21, 33)) <= ran.get("cell", set())
 
 
+_KNN_SPLIT = r"""
+import sys
+sys.path[:0] = [".", "tests"]
+import numpy as np
+import dispatch_cases as D
+from multimesh_amd.device import Context
+ctx = Context(0)
+src, tgt, ref, refd = D.split_cloud()
+tree = ctx.knn_build(src)
+for k in D.SPLIT_KS:
+    idx, dist = tree.query(tgt, k, want_dist=True)
+    assert "strip" in ctx.last_knn_kernels(), (k, sorted(ctx.last_knn_kernels()))
+    idx, dist = idx.numpy().reshape(len(tgt), k), dist.numpy().reshape(len(tgt), k)
+    assert np.array_equal(idx, ref[:, :k]), (k, int((idx != ref[:, :k]).any(axis=1).sum()))
+    assert np.array_equal(dist, refd[:, :k]), k
+print("split ok")
+"""
+
+
+def test_knn_strip_kernel_shares_a_strip_among_several_waves():
+    # ~800 targets per strip: the launcher gives every strip nsplit ~ 6 waves (tests/test_dispatch_cases.py checks the
+    # precondition); ids and distances bit-equal to the oracle, k = 8 (32 histogram buckets) and k = 25
+    env = dict(os.environ, MM_KNN_KERNEL="strip")
+    r = subprocess.run([sys.executable, "-c", _KNN_SPLIT], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
+    assert r.stdout.strip().splitlines()[-1] == "split ok"
+
+
 def test_knn_forced_list_mode_both_sides_of_8192(ctx, monkeypatch):
     monkeypatch.setenv("MM_KNN_FORCE_LIST", "1")
     ran = knn_sweep(ctx, ks=range(1, 33))

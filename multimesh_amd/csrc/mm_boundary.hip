@@ -43,7 +43,6 @@ namespace {
 using namespace mm_stream;   // kThreads, kWave
 typedef unsigned long long u64;
 constexpr i64 kMaxBlocks = 2048;           // 256 CUs x 8 workgroups; grid-stride beyond
-constexpr int kScanTileItems = 1024;       // mm_exclusive_scan_int's tile
 constexpr unsigned kNoSlot = 0xffffffffu;  // slot_of of a face with an id out of range
 constexpr int kSlot = 16, kWords = 8;      // the unit's words of mm_context::d_counters (mm_common.h)
 constexpr int kMaxDim = 1024;              // cells per axis of the cutoff grid
@@ -52,7 +51,6 @@ constexpr double kEdgeMargin = 1.0 + 0x1p-30;
 constexpr double kMinCutoff = 0x1p-500;
 
 unsigned stream_grid(i64 n) { return mm_blocks(n, kThreads, kMaxBlocks); }
-int scan_tiles(i64 n) { return (int)((n + 1 + kScanTileItems - 1) / kScanTileItems); }
 
 __device__ __forceinline__ bool is_finite(double v) { return fabs(v) < __builtin_inf(); }
 
@@ -433,7 +431,7 @@ extern "C" int64_t mm_boundary_faces(mm_context *ctx, const int64_t *corner_ids_
     lay.add(&slot_of, (size_t)nfaces);
     lay.add(&flag, (size_t)nfaces + 1);
     lay.add(&rank, (size_t)nfaces + 1);
-    lay.add(&tile_sums, (size_t)scan_tiles(nfaces));
+    lay.add(&tile_sums, mm_scan_scratch_ints(nfaces));
     int rc = lay.commit(ctx, __func__);
     if (rc != MM_OK) return rc;
     count = table + tsize;
@@ -510,7 +508,7 @@ extern "C" int64_t mm_boundary_nodes(mm_context *ctx, const double *points_d, in
     mm_scratch_layout lay;
     lay.add(&flag, (size_t)nb + 1);
     lay.add(&rank, (size_t)nb + 1);
-    lay.add(&tile_sums, (size_t)scan_tiles(nb));
+    lay.add(&tile_sums, mm_scan_scratch_ints(nb));
     int rc = lay.commit(ctx, __func__);
     if (rc != MM_OK) return rc;
     u64 *counters = mm_counters_begin(ctx, kSlot, 2);   // [0] bad codes or sides, [1] the selected faces
@@ -588,7 +586,7 @@ extern "C" int64_t mm_cutoff_distance(mm_context *ctx, const double *points_d, i
         lay.add(&cell_of, (size_t)K);
         lay.add(&count, (size_t)ncells + 1);
         lay.add(&start, (size_t)ncells + 1);
-        lay.add(&tile_sums, (size_t)scan_tiles(ncells));
+        lay.add(&tile_sums, mm_scan_scratch_ints(ncells));
         int rc = lay.commit(ctx, __func__);
         if (rc != MM_OK) return rc;
         if (mm_zero_async(ctx, count, (size_t)(ncells + 1) * sizeof(int)) != MM_OK) return MM_ERR_HIP;

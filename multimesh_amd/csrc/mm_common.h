@@ -278,9 +278,13 @@ int mm_launch_gather(mm_context *ctx, const double *fields, i64 nsrc, i64 ncomp,
                      const double *w, i64 npoints, i64 P, double *out, int out_point_major);
 // (mm_context.hip) the status mm_last_status reports back to MM_OK
 void mm_clear_status(void);
-// (mm_knn.hip) exclusive prefix sum of n ints on ctx->stream: start[0..n]; tile_sums: scratch of ceil(n / 1024) ints
+// (mm_scan.hip; device side: mm_scan.h) exclusive prefix sum of n ints on ctx->stream: start[0..n]; tile_sums: scratch of
+// mm_scan_scratch_ints(n) ints (with_total: one more, for the grand total mm_scan_launch_tile_offsets can write)
+size_t mm_scan_scratch_ints(i64 n, bool with_total = false);
 int mm_exclusive_scan_int(mm_context *ctx, const int *counts, i64 n, int *start, int *tile_sums);
-// (mm_unique.hip) the stable LSD radix sort of 64-bit keys with 32-bit values, and the bytes of scratch it asks for
+// (mm_radix_sort.hip) the stable LSD radix sort of 64-bit keys with 32-bit values: passes over the key bits [first_shift,
+// end_shift), 8 at a time, ping-pong between (ka, va) and (kb, vb); *in_a = the result lies in (ka, va).  scratch:
+// mm_radix_sort_scratch(n) bytes.
 size_t mm_radix_sort_scratch(i64 n);
 int mm_radix_sort_pairs(mm_context *ctx, unsigned long long *ka, unsigned long long *kb, unsigned *va, unsigned *vb, i64 n,
                         int first_shift, int end_shift, void *scratch, bool *in_a);

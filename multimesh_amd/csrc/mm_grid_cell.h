@@ -1,6 +1,7 @@
 // The search grid's cell arithmetic, the rank-handing histogram atomic and the 32-byte sorted record: what every kernel
 // that places a point into the grid must share to the bit -- the counting sorts of mm_knn.hip (mm_knn_grid.inc.h) and
-// the one-pass centroid kernel of mm_centroid.hip.  Device code only; nothing here may be re-derived elsewhere.
+// the one-pass centroid kernel of mm_centroid.hip; the GLL locate's visiting order (mm_locate_gll.hip) takes the
+// histogram atomic for its own bins.  Device code only; nothing here may be re-derived elsewhere.
 #pragma once
 
 #include "mm_common.h"

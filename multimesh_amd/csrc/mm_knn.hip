@@ -26,6 +26,7 @@
 
 #include "mm_common.h"
 #include "mm_grid_cell.h"
+#include "mm_scan.h"
 #include <cstring>
 
 namespace {
@@ -210,11 +211,11 @@ void launch_fast(mm_context *ctx, const mm_knn_index *ix, const GridParams &g, c
         // round 2's kernel: work items from the strips that hold targets, then one lane per target
         constexpr int KL = K <= kLaneMaxK ? K : 1;   // (the strip-only list lengths are never instantiated)
         const int per_item = kWave * kLaneRounds;
-        const int ntiles = (int)((lane->nstrips_total + kScanTile - 1) / kScanTile);
+        const int ntiles = mm_scan_tiles(lane->nstrips_total);
         if (!lane->items_kept) {
             hipLaunchKernelGGL(lane_items_sums_kernel, dim3(ntiles), dim3(kBlock), 0, ctx->stream, g, tstart, lane->Z, per_item,
                                lane->nstrips_total, lane->tile_sums, lane->items, lane->max_items);
-            hipLaunchKernelGGL(lane_items_offsets_kernel, dim3(1), dim3(kBlock), 0, ctx->stream, lane->tile_sums, ntiles);
+            mm_scan_launch_tile_offsets(ctx, lane->tile_sums, ntiles, true);
             hipLaunchKernelGGL(lane_items_place_kernel, dim3(ntiles), dim3(kBlock), 0, ctx->stream, g, tstart, lane->Z, per_item,
                                lane->nstrips_total, lane->tile_sums, ntiles, lane->items);
         }
@@ -334,35 +335,6 @@ using TreeOwner = std::unique_ptr<mm_knn_tree, TreeDeleter>;
 
 }  // namespace
 
-// Exclusive prefix sum of n ints on the context's stream: start[0..n] (start[n] = total).
-// tile_sums: scratch of ceil(n / 1024) ints.  Shared with the GLL locate's target ordering.
-// The scan behind scan_tile_sums_kernel: with few tiles every workgroup of the last kernel adds up the sums of the tiles
-// before its own by itself (at most kScanSelfTiles values, L2-resident) and the single-workgroup kernel in between -- a
-// dispatch of 5 us, thirty times per mm_unique_points -- is not launched; with many tiles the three-kernel form.
-// mirror_*: see scan_tile_offsets_kernel.
-static void launch_scan_tail(mm_context *ctx, const int *counts, i64 n, int *tile_sums, int ntiles, int *start,
-                             const long long *mirror_src = nullptr, long long *mirror_dst = nullptr, int mirror_n = 0)
-{
-    if (ntiles <= kScanSelfTiles) {
-        hipLaunchKernelGGL(scan_apply_self_kernel, dim3(ntiles), dim3(kBlock), 0, ctx->stream, counts, n, (const int *)tile_sums,
-                           start, mirror_src, mirror_dst, mirror_n);
-    } else {
-        hipLaunchKernelGGL(scan_tile_offsets_kernel, dim3(1), dim3(kBlock), 0, ctx->stream, tile_sums, ntiles, mirror_src,
-                           mirror_dst, mirror_n);
-        hipLaunchKernelGGL(scan_apply_kernel, dim3(ntiles), dim3(kBlock), 0, ctx->stream, counts, n, (const int *)tile_sums, start);
-    }
-}
-
-int mm_exclusive_scan_int(mm_context *ctx, const int *counts, i64 n, int *start, int *tile_sums)
-{
-    const int ntiles = (int)((n + kScanTile - 1) / kScanTile);
-    hipLaunchKernelGGL(scan_tile_sums_kernel, dim3(ntiles), dim3(kBlock), 0, ctx->stream, counts, n, tile_sums,
-                       (unsigned long long *)nullptr, 0);
-    launch_scan_tail(ctx, counts, n, tile_sums, ntiles, start);
-    MM_HIP_CHECK(hipGetLastError());
-    return MM_OK;
-}
-
 // One grid over the sources, laid out for ~per_cell sources per cell: counting sort of the sources by
 // cell into 32-byte records.  With level_extra != null the share of sources in well-filled cells is
 // read back (while the scan and the scatter are still queued, so a uniform cloud pays no idle time
@@ -430,16 +402,14 @@ static int sort_targets(mm_context *ctx, const GridParams &gl, i64 ncells, int n
                         double *tsorted, int *pos_out = nullptr)
 {
     const unsigned gpts = (unsigned)((npts + kBlock - 1) / kBlock);
-    const int ntiles = (int)((ncells + kScanTile - 1) / kScanTile);
     if (!list && ncells <= kHistCells && npts >= 64 * ncells)   // many targets over few cells (see the kernel)
         hipLaunchKernelGGL(cell_count_hist_kernel, dim3(256), dim3(kHistBlock), 0, ctx->stream, pts_d, npts, ndim, gl,
                            (int)ncells, cell_of, counts);
     else
         hipLaunchKernelGGL(cell_count_kernel, dim3(gpts), dim3(kBlock), 0, ctx->stream, pts_d, npts, ndim, gl, cell_of,
                            counts, list, list_count);
-    hipLaunchKernelGGL(scan_tile_sums_kernel, dim3(ntiles), dim3(kBlock), 0, ctx->stream, counts, ncells, tile_sums,
-                       (unsigned long long *)nullptr, 0);
-    launch_scan_tail(ctx, counts, ncells, tile_sums, ntiles, start);
+    const int rc = mm_exclusive_scan_int(ctx, counts, ncells, start, tile_sums);
+    if (rc != MM_OK) return rc;
     hipLaunchKernelGGL(target_scatter_kernel, dim3(gpts), dim3(kBlock), 0, ctx->stream, cell_of, npts, pts_d, ndim, gl,
                        start, tsorted, list, list_count, list ? (int *)nullptr : pos_out);
     MM_HIP_CHECK(hipGetLastError());
@@ -489,12 +459,11 @@ static int build_level(mm_context *ctx, const double *src_d, i64 nsrc, int ndim,
             return MM_ERR_ALLOC;
         }
     }
-    const int ntiles = (int)((ncells + kScanTile - 1) / kScanTile);
     int *cell_of, *counts, *tile_sums;
     mm_scratch_layout lay;
     lay.add(&cell_of, (size_t)(nsrc > 0 ? nsrc : 1));   // rank of every source in its cell
     lay.add(&counts, (size_t)(ncells + 1));
-    lay.add(&tile_sums, (size_t)ntiles);
+    lay.add(&tile_sums, mm_scan_scratch_ints(ncells));
     int rc = lay.commit(ctx, __func__);
     if (rc != MM_OK) return rc;
     // (whole 256-byte units -- the carve is rounded up to them --: an odd tail costs a second fill dispatch)
@@ -523,14 +492,12 @@ static int build_level(mm_context *ctx, const double *src_d, i64 nsrc, int ndim,
     // (slots kStatSlot .. +15 are the statistic's; bbox_final_kernel has cleared them for the
     // first grid of a build, a coarsened second one clears them here)
     if (want_stat && stat_dirty) e = hipMemsetAsync(stat, 0, 16 * sizeof(i64), ctx->stream);
-    if (e == hipSuccess)
-        hipLaunchKernelGGL(scan_tile_sums_kernel, dim3(ntiles), dim3(kBlock), 0, ctx->stream, counts, ncells, tile_sums,
-                           want_stat ? (unsigned long long *)stat : (unsigned long long *)nullptr, sample_shift);
     // (the scan's second kernel writes the statistic to the pinned mirror on its way; the host waits for it -- ev_misc --
     // only after the rest of the build is queued, or not at all: mm_knn_build_guessed)
-    launch_scan_tail(ctx, counts, ncells, tile_sums, ntiles, ix->cell_start,
-                     want_stat ? (const long long *)stat : (const long long *)nullptr,
-                     (long long *)(ctx->h_counters + kStatSlot), want_stat ? kMaxLevels : 0);
+    ScanMirror mirror;
+    if (want_stat) mirror = {(const long long *)stat, (long long *)(ctx->h_counters + kStatSlot), kMaxLevels};
+    mm_scan_launch(ctx, counts, ncells, ix->cell_start, tile_sums,
+                   GridStatHook{want_stat ? (unsigned long long *)stat : nullptr, sample_shift}, mirror);
     if (want_stat) {
         if (e == hipSuccess) e = hipEventRecord(ctx->ev_misc, ctx->stream);
         if (e != hipSuccess) {
@@ -944,7 +911,7 @@ struct TreeScratch {
         lay.add(&radix, mm_radix_sort_scratch(n));
         lay.add(&flag, n_sz + 1);
         lay.add(&rank, n_sz + 1);
-        lay.add(&scan_sums, (size_t)((n + 1 + kScanTile - 1) / kScanTile));
+        lay.add(&scan_sums, mm_scan_scratch_ints(n));
         lay.add(&items, n_sz + 1);
         lay.add(&fb_list, (size_t)npts);
         lay.add(&fb_count, 64);
@@ -1141,10 +1108,10 @@ static LaneWork choose_lane(const mm_context *ctx, const mm_knn_index *ix, i64 n
 static int lane_probe_readback(mm_context *ctx, const mm_knn_index *ix, const GridParams &gl, i64 npts, const int *start, LaneWork *lane)
 {
     const int per_item = kWave * kLaneRounds;
-    const int nt = (int)((lane->nstrips_total + kScanTile - 1) / kScanTile);
+    const int nt = mm_scan_tiles(lane->nstrips_total);
     hipLaunchKernelGGL(lane_items_sums_kernel, dim3(nt), dim3(kBlock), 0, ctx->stream, gl, start, lane->Z, per_item,
                        lane->nstrips_total, lane->tile_sums, lane->items, lane->max_items);
-    hipLaunchKernelGGL(lane_items_offsets_kernel, dim3(1), dim3(kBlock), 0, ctx->stream, lane->tile_sums, nt);
+    mm_scan_launch_tile_offsets(ctx, lane->tile_sums, nt, true);
     MM_HIP_CHECK(hipMemcpyAsync(ctx->h_counters + 2, lane->tile_sums + nt, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     const i64 items = (i64) * reinterpret_cast<const int *>(ctx->h_counters + 2);
@@ -1196,7 +1163,7 @@ struct LevelScratch {
         if (l->fine) lay.add(&down_list, (size_t)npts);
         if (level > 0) lay.add(&counts, (size_t)(l->ncells + 1));
         if (!kept) lay.add(&start, (size_t)(l->ncells + 1));
-        if (!replay) lay.add(&tile_sums, (size_t)((l->ncells + kScanTile - 1) / kScanTile));
+        if (!replay) lay.add(&tile_sums, mm_scan_scratch_ints(l->ncells));
         if (level > 0 || have_list) lay.add(&strip_list, (size_t)npts);
         if (!sorted_rows) lay.add(&tsorted, (size_t)npts * kRec);
     }
@@ -1312,7 +1279,7 @@ static int knn_query_typed(mm_context *ctx, const mm_knn_index *ix, const double
     lay.add(&fb_count, counter_ints);
     if (!keep.replay) lay.add(&lvs[0].counts, (size_t)(ix->ncells + 1));
     if (lane.use_lane) {
-        if (!keep.replay) lay.add(&lane.tile_sums, (size_t)((lane.nstrips_total + kScanTile) / kScanTile + 2));
+        if (!keep.replay) lay.add(&lane.tile_sums, mm_scan_scratch_ints(lane.nstrips_total, true));
         if (!keep_sort) lay.add(&lane.items, (size_t)lane.max_items);
     }
     if (!kn.force_list) {

@@ -212,51 +212,20 @@ __global__ __launch_bounds__(kHistBlock) void cell_count_hist_kernel(const doubl
     }
 }
 
-// ---- exclusive scan of the per-cell counts (three small kernels) --------------------
-constexpr int kScanItems = 4;                       // items per thread
-constexpr int kScanTile = kBlock * kScanItems;      // items per block
-
-__device__ __forceinline__ int block_exclusive_scan(int v, int *total)
-{
-    __shared__ int wave_sums[kBlock / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(incl, off);
-        if (lane >= off) incl += t;
-    }
-    if (lane == 63) wave_sums[wave] = incl;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int wv = 0; wv < kBlock / 64; ++wv) {
-        if (wv < wave) base += wave_sums[wv];
-        tot += wave_sums[wv];
-    }
-    __syncthreads();
-    *total = tot;
-    return base + incl - v;
-}
-
-// First kernel of the scan: per-tile sums.  With `level_total` it also accumulates the grid statistic of the build
-// from the counts it reads anyway (no kernel of its own):
+// ---- exclusive scan of the per-cell counts: mm_scan.h.  The build's scan carries this hook in its first kernel, which
+// accumulates the grid statistic from the counts it reads anyway (no kernel of its own; nothing with a null level_total):
 //   level_total[b] += the counts of the cells holding more than kLevelCount[b] sources (density levels);
 //   level_total[kMaxLevels - 1] += the counts of the cells holding at most kSparseCount sources, from every
 //   2^sample_shift-th run of 256 cells only (an estimate that steers a heuristic: nearly every wave of a uniform
 //   cloud has such a cell, and 17 k atomics on one address are 0.1 ms).
-__global__ __launch_bounds__(kBlock) void scan_tile_sums_kernel(const int *__restrict__ counts, i64 n,
-                                                                int *__restrict__ tile_sums,
-                                                                unsigned long long *__restrict__ level_total,
-                                                                int sample_shift)
-{
-    const i64 base = (i64)blockIdx.x * kScanTile + (i64)threadIdx.x * kScanItems;
-    int v[kScanItems];
-    int s = 0;
-#pragma unroll
-    for (int i = 0; i < kScanItems; ++i) {
-        v[i] = base + i < n ? counts[base + i] : 0;
-        s += v[i];
-    }
-    if (level_total) {
+static_assert(kBlock == kScanBlock, "the lane work list's kernels are launched as scan workgroups");
+struct GridStatHook {
+    unsigned long long *level_total;
+    int sample_shift;
+
+    __device__ __forceinline__ void operator()(const int (&v)[kScanItems]) const
+    {
+        if (!level_total) return;
         // (a wave holds one run of 256 consecutive cells: kScanItems = 4 per lane)
         static_assert(kScanItems * 64 == 256, "the sparse share is sampled per run of 256 cells");
         const unsigned run = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
@@ -265,7 +234,7 @@ __global__ __launch_bounds__(kBlock) void scan_tile_sums_kernel(const int *__res
 #pragma unroll
             for (int i = 0; i < kScanItems; ++i) w += v[i] <= kSparseCount ? v[i] : 0;
             if (__any(w > 0)) {
-                for (int off = 32; off > 0; off >>= 1) w += __shfl_down(w, off);
+                w = wave_sum(w);
                 if ((threadIdx.x & 63) == 0 && w > 0) atomicAdd(level_total + (kMaxLevels - 1), (unsigned long long)w);
             }
         }
@@ -280,96 +249,14 @@ __global__ __launch_bounds__(kBlock) void scan_tile_sums_kernel(const int *__res
 #pragma unroll
             for (int i = 0; i < kScanItems; ++i) w += v[i] > kLevelCount[b] ? v[i] : 0;
             if (!__any(w > 0)) break;   // thresholds ascend
-            for (int off = 32; off > 0; off >>= 1) w += __shfl_down(w, off);
+            w = wave_sum(w);
             if ((threadIdx.x & 63) == 0 && w > 0) atomicAdd(&s_bin[b], (unsigned)w);
         }
         __syncthreads();
         if (threadIdx.x < kMaxLevels - 1 && s_bin[threadIdx.x] > 0u)
             atomicAdd(level_total + threadIdx.x, (unsigned long long)s_bin[threadIdx.x]);
     }
-    int total;
-    (void)block_exclusive_scan(s, &total);
-    if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
-}
-
-// mirror_src / mirror_dst (nullable): mirror_n 64-bit words copied on the way from device memory to the context's
-// PINNED host mirror -- the grid statistic the kernel before this one accumulated (a copy command of the runtime's costs a
-// dispatch of 4 us behind a 6 us gap)
-__global__ __launch_bounds__(kBlock) void scan_tile_offsets_kernel(int *__restrict__ tile_sums, int ntiles,
-                                                                    const long long *__restrict__ mirror_src = nullptr,
-                                                                    long long *__restrict__ mirror_dst = nullptr,
-                                                                    int mirror_n = 0)
-{
-    if (mirror_src && (int)threadIdx.x < mirror_n) mirror_dst[threadIdx.x] = mirror_src[threadIdx.x];
-    // single block: running exclusive scan over the tile sums
-    __shared__ int carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < ntiles; base += kBlock) {
-        const int i = base + threadIdx.x;
-        const int v = i < ntiles ? tile_sums[i] : 0;
-        int total;
-        const int excl = block_exclusive_scan(v, &total);
-        const int c = carry;
-        if (i < ntiles) tile_sums[i] = c + excl;
-        __syncthreads();
-        if (threadIdx.x == 0) carry = c + total;
-        __syncthreads();
-    }
-}
-
-// scan_apply_kernel for few tiles, straight behind scan_tile_sums_kernel: the workgroup sums the tiles before its own
-// itself (tile_sums are the RAW sums here)
-constexpr int kScanSelfTiles = 2048;
-__global__ __launch_bounds__(kBlock) void scan_apply_self_kernel(const int *__restrict__ counts, i64 n,
-                                                                 const int *__restrict__ tile_sums,
-                                                                 int *__restrict__ start,
-                                                                 const long long *__restrict__ mirror_src,
-                                                                 long long *__restrict__ mirror_dst, int mirror_n)
-{
-    if (mirror_src && blockIdx.x == 0 && (int)threadIdx.x < mirror_n) mirror_dst[threadIdx.x] = mirror_src[threadIdx.x];
-    int before = 0;
-    for (int t = threadIdx.x; t < (int)blockIdx.x; t += kBlock) before += tile_sums[t];
-    int tile_base;
-    (void)block_exclusive_scan(before, &tile_base);
-    const i64 base = (i64)blockIdx.x * kScanTile + (i64)threadIdx.x * kScanItems;
-    int v[kScanItems];
-    int s = 0;
-    for (int i = 0; i < kScanItems; ++i) {
-        v[i] = base + i < n ? counts[base + i] : 0;
-        s += v[i];
-    }
-    int total;
-    int excl = block_exclusive_scan(s, &total) + tile_base;
-    for (int i = 0; i < kScanItems; ++i) {
-        if (base + i < n) start[base + i] = excl;
-        excl += v[i];
-    }
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == kBlock - 1) start[n] = excl;   // the total number of items
-}
-
-__global__ __launch_bounds__(kBlock) void scan_apply_kernel(const int *__restrict__ counts, i64 n,
-                                                            const int *__restrict__ tile_offsets,
-                                                            int *__restrict__ start)
-{
-    const i64 base = (i64)blockIdx.x * kScanTile + (i64)threadIdx.x * kScanItems;
-    int v[kScanItems];
-    int s = 0;
-    for (int i = 0; i < kScanItems; ++i) {
-        v[i] = base + i < n ? counts[base + i] : 0;
-        s += v[i];
-    }
-    int total;
-    int excl = block_exclusive_scan(s, &total) + tile_offsets[blockIdx.x];
-    for (int i = 0; i < kScanItems; ++i) {
-        if (base + i < n) {
-            start[base + i] = excl;
-        }
-        excl += v[i];
-    }
-    // start[n] = total number of items
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == kBlock - 1) start[n] = excl;
-}
+};
 
 __global__ __launch_bounds__(kBlock) void cell_scatter_kernel(const double *__restrict__ src, i64 nsrc, int ndim,
                                                               GridParams g, const int *__restrict__ rank_of,
@@ -389,16 +276,6 @@ constexpr int kHistBuckets = 64;
 constexpr int kTileCap = 256;       // sources per tile (27 cells x ~8 expected)
 constexpr int kMaxGroups = 8;       // targets per round at the narrowest split (S = 8)
 constexpr int kSlots = kTileCap / kMaxGroups;  // tile entries per lane at the narrowest split
-
-// inclusive prefix sum inside groups of S consecutive lanes (S a power of two)
-__device__ __forceinline__ int group_scan(int v, int sl, int S)
-{
-    for (int d = 1; d < S; d <<= 1) {
-        const int t = __shfl_up(v, d, S);
-        if (sl >= d) v += t;
-    }
-    return v;
-}
 
 // The fast kernel's workgroup is ONE wave: its LDS accesses are served in program order by the LDS
 // queue, so a later read sees an earlier write/atomic of any lane without waiting or s_barrier.  All

@@ -68,39 +68,6 @@ __device__ unsigned long long g_lane_stamps[kStampSlots * 8];   // per workgroup
 #else
 #define MM_STAMP(n) do { } while (0)
 #endif
-// Wave-wide inclusive prefix sum / maximum with DPP moves (row_shr 1, 2, 4, 8 inside the rows of 16 lanes, then the
-// row broadcasts 15 and 31): six VALU instructions with a few cycles of latency each, where __shfl_up is a
-// ds_bpermute through the LDS crossbar (~100 cycles each, six of them dependent).
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ int dpp_from(int v, int fill)
-{
-    // lanes without a source lane (shifted in from outside the row / rows not in ROW_MASK) read `fill`
-    return __builtin_amdgcn_update_dpp(fill, v, CTRL, ROW_MASK, 0xF, false);
-}
-
-__device__ __forceinline__ int wave_inclusive_sum(int v)
-{
-    v += dpp_from<0x111, 0xF>(v, 0);   // row_shr:1
-    v += dpp_from<0x112, 0xF>(v, 0);   // row_shr:2
-    v += dpp_from<0x114, 0xF>(v, 0);   // row_shr:4
-    v += dpp_from<0x118, 0xF>(v, 0);   // row_shr:8
-    v += dpp_from<0x142, 0xA>(v, 0);   // row_bcast:15 -> rows 1 and 3
-    v += dpp_from<0x143, 0xC>(v, 0);   // row_bcast:31 -> rows 2 and 3
-    return v;
-}
-
-// maximum over the wave of non-negative values (every lane's result is only meaningful in lane 63: read it there)
-__device__ __forceinline__ int wave_max_nonneg(int v)
-{
-    v = max(v, dpp_from<0x111, 0xF>(v, 0));
-    v = max(v, dpp_from<0x112, 0xF>(v, 0));
-    v = max(v, dpp_from<0x114, 0xF>(v, 0));
-    v = max(v, dpp_from<0x118, 0xF>(v, 0));
-    v = max(v, dpp_from<0x142, 0xA>(v, 0));
-    v = max(v, dpp_from<0x143, 0xC>(v, 0));
-    return __builtin_amdgcn_readlane(v, 63);
-}
-
 // Item q of the list (strips in spatial order) is stored at slot 8 m + x, x = the eighth of the list it lies in,
 // m = its place inside that eighth: workgroup b of the lane kernel simply takes slot b -- workgroups are dealt
 // round-robin over the 8 XCDs, so XCD x walks the x-th eighth of the list, a contiguous piece of space (its L2
@@ -119,67 +86,39 @@ __device__ __forceinline__ int lane_strip_parts(const GridParams &g, const int *
     return (tn + per_item - 1) / per_item;
 }
 
-// (1) per tile of kScanTile strips: the number of items; every slot of the list is pre-set to "no item" on the way
+// (1) per tile of kScanTile strips (the scan's tile, mm_scan.h): the number of items; every slot of the list is pre-set
+// to "no item" on the way
 __global__ __launch_bounds__(kBlock) void lane_items_sums_kernel(GridParams g, const int *__restrict__ tstart, int Z,
                                                                  int per_item, i64 nstrips_total, int *__restrict__ tile_sums,
                                                                  int2 *__restrict__ items, i64 nslots)
 {
-    const i64 base = (i64)blockIdx.x * kScanTile + (i64)threadIdx.x * kScanItems;
-    int sum = 0;
-    for (int q = 0; q < kScanItems; ++q) sum += lane_strip_parts(g, tstart, Z, per_item, base + q, nstrips_total);
-    int total;
-    (void)block_exclusive_scan(sum, &total);
-    if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
+    const ScanTile t = scan_tile_load([&](i64 s) { return lane_strip_parts(g, tstart, Z, per_item, s, nstrips_total); });
+    scan_tile_sum_store(t.sum, tile_sums);
     for (i64 q = (i64)blockIdx.x * blockDim.x + threadIdx.x; q < nslots; q += (i64)gridDim.x * blockDim.x)
         items[q] = make_int2(-1, -1);
 }
 
-// (2) single block: exclusive scan of the tile sums, the grand total behind them
-__global__ __launch_bounds__(kBlock) void lane_items_offsets_kernel(int *__restrict__ tile_sums, int ntiles)
-{
-    __shared__ int carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < ntiles; base += kBlock) {
-        const int i = base + threadIdx.x;
-        const int v = i < ntiles ? tile_sums[i] : 0;
-        int total;
-        const int excl = block_exclusive_scan(v, &total);
-        const int c = carry;
-        if (i < ntiles) tile_sums[i] = c + excl;
-        __syncthreads();
-        if (threadIdx.x == 0) carry = c + total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) tile_sums[ntiles] = carry;
-}
-
+// (2) mm_scan_launch_tile_offsets with the total: exclusive scan of the tile sums, the grand total behind them
 // (3) every strip's items into their slots (the slot rule above)
 __global__ __launch_bounds__(kBlock) void lane_items_place_kernel(GridParams g, const int *__restrict__ tstart, int Z,
                                                                   int per_item, i64 nstrips_total,
                                                                   const int *__restrict__ tile_sums, int ntiles,
                                                                   int2 *__restrict__ items)
 {
-    const i64 base = (i64)blockIdx.x * kScanTile + (i64)threadIdx.x * kScanItems;
-    int np[kScanItems];
-    int sum = 0;
-    for (int q = 0; q < kScanItems; ++q) {
-        np[q] = lane_strip_parts(g, tstart, Z, per_item, base + q, nstrips_total);
-        sum += np[q];
-    }
+    const ScanTile t = scan_tile_load([&](i64 s) { return lane_strip_parts(g, tstart, Z, per_item, s, nstrips_total); });
     int block_total;
-    int a = block_exclusive_scan(sum, &block_total) + tile_sums[blockIdx.x];
+    int a = block_exclusive_scan(t.sum, &block_total) + tile_sums[blockIdx.x];
     const i64 total = tile_sums[ntiles];
     for (int q = 0; q < kScanItems; ++q) {
-        for (int part = 0; part < np[q]; ++part) {
+        for (int part = 0; part < t.v[q]; ++part) {
             const i64 it = (i64)a + part;
             int x = (int)((it * 8) / total);
             while (x > 0 && it < ((total * x) >> 3)) --x;
             while (x < 7 && it >= ((total * (x + 1)) >> 3)) ++x;
             const i64 m = it - ((total * x) >> 3);
-            items[8 * m + x] = make_int2((int)(base + q), part);
+            items[8 * m + x] = make_int2((int)(t.base + q), part);
         }
-        a += np[q];
+        a += t.v[q];
     }
 }
 

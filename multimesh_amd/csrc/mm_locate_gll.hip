@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "mm_common.h"
+#include "mm_grid_cell.h"
 #include "mm_newton_hex8.h"
 
 namespace {
@@ -982,22 +983,9 @@ __global__ __launch_bounds__(256) void gll_key_kernel(i64 k, i64 npoints, const 
         const i64 e = (i64)nn[t * k];
         key = (unsigned long long)e < (unsigned long long)nelem ? (int)e : (int)nelem;  // invalid -> last bin
     }
-    // targets in mesh order arrive in runs with the same first candidate, and same-address atomics
-    // serialise in L2: one atomic per run inside the wave (as in the kNN stage's cell_count_kernel)
-    const int lane = threadIdx.x & 63;
-    const int prev = __shfl_up(key, 1);
-    const bool head = lane == 0 || key != prev;
-    const unsigned long long heads = __ballot(head);
-    const unsigned long long upto = heads & (~0ull >> (63 - lane));
-    const int head_lane = 63 - __clzll((long long)upto);
-    const unsigned long long after = lane == 63 ? 0ull : heads & (~0ull << (lane + 1));
-    int base = 0;
-    if (head && live) {
-        const int next_head = after ? __ffsll((long long)after) - 1 : 64;
-        base = atomicAdd(&counts[key], next_head - lane);
-    }
-    base = __shfl(base, head_lane);
-    if (live) key_rank[t] = make_int2(key, base + (lane - head_lane));
+    // (targets in mesh order arrive in runs with the same first candidate: one atomic per run inside the wave)
+    const int rank = count_and_rank(key, live, counts);
+    if (live) key_rank[t] = make_int2(key, rank);
 }
 
 __global__ __launch_bounds__(256) void gll_order_kernel(i64 npoints, const int2 *__restrict__ key_rank,
@@ -1041,7 +1029,7 @@ struct GllVisit {
         lay.add(&ord, (size_t)npoints);
         lay.add(&counts, (size_t)(nbins + 1));
         lay.add(&start, (size_t)(nbins + 1));
-        lay.add(&tile_sums, (size_t)((nbins + 1023) / 1024));
+        lay.add(&tile_sums, mm_scan_scratch_ints(nbins));
     }
     template <typename IDX>
     int run(mm_context *ctx, const IDX *nn, const int **visit) const

@@ -162,8 +162,7 @@ __global__ __launch_bounds__(kThreads) void idw_gather_kernel(const IdwArgs a)
         if (a.nused) a.nused[i] = m;
     }
     // one integer atomic per workgroup
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) outside += __shfl_down(outside, off, kWave);
+    outside = wave_sum(outside);
     if ((threadIdx.x & (kWave - 1)) == 0) s_count[threadIdx.x / kWave] = outside;
     __syncthreads();
     if (threadIdx.x == 0) {

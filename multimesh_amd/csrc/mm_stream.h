@@ -6,6 +6,7 @@
 #pragma once
 
 #include "mm_common.h"
+#include "mm_scan.h"
 
 namespace mm_stream {
 constexpr int kThreads = 256;               // lanes of a workgroup
@@ -28,8 +29,7 @@ inline unsigned mm_blocks(i64 n, i64 per_block, i64 cap)
 // wave calls it.
 __device__ __forceinline__ void mm_count_to(unsigned long long *counter, unsigned mine)
 {
-#pragma unroll
-    for (int off = mm_stream::kWave / 2; off > 0; off >>= 1) mine += __shfl_down(mine, off, mm_stream::kWave);
+    mine = wave_sum(mine);
     if ((threadIdx.x & (mm_stream::kWave - 1)) == 0 && mine != 0) atomicAdd(counter, (unsigned long long)mine);
 }
 

@@ -11,7 +11,7 @@
 //                the n with elem[n] == e, ascending n; rows with elem[n] == -1 are skipped.
 // No float atomics and no reordering anywhere: the result is the same on every run.
 //
-// How.  create groups the contributions by destination ONCE: a stable LSD radix sort (mm_radix_sort_pairs, mm_unique.hip)
+// How.  create groups the contributions by destination ONCE: a stable LSD radix sort (mm_radix_sort_pairs, mm_radix_sort.hip)
 // of (destination, flat index), only the passes the destination count needs; stability keeps the flat indices of a
 // destination ascending.  Row offsets are a bisection of the sorted keys per destination.  The node form then stores the
 // weights and the target index of every contribution in destination order (8 + 4 bytes per contribution, 4 bytes per

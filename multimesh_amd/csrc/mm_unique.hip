@@ -15,11 +15,9 @@
 // are short runs of rows with bit-equal x (the 2 / 4 / 8 copies of a face / edge / corner node), put in
 // (y, z, index) order by the thread that finds the run's head.  A cloud with long runs (an unjittered
 // structured mesh: x takes n values, runs of n^2 rows) is detected by that same kernel and redone as dim
-// stable sorts, least significant coordinate first.  The sort is a hand-written LSD radix sort, 8 bits a
-// pass (radix_hist_kernel -> exclusive scan of the [digit][tile] counts -> radix_scatter_kernel); a
-// workgroup ranks its tile of 4096 keys in order -- per wave and batch of 64 keys: the lanes with the same
-// digit by eight ballots, their rank by a popcount, the wave's running offsets of the 256 digits in LDS --
-// so the scatter is stable.  Then head flags / prefix sum / scatter of the unique rows and the inverse.
+// stable sorts, least significant coordinate first.  The sort is the library's LSD radix sort
+// (mm_radix_sort_pairs, mm_radix_sort.hip).  Then head flags / prefix sum (mm_exclusive_scan_int,
+// mm_scan.hip) / scatter of the unique rows and the inverse.
 #include <algorithm>
 #include <cstring>
 #include <stdlib.h>
@@ -30,18 +28,11 @@
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kScanTileItems = 1024;  // items per block of mm_exclusive_scan_int
-constexpr int kWave = 64;
-constexpr int kBins = 256;            // 8 bits a pass
 // The main sort of mm_unique_points orders the rows by the top 64 - kKeyLowBits bits of x's sortable image (sign, exponent,
 // 36 bits of mantissa: six passes instead of eight); rows that agree in those bits form a "run" whatever the rest of x says,
 // and the runs are put in full (x, y, z, index) order afterwards -- as the runs of bit-equal x (shared nodes) always were.
 // Two different x within 1.5e-11 of each other (relative) merely share a run.
 constexpr int kKeyLowBits = 16;
-constexpr int kSortWaves = 4;
-constexpr int kSortBlock = kSortWaves * kWave;
-constexpr int kItems = 16;            // keys per thread: batches of 64 consecutive keys per wave
-constexpr int kTile = kSortBlock * kItems;
 constexpr int kMaxRun = 32;           // longest run of equal x the fix-up kernel sorts in place
 constexpr int kMaxLongRuns = 4096;    // longer runs handled as a sub-sort; more of them: the general path
 
@@ -67,135 +58,6 @@ __global__ __launch_bounds__(kBlock) void key_kernel(const double *__restrict__ 
 {
     const i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     if (j < n) key[j] = sortable(pts[(i64)order[j] * dim + comp]);
-}
-
-// ---- LSD radix sort, one pass = hist -> scan -> scatter ------------------------------------------
-// counts[digit * ntiles + tile]: in that order the exclusive scan is the output offset of the tile's first
-// key with that digit
-__global__ __launch_bounds__(kSortBlock) void radix_hist_kernel(const u64 *__restrict__ key, i64 n, int shift, int ntiles,
-                                                                int *__restrict__ counts)
-{
-    __shared__ int s_hist[kBins];
-    for (int t = threadIdx.x; t < kBins; t += kSortBlock) s_hist[t] = 0;
-    __syncthreads();
-    const i64 base = (i64)blockIdx.x * kTile;
-#pragma unroll 4
-    for (int b = 0; b < kItems; ++b) {
-        const i64 j = base + (i64)b * kSortBlock + threadIdx.x;   // (any order: this is only a count)
-        if (j < n) atomicAdd(&s_hist[(int)((key[j] >> shift) & (kBins - 1))], 1);
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < kBins; t += kSortBlock) counts[(i64)t * ntiles + blockIdx.x] = s_hist[t];
-}
-
-__global__ __launch_bounds__(kSortBlock) void radix_scatter_kernel(const u64 *__restrict__ key_in,
-                                                                   const unsigned *__restrict__ val_in, i64 n, int shift,
-                                                                   int ntiles, const int *__restrict__ offsets,
-                                                                   u64 *__restrict__ key_out,
-                                                                   unsigned *__restrict__ val_out)
-{
-    // The tile is first put in digit order in LDS (stable), then written out: consecutive threads write
-    // consecutive addresses inside a digit's run (~16 keys = 128 bytes at 256 digits per 4096 keys) -- scattering
-    // straight from registers costs a cache line per 8-byte key in the passes over the mantissa's random bits.
-    __shared__ u64 s_key[kTile];
-    __shared__ unsigned s_val[kTile];
-    __shared__ int s_off[kSortWaves][kBins];   // first the waves' digit counts, then their running positions in the tile
-    __shared__ int s_start[kBins];             // where a digit's run starts in the sorted tile
-    __shared__ int s_gbase[kBins];             // ... and in the output
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-    for (int t = threadIdx.x; t < kSortWaves * kBins; t += kSortBlock) (&s_off[0][0])[t] = 0;
-    __syncthreads();
-    // wave w owns keys [w * 1024, (w + 1) * 1024) of the tile, batch b = 64 consecutive keys: batch order, then
-    // lane order, is the input order
-    const i64 tbase = (i64)blockIdx.x * kTile;
-    const i64 wbase = tbase + (i64)wave * (kItems * kWave);
-    u64 k[kItems];
-    unsigned v[kItems];
-#pragma unroll
-    for (int b = 0; b < kItems; ++b) {
-        const i64 j = wbase + b * kWave + lane;
-        k[b] = j < n ? key_in[j] : 0;
-        v[b] = j < n ? val_in[j] : 0;
-        if (j < n) atomicAdd(&s_off[wave][(int)((k[b] >> shift) & (kBins - 1))], 1);
-    }
-    __syncthreads();
-    // digit t (one thread each): its count in the tile; exclusive prefix over the digits by the first wave
-    int total = 0;
-    if (threadIdx.x < kBins) {
-#pragma unroll
-        for (int w = 0; w < kSortWaves; ++w) total += s_off[w][threadIdx.x];
-        s_start[threadIdx.x] = total;
-        s_gbase[threadIdx.x] = offsets[(i64)threadIdx.x * ntiles + blockIdx.x];
-    }
-    __syncthreads();
-    if (wave == 0) {
-        // 256 counts, four per lane
-        int c[4], sum = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            c[q] = s_start[4 * lane + q];
-            sum += c[q];
-        }
-        int incl = sum;
-        for (int dlt = 1; dlt < kWave; dlt <<= 1) {
-            const int t = __shfl_up(incl, dlt);
-            if (lane >= dlt) incl += t;
-        }
-        int run = incl - sum;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            s_start[4 * lane + q] = run;
-            run += c[q];
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < kBins) {
-        int run = s_start[threadIdx.x];
-#pragma unroll
-        for (int w = 0; w < kSortWaves; ++w) {
-            const int c = s_off[w][threadIdx.x];
-            s_off[w][threadIdx.x] = run;
-            run += c;
-        }
-    }
-    __syncthreads();
-    const u64 lt = (1ull << lane) - 1ull;
-#pragma unroll
-    for (int b = 0; b < kItems; ++b) {
-        const i64 j = wbase + b * kWave + lane;
-        const bool active = j < n;
-        const int d = (int)((k[b] >> shift) & (kBins - 1));
-        // the lanes of this batch that hold the same digit
-        u64 same = __ballot(active);
-#pragma unroll
-        for (int bit = 0; bit < 8; ++bit) {
-            const u64 vote = __ballot((d >> bit) & 1);
-            same &= ((d >> bit) & 1) ? vote : ~vote;
-        }
-        const int rank = __popcll(same & lt);
-        const int off = active ? s_off[wave][d] : 0;   // (read by every lane of the group before its head moves it on)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (active && rank == 0) s_off[wave][d] = off + __popcll(same);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (active) {
-            s_key[off + rank] = k[b];
-            s_val[off + rank] = v[b];
-        }
-    }
-    __syncthreads();
-    const int valid = (int)(n - tbase < kTile ? n - tbase : kTile);
-#pragma unroll 4
-    for (int t = threadIdx.x; t < valid; t += kSortBlock) {
-        const u64 key = s_key[t];
-        const int d = (int)((key >> shift) & (kBins - 1));
-        const i64 pos = (i64)s_gbase[d] + (t - s_start[d]);
-        key_out[pos] = key;
-        val_out[pos] = s_val[t];
-    }
 }
 
 // Runs of bit-equal keys in the sorted order: the thread at a run's head puts its rows in (y, z, index)
@@ -304,48 +166,6 @@ __global__ __launch_bounds__(kBlock) void emit_kernel(const double *__restrict__
 
 }  // namespace
 
-// The sort above for other callers (the kNN tree's Morton keys): stable LSD passes over the key bits [first_shift,
-// end_shift), 8 at a time, ping-pong between (ka, va) and (kb, vb); *in_a = the result lies in (ka, va).  scratch:
-// mm_radix_sort_scratch(n) bytes.
-size_t mm_radix_sort_scratch(i64 n)
-{
-    const i64 tiles = (n + kTile - 1) / kTile;
-    const i64 ncounts = (i64)kBins * tiles;
-    const i64 count_tiles = (ncounts + 1 + kScanTileItems - 1) / kScanTileItems;
-    return 2 * mm_round256((size_t)(ncounts + 1) * sizeof(int)) + mm_round256((size_t)count_tiles * sizeof(int));
-}
-
-int mm_radix_sort_pairs(mm_context *ctx, unsigned long long *ka, unsigned long long *kb, unsigned *va, unsigned *vb, i64 n,
-                        int first_shift, int end_shift, void *scratch, bool *in_a)
-{
-    *in_a = true;
-    if (n <= 0) return MM_OK;
-    const int tiles = (int)((n + kTile - 1) / kTile);
-    const i64 ncounts = (i64)kBins * tiles;
-    char *sp = (char *)scratch;
-    int *counts = (int *)sp;
-    sp += mm_round256((size_t)(ncounts + 1) * sizeof(int));
-    int *offsets = (int *)sp;
-    sp += mm_round256((size_t)(ncounts + 1) * sizeof(int));
-    int *count_sums = (int *)sp;
-    for (int shift = first_shift; shift < end_shift; shift += 8) {
-        hipLaunchKernelGGL(radix_hist_kernel, dim3((unsigned)tiles), dim3(kSortBlock), 0, ctx->stream, ka, n, shift, tiles, counts);
-        const int src = mm_exclusive_scan_int(ctx, counts, ncounts, offsets, count_sums);
-        if (src != MM_OK) return src;
-        hipLaunchKernelGGL(radix_scatter_kernel, dim3((unsigned)tiles), dim3(kSortBlock), 0, ctx->stream, ka, va, n, shift, tiles,
-                           offsets, kb, vb);
-        u64 *tk = ka;
-        ka = kb;
-        kb = tk;
-        unsigned *tv = va;
-        va = vb;
-        vb = tv;
-        *in_a = !*in_a;
-    }
-    MM_HIP_CHECK(hipGetLastError());
-    return MM_OK;
-}
-
 extern "C" int64_t mm_unique_points(mm_context *ctx, const double *points_d, int64_t npoints, int64_t dim,
                                     double *unique_d, int64_t *inverse_d)
 {
@@ -358,13 +178,10 @@ extern "C" int64_t mm_unique_points(mm_context *ctx, const double *points_d, int
     const i64 n = npoints;
     const size_t n_sz = (size_t)n;
 
-    const int ntiles = (int)((n + 1 + kScanTileItems - 1) / kScanTileItems);
-    const int sort_tiles = (int)((n + kTile - 1) / kTile);
-    const i64 ncounts = (i64)kBins * sort_tiles;
-    const int count_tiles = (int)((ncounts + 1 + kScanTileItems - 1) / kScanTileItems);
     u64 *key_a, *key_b;
     unsigned *ord_a, *ord_b, *sub_a, *sub_b;
-    int *head, *before, *tile_sums, *counts, *offsets, *count_sums, *long_runs;
+    int *head, *before, *tile_sums, *long_runs;
+    void *radix;
     mm_scratch_layout lay;
     lay.add(&key_a, n_sz);
     lay.add(&key_b, n_sz);
@@ -372,10 +189,8 @@ extern "C" int64_t mm_unique_points(mm_context *ctx, const double *points_d, int
     lay.add(&ord_b, n_sz);
     lay.add(&head, n_sz + 1);
     lay.add(&before, n_sz + 1);
-    lay.add(&tile_sums, (size_t)ntiles);
-    lay.add(&counts, (size_t)(ncounts + 1));
-    lay.add(&offsets, (size_t)(ncounts + 1));
-    lay.add(&count_sums, (size_t)count_tiles);
+    lay.add(&tile_sums, mm_scan_scratch_ints(n));
+    lay.add(&radix, mm_radix_sort_scratch(n));   // (the sub-sort of the long runs, at most n / 4 rows, uses it again)
     lay.add(&long_runs, 1 + 5 * (size_t)kMaxLongRuns);   // count, starts, lengths, table
     lay.add(&sub_a, n_sz / 4 + 1);
     lay.add(&sub_b, n_sz / 4 + 1);
@@ -383,34 +198,23 @@ extern "C" int64_t mm_unique_points(mm_context *ctx, const double *points_d, int
     if (rc != MM_OK) return rc;
 
     const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
-    // stable sort of (ka, va)[0 .. cnt) by the keys' 64 bits with (kb, vb) as the other buffer; eight passes, so the
-    // result is back in (ka, va)
-    // (first_shift: bits below it are not sorted by; the number of passes stays even)
-    auto radix_sort = [&](u64 *ka, u64 *kb, unsigned *va, unsigned *vb, i64 cnt, int first_shift) -> int {
-        const int tiles = (int)((cnt + kTile - 1) / kTile);
-        for (int shift = first_shift; shift < 64; shift += 8) {
-            hipLaunchKernelGGL(radix_hist_kernel, dim3((unsigned)tiles), dim3(kSortBlock), 0, ctx->stream, ka, cnt, shift, tiles,
-                               counts);
-            int src = mm_exclusive_scan_int(ctx, counts, (i64)kBins * tiles, offsets, count_sums);
-            if (src != MM_OK) return src;
-            hipLaunchKernelGGL(radix_scatter_kernel, dim3((unsigned)tiles), dim3(kSortBlock), 0, ctx->stream, ka, va, cnt, shift,
-                               tiles, offsets, kb, vb);
-            u64 *tk = ka;
-            ka = kb;
-            kb = tk;
-            unsigned *tv = va;
-            va = vb;
-            vb = tv;
-        }
+    // stable sort of the rows va[0 .. cnt) by coordinate `comp`, bits [first_shift, 64) of its sortable image, with
+    // (kb, vb) as the other buffer; the number of passes is even, so the result is back in (ka, va)
+    static_assert(kKeyLowBits % 16 == 0, "an even number of 8-bit passes");
+    auto sort_by = [&](int comp, int first_shift, u64 *ka, u64 *kb, unsigned *va, unsigned *vb, i64 cnt) -> int {
+        hipLaunchKernelGGL(key_kernel, dim3((unsigned)((cnt + kBlock - 1) / kBlock)), block, 0, ctx->stream, points_d, cnt,
+                           (int)dim, comp, va, ka);
+        bool in_a = false;
+        const int src = mm_radix_sort_pairs(ctx, ka, kb, va, vb, cnt, first_shift, 64, radix, &in_a);
+        if (src != MM_OK) return src;
+        MM_REQUIRE_AS("mm_unique_points", in_a, "the sort left its result in the second buffer pair");
         return MM_OK;
     };
     // rows (va, any order that is ascending in the original index among equal rows) -> lexicographic order: dim stable
     // sorts, least significant coordinate first
     auto sort_rows = [&](u64 *ka, u64 *kb, unsigned *va, unsigned *vb, i64 cnt) -> int {
-        const dim3 g((unsigned)((cnt + kBlock - 1) / kBlock));
         for (int comp = (int)dim - 1; comp >= 0; --comp) {
-            hipLaunchKernelGGL(key_kernel, g, block, 0, ctx->stream, points_d, cnt, (int)dim, comp, va, ka);
-            int src = radix_sort(ka, kb, va, vb, cnt, 0);
+            const int src = sort_by(comp, 0, ka, kb, va, vb, cnt);
             if (src != MM_OK) return src;
         }
         return MM_OK;
@@ -418,10 +222,8 @@ extern "C" int64_t mm_unique_points(mm_context *ctx, const double *points_d, int
     // fast path: one sort by x, then the runs of equal x: short ones in place, long ones as a sub-sort
     bool general = false;
     hipLaunchKernelGGL(iota_kernel, grid, block, 0, ctx->stream, ord_a, n);
-    hipLaunchKernelGGL(key_kernel, grid, block, 0, ctx->stream, points_d, n, (int)dim, 0, ord_a, key_a);
-    static_assert(kKeyLowBits % 16 == 0, "an even number of 8-bit passes");
     // (1-D: nothing follows that could order the rest of x -- all 64 bits)
-    if ((rc = radix_sort(key_a, key_b, ord_a, ord_b, n, dim > 1 ? kKeyLowBits : 0)) != MM_OK) return rc;
+    if ((rc = sort_by(0, dim > 1 ? kKeyLowBits : 0, key_a, key_b, ord_a, ord_b, n)) != MM_OK) return rc;
     if (dim > 1) {
         MM_HIP_CHECK(hipMemsetAsync(long_runs, 0, sizeof(int), ctx->stream));
         hipLaunchKernelGGL(run_fixup_kernel, grid, block, 0, ctx->stream, key_a, n, points_d, (int)dim, ord_a, long_runs);

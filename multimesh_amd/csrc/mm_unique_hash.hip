@@ -18,7 +18,6 @@ namespace {
 
 typedef unsigned long long u64;
 constexpr int kBlock = 256;
-constexpr int kScanTileItems = 1024;
 
 __device__ __forceinline__ u64 canon_bits(double v)
 {
@@ -116,7 +115,6 @@ int64_t unique_any_order(mm_context *ctx, const double *pts, i64 n, double *uniq
     unsigned tsize = 1024;
     while ((u64)tsize < 2ull * (u64)n) tsize <<= 1;
     const size_t n_sz = (size_t)n;
-    const int ntiles = (int)((n + 1 + kScanTileItems - 1) / kScanTileItems);
     int *table, *rep, *flag, *rank, *tile_sums;
     unsigned *slot_of;
     mm_scratch_layout lay;
@@ -125,7 +123,7 @@ int64_t unique_any_order(mm_context *ctx, const double *pts, i64 n, double *uniq
     lay.add(&rep, n_sz);
     lay.add(&flag, n_sz + 1);
     lay.add(&rank, n_sz + 1);
-    lay.add(&tile_sums, (size_t)ntiles);
+    lay.add(&tile_sums, mm_scan_scratch_ints(n));
     int rc = lay.commit(ctx, __func__);
     if (rc != MM_OK) return rc;
     MM_HIP_CHECK(hipMemsetAsync(table, 0xff, (size_t)tsize * sizeof(int), ctx->stream));

@@ -4,7 +4,6 @@ from __future__ import annotations
 import numpy as np
 
 from ..device import default_context
-from ..helpers import check
 from ..mesh import HexMesh
 from ._common import GllMesh, _components_first, _order_from_point_count, _report_not_found, _scatter_back
 from .earth import _sphere_mapped
@@ -135,7 +134,7 @@ def _gll_operator_over_all_points(ctx, gll_points, points, nelem_to_search, igno
     pts = ctx.asdevice(points if hasattr(points, "numpy") else np.ascontiguousarray(points, dtype=np.float64),
                        np.float64)
     nearest = tree.query(pts, nelem_to_search)
-    check(ctx.lib.mm_points_to_elements(ctx.handle, nearest.ptr, nearest.size, P), "mm_points_to_elements")   # floor(index / P), on the device
+    ctx.points_to_elements(nearest, P)                           # floor(index / P), on the device
     elem, coeffs, hard = ctx.locate_gll_bbox(gll_order, nearest, gll_points, pts)
     if hard and not ignore_hard_elements:
         raise ValueError("Can't find an appropriate element.")

@@ -6,7 +6,6 @@ import numpy as np
 
 from .. import io as mio
 from ..device import _Released, default_context
-from ..helpers import check
 from ..mesh import HexMesh
 from ._common import GllMesh, ImportTarget, _order_from_point_count, is_mesh, named_fields, points_of
 from .earth import _sphere_mapped
@@ -661,9 +660,7 @@ def regular_grid_adjoint(grid, mesh, parameters, mass=True, normalise=False, out
     # product mass[i] * row[i], one rounding; M * 1.0 is M)
     values = ctx.to_device(np.concatenate([np.asarray(fields, dtype=np.float64).reshape(ncomp, n), np.ones((1, n))]))
     if mass and n:
-        weighted = ctx.empty(values.shape, np.float64)
-        check(ctx.lib.mm_pcg_combine(ctx.handle, weight.ptr, values.ptr, 0.0, None, n, ncomp + 1, weighted.ptr), "mm_pcg_combine")
-        values = weighted
+        values = ctx.multiply_rows(weight, values)
     with GridOperator(ctx, points.reshape(n, 3), dict(grid.coords), axes, periodic, flipped, appended, clamp) as op:
         back = op.transpose(values)
         nmissing = op.noutside

@@ -54,9 +54,41 @@ class _Handle(_Released):
         self.handle = None
 
 
+# ---- the one place where Python calls the library ---------------------------------------------------
+# (what releases -- DeviceArray.free, _Handle.free, Context.close -- stays direct: no status comes back and nothing may raise)
+def _call(lib, symbol, *args, what=None, arg_error=False):
+    """``lib.symbol(*args)`` with every :class:`DeviceArray` passed as its address; None (a null pointer), flags (ctypes
+    takes a ``bool`` as 0 / 1), numbers, addresses and ctypes objects go as they are.  Returns the status, a count >= 0; a
+    negative one raises through :func:`check`, which names ``what`` (the symbol unless given) -- or, with ``arg_error``,
+    status -1 (MM_ERR_ARG) is the caller's mistake: ``ValueError`` with the library's message."""
+    rc = getattr(lib, symbol)(*[a.ptr if type(a) is DeviceArray else a for a in args])
+    if rc < 0:
+        if arg_error and rc == -1:
+            raise ValueError(lib.mm_last_error().decode(errors="replace"))
+        check(rc, what or symbol)
+    return rc
+
+
+def _create(lib, symbol, *args):
+    """The value of the handle that ``symbol`` writes through its last argument."""
+    h = C.c_void_p()
+    _call(lib, symbol, *args, C.byref(h))
+    return h.value
+
+
 def _components(x, ndim):
     """A single component given without its leading axis ([M], [E, P], [D, LA, LO]: ``ndim`` axes) as [1, ...]."""
     return x.reshape(1, *x.shape) if len(x.shape) == ndim else x
+
+
+def _major(n, ncomp, point_major):
+    """The shape of ``ncomp`` values at each of ``n`` points: [N, C] point-major, else [C, N]."""
+    return (n, ncomp) if point_major else (ncomp, n)
+
+
+def _list_width(nn):
+    """``k`` of candidate lists int64[N, k]; a flat array holds no lists."""
+    return nn.shape[1] if len(nn.shape) == 2 else 0
 
 
 def _element_nodal(ctx, values, nelem, P, name):
@@ -76,9 +108,7 @@ def _hex8_arrays(ctx, nnodes, points, fields, want_operator, out):
         raise ValueError("fields must be [C, number of nodes]")
     n = pts.shape[0]
     out = ctx._out(out, (n, f.shape[0]))
-    enc = ctx.empty((n, 8), np.int64) if want_operator else None
-    w = ctx.empty((n, 8), np.float64) if want_operator else None
-    return pts, f, out, enc, w
+    return pts, f, out, ctx._wanted(want_operator, (n, 8), np.int64), ctx._wanted(want_operator, (n, 8))
 
 
 def _with_operator(want_operator, values, index, weights, count):
@@ -111,7 +141,7 @@ class DeviceArray(_Released):
     def numpy(self):
         out = np.empty(self.shape, dtype=self.dtype)
         if out.nbytes:
-            check(self.ctx.lib.mm_copy_d2h(self.ctx.handle, out.ctypes.data, self.ptr, out.nbytes), "mm_copy_d2h")
+            self.ctx._call("mm_copy_d2h", out.ctypes.data, self, out.nbytes)
         return out
 
     def rows(self, start, stop):
@@ -152,9 +182,8 @@ class KnnIndex(_Handle):
             raise ValueError(f"k must be in 0..{MM_KNN_MAX_K}")
         n = pts.shape[0]
         idx = ctx.empty((n, k), np.int64)
-        dist = ctx.empty((n, k), np.float64) if want_dist else None
-        check(ctx.lib.mm_knn_query(ctx.handle, self.handle, pts.ptr, n, k, idx.ptr, dist.ptr if dist else None),
-              "mm_knn_query")
+        dist = ctx._wanted(want_dist, (n, k))
+        ctx._call("mm_knn_query", self.handle, pts, n, k, idx, dist)
         return (idx, dist) if want_dist else idx
 
 
@@ -171,9 +200,7 @@ class Source(_Handle):
         """:meth:`Context.interpolate_hex8` without the centroid and grid-build stages; identical results."""
         ctx = self.ctx
         pts, f, out, enc, w = _hex8_arrays(ctx, self.nodes.shape[0], points, fields, want_operator, out)
-        nf = check(ctx.lib.mm_interpolate_hex8_on(ctx.handle, self.handle, pts.ptr, pts.shape[0], f.ptr, f.shape[0],
-                                                  nelem_to_search, out.ptr, enc.ptr if enc else None,
-                                                  w.ptr if w else None), "mm_interpolate_hex8_on")
+        nf = ctx._call("mm_interpolate_hex8_on", self.handle, pts, pts.shape[0], f, f.shape[0], nelem_to_search, out, enc, w)
         return _with_operator(want_operator, out, enc, w, nf)
 
 
@@ -194,14 +221,13 @@ class TransposedOperator(_Handle):
             raise ValueError("the operator has been freed")
         v = ctx.asdevice(values, np.float64)
         if len(v.shape) == 1:
-            v = v.reshape(v.shape[0], 1) if point_major else v.reshape(1, v.shape[0])
+            v = v.reshape(*_major(v.shape[0], 1, point_major))
         if len(v.shape) != 2 or v.shape[0 if point_major else 1] != self.npoints:
             raise ValueError("values must be [N, C] (point_major) or [C, N]")
         ncomp = v.shape[1 if point_major else 0]
         shape = (ncomp,) + self.out_shape
         out = ctx._out(out, shape, f"out must be {shape}")
-        check(ctx.lib.mm_transpose_apply(ctx.handle, self.handle, v.ptr, ncomp, 1 if point_major else 0, out.ptr),
-              "mm_transpose_apply")
+        ctx._call("mm_transpose_apply", self.handle, v, ncomp, bool(point_major), out)
         return out
 
     def free(self):
@@ -225,14 +251,11 @@ class Diffusion(_Released):
         self.last_iterations = []                               # of the last smooth(): [steps][C] PCG iterations
 
     # ---- K u ------------------------------------------------------------------------------
-    def _apply(self, u_ptr, ncomp, y_ptr):
+    def _apply(self, u, ncomp, y):
         kh_s, kh_a = self.kappa_h
         kr_s, kr_a = self.kappa_r if self.kappa_r is not None else (0.0, None)
-        check(self.ctx.lib.mm_gll_diffusion_apply(self.ctx.handle, self.order, self.dim, self.gp.ptr, self.nelem,
-                                                  self._deriv.ptr, self._weights.ptr, u_ptr, ncomp, float(kh_s),
-                                                  kh_a.ptr if kh_a else None, 1 if self.kappa_r is not None else 0,
-                                                  float(kr_s), kr_a.ptr if kr_a else None, y_ptr),
-              "mm_gll_diffusion_apply")
+        self.ctx._call("mm_gll_diffusion_apply", self.order, self.dim, self.gp, self.nelem, self._deriv, self._weights, u,
+                       ncomp, float(kh_s), kh_a, self.kappa_r is not None, float(kr_s), kr_a, y)
 
     def _fields(self, values):
         return _element_nodal(self.ctx, values, self.nelem, self.P, "values")
@@ -245,7 +268,7 @@ class Diffusion(_Released):
         out = self.ctx._out(out, v.shape, "out must be another array of the shape of u")
         if out.ptr == v.ptr:
             raise ValueError("out must be another array of the shape of u")
-        self._apply(v.ptr, v.shape[0], out.ptr)
+        self._apply(v, v.shape[0], out)
         return out
 
     def roughness(self, u):
@@ -257,8 +280,7 @@ class Diffusion(_Released):
         n, ncomp = self.nelem * self.P, v.shape[0]
         out = ctx.empty((ncomp,), np.float64)
         for c in range(ncomp):
-            check(ctx.lib.mm_weighted_sum(ctx.handle, v.ptr + 8 * c * n, y.ptr + 8 * c * n, n, 1, out.ptr + 8 * c),
-                  "mm_weighted_sum")
+            ctx._call("mm_weighted_sum", v.ptr + 8 * c * n, y.ptr + 8 * c * n, n, 1, out.ptr + 8 * c)
         return out.numpy()
 
     # ---- the assembled space ------------------------------------------------------------------
@@ -278,20 +300,16 @@ class Diffusion(_Released):
 
     def _gather(self, x, ncomp, out):
         """unique nodes [C, U] -> every copy [C, N]"""
-        a, ctx = self._asm, self.ctx
-        check(ctx.lib.mm_gather(ctx.handle, x.ptr, a["nu"], ncomp, a["inverse"].ptr, a["ones"].ptr, a["n"], 1, out.ptr, 0),
-              "mm_gather")
+        a = self._asm
+        self.ctx._call("mm_gather", x, a["nu"], ncomp, a["inverse"], a["ones"], a["n"], 1, out, 0)
 
     def _combine(self, mass, p, tau, kp, n, ncomp, out):
-        ctx = self.ctx
-        check(ctx.lib.mm_pcg_combine(ctx.handle, mass.ptr if mass else None, p.ptr if p else None, float(tau),
-                                     kp.ptr if kp else None, n, ncomp, out.ptr), "mm_pcg_combine")
+        self.ctx._call("mm_pcg_combine", mass, p, float(tau), kp, n, ncomp, out)
 
     def _dots(self, a, b, n, ncomp, state, slot):
-        ctx = self.ctx
         for c in range(ncomp):
-            check(ctx.lib.mm_weighted_sum(ctx.handle, a.ptr + 8 * c * n, b.ptr + 8 * c * n, n, 1,
-                                          state.ptr + 8 * (c * H.MM_PCG_STATE + slot)), "mm_weighted_sum")
+            self.ctx._call("mm_weighted_sum", a.ptr + 8 * c * n, b.ptr + 8 * c * n, n, 1,
+                           state.ptr + 8 * (c * H.MM_PCG_STATE + slot))
 
     def smooth(self, values, steps=4, rtol=1e-10, max_iter=2000):
         """``steps`` backward-Euler steps of ``tau = 1 / (2 steps)`` each: ``(M + tau K) u_new = M u_old`` on the unique
@@ -306,7 +324,7 @@ class Diffusion(_Released):
         steps, max_iter, rtol = int(steps), int(max_iter), float(rtol)
         if steps < 0 or max_iter < 1 or not 0.0 < rtol < 1.0:
             raise ValueError("need steps >= 0, max_iter >= 1 and 0 < rtol < 1")
-        ctx, lib = self.ctx, self.ctx.lib
+        ctx = self.ctx
         v = self._fields(values)
         ncomp = v.shape[0]
         a = self._assembly()
@@ -315,7 +333,7 @@ class Diffusion(_Released):
         ye = ctx.empty((ncomp, n), np.float64)
         self._combine(a["elem_mass"], v, 0.0, None, n, ncomp, ve)
         x = op.apply(ve, point_major=False)                     # [C, U]
-        check(lib.mm_divide_rows(ctx.handle, x.ptr, mass.ptr, nu, ncomp, x.ptr), "mm_divide_rows")
+        ctx._call("mm_divide_rows", x, mass, nu, ncomp, x)
         self.last_iterations = []
         if steps and ncomp and n:
             tau = 1.0 / (2.0 * steps)
@@ -326,11 +344,11 @@ class Diffusion(_Released):
 
             def stiffness(src):                                 # kp = A^T K_e A src
                 self._gather(src, ncomp, ve)
-                self._apply(ve.ptr, ncomp, ye.ptr)
+                self._apply(ve, ncomp, ye)
                 op.apply(ye, point_major=False, out=kp)
 
             for _ in range(steps):
-                check(lib.mm_pcg_scalars(ctx.handle, state.ptr, ncomp, H.MM_PCG_PHASE_START, rtol, None), "mm_pcg_scalars")
+                ctx._call("mm_pcg_scalars", state, ncomp, H.MM_PCG_PHASE_START, rtol, None)
                 self._combine(mass, x, 0.0, None, nu, ncomp, ap)            # b = M u_old
                 self._dots(ap, x, nu, ncomp, state, H.MM_PCG_BB)            # b^T M^-1 b = ||u_old||_M^2
                 stiffness(x)
@@ -338,10 +356,9 @@ class Diffusion(_Released):
                 done_at = [None] * ncomp
                 left = ncomp
                 for it in range(max_iter + 1):
-                    check(lib.mm_divide_rows(ctx.handle, r.ptr, mass.ptr, nu, ncomp, z.ptr), "mm_divide_rows")
+                    ctx._call("mm_divide_rows", r, mass, nu, ncomp, z)
                     self._dots(r, z, nu, ncomp, state, H.MM_PCG_RZ)
-                    check(lib.mm_pcg_scalars(ctx.handle, state.ptr, ncomp, H.MM_PCG_PHASE_BETA, rtol, nactive.ptr),
-                          "mm_pcg_scalars")
+                    ctx._call("mm_pcg_scalars", state, ncomp, H.MM_PCG_PHASE_BETA, rtol, nactive)
                     now = int(nactive.numpy()[0])                           # the one number read back per iteration
                     if now != left:
                         active = state.numpy()[:, H.MM_PCG_ACTIVE]
@@ -354,13 +371,12 @@ class Diffusion(_Released):
                     if it == max_iter:
                         raise RuntimeError(f"smooth: {now} of {ncomp} components did not reach rtol = {rtol} within "
                                            f"{max_iter} iterations of a diffusion step")
-                    check(lib.mm_pcg_direction(ctx.handle, state.ptr, z.ptr, nu, ncomp, p.ptr), "mm_pcg_direction")
+                    ctx._call("mm_pcg_direction", state, z, nu, ncomp, p)
                     stiffness(p)
                     self._combine(mass, p, tau, kp, nu, ncomp, ap)
                     self._dots(p, ap, nu, ncomp, state, H.MM_PCG_PAP)
-                    check(lib.mm_pcg_scalars(ctx.handle, state.ptr, ncomp, H.MM_PCG_PHASE_ALPHA, rtol, None),
-                          "mm_pcg_scalars")
-                    check(lib.mm_pcg_advance(ctx.handle, state.ptr, p.ptr, ap.ptr, nu, ncomp, x.ptr, r.ptr), "mm_pcg_advance")
+                    ctx._call("mm_pcg_scalars", state, ncomp, H.MM_PCG_PHASE_ALPHA, rtol, None)
+                    ctx._call("mm_pcg_advance", state, p, ap, nu, ncomp, x, r)
                 self.last_iterations.append(done_at)
         out = ctx.empty((ncomp, self.nelem, self.P), np.float64)
         if n and ncomp:
@@ -383,32 +399,39 @@ class Context(_Released):
 
     def __init__(self, device=0, stream=None):
         self.lib = load_lib()
-        h = C.c_void_p()
-        check(self.lib.mm_context_create(int(device), C.c_void_p(stream) if stream else None, C.byref(h)),
-              "mm_context_create")
-        self.handle = h.value
+        self.handle = _create(self.lib, "mm_context_create", int(device), C.c_void_p(stream) if stream else None)
         self.device = int(device)
+
+    # ---- library calls on this context: the handle goes first ------------------------------
+    def _call(self, symbol, *args, what=None):
+        return _call(self.lib, symbol, self.handle, *args, what=what)
+
+    def _call_args(self, symbol, *args):
+        """:meth:`_call` for the symbols whose status -1 (MM_ERR_ARG) is the caller's mistake: ``ValueError`` with the
+        library's message."""
+        return _call(self.lib, symbol, self.handle, *args, arg_error=True)
+
+    def _create(self, symbol, *args):
+        return _create(self.lib, symbol, self.handle, *args)
 
     # ---- memory -------------------------------------------------------------------------
     def empty(self, shape, dtype):
         shape = tuple(int(s) for s in (shape if isinstance(shape, (tuple, list)) else (shape,)))
         dtype = np.dtype(dtype)
-        p = C.c_void_p()
         nbytes = int(np.prod(shape, dtype=np.int64)) * dtype.itemsize
-        check(self.lib.mm_device_alloc(self.handle, nbytes, C.byref(p)), "mm_device_alloc")
-        return DeviceArray(self, p.value, shape, dtype)
+        return DeviceArray(self, self._create("mm_device_alloc", nbytes), shape, dtype)
 
     def zeros(self, shape, dtype):
         a = self.empty(shape, dtype)
         if a.nbytes:
-            check(self.lib.mm_memset(self.handle, a.ptr, 0, a.nbytes), "mm_memset")
+            self._call("mm_memset", a, 0, a.nbytes)
         return a
 
     def to_device(self, array, dtype=None):
         a = np.ascontiguousarray(array, dtype=dtype)
         d = self.empty(a.shape, a.dtype)
         if a.nbytes:
-            check(self.lib.mm_copy_h2d(self.handle, d.ptr, a.ctypes.data, a.nbytes), "mm_copy_h2d")
+            self._call("mm_copy_h2d", d, a.ctypes.data, a.nbytes)
         return d
 
     @staticmethod
@@ -439,7 +462,7 @@ class Context(_Released):
         return self.to_device(np.asarray(x), dtype)
 
     def synchronize(self):
-        check(self.lib.mm_synchronize(self.handle), "mm_synchronize")
+        self._call("mm_synchronize")
 
     # ---- checks that many methods share ------------------------------------------------------
     def _out(self, out, shape, message=None, size_only=False):
@@ -457,11 +480,27 @@ class Context(_Released):
             raise ValueError(message)
         return out
 
-    def _check_args(self, rc, what):
-        """Status -1 (MM_ERR_ARG) is the caller's mistake: ``ValueError`` with the library's message; else :func:`check`."""
-        if rc == -1:
-            raise ValueError(self.lib.mm_last_error().decode(errors="replace"))
-        return check(rc, what)
+    def _wanted(self, want, shape, dtype=np.float64):
+        """An optional output: a new array when it is wanted, else None -- a null pointer to the library."""
+        return self.empty(shape, dtype) if want else None
+
+    def _node_groups(self, points):
+        """(points f64[G, P, 3] on the device -- or [N, 3]: P = 1 --, G, P) with at most 256 nodes per group."""
+        pts = self.asdevice(points, np.float64)
+        if len(pts.shape) not in (2, 3) or pts.shape[-1] != 3:
+            raise ValueError("points must be [G, P, 3] or [N, 3]")
+        ngroups, P = (pts.shape[0], pts.shape[1]) if len(pts.shape) == 3 else (pts.shape[0], 1)
+        if not 1 <= P <= 256:
+            raise ValueError("P must lie in [1, 256]")
+        return pts, ngroups, P
+
+    def _flat_rows(self, values, message):
+        """(values on the device, rows, values per row) of f64[C, ...], every row read flat, or f64[n]: one row."""
+        v = self.asdevice(values, np.float64)
+        if len(v.shape) == 0:
+            raise ValueError(message)
+        nrows = v.shape[0] if len(v.shape) > 1 else 1
+        return v, nrows, v.size // nrows if nrows else 0
 
     def _pairs(self, ids, weights):
         """(ids int64[N, P], weights f64[N, P], N, P) of an operator on the device."""
@@ -492,41 +531,41 @@ class Context(_Released):
     # ---- timers -------------------------------------------------------------------------
     def set_profiling(self, on=True):
         """Stage timers: False / True (all stages) / 2 (only the kNN tile kernel and the first locate pass)."""
-        check(self.lib.mm_set_profiling(self.handle, 2 if on == 2 and on is not True else (1 if on else 0)), "mm_set_profiling")
+        self._call("mm_set_profiling", 2 if on == 2 and on is not True else bool(on))
 
     def set_lazy_lists(self, on=True):
         """interpolate_hex8 asks the kNN stage for the 8 nearest first and for the full list only for
         targets that exhaust them (bit-identical outputs; default on)."""
-        check(self.lib.mm_set_lazy_lists(self.handle, 1 if on else 0), "mm_set_lazy_lists")
+        self._call("mm_set_lazy_lists", bool(on))
 
     def set_fp_mode(self, mode):
         """Arithmetic of the hex8 locate stage: "exact" (default: the reference's operations, every output bit-identical)
         or "tol" (cheaper Newton arithmetic that certifies every decision of the reference's iteration or repeats the
         solve exactly: node ids / failed count still bit-identical, weights and values to ~1e-12; include/multimesh_hip.h)."""
         m = {"exact": MM_FP_EXACT, "tol": MM_FP_TOL, MM_FP_EXACT: MM_FP_EXACT, MM_FP_TOL: MM_FP_TOL}[mode]
-        check(self.lib.mm_set_fp_mode(self.handle, m), "mm_set_fp_mode")
+        self._call("mm_set_fp_mode", m)
 
     def fp_mode(self):
-        return "tol" if check(self.lib.mm_get_fp_mode(self.handle), "mm_get_fp_mode") == MM_FP_TOL else "exact"
+        return "tol" if self._call("mm_get_fp_mode") == MM_FP_TOL else "exact"
 
     def last_locate_stats(self):
         """Of the last hex8 locate stage: solves MM_FP_TOL repeated in the reference's arithmetic, targets the first pass
         left over (for the reference-order kernel, or a long on-demand list's second pass), targets that second pass left
         over for the reference-order kernel (synchronises)."""
         buf = (C.c_longlong * 4)()
-        check(self.lib.mm_last_locate_stats(self.handle, buf), "mm_last_locate_stats")
+        self._call("mm_last_locate_stats", buf)
         return {"redone_exact": int(buf[0]), "reference_order": int(buf[1]), "second_pass": int(buf[2])}
 
     def last_knn_kernels(self):
         """Names of the kNN kernels the last call launched: a subset of KNN_KERNELS (include/multimesh_hip.h)."""
         m = C.c_int()
-        check(self.lib.mm_last_knn_kernels(self.handle, C.byref(m)), "mm_last_knn_kernels")
+        self._call("mm_last_knn_kernels", C.byref(m))
         return {name for bit, name in enumerate(KNN_KERNELS) if m.value >> bit & 1}
 
     def last_timings(self):
         """Per-stage milliseconds of the last call (hipEvents on this context's stream)."""
         buf = (C.c_double * len(STAGES))()
-        check(self.lib.mm_last_timings(self.handle, buf, len(STAGES)), "mm_last_timings")
+        self._call("mm_last_timings", buf, len(STAGES))
         return {name: buf[i] for i, name in enumerate(STAGES)}
 
     # ---- A1 -----------------------------------------------------------------------------
@@ -536,7 +575,7 @@ class Context(_Released):
         nelem, nper = conn.shape
         ndim = pts.shape[1]
         out = self.empty((nelem, ndim), np.float64)
-        check(self.lib.mm_centroid(self.handle, ndim, nelem, nper, conn.ptr, pts.ptr, out.ptr), "mm_centroid")
+        self._call("mm_centroid", ndim, nelem, nper, conn, pts, out)
         return out
 
     # ---- A2 -----------------------------------------------------------------------------
@@ -544,9 +583,8 @@ class Context(_Released):
         src = self.asdevice(sources, np.float64)
         if len(src.shape) != 2 or not 1 <= src.shape[1] <= 3:
             raise ValueError("sources must be [nsrc, ndim] with ndim in 1..3")
-        h = C.c_void_p()
-        check(self.lib.mm_knn_build(self.handle, src.ptr, src.shape[0], src.shape[1], C.byref(h)), "mm_knn_build")
-        return KnnIndex(self, h.value, src.shape[0], src.shape[1], keepalive=src)
+        handle = self._create("mm_knn_build", src, src.shape[0], src.shape[1])
+        return KnnIndex(self, handle, src.shape[0], src.shape[1], keepalive=src)
 
     # ---- A4 -----------------------------------------------------------------------------
     def locate_hex8(self, nearest_element_indices, connectivity, nodes, points, enc=None, weights=None,
@@ -559,14 +597,11 @@ class Context(_Released):
         nod = self.asdevice(nodes, np.float64)
         pts = self.asdevice(points, np.float64)
         n = pts.shape[0]
-        k = nn.shape[1] if len(nn.shape) == 2 else 0
         if conn.shape[1] != 8 or nod.shape[1] != 3 or pts.shape[1] != 3 or nn.shape[0] != n:
             raise ValueError("shape mismatch: need nn[N,k], connectivity[E,8], nodes[M,3], points[N,3]")
         enc = self.zeros((n, 8), np.int64) if enc is None else self.asdevice(enc, np.int64)
         w = self.zeros((n, 8), np.float64) if weights is None else self.asdevice(weights, np.float64)
-        nf = check(self.lib.mm_locate_hex8(self.handle, k, n, nn.ptr, conn.ptr, conn.shape[0],
-                                           1 if conn_is_exodus else 0, enc.ptr, nod.ptr, w.ptr, pts.ptr),
-                   "mm_locate_hex8")
+        nf = self._call("mm_locate_hex8", _list_width(nn), n, nn, conn, conn.shape[0], bool(conn_is_exodus), enc, nod, w, pts)
         return enc, w, int(nf)
 
     # ---- A9 -----------------------------------------------------------------------------
@@ -575,9 +610,8 @@ class Context(_Released):
         f = _components(self.asdevice(fields, np.float64), 1)
         idv, w, n, p = self._pairs(ids, weights)
         ncomp, nsrc = f.shape
-        out = self.empty((n, ncomp) if point_major else (ncomp, n), np.float64)
-        check(self.lib.mm_gather(self.handle, f.ptr, nsrc, ncomp, idv.ptr, w.ptr, n, p, out.ptr,
-                                 1 if point_major else 0), "mm_gather")
+        out = self.empty(_major(n, ncomp, point_major), np.float64)
+        self._call("mm_gather", f, nsrc, ncomp, idv, w, n, p, out, bool(point_major))
         return out
 
     # ---- A10 (GLL) ------------------------------------------------------------------------
@@ -589,11 +623,9 @@ class Context(_Released):
         if P != (shape_order + 1) ** dim or pts.shape[1] != dim:
             raise ValueError("gll_points must be [nelem, (order+1)^dim, dim] and points [N, dim]")
         n = pts.shape[0]
-        k = nn.shape[1] if len(nn.shape) == 2 else 0
         elem = self.empty((n,), np.int64)
         coeffs = self.empty((n, P), np.float64)
-        count = check(getattr(self.lib, symbol)(self.handle, shape_order, dim, k, n, nn.ptr, gp.ptr, nelem, pts.ptr,
-                                                *options, elem.ptr, coeffs.ptr), symbol)
+        count = self._call(symbol, shape_order, dim, _list_width(nn), n, nn, gp, nelem, pts, *options, elem, coeffs)
         return elem, coeffs, int(count)
 
     def locate_gll(self, shape_order, nearest_element_indices, gll_points, points, tolerance=1.05,
@@ -601,13 +633,20 @@ class Context(_Released):
         """``get_element_weights`` core (reference interpolator.py:1181-1233) for
         gll_points f64[E, (order+1)^dim, dim].  Returns (elem int64[N], coeffs f64[N,P], nmissing)."""
         return self._locate_gll("mm_locate_gll", shape_order, nearest_element_indices, gll_points, points,
-                                float(tolerance), 1 if snap_to_nearest else 0)
+                                float(tolerance), bool(snap_to_nearest))
 
     def locate_gll_bbox(self, shape_order, nearest_element_indices, gll_points, points):
         """The bounding-box variant ``_check_if_inside_element`` (reference interpolator.py:1409-1473)
         for gll_points f64[E, (order+1)^dim, dim].  Returns (elem int64[N], coeffs f64[N,P], number
         of points whose final inverse transform failed)."""
         return self._locate_gll("mm_locate_gll_bbox", shape_order, nearest_element_indices, gll_points, points)
+
+    def points_to_elements(self, indices, nodes_per_element):
+        """Indices of GLL points, int64 of any shape on the device, replaced in place by the element each point belongs
+        to, ``floor(index / nodes_per_element)`` (``mm_points_to_elements``).  Returns the array."""
+        idx = self.asdevice(indices, np.int64)
+        self._call("mm_points_to_elements", idx, idx.size, int(nodes_per_element))
+        return idx
 
     def gather_elem(self, element_nodal_fields, elem, coeffs, point_major=True):
         """``np.sum(coeffs * field[elem], axis=1)`` (reference interpolator.py:976);
@@ -619,9 +658,8 @@ class Context(_Released):
         n = el.shape[0]
         if co.shape != (n, P):
             raise ValueError("coeffs must be [N, P]")
-        out = self.empty((n, ncomp) if point_major else (ncomp, n), np.float64)
-        check(self.lib.mm_gather_elem(self.handle, f.ptr, nelem, ncomp, el.ptr, co.ptr, n, P, out.ptr,
-                                      1 if point_major else 0), "mm_gather_elem")
+        out = self.empty(_major(n, ncomp, point_major), np.float64)
+        self._call("mm_gather_elem", f, nelem, ncomp, el, co, n, P, out, bool(point_major))
         return out
 
     # ---- the transposes of gather / gather_elem ------------------------------------------------
@@ -629,10 +667,8 @@ class Context(_Released):
         """Group the operator (ids int64[N, P], weights f64[N, P]) by source node: a :class:`TransposedOperator` whose
         ``apply(values)`` is ``np.add.at(out[c], ids, weights * values[:, c, None])`` -> f64[C, nsrc]."""
         idv, w, n, p = self._pairs(ids, weights)
-        h = C.c_void_p()
-        check(self.lib.mm_transpose_create_nodes(self.handle, idv.ptr, w.ptr, n, p, int(nsrc), C.byref(h)),
-              "mm_transpose_create_nodes")
-        return TransposedOperator(self, h.value, n, (int(nsrc),), None)   # (the handle owns its sorted copy)
+        handle = self._create("mm_transpose_create_nodes", idv, w, n, p, int(nsrc))
+        return TransposedOperator(self, handle, n, (int(nsrc),), None)   # (the handle owns its sorted copy)
 
     def transpose_elem(self, elem, coeffs, nelem):
         """Group the GLL operator (elem int64[N], coeffs f64[N, P]) by source element: ``apply(values)`` ->
@@ -642,10 +678,8 @@ class Context(_Released):
         if len(el.shape) != 1 or len(co.shape) != 2 or co.shape[0] != el.shape[0]:
             raise ValueError("elem must be [N] and coeffs [N, P]")
         n, p = co.shape
-        h = C.c_void_p()
-        check(self.lib.mm_transpose_create_elem(self.handle, el.ptr, co.ptr, n, p, int(nelem), C.byref(h)),
-              "mm_transpose_create_elem")
-        return TransposedOperator(self, h.value, n, (int(nelem), p), co)
+        handle = self._create("mm_transpose_create_elem", el, co, n, p, int(nelem))
+        return TransposedOperator(self, handle, n, (int(nelem), p), co)
 
     # ---- the GLL mass matrix and what it weights ----------------------------------------------
     def gll_mass(self, shape_order, gll_points, want_det=False):
@@ -655,10 +689,9 @@ class Context(_Released):
         deriv, weights = gll_derivative_matrix(shape_order), gll_weights_1d(shape_order)
         gp, nelem, P, dim = self._gll_points(shape_order, gll_points)
         mass = self.empty((nelem, P), np.float64)
-        det = self.empty((nelem, P), np.float64) if want_det else None
+        det = self._wanted(want_det, (nelem, P))
         d_d, w_d = self.to_device(deriv), self.to_device(weights)
-        n_bad = check(self.lib.mm_gll_mass(self.handle, int(shape_order), dim, gp.ptr, nelem, d_d.ptr, w_d.ptr, mass.ptr,
-                                           det.ptr if det else None), "mm_gll_mass")
+        n_bad = self._call("mm_gll_mass", int(shape_order), dim, gp, nelem, d_d, w_d, mass, det)
         return (mass, int(n_bad), det) if want_det else (mass, int(n_bad))
 
     def weighted_sum(self, mass, fields=None):
@@ -668,8 +701,19 @@ class Context(_Released):
         m = self.asdevice(mass, np.float64)
         f, ncomp = self._fields_over(m, fields)
         out = self.empty((ncomp,), np.float64)
-        check(self.lib.mm_weighted_sum(self.handle, m.ptr, f.ptr if f else None, m.size, ncomp, out.ptr), "mm_weighted_sum")
+        self._call("mm_weighted_sum", m, f, m.size, ncomp, out)
         return out.numpy()
+
+    def multiply_rows(self, mass, values):
+        """``mass[i] * values[c][i]`` for values f64[C, n] over the n values of mass (any shape): the plain product, one
+        rounding (``mm_pcg_combine`` with ``tau = 0``).  Returns a new f64[C, n] on the device."""
+        m = self.asdevice(mass, np.float64)
+        v = self.asdevice(values, np.float64)
+        if len(v.shape) != 2 or v.shape[1] != m.size:
+            raise ValueError("values must be [C, n] over the n values of mass")
+        out = self.empty(v.shape, np.float64)
+        self._call("mm_pcg_combine", m, v, 0.0, None, m.size, v.shape[0], out)
+        return out
 
     def divide_rows(self, num, den, out=None):
         """``num[c] / den`` for num f64[C, ...] over den's shape (or the shape of den); ``out`` may be ``num``."""
@@ -678,7 +722,7 @@ class Context(_Released):
         if a.shape != d.shape and a.shape[1:] != d.shape:
             raise ValueError("num must be [C, ...] over the shape of den, or the shape of den")
         out = self._out(out, a.shape, "out must have the shape of num")
-        check(self.lib.mm_divide_rows(self.handle, a.ptr, d.ptr, d.size, a.size // max(d.size, 1), out.ptr), "mm_divide_rows")
+        self._call("mm_divide_rows", a, d, d.size, a.size // max(d.size, 1), out)
         return out
 
     # ---- radial 1-D profiles: bins, binned sums, a 1-D table on the nodes -----------------------------
@@ -692,9 +736,8 @@ class Context(_Released):
         if len(e.shape) != 1 or e.shape[0] < 2:
             raise ValueError("edges must be 1-D with at least two entries")
         bins = self.empty((n,), np.int32)
-        radius = self.empty((n,), np.float64) if want_radius else None
-        rc = self.lib.mm_radial_bins(self.handle, pts.ptr, n, e.ptr, e.shape[0] - 1, bins.ptr, radius.ptr if radius else None)
-        self._check_args(rc, "mm_radial_bins")
+        radius = self._wanted(want_radius, (n,))
+        rc = self._call_args("mm_radial_bins", pts, n, e, e.shape[0] - 1, bins, radius)
         return (bins, int(rc), radius) if want_radius else (bins, int(rc))
 
     def binned_weighted_sum(self, mass, bins, nbins, fields=None, square=False, want_count=False):
@@ -712,10 +755,8 @@ class Context(_Released):
             raise ValueError("nbins must be at least 1")
         f, ncomp = self._fields_over(m, fields)
         out = self.empty((ncomp, nbins), np.float64)
-        count = self.empty((nbins,), np.int64) if want_count else None
-        check(self.lib.mm_binned_weighted_sum(self.handle, m.ptr, f.ptr if f else None, b.ptr, m.size, ncomp, nbins,
-                                              1 if square else 0, out.ptr, count.ptr if count else None),
-              "mm_binned_weighted_sum")
+        count = self._wanted(want_count, (nbins,), np.int64)
+        self._call("mm_binned_weighted_sum", m, f, b, m.size, ncomp, nbins, bool(square), out, count)
         return (out.numpy(), count.numpy()) if want_count else out.numpy()
 
     def radial_model_apply(self, points, radius, values, mode=0, values_in=None, out=None):
@@ -725,12 +766,7 @@ class Context(_Released):
         ``values_in`` f64[C, G * P] (any shape of that size): 1 ``in - ref``, 2 ``(in - ref) / ref``, 3 ``in + ref``,
         4 ``ref + in * ref``.  ``out`` may be ``values_in``.  Returns f64[C, G, P] (or [C, N]) on the device.  A table
         that is not a set of layers raises ``ValueError``."""
-        pts = self.asdevice(points, np.float64)
-        if len(pts.shape) not in (2, 3) or pts.shape[-1] != 3:
-            raise ValueError("points must be [G, P, 3] or [N, 3]")
-        ngroups, P = (pts.shape[0], pts.shape[1]) if len(pts.shape) == 3 else (pts.shape[0], 1)
-        if not 1 <= P <= 256:
-            raise ValueError("P must lie in [1, 256]")
+        pts, ngroups, P = self._node_groups(points)
         r = self.asdevice(radius, np.float64)
         v = self.asdevice(values, np.float64)
         if len(r.shape) != 1 or v.shape[-1:] != r.shape or len(v.shape) > 2:
@@ -747,9 +783,7 @@ class Context(_Released):
             if src.size != ncomp * n:
                 raise ValueError("values_in must hold one value per component and node")
         out = self._out(out, (ncomp,) + pts.shape[:-1], "out must hold one value per component and node", size_only=True)
-        rc = self.lib.mm_radial_model_apply(self.handle, pts.ptr, ngroups, P, r.ptr, v.ptr, r.shape[0], ncomp, int(mode),
-                                            src.ptr if src else None, out.ptr)
-        self._check_args(rc, "mm_radial_model_apply")
+        self._call_args("mm_radial_model_apply", pts, ngroups, P, r, v, r.shape[0], ncomp, int(mode), src, out)
         return out
 
     # ---- kernel preconditioning: the cut-out weight, order statistics, clipping -------------------------
@@ -762,12 +796,7 @@ class Context(_Released):
         [C, N] on the device, or None without ``values_in``; the number of nodes with weight < 1) and, with
         ``want_weight``, the weight f64[G, P] / [N] as a third entry.  Centres or radii that are not finite, a negative
         inner, an outer below its inner raise ``ValueError`` and nothing is written."""
-        pts = self.asdevice(points, np.float64)
-        if len(pts.shape) not in (2, 3) or pts.shape[-1] != 3:
-            raise ValueError("points must be [G, P, 3] or [N, 3]")
-        ngroups, P = (pts.shape[0], pts.shape[1]) if len(pts.shape) == 3 else (pts.shape[0], 1)
-        if not 1 <= P <= 256:
-            raise ValueError("P must lie in [1, 256]")
+        pts, ngroups, P = self._node_groups(points)
         c = self.asdevice(centres, np.float64)
         ri, ro = self.asdevice(inner, np.float64), self.asdevice(outer, np.float64)
         if len(c.shape) != 2 or c.shape[1] != 3 or ri.shape != (c.shape[0],) or ro.shape != (c.shape[0],):
@@ -784,10 +813,8 @@ class Context(_Released):
             raise ValueError("out without values_in")
         elif not want_weight:
             raise ValueError("ask for the weight or pass values_in")
-        weight = self.empty(pts.shape[:-1], np.float64) if want_weight else None
-        rc = self.lib.mm_point_taper(self.handle, pts.ptr, ngroups, P, c.ptr, ri.ptr, ro.ptr, c.shape[0], ncomp,
-                                     src.ptr if src else None, out.ptr if src else None, weight.ptr if weight else None)
-        self._check_args(rc, "mm_point_taper")
+        weight = self._wanted(want_weight, pts.shape[:-1])
+        rc = self._call_args("mm_point_taper", pts, ngroups, P, c, ri, ro, c.shape[0], ncomp, src, out, weight)
         return (out, int(rc), weight) if want_weight else (out, int(rc))
 
     def order_statistics(self, values, q, absolute=False, method="lower"):
@@ -796,11 +823,7 @@ class Context(_Released):
         values) the one of rank ``floor(q * (nvalid - 1))`` (``method="lower"``) or ``ceil`` (``"higher"``) in the numeric
         order, -0.0 before +0.0; NaN for a row without a valid value.  Returns (out f64[C, m], nvalid int64[C]), both on
         the device: nothing is read back."""
-        v = self.asdevice(values, np.float64)
-        if len(v.shape) == 0:
-            raise ValueError("values must be [C, ...] or [n]")
-        ncomp = v.shape[0] if len(v.shape) > 1 else 1
-        n = v.size // ncomp if ncomp else 0
+        v, ncomp, n = self._flat_rows(values, "values must be [C, ...] or [n]")
         if method not in ("lower", "higher"):
             raise ValueError('method must be "lower" or "higher"')
         if not isinstance(q, DeviceArray):
@@ -811,9 +834,7 @@ class Context(_Released):
         m = qd.size
         out = self.empty((ncomp, m), np.float64)
         nvalid = self.empty((ncomp,), np.int64)
-        rc = self.lib.mm_order_statistics(self.handle, v.ptr, n, ncomp, 1 if absolute else 0, qd.ptr, m,
-                                          0 if method == "lower" else 1, out.ptr, nvalid.ptr)
-        self._check_args(rc, "mm_order_statistics")
+        self._call_args("mm_order_statistics", v, n, ncomp, bool(absolute), qd, m, method != "lower", out, nvalid)
         return out, nvalid
 
     def clamp(self, values, lower=None, upper=None, symmetric=False, out=None, want_count=True):
@@ -822,11 +843,7 @@ class Context(_Released):
         :meth:`order_statistics`) or are copied there; None: no bound on that side; ``symmetric``: ``lower`` must be None
         and is ``-upper``.  A NaN passes through, -0.0 is kept.  ``out`` may be ``values``.  Returns (out on the device,
         changed int64[C] on the device -- the number of values replaced -- or None without ``want_count``)."""
-        v = self.asdevice(values, np.float64)
-        if len(v.shape) == 0:
-            raise ValueError("values must be [C, ...] or [n]")
-        ncomp = v.shape[0] if len(v.shape) > 1 else 1
-        n = v.size // ncomp if ncomp else 0
+        v, ncomp, n = self._flat_rows(values, "values must be [C, ...] or [n]")
         if symmetric and (lower is not None or upper is None):
             raise ValueError("symmetric takes upper alone")
         lo = None if lower is None else self.asdevice(lower, np.float64)
@@ -835,10 +852,8 @@ class Context(_Released):
             if b is not None and b.size != ncomp:
                 raise ValueError("a bound per component")
         out = self._out(out, v.shape, "out must hold one value per value", size_only=True)
-        changed = self.empty((ncomp,), np.int64) if want_count else None
-        rc = self.lib.mm_clamp(self.handle, v.ptr, n, ncomp, lo.ptr if lo else None, hi.ptr if hi else None,
-                               1 if symmetric else 0, out.ptr, changed.ptr if changed else None)
-        self._check_args(rc, "mm_clamp")
+        changed = self._wanted(want_count, (ncomp,), np.int64)
+        self._call_args("mm_clamp", v, n, ncomp, lo, hi, bool(symmetric), out, changed)
         return out, changed
 
     # ---- boundaries: faces, their side and nodes, the distance to them, the taper and blend it drives ------
@@ -865,8 +880,7 @@ class Context(_Released):
             raise ValueError("nnodes must lie in [0, 2^31) and E below 2^27")
         faces = self.empty((6 * ids.shape[0],), np.int64)
         info = self.empty((1,), np.int64)
-        rc = self.lib.mm_boundary_faces(self.handle, ids.ptr, ids.shape[0], nnodes, faces.ptr, info.ptr)
-        self._check_args(rc, "mm_boundary_faces")
+        rc = self._call_args("mm_boundary_faces", ids, ids.shape[0], nnodes, faces, info)
         return faces.rows(0, int(rc)), int(info.numpy()[0])
 
     def boundary_classify(self, corners, faces, up=None, cos_min=0.5):
@@ -886,9 +900,7 @@ class Context(_Released):
             if len(u) != 3 or not np.isfinite(u).all() or not any(u):
                 raise ValueError("up must be three finite numbers, not all zero")
         side = self.empty((nb,), np.int32)
-        rc = self.lib.mm_boundary_classify(self.handle, c.ptr, c.shape[0], fd.ptr, nb, 1 if up is None else 0, u[0], u[1],
-                                           u[2], float(cos_min), side.ptr)
-        self._check_args(rc, "mm_boundary_classify")
+        self._call_args("mm_boundary_classify", c, c.shape[0], fd, nb, up is None, u[0], u[1], u[2], float(cos_min), side)
         return side
 
     def boundary_nodes(self, points, shape_order, faces, side=None, side_mask=7):
@@ -906,9 +918,7 @@ class Context(_Released):
         if not 0 <= int(side_mask) <= 7:
             raise ValueError("side_mask must lie in [0, 7]")
         out = self.empty((nb * (order + 1) ** 2, 3), np.float64)
-        rc = self.lib.mm_boundary_nodes(self.handle, pts.ptr, pts.shape[0], order, fd.ptr, sd.ptr if sd else None, nb,
-                                        int(side_mask), out.ptr)
-        self._check_args(rc, "mm_boundary_nodes")
+        rc = self._call_args("mm_boundary_nodes", pts, pts.shape[0], order, fd, sd, nb, int(side_mask), out)
         return out.rows(0, int(rc))
 
     def cutoff_distance(self, points, sources, cutoff):
@@ -925,8 +935,7 @@ class Context(_Released):
         if not (np.isfinite(cutoff) and cutoff > 0.0):
             raise ValueError("cutoff must be positive and finite")
         dist = self.empty(pts.shape[:-1], np.float64)
-        rc = self.lib.mm_cutoff_distance(self.handle, pts.ptr, n, s.ptr, s.shape[0], cutoff, dist.ptr)
-        self._check_args(rc, "mm_cutoff_distance")
+        rc = self._call_args("mm_cutoff_distance", pts, n, s, s.shape[0], cutoff, dist)
         return dist, int(rc)
 
     def distance_taper(self, dist, inner, outer, a, b=None, elem=None, out=None, want_weight=False):
@@ -959,12 +968,9 @@ class Context(_Released):
         ev = None if elem is None else self.asdevice(elem, np.int64)
         if ev is not None and ev.size != n:
             raise ValueError("elem must hold one entry per node")
-        weight = self.empty(d.shape, np.float64) if want_weight else None
-        rc = self.lib.mm_distance_taper(self.handle, d.ptr, n, inner, outer, ncomp, av.ptr if av else None,
-                                        bv.ptr if bv else None, ev.ptr if ev else None, out.ptr if av else None,
-                                        weight.ptr if weight else None)
-        self._check_args(rc, "mm_distance_taper")
-        return (out if av else None, int(rc), weight) if want_weight else (out, int(rc))
+        weight = self._wanted(want_weight, d.shape)
+        rc = self._call_args("mm_distance_taper", d, n, inner, outer, ncomp, av, bv, ev, out, weight)
+        return (out, int(rc), weight) if want_weight else (out, int(rc))
 
     # ---- scattered models: kNN rows -> inverse-distance values ------------------------------------------
     def idw_gather(self, fields, idx, dist, power=2, max_distance=np.inf, outside="fill", fill_value=np.nan, out=None,
@@ -994,16 +1000,14 @@ class Context(_Released):
         if not 1 <= k <= MM_KNN_MAX_K:
             raise ValueError(f"k must be in 1..{MM_KNN_MAX_K}")
         ncomp, nsrc = f.shape
-        shape = (n, ncomp) if point_major else (ncomp, n)
+        shape = _major(n, ncomp, point_major)
         if out is None and outside == "keep":
             raise ValueError('outside="keep" keeps the entries of out: pass out')
         out = self._out(out, shape, f"out must be {list(shape)}")
-        nearest = self.empty((n,), np.float64) if want_nearest else None
-        nused = self.empty((n,), np.int32) if want_count else None
-        rc = self.lib.mm_idw_gather(self.handle, f.ptr, nsrc, ncomp, idv.ptr, d.ptr, n, k, int(power), max_distance,
-                                    modes[outside], float(fill_value), out.ptr, 1 if point_major else 0,
-                                    nearest.ptr if nearest else None, nused.ptr if nused else None)
-        self._check_args(rc, "mm_idw_gather")
+        nearest = self._wanted(want_nearest, (n,))
+        nused = self._wanted(want_count, (n,), np.int32)
+        rc = self._call_args("mm_idw_gather", f, nsrc, ncomp, idv, d, n, k, int(power), max_distance, modes[outside],
+                             float(fill_value), out, bool(point_major), nearest, nused)
         return (out, int(rc)) + ((nearest,) if want_nearest else ()) + ((nused,) if want_count else ())
 
     # ---- resolution: node spacing, edge lengths, the time step and the resolved period of a model ------
@@ -1020,11 +1024,9 @@ class Context(_Released):
         s = None if slow is None else _element_nodal(self, slow, nelem, P, "slow")
         out = self.empty((5 if f else 3, nelem), np.float64)
         info = self.empty((2,), np.int64)
-        node_h = self.empty((nelem, P), np.float64) if want_node_spacing else None
-        rc = self.lib.mm_gll_resolution(self.handle, int(shape_order), dim, gp.ptr, nelem, f.ptr if f else None,
-                                        f.shape[0] if f else 0, s.ptr if s else None, s.shape[0] if s else 0,
-                                        node_h.ptr if node_h else None, out.ptr, info.ptr)
-        self._check_args(rc, "mm_gll_resolution")
+        node_h = self._wanted(want_node_spacing, (nelem, P))
+        self._call_args("mm_gll_resolution", int(shape_order), dim, gp, nelem, f, f.shape[0] if f else 0, s,
+                        s.shape[0] if s else 0, node_h, out, info)
         return (out, info, node_h) if want_node_spacing else (out, info)
 
     def arg_extreme(self, values, want_max=False):
@@ -1032,15 +1034,10 @@ class Context(_Released):
         row) that is not a NaN, and its place (``mm_arg_extreme``): the lowest index among equal values, -0.0 equal to
         +0.0, NaN and -1 for a row without a valid value.  Returns (value f64[R], index int64[R], nvalid int64[R]), all on
         the device: nothing is read back.  Deterministic (integer atomics only)."""
-        v = self.asdevice(values, np.float64)
-        if len(v.shape) == 0:
-            raise ValueError("values must be [R, ...] or [n]")
-        nrows = v.shape[0] if len(v.shape) > 1 else 1
-        n = v.size // nrows if nrows else 0
+        v, nrows, n = self._flat_rows(values, "values must be [R, ...] or [n]")
         value = self.empty((nrows,), np.float64)
         index, nvalid = self.empty((nrows,), np.int64), self.empty((nrows,), np.int64)
-        rc = self.lib.mm_arg_extreme(self.handle, v.ptr, nrows, n, 1 if want_max else 0, value.ptr, index.ptr, nvalid.ptr)
-        self._check_args(rc, "mm_arg_extreme")
+        self._call_args("mm_arg_extreme", v, nrows, n, bool(want_max), value, index, nvalid)
         return value, index, nvalid
 
     # ---- diffusion: the stiffness operator and the smoothing it gives -------------------------------
@@ -1088,11 +1085,10 @@ class Context(_Released):
             raise ValueError("the radial / lateral split needs a 3-D mesh")
         v = _element_nodal(self, u, nelem, P, "u")
         ncomp = v.shape[0]
-        outs = [self.empty((ncomp, dim, nelem, P) if full else (ncomp, nelem, P), np.float64) if want else None
+        outs = [self._wanted(want, (ncomp, dim, nelem, P) if full else (ncomp, nelem, P))
                 for want, full in ((grad, True), (radial, False), (lateral, False), (norm, False))]
         d_d = self.to_device(deriv)
-        check(self.lib.mm_gll_gradient(self.handle, int(shape_order), dim, gp.ptr, nelem, d_d.ptr, v.ptr, ncomp,
-                                       *(o.ptr if o else None for o in outs)), "mm_gll_gradient")
+        self._call("mm_gll_gradient", int(shape_order), dim, gp, nelem, d_d, v, ncomp, *outs)
         got = tuple(o for o in outs if o is not None)
         return got[0] if len(got) == 1 else got
 
@@ -1132,9 +1128,7 @@ class Context(_Released):
                 raise ValueError(f"div_out must be [{nelem}, {pout}]")
         out = self._out(out, shape, f"out must be {shape}")
         t_d = self.to_device(table)
-        check(self.lib.mm_gll_tensor_apply(self.handle, dim, order_in, order_out, t_d.ptr, layout, v.ptr, out.ptr, nelem,
-                                           ncomp, scale.ptr if scale else None, div.ptr if div else None),
-              "mm_gll_tensor_apply")
+        self._call("mm_gll_tensor_apply", dim, order_in, order_out, t_d, layout, v, out, nelem, ncomp, scale, div)
         return out
 
     def element_deviation(self, a, b):
@@ -1146,8 +1140,7 @@ class Context(_Released):
             raise ValueError(f"a and b must both be [nelem, P, dim] with dim 2 or 3, got {a.shape} and {b.shape}")
         nelem, npts, dim = a.shape
         deviation, edge = self.empty((nelem,), np.float64), self.empty((nelem,), np.float64)
-        check(self.lib.mm_element_deviation(self.handle, dim, npts, a.ptr, b.ptr, nelem, deviation.ptr, edge.ptr),
-              "mm_element_deviation")
+        self._call("mm_element_deviation", dim, npts, a, b, nelem, deviation, edge)
         return deviation, edge
 
     # ---- fused ---------------------------------------------------------------------------
@@ -1166,12 +1159,10 @@ class Context(_Released):
             raise ValueError("element_nodal_fields must be [C, nelem, P]")
         n, ncomp = pts.shape[0], f.shape[0]
         out = self._out(out, (n, ncomp), "out must be [N, C]")
-        elem = self.empty((n,), np.int64) if want_operator else None
-        coeffs = self.empty((n, P), np.float64) if want_operator else None
-        miss = check(self.lib.mm_interpolate_gll(self.handle, shape_order, dim, gp.ptr, nelem, pts.ptr, n, f.ptr, ncomp,
-                                                 nelem_to_search, float(tolerance), 1 if snap_to_nearest else 0,
-                                                 out.ptr, elem.ptr if elem else None, coeffs.ptr if coeffs else None),
-                     "mm_interpolate_gll")
+        elem = self._wanted(want_operator, (n,), np.int64)
+        coeffs = self._wanted(want_operator, (n, P))
+        miss = self._call("mm_interpolate_gll", shape_order, dim, gp, nelem, pts, n, f, ncomp, nelem_to_search,
+                          float(tolerance), bool(snap_to_nearest), out, elem, coeffs)
         return _with_operator(want_operator, out, elem, coeffs, miss)
 
     def sample_columns_gll(self, shape_order, gll_points, element_nodal_fields, lat_table, lon_table, radius,
@@ -1204,15 +1195,11 @@ class Context(_Released):
         ncol = nlat if paired else nlat * nlon
         ncomp = f.shape[0]
         out = self._out(out, (ncomp, nd, ncol), "out must be [C, D, H]")
-        pts = self.empty((nd, ncol, 3), np.float64) if want_points else None
-        miss = check(self.lib.mm_sample_columns_gll(self.handle, int(shape_order), gp.ptr, nelem, f.ptr, ncomp, lat.ptr,
-                                                    nlat, lon.ptr, nlon, 1 if paired else 0, rad.ptr, nd,
-                                                    int(nelem_to_search), float(tolerance), float(fill_value),
-                                                    int(chunk_points or 0), out.ptr, pts.ptr if pts else None),
-                     "mm_sample_columns_gll")
-        if want_points:
-            return out, int(miss), pts
-        return out, int(miss)
+        pts = self._wanted(want_points, (nd, ncol, 3))
+        miss = self._call("mm_sample_columns_gll", int(shape_order), gp, nelem, f, ncomp, lat, nlat, lon, nlon, bool(paired),
+                          rad, nd, int(nelem_to_search), float(tolerance), float(fill_value), int(chunk_points or 0), out,
+                          pts)
+        return (out, int(miss), pts) if want_points else (out, int(miss))
 
     def sample_grid(self, points, grid_values, depth, lat, lon, outside="fill", fill_value=np.nan, lon_periodic=False,
                     out=None, want_latlondepth=False):
@@ -1242,13 +1229,10 @@ class Context(_Released):
             out = self.asdevice(out, np.float64)
             if len(out.shape) < 2 or out.shape[0] != ncomp or out.size != ncomp * n:
                 raise ValueError("out must be [C, N] (or [C, ...] over the leading shape of points)")
-        lld = self.empty((n, 3), np.float64) if want_latlondepth else None
-        miss = check(self.lib.mm_sample_grid(self.handle, pts.ptr, n, d.ptr, d.shape[0], la.ptr, la.shape[0], lo.ptr,
-                                             lo.shape[0], g.ptr, ncomp, 1 if lon_periodic else 0, modes[outside],
-                                             float(fill_value), out.ptr, lld.ptr if lld else None), "mm_sample_grid")
-        if want_latlondepth:
-            return out, int(miss), lld
-        return out, int(miss)
+        lld = self._wanted(want_latlondepth, (n, 3))
+        miss = self._call("mm_sample_grid", pts, n, d, d.shape[0], la, la.shape[0], lo, lo.shape[0], g, ncomp,
+                          bool(lon_periodic), modes[outside], float(fill_value), out, lld)
+        return (out, int(miss), lld) if want_latlondepth else (out, int(miss))
 
     def _grid_axes(self, depth, lat, lon, lon_periodic):
         """The three axes of a regular grid on the device.  Host axes are checked here (1-D, finite, strictly ascending; a
@@ -1284,13 +1268,10 @@ class Context(_Released):
         w = self.empty((n, 8), np.float64) if weights_out is None else self._out(weights_out, (n, 8))
         if ids.shape != (n, 8) or w.shape != (n, 8):
             raise ValueError("ids_out must be i64[N, 8] and weights_out f64[N, 8]")
-        lld = self.empty((n, 3), np.float64) if latlondepth else None
-        miss = check(self.lib.mm_grid_operator(self.handle, pts.ptr, n, d.ptr, d.shape[0], la.ptr, la.shape[0], lo.ptr,
-                                               lo.shape[0], 1 if lon_periodic else 0, 1 if clamp else 0, ids.ptr, w.ptr,
-                                               lld.ptr if lld else None), "mm_grid_operator")
-        if latlondepth:
-            return ids, w, int(miss), lld
-        return ids, w, int(miss)
+        lld = self._wanted(latlondepth, (n, 3))
+        miss = self._call("mm_grid_operator", pts, n, d, d.shape[0], la, la.shape[0], lo, lo.shape[0], bool(lon_periodic),
+                          bool(clamp), ids, w, lld)
+        return (ids, w, int(miss), lld) if latlondepth else (ids, w, int(miss))
 
     def interpolate_hex8(self, nodes, connectivity, points, fields, nelem_to_search=20, want_operator=False,
                          out=None):
@@ -1300,19 +1281,15 @@ class Context(_Released):
         nod = self.asdevice(nodes, np.float64)
         conn = self.asdevice(connectivity, np.int64)
         pts, f, out, enc, w = _hex8_arrays(self, nod.shape[0], points, fields, want_operator, out)
-        nf = check(self.lib.mm_interpolate_hex8(self.handle, nod.ptr, nod.shape[0], conn.ptr, conn.shape[0],
-                                                pts.ptr, pts.shape[0], f.ptr, f.shape[0], nelem_to_search, out.ptr,
-                                                enc.ptr if enc else None, w.ptr if w else None),
-                   "mm_interpolate_hex8")
+        nf = self._call("mm_interpolate_hex8", nod, nod.shape[0], conn, conn.shape[0], pts, pts.shape[0], f, f.shape[0],
+                        nelem_to_search, out, enc, w)
         return _with_operator(want_operator, out, enc, w, nf)
 
     def source(self, nodes, connectivity):
         """Keep a hex8 source mesh resident (centroids + search grid built once): :class:`Source`."""
         nod = self.asdevice(nodes, np.float64)
         conn = self.asdevice(connectivity, np.int64)
-        h = C.c_void_p()
-        check(self.lib.mm_source_create(self.handle, nod.ptr, nod.shape[0], conn.ptr, conn.shape[0], C.byref(h)), "mm_source_create")
-        return Source(self, h.value, nod, conn)
+        return Source(self, self._create("mm_source_create", nod, nod.shape[0], conn, conn.shape[0]), nod, conn)
 
     def interpolate_hex8_host(self, nodes, connectivity, points, fields, nelem_to_search=20, want_operator=False,
                               out=None):
@@ -1336,12 +1313,9 @@ class Context(_Released):
             raise ValueError("out must be a C-contiguous f64[N, C] array")
         enc = np.empty((n, 8), dtype=np.int64) if want_operator else None
         w = np.empty((n, 8), dtype=np.float64) if want_operator else None
-        nf = check(self.lib.mm_interpolate_hex8_host(self.handle, nod.ctypes.data, nod.shape[0], conn.ctypes.data,
-                                                     conn.shape[0], pts.ctypes.data, n, f.ctypes.data, ncomp,
-                                                     nelem_to_search, out.ctypes.data,
-                                                     enc.ctypes.data if want_operator else None,
-                                                     w.ctypes.data if want_operator else None),
-                   "mm_interpolate_hex8_host")
+        nf = self._call("mm_interpolate_hex8_host", nod.ctypes.data, nod.shape[0], conn.ctypes.data, conn.shape[0],
+                        pts.ctypes.data, n, f.ctypes.data, ncomp, nelem_to_search, out.ctypes.data,
+                        enc.ctypes.data if want_operator else None, w.ctypes.data if want_operator else None)
         return _with_operator(want_operator, out, enc, w, nf)
 
     # ---- section 8f-4: device passes of the layer-aware drivers ------------------------------------
@@ -1356,8 +1330,7 @@ class Context(_Released):
         ncomp, nelem_out, P = o.shape
         if v.shape[1] != ncomp or inv.size != ids.size * P:
             raise ValueError("need values[U, C], inverse[len(elem_ids) * P], out[C, E, P]")
-        check(self.lib.mm_scatter_elements(self.handle, v.ptr, v.shape[0], ncomp, inv.ptr, ids.ptr, ids.size, P,
-                                           nelem_out, o.ptr), "mm_scatter_elements")
+        self._call("mm_scatter_elements", v, v.shape[0], ncomp, inv, ids, ids.size, P, nelem_out, o)
         return o
 
     def fluid_solid_fix(self, values, previous, solid, vs_index):
@@ -1370,8 +1343,7 @@ class Context(_Released):
         nelem, ncomp, P = v.shape
         if prev.shape != v.shape or sol.size != nelem:
             raise ValueError("need values[E, C, P], previous[E, C, P], solid[E]")
-        return int(check(self.lib.mm_fluid_solid_fix(self.handle, v.ptr, prev.ptr, sol.ptr, nelem, ncomp, P, int(vs_index)),
-                         "mm_fluid_solid_fix"))
+        return int(self._call("mm_fluid_solid_fix", v, prev, sol, nelem, ncomp, P, int(vs_index)))
 
     # ---- Earth meshes onto their 1-D sphere (reference interpolator.py:1085-1144) ------------------------------
     def _points3(self, points):
@@ -1386,8 +1358,7 @@ class Context(_Released):
         referenced (the reference would fail there with an index error) or an entry lies outside [0, nnodes)."""
         conn = self.asdevice(connectivity, np.int64)
         first = self.empty((int(nnodes),), np.int64)
-        rc = self.lib.mm_first_occurrence(self.handle, conn.ptr, conn.size, int(nnodes), first.ptr)
-        unreferenced = self._check_args(rc, "mm_first_occurrence")
+        unreferenced = self._call_args("mm_first_occurrence", conn, conn.size, int(nnodes), first)
         if unreferenced:
             raise ValueError(f"{unreferenced} nodes are not referenced by the connectivity: z_node_1D has no value "
                              "for them")
@@ -1429,10 +1400,9 @@ class Context(_Released):
                 raise ValueError("out must be a C-contiguous f64 array of the shape of points")
             out = pts if host_out is points else None
         out = self._out(out, pts.shape, "out must have the shape of points", size_only=True)
-        check(self.lib.mm_map_to_sphere(self.handle, pts.ptr, n, r.ptr, r.size, first.ptr if first else None,
-                                        float(r_ref), out.ptr), "mm_map_to_sphere")
+        self._call("mm_map_to_sphere", pts, n, r, r.size, first, float(r_ref), out)
         if host_out is not None:      # a NumPy ``out`` (``points`` itself for the in-place map) receives the result
-            check(self.lib.mm_copy_d2h(self.handle, host_out.ctypes.data, out.ptr, host_out.nbytes), "mm_copy_d2h")
+            self._call("mm_copy_d2h", host_out.ctypes.data, out, host_out.nbytes)
             return host_out
         return out
 
@@ -1442,8 +1412,7 @@ class Context(_Released):
         pts, n = self._points3(points)
         r, first = self._radius_index(n, rad, connectivity, first)
         out = self.empty(pts.shape[:-1], np.float64)
-        check(self.lib.mm_sphere_ratio(self.handle, pts.ptr, n, r.ptr, r.size, first.ptr if first else None,
-                                       float(r_ref), out.ptr), "mm_sphere_ratio")
+        self._call("mm_sphere_ratio", pts, n, r, r.size, first, float(r_ref), out)
         return out
 
     def scale_points(self, points, factor, out=None):
@@ -1453,7 +1422,7 @@ class Context(_Released):
         if f.size != n:
             raise ValueError("factor needs one value per point")
         out = self._out(out, pts.shape, "out must have the shape of points", size_only=True)
-        check(self.lib.mm_scale_points(self.handle, pts.ptr, n, f.ptr, out.ptr), "mm_scale_points")
+        self._call("mm_scale_points", pts, n, f, out)
         return out
 
     # ---- A11 ----------------------------------------------------------------------------
@@ -1469,20 +1438,14 @@ class Context(_Released):
         inv = self.empty((max(n, 1),), np.int64) if inverse_out is None else self.asdevice(inverse_out, np.int64)
         if uniq.size < n * dim or inv.size < n:
             raise ValueError("unique_out / inverse_out too small: need [N, dim] and [N]")
-        fn = self.lib.mm_unique_points if ordered else self.lib.mm_unique_points_any_order
-        nu = check(fn(self.handle, pts.ptr, n, dim, uniq.ptr, inv.ptr), "mm_unique_points")
+        nu = self._call("mm_unique_points" if ordered else "mm_unique_points_any_order", pts, n, dim, uniq, inv,
+                        what="mm_unique_points")      # (a failure of either has always been reported under this name)
         return uniq.rows(0, int(nu)), inv.rows(0, n)
 
     def close(self):
         if self.handle:
             self.lib.mm_context_destroy(self.handle)
         self.handle = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 _default = {}

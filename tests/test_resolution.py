@@ -116,10 +116,7 @@ def test_the_modules_surface():
     assert resolution.ModelCheck.__doc__ and resolution.ModelCheck.ok.__doc__
     from multimesh_amd.device import Context
     for name in ("gll_resolution", "arg_extreme"):
-        assert (getattr(Context, name).__doc__ or "").strip(), name
-    assert str(inspect.signature(Context.gll_resolution)) == \
-        "(self, shape_order, gll_points, fast=None, slow=None, want_node_spacing=False)"
-    assert str(inspect.signature(Context.arg_extreme)) == "(self, values, want_max=False)"
+        assert (getattr(Context, name).__doc__ or "").strip(), name     # (signatures: tests/test_device_calls.py)
 
 
 def test_the_binding_layer_knows_the_two_symbols():

@@ -4,7 +4,8 @@ boundary and the blend of a regional model into a larger one -- on the GPU, on a
 (include/multimesh_hip.h: mm_boundary_faces, mm_boundary_classify, mm_boundary_nodes, mm_cutoff_distance,
 mm_distance_taper).  Imported explicitly (``from multimesh_amd import boundary``); the reference has no counterpart.
 
-The distance is to the nearest boundary NODE, not to the boundary surface: its resolution is the node spacing of the faces.
+The distance is to the nearest boundary NODE, not to the boundary surface: its resolution is the node spacing of the faces
+(:mod:`multimesh_amd.surface` has the distance to the faces themselves, with the same tools on top of it).
 3-D meshes only."""
 from __future__ import annotations
 
@@ -163,6 +164,39 @@ def taper_to_boundary(mesh, params, inner, outer, sides=("side", "bottom"), boun
     return out.numpy().reshape(fields.shape), ntapered
 
 
+def _node_distance(ctx, bnd, points, mask, cutoff):
+    """The distance step of this module: to the nearest node of ``bnd``'s faces of ``mask``, up to ``cutoff``, on the device."""
+    return ctx.cutoff_distance(points, bnd._nodes(mask), max(cutoff, _MIN_CUTOFF))[0]
+
+
+def _blend(distance, regional, host, params, inner, outer, sides, nelem_to_search, tolerance, context):
+    """:func:`blend_models` with the distance step as an argument: ``distance(ctx, boundary, points, mask, outer)`` gives
+    the device array f64[U] that drives the weight (multimesh_amd.surface passes the distance to the faces themselves)."""
+    inner, outer = _radii(inner, outer)
+    mask = _side_mask(sides)
+    gp_r, order_r = _gll_points_order(regional)
+    gp_h, _ = _gll_points_order(host)
+    if gp_r.shape[2] != 3 or gp_h.shape[2] != 3:
+        raise ValueError("3-D meshes only")
+    names, f_r = _mesh_fields(regional, params)
+    _, f_h = _mesh_fields(host, names)
+    ctx = context or default_context()
+    bnd = mesh_boundary(regional, context=ctx)
+    uniq, inv = ctx.unique_points(gp_h.reshape(-1, 3), ordered=False)
+    vals, elem, _, _ = ctx.interpolate_gll(order_r, bnd._points, uniq, f_r, nelem_to_search=nelem_to_search,
+                                           tolerance=tolerance, want_operator=True)
+    dist = distance(ctx, bnd, uniq, mask, outer)
+    inverse = inv.numpy()
+    shape = gp_h.shape[:2]
+    a = _scatter_back(vals.numpy(), inverse, f_h.shape)
+    out, _, w = ctx.distance_taper(dist.numpy()[inverse].reshape(shape), inner, outer, a, b=f_h,
+                                   elem=elem.numpy()[inverse].reshape(shape), want_weight=True)
+    w = w.numpy()
+    info = {"nlocated": int((elem.numpy()[inverse] >= 0).sum()), "nblended": int(((w > 0.0) & (w < 1.0)).sum()),
+            "nreplaced": int((w == 1.0).sum())}
+    return out.numpy().reshape(f_h.shape), info
+
+
 def blend_models(regional, host, params, inner, outer, sides=("side", "bottom"), nelem_to_search=20, tolerance=1.05,
                  context=None):
     """A regional model put inside a larger one without a step along the region's outline: ``(values f64[C, E_h, P_h],
@@ -178,26 +212,4 @@ def blend_models(regional, host, params, inner, outer, sides=("side", "bottom"),
     ``info = {"nlocated", "nblended", "nreplaced"}``: the host's element-nodal nodes inside a regional element, those with
     0 < w < 1 and those with w == 1.  The default ``sides`` leave the free surface ("top") alone: the regional model
     reaches the surface at full weight."""
-    inner, outer = _radii(inner, outer)
-    mask = _side_mask(sides)
-    gp_r, order_r = _gll_points_order(regional)
-    gp_h, _ = _gll_points_order(host)
-    if gp_r.shape[2] != 3 or gp_h.shape[2] != 3:
-        raise ValueError("3-D meshes only")
-    names, f_r = _mesh_fields(regional, params)
-    _, f_h = _mesh_fields(host, names)
-    ctx = context or default_context()
-    bnd = mesh_boundary(regional, context=ctx)
-    uniq, inv = ctx.unique_points(gp_h.reshape(-1, 3), ordered=False)
-    vals, elem, _, _ = ctx.interpolate_gll(order_r, bnd._points, uniq, f_r, nelem_to_search=nelem_to_search,
-                                           tolerance=tolerance, want_operator=True)
-    dist, _ = ctx.cutoff_distance(uniq, bnd._nodes(mask), max(outer, _MIN_CUTOFF))
-    inverse = inv.numpy()
-    shape = gp_h.shape[:2]
-    a = _scatter_back(vals.numpy(), inverse, f_h.shape)
-    out, _, w = ctx.distance_taper(dist.numpy()[inverse].reshape(shape), inner, outer, a, b=f_h,
-                                   elem=elem.numpy()[inverse].reshape(shape), want_weight=True)
-    w = w.numpy()
-    info = {"nlocated": int((elem.numpy()[inverse] >= 0).sum()), "nblended": int(((w > 0.0) & (w < 1.0)).sum()),
-            "nreplaced": int((w == 1.0).sum())}
-    return out.numpy().reshape(f_h.shape), info
+    return _blend(_node_distance, regional, host, params, inner, outer, sides, nelem_to_search, tolerance, context)

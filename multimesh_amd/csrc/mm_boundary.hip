@@ -33,26 +33,12 @@
 // from x - lo, one correctly rounded difference, so its error is relative to the offset within the box and NOT to |x|: a
 // mesh at 6.3e6 m needs no absolute term.  Capping the cells only enlarges H.  A target whose index falls outside
 // [-1, dims] on an axis -- or is a NaN -- is more than H from every source and keeps the cutoff at once.
-#include "mm_stream.h"
-
-#include <math.h>
-#include <string.h>
+#include "mm_boundary_parts.h"   // shared with mm_surface.hip: launch shape, counter words, grid caps, select and box kernels
 
 namespace {
 
-using namespace mm_stream;   // kThreads, kWave
-typedef unsigned long long u64;
-constexpr i64 kMaxBlocks = 2048;           // 256 CUs x 8 workgroups; grid-stride beyond
 constexpr unsigned kNoSlot = 0xffffffffu;  // slot_of of a face with an id out of range
-constexpr int kSlot = 16, kWords = 8;      // the unit's words of mm_context::d_counters (mm_common.h)
-constexpr int kMaxDim = 1024;              // cells per axis of the cutoff grid
-constexpr i64 kMaxCells = (i64)1 << 22;    // ... and in all
 constexpr double kEdgeMargin = 1.0 + 0x1p-30;
-constexpr double kMinCutoff = 0x1p-500;
-
-unsigned stream_grid(i64 n) { return mm_blocks(n, kThreads, kMaxBlocks); }
-
-__device__ __forceinline__ bool is_finite(double v) { return fabs(v) < __builtin_inf(); }
 
 __device__ __forceinline__ u64 mix64(u64 h)
 {
@@ -213,21 +199,7 @@ __global__ __launch_bounds__(kThreads) void classify_kernel(const ClassifyArgs a
 }
 
 // ------------------------------------------------------------------------------------------------ mm_boundary_nodes
-// flag[b] = face b is selected; *bad counts the codes outside [0, 6 nelem) and the sides outside [0, 2]
-__global__ __launch_bounds__(kThreads) void select_kernel(const i64 *__restrict__ faces, const int *__restrict__ side, i64 nb,
-                                                          i64 nelem, int side_mask, int *__restrict__ flag, u64 *bad)
-{
-    unsigned mine = 0;
-    const i64 stride = (i64)gridDim.x * blockDim.x;
-    for (i64 b = (i64)blockIdx.x * blockDim.x + threadIdx.x; b < nb; b += stride) {
-        const int s = side ? side[b] : 0;
-        const bool ok = (u64)faces[b] < (u64)(6 * nelem) && s >= 0 && s <= 2;
-        mine += !ok;
-        flag[b] = ok && (side == nullptr || ((side_mask >> s) & 1)) ? 1 : 0;
-    }
-    mm_count_to(bad, mine);
-}
-
+// (select_kernel: mm_boundary_parts.h)
 // one lane per node of a face: item = b * m^2 + q, q = lo + m * hi over the face's two free axes
 __global__ __launch_bounds__(kThreads) void nodes_emit_kernel(const double *__restrict__ points, int m, const i64 *__restrict__ faces,
                                                               i64 nb, const int *__restrict__ flag, const int *__restrict__ rank,
@@ -252,43 +224,7 @@ __global__ __launch_bounds__(kThreads) void nodes_emit_kernel(const double *__re
 }
 
 // ----------------------------------------------------------------------------------------------- mm_cutoff_distance
-// The unsigned order of key_of(bits) is the numeric order of the doubles (mm_precondition.hip's select uses the same key).
-__device__ __host__ __forceinline__ u64 key_of(u64 u) { return (u >> 63) ? ~u : (u | ((u64)1 << 63)); }
-__device__ __host__ __forceinline__ u64 bits_of_key(u64 k) { return (k >> 63) ? (k & ~((u64)1 << 63)) : ~k; }
-
-// words[1] += the sources with a coordinate that is not finite; words[2 + a] = max of ~key(x_a) (the minimum),
-// words[5 + a] = max of key(x_a): integer maxima of the finite coordinates, zero on entry
-__global__ __launch_bounds__(kThreads) void sources_box_kernel(const double *__restrict__ src, i64 K, u64 *words)
-{
-    const double inf = __builtin_inf();
-    double b[6] = {inf, -inf, inf, -inf, inf, -inf};
-    unsigned mine = 0;
-    const i64 stride = (i64)gridDim.x * blockDim.x;
-    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < K; j += stride) {
-        const double x[3] = {src[3 * j], src[3 * j + 1], src[3 * j + 2]};
-        if (is_finite(x[0]) && is_finite(x[1]) && is_finite(x[2])) {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) b[2 * a] = fmin(b[2 * a], x[a]), b[2 * a + 1] = fmax(b[2 * a + 1], x[a]);
-        } else {
-            ++mine;
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-        for (int off = kWave / 2; off > 0; off >>= 1) {
-            const double o = __shfl_xor(b[a], off, kWave);
-            b[a] = (a & 1) ? fmax(b[a], o) : fmin(b[a], o);
-        }
-    if ((threadIdx.x & (kWave - 1)) == 0 && b[0] <= b[1]) {   // (the wave has seen a finite source)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            atomicMax(words + 2 + a, ~key_of((u64)__double_as_longlong(b[2 * a])));
-            atomicMax(words + 5 + a, key_of((u64)__double_as_longlong(b[2 * a + 1])));
-        }
-    }
-    mm_count_to(words + 1, mine);
-}
-
+// (sources_box_kernel and the order-preserving key of a double: mm_boundary_parts.h)
 struct CellGrid {
     double lo[3], inv_h;
     int dims[3];
@@ -554,14 +490,10 @@ extern "C" int64_t mm_cutoff_distance(mm_context *ctx, const double *points_d, i
             mm_set_error(MM_ERR_ARG, "mm_cutoff_distance: %lld sources are not finite", (long long)got[1]);
             return MM_ERR_ARG;
         }
-        double extent[3];
+        double extent[3], hi[3];
+        box_of_words(got, g.lo, hi);
         for (int a = 0; a < 3; ++a) {
-            const u64 lo_bits = bits_of_key(~(u64)got[2 + a]), hi_bits = bits_of_key((u64)got[5 + a]);
-            double lo, hi;
-            memcpy(&lo, &lo_bits, sizeof(double));
-            memcpy(&hi, &hi_bits, sizeof(double));
-            g.lo[a] = lo;
-            extent[a] = hi - lo;
+            extent[a] = hi[a] - g.lo[a];
             MM_REQUIRE(extent[a] < __builtin_inf(), "the sources' extent overflows");
         }
         // the edge: above the cutoff by the margin, enlarged until the grid fits its caps (a larger edge keeps the search valid)

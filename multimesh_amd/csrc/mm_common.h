@@ -220,7 +220,8 @@ void mm_stage_end(mm_context *ctx, int stage);
 
 // Slots of mm_context::d_counters (64 x i64, zeroed when the context is created) / its pinned mirror h_counters:
 //   0 failed / missing points of the call    1 mm_layers' counter    8..15 the hex8 locate stage's 16 counters
-//   16..23 mm_boundary.hip's counts and the sources' bounding box of mm_cutoff_distance
+//   16..23 mm_boundary.hip's and mm_surface.hip's counts and the bounding box of mm_cutoff_distance / mm_surface_distance
+//   28..29 mm_surface_distance: the entries of its grid, the median exponent of the triangles' extents
 //   32..47 the grid statistic                48..53 (h_counters) the sources' bounding box
 // ("The last workgroup of a launch finishes the reduction" was tried for the bounding box and the scans and
 // measured: on this multi-XCD part the device-scope fence every workgroup needs before it takes its ticket writes

@@ -130,12 +130,11 @@ def distance_to_boundary(mesh_or_points, boundary, cutoff, sides=("side", "botto
     minimum of ``sqrt((dx*dx + dy*dy) + dz*dz)``.  The distance is to the nearest boundary node, so its resolution is the
     node spacing.  The default ``sides`` leave the free surface ("top") out.  The call runs on the boundary's own context:
     ``context`` is that one or ``None`` (``ValueError`` otherwise)."""
-    if not isinstance(boundary, Boundary):
-        raise ValueError("boundary must come from mesh_boundary")
+    bnd = _boundary_of(boundary)
     cutoff, mask = _cutoff(cutoff), _side_mask(sides)
     pts = points_of(mesh_or_points)                       # ([..., 3]: cutoff_distance refuses anything else)
-    ctx = boundary._context(context)
-    return ctx.cutoff_distance(pts, boundary._nodes(mask), cutoff)[0].numpy()
+    ctx = bnd._context(context)
+    return ctx.cutoff_distance(pts, bnd._nodes(mask), cutoff)[0].numpy()
 
 
 def _radii(inner, outer):
@@ -152,21 +151,33 @@ def taper_to_boundary(mesh, params, inner, outer, sides=("side", "bottom"), boun
     The boundary's own nodes get exactly 0; nodes beyond ``outer`` keep their bits.  ``boundary``: what
     :func:`mesh_boundary` returned for this mesh (``None``: computed here, with radial up; given: ``context`` is its own or ``None``).  The default ``sides`` leave the
     free surface ("top") alone: a kernel is damped towards absorbing sides and bottom, not towards the surface."""
+    return _taper(_node_distance, mesh, params, inner, outer, sides, boundary, context)
+
+
+def _boundary_of(boundary):
+    """``boundary`` itself; anything that :func:`mesh_boundary` did not return is refused."""
+    if not isinstance(boundary, Boundary):
+        raise ValueError("boundary must come from mesh_boundary")
+    return boundary
+
+
+def _node_distance(ctx, bnd, points, mask, cutoff):
+    """The distance step of this module: to the nearest node of ``bnd``'s faces of ``mask``, up to ``cutoff``, on the device."""
+    return ctx.cutoff_distance(points, bnd._nodes(mask), max(cutoff, _MIN_CUTOFF))[0]
+
+
+def _taper(distance, mesh, params, inner, outer, sides, boundary, context):
+    """:func:`taper_to_boundary` with the distance step as an argument, as :func:`_blend` has it."""
     inner, outer = _radii(inner, outer)
     mask = _side_mask(sides)
     pts = points_of(mesh)
     _, fields = named_fields(mesh, params)
     if boundary is None:
         boundary = mesh_boundary(mesh, context=context)
-    ctx = boundary._context(context)
-    dist, _ = ctx.cutoff_distance(pts, boundary._nodes(mask), max(outer, _MIN_CUTOFF))
+    ctx = _boundary_of(boundary)._context(context)
+    dist = distance(ctx, boundary, pts, mask, outer)
     out, ntapered = ctx.distance_taper(dist, inner, outer, fields.reshape(fields.shape[0], -1))
     return out.numpy().reshape(fields.shape), ntapered
-
-
-def _node_distance(ctx, bnd, points, mask, cutoff):
-    """The distance step of this module: to the nearest node of ``bnd``'s faces of ``mask``, up to ``cutoff``, on the device."""
-    return ctx.cutoff_distance(points, bnd._nodes(mask), max(cutoff, _MIN_CUTOFF))[0]
 
 
 def _blend(distance, regional, host, params, inner, outer, sides, nelem_to_search, tolerance, context):

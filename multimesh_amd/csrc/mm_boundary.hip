@@ -13,8 +13,9 @@
 // and the counts returned are integer sums; the order of the sources within a cell is free because a minimum has none.
 //
 // Conventions (include/multimesh_hip.h): corner c = i + 2 j + 4 k; local face f = 2 * axis + side; face code 6 e + f.
-// With a the face's axis and p < q the two others, the face's corners are ((f & 1) << a) | (i << p) | (j << q) for (i, j) =
-// (0,0), (1,0), (0,1), (1,1) in ascending order and (0,0), (1,0), (1,1), (0,1) in cyclic order.
+// mm_boundary_parts.h states the decoding of a code and the node of a face position once (face_of, face_node); a face's
+// corners are its nodes at m = 2: (i, j) = (0,0), (1,0), (0,1), (1,1) in ascending order, (0,0), (1,0), (1,1), (0,1) in
+// cyclic order.
 //
 // The faces.  A table of face indices with twice as many slots as faces (a power of two): a face hashes its sorted ids,
 // claims an empty slot with one compare-and-swap or, where the slot is taken, compares its ids with the claimant's (read
@@ -23,7 +24,8 @@
 // come out ascending whatever the atomics did.
 //
 // The cutoff search and its margin (DESIGN.md section 5 has the derivation in full).  Cells of edge H > cutoff over the
-// sources' bounding box, index floor(fl(fl(x - lo) * inv_h)) per axis with H = 1 / inv_h; a target looks at the 27 cells
+// sources' bounding box -- the search grid, its fit to the caps and its bins are mm_surface.hip's too: mm_search_grid.h,
+// mm_boundary_parts.h --, index floor(fl(fl(x - lo) * inv_h)) per axis with H = 1 / inv_h; a target looks at the 27 cells
 // around its own.  Writing u = 2^-53: a source whose ROUNDED r is below cutoff has a true offset below cutoff * (1 + 4 u) on
 // every axis (three roundings under the root, the root, the difference; with cutoff >= 2^-500 the squares' underflow is
 // below 2^-73 of that).  The index argument v(x) = (x - lo) / H * (1 + delta), |delta| <= 2.01 u, is monotone in x, and
@@ -33,29 +35,13 @@
 // from x - lo, one correctly rounded difference, so its error is relative to the offset within the box and NOT to |x|: a
 // mesh at 6.3e6 m needs no absolute term.  Capping the cells only enlarges H.  A target whose index falls outside
 // [-1, dims] on an axis -- or is a NaN -- is more than H from every source and keeps the cutoff at once.
-#include "mm_boundary_parts.h"   // shared with mm_surface.hip: launch shape, counter words, grid caps, select and box kernels
+#include "mm_boundary_parts.h"   // shared with mm_surface.hip: launch shape, counter words, faces, box, search grid
+#include "mm_hash.h"
 
 namespace {
 
 constexpr unsigned kNoSlot = 0xffffffffu;  // slot_of of a face with an id out of range
 constexpr double kEdgeMargin = 1.0 + 0x1p-30;
-
-__device__ __forceinline__ u64 mix64(u64 h)
-{
-    h ^= h >> 33;
-    h *= 0xff51afd7ed558ccdull;
-    h ^= h >> 33;
-    h *= 0xc4ceb9fe1a85ec53ull;
-    h ^= h >> 33;
-    return h;
-}
-
-// corner (i, j) of local face f: (0,0), (1,0), (0,1), (1,1) ascend; (0,0), (1,0), (1,1), (0,1) go round
-__device__ __forceinline__ int face_corner(int f, int i, int j)
-{
-    const int a = f >> 1, p = a == 0 ? 1 : 0, q = a == 2 ? 1 : 2;
-    return ((f & 1) << a) | (i << p) | (j << q);
-}
 
 __device__ __forceinline__ void order2(unsigned &a, unsigned &b)
 {
@@ -66,12 +52,11 @@ __device__ __forceinline__ void order2(unsigned &a, unsigned &b)
 // the four corner ids of face g = 6 e + f, sorted; false when one lies outside [0, nnodes) (nnodes < 2^31)
 __device__ __forceinline__ bool face_key(const i64 *__restrict__ ids, i64 g, i64 nnodes, unsigned (&k)[4])
 {
-    const i64 e = g / 6;
-    const int f = (int)(g - 6 * e);
+    const Face face = face_of(g, 2);
     bool ok = true;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-        const i64 id = ids[8 * e + face_corner(f, c & 1, c >> 1)];
+        const i64 id = ids[8 * face.e + face_node(face.a, face.fix, 2, c & 1, c >> 1)];
         ok = ok && (u64)id < (u64)nnodes;
         k[c] = (unsigned)id;
     }
@@ -95,7 +80,7 @@ __global__ __launch_bounds__(kThreads) void faces_insert_kernel(const i64 *__res
             slot_of[g] = kNoSlot;
             continue;
         }
-        unsigned s = (unsigned)mix64(((u64)k[0] | ((u64)k[1] << 32)) ^ mix64(((u64)k[2] | ((u64)k[3] << 32)) + 0x9e3779b97f4a7c15ull)) & mask;
+        unsigned s = (unsigned)mm_mix64(((u64)k[0] | ((u64)k[1] << 32)) ^ mm_mix64(((u64)k[2] | ((u64)k[3] << 32)) + 0x9e3779b97f4a7c15ull)) & mask;
         for (;;) {
             int cur = __atomic_load_n(&table[s], __ATOMIC_RELAXED);
             if (cur == 0) {
@@ -168,14 +153,14 @@ __global__ __launch_bounds__(kThreads) void classify_kernel(const ClassifyArgs a
     if (*args.bad != 0) return;
     const i64 stride = (i64)gridDim.x * blockDim.x;
     for (i64 b = (i64)blockIdx.x * blockDim.x + threadIdx.x; b < args.nb; b += stride) {
-        const i64 code = args.faces[b], e = code / 6;
-        const int f = (int)(code - 6 * e);
-        const double *X = args.corners + 24 * e;
+        const Face face = face_of(args.faces[b], 2);
+        const double *X = args.corners + 24 * face.e;
+        const int c0 = face_node(face.a, face.fix, 2, 0, 0), c1 = face_node(face.a, face.fix, 2, 1, 0);   // round the face
+        const int c2 = face_node(face.a, face.fix, 2, 1, 1), c3 = face_node(face.a, face.fix, 2, 0, 1);
         double n[3], g[3], u[3], av[3], bv[3], fc[3], ec[3];
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
-            const double q0 = X[3 * face_corner(f, 0, 0) + a], q1 = X[3 * face_corner(f, 1, 0) + a];
-            const double q2 = X[3 * face_corner(f, 1, 1) + a], q3 = X[3 * face_corner(f, 0, 1) + a];
+            const double q0 = X[3 * c0 + a], q1 = X[3 * c1 + a], q2 = X[3 * c2 + a], q3 = X[3 * c3 + a];
             av[a] = q2 - q0;
             bv[a] = q3 - q1;
             fc[a] = ((q0 + q1) + (q2 + q3)) * 0.25;
@@ -199,78 +184,33 @@ __global__ __launch_bounds__(kThreads) void classify_kernel(const ClassifyArgs a
 }
 
 // ------------------------------------------------------------------------------------------------ mm_boundary_nodes
-// (select_kernel: mm_boundary_parts.h)
-// one lane per node of a face: item = b * m^2 + q, q = lo + m * hi over the face's two free axes
-__global__ __launch_bounds__(kThreads) void nodes_emit_kernel(const double *__restrict__ points, int m, const i64 *__restrict__ faces,
-                                                              i64 nb, const int *__restrict__ flag, const int *__restrict__ rank,
-                                                              double *__restrict__ out, u64 *counters)
-{
-    if (blockIdx.x == 0 && threadIdx.x == 0) counters[1] = (u64)rank[nb];   // the selected faces
-    if (counters[0] != 0) return;   // (a refused call writes no node)
-    const int mm = m * m;
-    const i64 P = (i64)mm * m, nitems = nb * mm;
-    const i64 stride = (i64)gridDim.x * blockDim.x;
-    for (i64 item = (i64)blockIdx.x * blockDim.x + threadIdx.x; item < nitems; item += stride) {
-        const i64 b = item / mm;
-        if (!flag[b]) continue;
-        const int q = (int)(item - b * mm), lo = q % m, hi = q / m;
-        const i64 code = faces[b], e = code / 6;
-        const int f = (int)(code - 6 * e), a = f >> 1, fix = (f & 1) * (m - 1);
-        const int p = a == 0 ? fix + m * lo + mm * hi : (a == 1 ? lo + m * fix + mm * hi : lo + m * hi + mm * fix);
-        const double *src = points + 3 * (e * P + p);
-        double *dst = out + 3 * ((i64)rank[b] * mm + q);
+// (select_kernel, face_items_kernel and their driver: mm_boundary_parts.h)
+// the (order + 1)^2 nodes of a face: k = lo + m * hi over the face's two free axes
+struct NodeItems {
+    static constexpr int kDoubles = 3;
+    __host__ __device__ static int per_face(int m) { return m * m; }
+    __device__ static void write(const double *__restrict__ X, int m, const Face &face, int k, double *__restrict__ dst)
+    {
+        const double *src = X + 3 * face_node(face.a, face.fix, m, k % m, k / m);
         dst[0] = src[0], dst[1] = src[1], dst[2] = src[2];
     }
-}
-
-// ----------------------------------------------------------------------------------------------- mm_cutoff_distance
-// (sources_box_kernel and the order-preserving key of a double: mm_boundary_parts.h)
-struct CellGrid {
-    double lo[3], inv_h;
-    int dims[3];
 };
 
-// the cell of a source: 0 <= x - lo, and the index stays below dims; the clamp only guards the memory
-__device__ __forceinline__ int source_cell(const CellGrid &g, double x, double y, double z)
-{
-    int c[3];
-    const double p[3] = {x, y, z};
+// ----------------------------------------------------------------------------------------------- mm_cutoff_distance
+// (sources_box_kernel, the search grid and its bins: mm_boundary_parts.h)
+// a source is a record of its own in the one cell that holds it
+struct PointBins {
+    static constexpr int kDoubles = 3;
+    __device__ static void cells(const Grid &g, const double *__restrict__ s, int (&c0)[3], int (&c1)[3])
+    {
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double v = floor((p[a] - g.lo[a]) * g.inv_h);
-        const int i = v >= 0.0 ? (v < (double)g.dims[a] ? (int)v : g.dims[a] - 1) : 0;
-        c[a] = i;
+        for (int a = 0; a < 3; ++a) c0[a] = c1[a] = grid_cell(g, a, s[a]);
     }
-    return (c[2] * g.dims[1] + c[1]) * g.dims[0] + c[0];
-}
-
-__global__ __launch_bounds__(kThreads) void cells_count_kernel(const double *__restrict__ src, i64 K, const CellGrid g,
-                                                               int *__restrict__ cell_of, int *__restrict__ count)
-{
-    const i64 stride = (i64)gridDim.x * blockDim.x;
-    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < K; j += stride) {
-        const int c = source_cell(g, src[3 * j], src[3 * j + 1], src[3 * j + 2]);
-        cell_of[j] = c;
-        atomicAdd(&count[c], 1);
-    }
-}
-
-// count[c] runs down to zero while the cell's sources take their places: any order, the minimum has none
-__global__ __launch_bounds__(kThreads) void cells_scatter_kernel(const double *__restrict__ src, i64 K, const int *__restrict__ cell_of,
-                                                                 const int *__restrict__ start, int *__restrict__ count,
-                                                                 double *__restrict__ sorted)
-{
-    const i64 stride = (i64)gridDim.x * blockDim.x;
-    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < K; j += stride) {
-        const int c = cell_of[j];
-        const i64 at = (i64)start[c] + (atomicSub(&count[c], 1) - 1);
-        sorted[3 * at] = src[3 * j], sorted[3 * at + 1] = src[3 * j + 1], sorted[3 * at + 2] = src[3 * j + 2];
-    }
-}
+};
 
 // start == nullptr: no sources, every distance is the cutoff
 __global__ __launch_bounds__(kThreads) void cutoff_query_kernel(const double *__restrict__ pts, i64 n, const double *__restrict__ sorted,
-                                                                const int *__restrict__ start, const CellGrid g, double cutoff,
+                                                                const int *__restrict__ start, const Grid g, double cutoff,
                                                                 double *__restrict__ dist, u64 *count)
 {
     unsigned mine = 0;
@@ -279,7 +219,8 @@ __global__ __launch_bounds__(kThreads) void cutoff_query_kernel(const double *__
     for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const double x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
         double d = cutoff;
-        const double vx = floor((x - g.lo[0]) * g.inv_h), vy = floor((y - g.lo[1]) * g.inv_h), vz = floor((z - g.lo[2]) * g.inv_h);
+        // the UNCLAMPED index, not grid_cell: the test against [-1, dims] below is the margin argument's own statement
+        const double vx = floor(grid_coord(g, 0, x)), vy = floor(grid_coord(g, 1, y)), vz = floor(grid_coord(g, 2, z));
         // (a NaN fails the test: a point with a NaN coordinate keeps the cutoff)
         if (start && vx >= -1.0 && vx <= (double)dx && vy >= -1.0 && vy <= (double)dy && vz >= -1.0 && vz <= (double)dz) {
             const int cx = (int)vx, cy = (int)vy, cz = (int)vz;
@@ -288,7 +229,7 @@ __global__ __launch_bounds__(kThreads) void cutoff_query_kernel(const double *__
             const int z0 = cz > 0 ? cz - 1 : 0, z1 = cz + 1 < dz ? cz + 1 : dz - 1;
             for (int kz = z0; kz <= z1; ++kz)
                 for (int ky = y0; ky <= y1; ++ky) {
-                    const int row = (kz * dy + ky) * dx;   // (the row's cells x0 .. x1 are one run of sources)
+                    const int row = grid_index(g, 0, ky, kz);   // (the row's cells x0 .. x1 are one run of sources)
                     const int b = start[row + x0], e = start[row + x1 + 1];
                     const double *s = sorted + 3 * (i64)b;   // (64-bit: 3 * K passes 2^31)
                     for (int j = b; j < e; ++j, s += 3) {
@@ -431,39 +372,7 @@ extern "C" int mm_boundary_classify(mm_context *ctx, const double *corners_d, in
 extern "C" int64_t mm_boundary_nodes(mm_context *ctx, const double *points_d, int64_t nelem, int order, const int64_t *faces_d,
                                      const int *side_d, int64_t nb, int side_mask, double *out_d)
 {
-    MM_REQUIRE(ctx != nullptr, "ctx is null");
-    MM_REQUIRE(order == 1 || order == 2 || order == 4, "order must be 1, 2 or 4");
-    MM_REQUIRE(nelem >= 0 && nelem < ((i64)1 << 27), "nelem must lie in [0, 2^27)");
-    MM_REQUIRE(nb >= 0 && nb <= 6 * nelem, "nb must lie in [0, 6 nelem]");
-    MM_REQUIRE(side_mask >= 0 && side_mask <= 7, "side_mask must lie in [0, 7]");
-    MM_REQUIRE(nb == 0 || (points_d != nullptr && faces_d != nullptr && out_d != nullptr), "null array");
-    MM_HIP_CHECK(hipSetDevice(ctx->device));
-    if (nb == 0) return 0;
-    const int m = order + 1;
-    int *flag, *rank, *tile_sums;
-    mm_scratch_layout lay;
-    lay.add(&flag, (size_t)nb + 1);
-    lay.add(&rank, (size_t)nb + 1);
-    lay.add(&tile_sums, mm_scan_scratch_ints(nb));
-    int rc = lay.commit(ctx, __func__);
-    if (rc != MM_OK) return rc;
-    u64 *counters = mm_counters_begin(ctx, kSlot, 2);   // [0] bad codes or sides, [1] the selected faces
-    if (!counters) return MM_ERR_HIP;
-    hipLaunchKernelGGL(select_kernel, dim3(stream_grid(nb)), dim3(kThreads), 0, ctx->stream, (const i64 *)faces_d, side_d, (i64)nb,
-                       (i64)nelem, side_mask, flag, counters);
-    MM_HIP_CHECK(hipGetLastError());
-    rc = mm_exclusive_scan_int(ctx, flag, nb, rank, tile_sums);
-    if (rc != MM_OK) return rc;
-    hipLaunchKernelGGL(nodes_emit_kernel, dim3(stream_grid(nb * m * m)), dim3(kThreads), 0, ctx->stream, points_d, m,
-                       (const i64 *)faces_d, (i64)nb, (const int *)flag, (const int *)rank, out_d, counters);
-    const i64 *got = mm_counters_end(ctx, kSlot, 2);
-    if (!got) return MM_ERR_HIP;
-    if (got[0] != 0) {
-        mm_set_error(MM_ERR_ARG, "mm_boundary_nodes: %lld faces have a code outside [0, %lld) or a side outside [0, 2]",
-                     (long long)got[0], (long long)(6 * nelem));
-        return MM_ERR_ARG;
-    }
-    return got[1] * m * m;
+    return selected_face_items<NodeItems>(ctx, __func__, points_d, nelem, order, (const i64 *)faces_d, side_d, nb, side_mask, out_d);
 }
 
 extern "C" int64_t mm_cutoff_distance(mm_context *ctx, const double *points_d, int64_t n, const double *sources_d, int64_t K,
@@ -479,7 +388,7 @@ extern "C" int64_t mm_cutoff_distance(mm_context *ctx, const double *points_d, i
     MM_HIP_CHECK(hipSetDevice(ctx->device));
     u64 *words = mm_counters_begin(ctx, kSlot, kWords);   // [0] points with d < cutoff, [1] bad sources, [2..7] the box
     if (!words) return MM_ERR_HIP;
-    CellGrid g = {{0.0, 0.0, 0.0}, 0.0, {1, 1, 1}};
+    Grid g = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, 1.0, 0.0, 0.0, {1, 1, 1}};
     double *sorted = nullptr;
     int *start = nullptr;
     if (K > 0) {
@@ -490,45 +399,16 @@ extern "C" int64_t mm_cutoff_distance(mm_context *ctx, const double *points_d, i
             mm_set_error(MM_ERR_ARG, "mm_cutoff_distance: %lld sources are not finite", (long long)got[1]);
             return MM_ERR_ARG;
         }
-        double extent[3], hi[3];
-        box_of_words(got, g.lo, hi);
+        double extent[3];
+        box_of_words(got, g.lo, g.hi);
         for (int a = 0; a < 3; ++a) {
-            extent[a] = hi[a] - g.lo[a];
+            extent[a] = g.hi[a] - g.lo[a];
             MM_REQUIRE(extent[a] < __builtin_inf(), "the sources' extent overflows");
         }
         // the edge: above the cutoff by the margin, enlarged until the grid fits its caps (a larger edge keeps the search valid)
-        double h = cutoff * kEdgeMargin;
-        for (;;) {
-            g.inv_h = 1.0 / h;
-            double cells = 1.0;
-            bool fits = true;
-            for (int a = 0; a < 3; ++a) {
-                const double da = floor(extent[a] * g.inv_h) + 2.0;
-                fits = fits && da <= (double)kMaxDim;
-                g.dims[a] = fits ? (int)da : 1;
-                cells *= da;
-            }
-            if (fits && cells <= (double)kMaxCells) break;
-            h *= 1.25;
-        }
-        const i64 ncells = (i64)g.dims[0] * g.dims[1] * g.dims[2];
-        int *cell_of, *count, *tile_sums;
-        mm_scratch_layout lay;
-        lay.add(&sorted, (size_t)K * 3);
-        lay.add(&cell_of, (size_t)K);
-        lay.add(&count, (size_t)ncells + 1);
-        lay.add(&start, (size_t)ncells + 1);
-        lay.add(&tile_sums, mm_scan_scratch_ints(ncells));
-        int rc = lay.commit(ctx, __func__);
+        mm_search_grid_fit(g, extent, cutoff * kEdgeMargin, 2);
+        const int rc = bins_build<PointBins>(ctx, __func__, sources_d, K, K, g, sorted, start);
         if (rc != MM_OK) return rc;
-        if (mm_zero_async(ctx, count, (size_t)(ncells + 1) * sizeof(int)) != MM_OK) return MM_ERR_HIP;
-        const dim3 grid(stream_grid(K)), block(kThreads);
-        hipLaunchKernelGGL(cells_count_kernel, grid, block, 0, ctx->stream, sources_d, (i64)K, g, cell_of, count);
-        MM_HIP_CHECK(hipGetLastError());
-        rc = mm_exclusive_scan_int(ctx, count, ncells, start, tile_sums);
-        if (rc != MM_OK) return rc;
-        hipLaunchKernelGGL(cells_scatter_kernel, grid, block, 0, ctx->stream, sources_d, (i64)K, (const int *)cell_of,
-                           (const int *)start, count, sorted);
     }
     if (n > 0)
         hipLaunchKernelGGL(cutoff_query_kernel, dim3(stream_grid(n)), dim3(kThreads), 0, ctx->stream, points_d, (i64)n,

@@ -32,7 +32,7 @@
 namespace gll {
 
 using mm_stream::kThreads;
-constexpr i64 kMaxBlocks = 2048;   // 256 CUs x 8 resident blocks; blocks stride over the rest
+using mm_stream::kMaxBlocks;   // blocks stride over the rest of the tiles
 
 constexpr int ipow(int b, int e) { return e == 0 ? 1 : b * ipow(b, e - 1); }
 

@@ -29,7 +29,7 @@
 namespace {
 
 using mm_stream::kThreads;
-constexpr i64 kMaxBlocks = 2048;    // 256 CUs x 8 workgroups; the grid-stride loop takes the rest
+using mm_stream::kMaxBlocks;
 constexpr int kAxisLds = 2048;      // doubles of LDS for the three axes together (16 KiB: eight workgroups per CU)
 constexpr double kEarthRadius = 6371000.0;
 constexpr double kRadToDeg = 180.0 / 3.14159265358979323846;

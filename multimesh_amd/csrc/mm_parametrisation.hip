@@ -23,8 +23,7 @@
 
 namespace {
 
-using namespace mm_stream;   // kThreads
-constexpr i64 kMaxBlocks = 2048;    // 256 CUs x 8 workgroups; grid-stride beyond
+using namespace mm_stream;   // kThreads, kMaxBlocks
 constexpr int kMaxComp = MM_PARAM_MAX_COMPONENTS;
 constexpr int kMaxSteps = 4;
 constexpr int kNumParams = 5;
@@ -52,8 +51,6 @@ const int kRoute[kNumParams][kNumParams][kMaxSteps] = {
     {{5, 8, 4, 2}, {5, 8, 4}, {5, 8}, {0}, {5}},
     {{8, 4, 2}, {8, 4}, {8}, {6}, {0}},
 };
-
-__device__ __forceinline__ bool is_finite(double v) { return fabs(v) < __builtin_inf(); }
 
 // ---- the statement, step by step: v holds the step's input on entry and its output on return
 __device__ __forceinline__ void step_forward(int step, double (&v)[kMaxComp])
@@ -248,7 +245,7 @@ __global__ __launch_bounds__(kThreads) void convert_kernel(const ConvertArgs a)
         for (int c = 0; c < kMaxComp; ++c) {
             if (c < a.out.ncomp) {
                 a.out.base[at + a.out.cols[c] * a.out.comp_stride] = v[c];
-                bad = bad || !is_finite(v[c]);
+                bad = bad || !mm_is_finite(v[c]);
             }
         }
         if (bad) ++mine;

@@ -44,9 +44,8 @@
 
 namespace {
 
-using namespace mm_stream;   // kThreads, kWave
+using namespace mm_stream;   // kThreads, kWave, kMaxBlocks
 constexpr int kWaves = kThreads / kWave;
-constexpr i64 kMaxBlocks = 2048;    // 256 CUs x 8 workgroups; grid-stride beyond
 constexpr int kBatch = kThreads;    // centres per batch: one per lane (multimesh_amd.device.POINT_TAPER_BATCH)
 constexpr int kSub = 8;            // lanes that share the nodes of an element for its bounding box
 constexpr i64 kMaxCentres = (i64)1 << 20;
@@ -55,8 +54,6 @@ constexpr int kBins = 256;          // one byte of the key per pass
 constexpr int kPasses = 8;
 constexpr int kSelectLoads = 4;     // values per lane and step of the histogram kernel
 typedef unsigned long long u64;
-
-__device__ __forceinline__ bool is_finite(double v) { return fabs(v) < __builtin_inf(); }
 
 // ---------------------------------------------------------------------------------------------------- mm_point_taper
 // *bad = the number of centres with a non-finite coordinate, a non-finite radius, inner < 0 or outer < inner
@@ -68,8 +65,8 @@ __global__ __launch_bounds__(kThreads) void centres_check_kernel(const double *_
     const int stride = gridDim.x * blockDim.x;
     for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < K; k += stride) {
         const double a = inner[k], b = outer[k];
-        const bool ok = is_finite(centres[3 * k]) && is_finite(centres[3 * k + 1]) && is_finite(centres[3 * k + 2]) &&
-                        is_finite(a) && is_finite(b) && a >= 0.0 && b >= a;
+        const bool ok = mm_is_finite(centres[3 * k]) && mm_is_finite(centres[3 * k + 1]) && mm_is_finite(centres[3 * k + 2]) &&
+                        mm_is_finite(a) && mm_is_finite(b) && a >= 0.0 && b >= a;
         if (!ok) ++mine;
     }
     mm_count_to(bad, mine);
@@ -260,9 +257,6 @@ struct SelectState {
     i64 nvalid;
 };
 
-__device__ __forceinline__ u64 key_of(u64 u) { return (u >> 63) ? ~u : (u | ((u64)1 << 63)); }
-__device__ __forceinline__ u64 bits_of_key(u64 k) { return (k >> 63) ? (k & ~((u64)1 << 63)) : ~k; }
-
 // every candidate lane of the wave adds one to its bin of h; one add of their number when they all share a bin
 __device__ __forceinline__ void vote(unsigned *h, bool candidate, int digit, int lane)
 {
@@ -310,7 +304,7 @@ __global__ __launch_bounds__(kThreads) void select_hist_kernel(const double *__r
         for (int r = 0; r < kSelectLoads; ++r) {
             const u64 bits = absolute ? (u[r] & ~sign) : u[r];
             const bool valid = ok[r] && (bits & ~sign) <= 0x7ff0000000000000ull;   // (not a NaN)
-            const u64 key = key_of(bits);
+            const u64 key = mm_key_of(bits);
             const int digit = (int)((key >> shift) & (kBins - 1));
             if (FIRST) {
                 vote(h, valid, digit, lane);
@@ -376,7 +370,7 @@ __global__ __launch_bounds__(kWave) void select_pick_kernel(const u64 *__restric
         const u64 prefix = st->prefix[j] | ((u64)digit << shift);
         st->rank[j] = r - below;
         st->prefix[j] = prefix;
-        if (pass == kPasses - 1) out[c * m + j] = __longlong_as_double((long long)bits_of_key(prefix));
+        if (pass == kPasses - 1) out[c * m + j] = __longlong_as_double((long long)mm_bits_of_key(prefix));
     }
     __syncthreads();
     if (j == 0) {

@@ -28,9 +28,8 @@
 
 namespace {
 
-using namespace mm_stream;   // kThreads, kWave, kChunk, kTerms
+using namespace mm_stream;   // kThreads, kWave, kChunk, kTerms, kMaxBlocks
 constexpr int kWindow = 8;          // bins per LDS window: 16 KiB of doubles (+ 8 KiB of counts when asked for)
-constexpr i64 kMaxBlocks = 2048;    // 256 CUs x 8 workgroups; grid-stride beyond
 constexpr int kEdgeLds = 2048;      // doubles of LDS for the edges (16 KiB)
 constexpr int kTableLds = 4096;     // doubles of LDS for the table, radii and values together (32 KiB)
 constexpr i64 kMaxBins = (i64)1 << 20;

@@ -36,8 +36,6 @@ namespace {
 using namespace mm_stream;   // kThreads, kWave
 typedef unsigned long long u64;
 
-__device__ __forceinline__ bool is_finite(double v) { return fabs(v) < __builtin_inf(); }
-
 struct ResolutionArgs {
     const double *gp;
     i64 nelem;
@@ -100,8 +98,8 @@ __global__ __launch_bounds__(kThreads) void gll_resolution_kernel(const Resoluti
         double s = inf, q = inf, vs = inf, h = 0.0;
         if (live) {
             const double *x = xs + tid * DIM;
-            bool finite = is_finite(x[0]) && is_finite(x[1]);
-            if constexpr (DIM == 3) finite = finite && is_finite(x[2]);
+            bool finite = mm_is_finite(x[0]) && mm_is_finite(x[1]);
+            if constexpr (DIM == 3) finite = finite && mm_is_finite(x[2]);
             if (!finite) flag[0][nd.el] = 1;
             double cmin = inf, cmax = -inf;
 #pragma unroll
@@ -128,13 +126,13 @@ __global__ __launch_bounds__(kThreads) void gll_resolution_kernel(const Resoluti
                 bool refused = false;
                 for (int k = 0; k < a.nfast; ++k) {
                     const double v = a.fast[k * nnodes + node];
-                    refused = refused || !(is_finite(v) && v > 0.0);
+                    refused = refused || !(mm_is_finite(v) && v > 0.0);
                     vf = v > vf ? v : vf;
                     vfmin = v < vfmin ? v : vfmin;
                 }
                 for (int k = 0; k < a.nslow; ++k) {
                     const double v = a.slow[k * nnodes + node];
-                    refused = refused || !(is_finite(v) && v >= 0.0);
+                    refused = refused || !(mm_is_finite(v) && v >= 0.0);
                     if (v > 0.0 && v < vs) vs = v;
                 }
                 if (!(vs < inf)) vs = vfmin;   // no slow velocity above zero (a fluid): the least fast one

@@ -32,8 +32,8 @@ namespace {
 
 using mm_stream::kThreads;
 using mm_stream::kWave;
+using mm_stream::kMaxBlocks;
 typedef unsigned long long u64;
-constexpr i64 kMaxBlocks = 2048;   // 256 CUs x 8 workgroups; the grid-stride loop takes the rest
 constexpr int kGroup = 4;          // components held in registers at once
 
 enum { kFill = 0, kKeep = 2 };

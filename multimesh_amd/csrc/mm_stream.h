@@ -1,7 +1,9 @@
 // What a streaming or tile kernel of the model tools needs, each stated once: the launch shape, the integer count of a
 // launch, the chunked sum of mm_weighted_sum, and the three expressions that are under a bit-parity contract with NumPy
-// wherever they appear.  Users: mm_sphere, mm_mass, mm_diffusion, mm_transpose, mm_grid_sample, mm_radial,
-// mm_precondition and, through mm_gll_tile.h, mm_gradient and mm_order.  A new unit starts from these.
+// wherever they appear, the finiteness test and the order-preserving integer key of a double.  Users: mm_sphere, mm_mass,
+// mm_diffusion, mm_transpose, mm_grid_sample, mm_radial, mm_precondition, mm_scattered, mm_parametrisation, mm_resolution;
+// through mm_gll_tile.h, mm_gradient and mm_order; through mm_boundary_parts.h, mm_boundary and mm_surface.  A new unit
+// starts from these.
 // (The library is built with -ffp-contract=off: every product, quotient and sum below is rounded on its own.)
 #pragma once
 
@@ -13,11 +15,12 @@ constexpr int kThreads = 256;               // lanes of a workgroup
 constexpr int kWave = 64;
 constexpr int kChunk = 4096;                // values per chunk of a chunked sum (its definition, not a launch shape)
 constexpr int kTerms = kChunk / kThreads;   // ... per lane
+constexpr i64 kMaxBlocks = 2048;            // 256 CUs x 8 workgroups; grid-stride beyond
 }  // namespace mm_stream
 
 // ---- launch shape.  Blocks of a launch over n items, per_block of them per block and step: at least one, at most cap.
-// The caps in use: 2048 (256 CUs x 8 resident workgroups) and 8192 for kernels that stride over the rest; a kernel that
-// does not stride passes the largest grid, 2^31 - 1.
+// The caps in use: mm_stream::kMaxBlocks and 8192 for kernels that stride over the rest; a kernel that does not stride
+// passes the largest grid, 2^31 - 1.
 inline unsigned mm_blocks(i64 n, i64 per_block, i64 cap)
 {
     const i64 b = (n + per_block - 1) / per_block;
@@ -105,3 +108,16 @@ __device__ __forceinline__ int mm_upper_bound(Axis a, int b, int e, double v)
 
 // (1 - t) * p + t * q
 __device__ __forceinline__ double mm_lerp(double t, double p, double q) { return (1.0 - t) * p + t * q; }
+
+// ---- bits.  np.isfinite(v)
+__device__ __forceinline__ bool mm_is_finite(double v) { return fabs(v) < __builtin_inf(); }
+
+// The unsigned order of mm_key_of(bits of a double) is the numeric order of the doubles; mm_bits_of_key is its inverse.
+__device__ __host__ __forceinline__ unsigned long long mm_key_of(unsigned long long u)
+{
+    return (u >> 63) ? ~u : (u | (1ull << 63));
+}
+__device__ __host__ __forceinline__ unsigned long long mm_bits_of_key(unsigned long long k)
+{
+    return (k >> 63) ? (k & ~(1ull << 63)) : ~k;
+}

@@ -13,7 +13,8 @@
 // The search ("Boundaries", has the derivation in full).  A uniform grid of cells of edge h over the
 // bounding box [lo, hi] of the triangles' vertices; h follows the triangles -- 2^(e + 1) with 2^e <= the median of their
 // largest bounding-box extents < 2^(e + 1), from a histogram of the exponents -- and not the cutoff; it is enlarged until
-// the grid fits mm_cutoff_distance's caps (1024 cells per axis, 2^22 in all) and until the entries are at most 16 T.  The
+// the grid fits mm_cutoff_distance's caps (1024 cells per axis, 2^22 in all: mm_search_grid_fit) and until the entries are
+// at most 16 T.  The grid, its cells and its bins are mm_cutoff_distance's (mm_search_grid.h, mm_boundary_parts.h).  The
 // cell of a coordinate is clamp(floor(fl(fl(x - lo) * inv_h)), 0, dims - 1), a MONOTONE function of x, so a triangle
 // entered into the cells of its bounding box's corners and all between is in the cell of each of its points.  A lane walks
 // the Chebyshev rings k = 0, 1, ... of cells around the cell of p' = clamp(p, lo, hi) and stops when
@@ -35,41 +36,24 @@ constexpr double kShrink = 1.0 - 0x1p-24;     // the stopping bound's relative a
 constexpr double kAbsMargin = 0x1p-36;
 constexpr double kMinEdge = 0x1p-1000;
 
-struct SurfGrid {
-    double lo[3], hi[3], h, inv_h, mbox;
-    int dims[3];
-};
-
 // ------------------------------------------------------------------------------------------- mm_boundary_triangles
-// one lane per triangle: item = b * 2 o^2 + k, k = 2 * (j * o + i) + (0: the triangle at (j, i)'s lower side, 1: the other)
-__global__ __launch_bounds__(kThreads) void triangles_emit_kernel(const double *__restrict__ points, int m,
-                                                                  const i64 *__restrict__ faces, i64 nb,
-                                                                  const int *__restrict__ flag, const int *__restrict__ rank,
-                                                                  double *__restrict__ out, u64 *counters)
-{
-    if (blockIdx.x == 0 && threadIdx.x == 0) counters[1] = (u64)rank[nb];   // the selected faces
-    if (counters[0] != 0) return;   // (a refused call writes no triangle)
-    const int o = m - 1, per = 2 * o * o, mm = m * m;
-    const i64 P = (i64)mm * m, nitems = nb * per;
-    const i64 stride = (i64)gridDim.x * blockDim.x;
-    for (i64 item = (i64)blockIdx.x * blockDim.x + threadIdx.x; item < nitems; item += stride) {
-        const i64 b = item / per;
-        if (!flag[b]) continue;
-        const int k = (int)(item - b * per), second = k & 1, j = (k >> 1) / o, i = (k >> 1) - j * o;
-        const i64 code = faces[b], e = code / 6;
-        const int f = (int)(code - 6 * e), a = f >> 1, fix = (f & 1) * (m - 1);
+// (select_kernel, face_items_kernel and their driver: mm_boundary_parts.h)
+// the 2 o^2 triangles of a face: k = 2 * (j * o + i) + (0: the triangle at (j, i)'s lower side, 1: the other)
+struct TriangleItems {
+    static constexpr int kDoubles = 9;
+    __host__ __device__ static int per_face(int m) { return 2 * (m - 1) * (m - 1); }
+    __device__ static void write(const double *__restrict__ X, int m, const Face &face, int k, double *__restrict__ dst)
+    {
+        const int o = m - 1, second = k & 1, j = (k >> 1) / o, i = (k >> 1) - j * o;
         // the vertices (lo, hi) on the face's grid: (i, j), then (i+1, j), (i+1, j+1) or (i+1, j+1), (i, j+1)
         const int vlo[3] = {i, i + 1, second ? i : i + 1}, vhi[3] = {j, second ? j + 1 : j, j + 1};
-        double *dst = out + 9 * ((i64)rank[b] * per + k);
 #pragma unroll
         for (int v = 0; v < 3; ++v) {
-            const int lo = vlo[v], hi = vhi[v];
-            const int p = a == 0 ? fix + m * lo + mm * hi : (a == 1 ? lo + m * fix + mm * hi : lo + m * hi + mm * fix);
-            const double *src = points + 3 * (e * P + p);
+            const double *src = X + 3 * face_node(face.a, face.fix, m, vlo[v], vhi[v]);
             dst[3 * v] = src[0], dst[3 * v + 1] = src[1], dst[3 * v + 2] = src[2];
         }
     }
-}
+};
 
 // --------------------------------------------------------------------------------------------- mm_surface_distance
 __device__ __forceinline__ double dot3(const double (&u)[3], const double (&v)[3]) { return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2]; }
@@ -115,22 +99,18 @@ __device__ __forceinline__ double triangle_distance(const double (&p)[3], const 
     return mm_norm3(p[0] - q[0], p[1] - q[1], p[2] - q[2]);
 }
 
-// the cell of a coordinate of a vertex on axis a: monotone in x; 0 <= x - lo, the clamps only guard the memory
-__device__ __forceinline__ int axis_cell(const SurfGrid &g, int a, double x)
-{
-    const double v = floor((x - g.lo[a]) * g.inv_h);
-    return v >= 0.0 ? (v < (double)g.dims[a] ? (int)v : g.dims[a] - 1) : 0;
-}
-
-// the cells [c0[a], c1[a]] per axis that the triangle's bounding box overlaps
-__device__ __forceinline__ void triangle_cells(const SurfGrid &g, const double *__restrict__ s, int (&c0)[3], int (&c1)[3])
-{
+// a triangle is a record in every cell [c0[a], c1[a]] per axis that its bounding box overlaps
+struct TriangleBins {
+    static constexpr int kDoubles = 9;
+    __device__ static void cells(const Grid &g, const double *__restrict__ s, int (&c0)[3], int (&c1)[3])
+    {
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        c0[a] = axis_cell(g, a, fmin(fmin(s[a], s[3 + a]), s[6 + a]));
-        c1[a] = axis_cell(g, a, fmax(fmax(s[a], s[3 + a]), s[6 + a]));
+        for (int a = 0; a < 3; ++a) {
+            c0[a] = grid_cell(g, a, fmin(fmin(s[a], s[3 + a]), s[6 + a]));
+            c1[a] = grid_cell(g, a, fmax(fmax(s[a], s[3 + a]), s[6 + a]));
+        }
     }
-}
+};
 
 // hist[e] += the triangles whose largest bounding-box extent has the binary exponent field e (through LDS: the triangles
 // of a mesh are of one size, and a global atomic per triangle would queue on one address)
@@ -173,60 +153,22 @@ __global__ __launch_bounds__(kThreads) void median_bin_kernel(const int *__restr
 }
 
 // *total += the entries of the grid: the cells every triangle's bounding box overlaps
-__global__ __launch_bounds__(kThreads) void entries_total_kernel(const double *__restrict__ tri, i64 T, const SurfGrid g, u64 *total)
+__global__ __launch_bounds__(kThreads) void entries_total_kernel(const double *__restrict__ tri, i64 T, const Grid g, u64 *total)
 {
     u64 mine = 0;
     const i64 stride = (i64)gridDim.x * blockDim.x;
     for (i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x; t < T; t += stride) {
         int c0[3], c1[3];
-        triangle_cells(g, tri + 9 * t, c0, c1);
+        TriangleBins::cells(g, tri + 9 * t, c0, c1);
         mine += (u64)(c1[0] - c0[0] + 1) * (u64)(c1[1] - c0[1] + 1) * (u64)(c1[2] - c0[2] + 1);   // (below 2^30 each)
     }
     mine = wave_sum(mine);
     if ((threadIdx.x & (kWave - 1)) == 0 && mine != 0) atomicAdd(total, mine);
 }
 
-__global__ __launch_bounds__(kThreads) void entries_count_kernel(const double *__restrict__ tri, i64 T, const SurfGrid g,
-                                                                 int *__restrict__ count)
-{
-    const i64 stride = (i64)gridDim.x * blockDim.x;
-    for (i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x; t < T; t += stride) {
-        int c0[3], c1[3];
-        triangle_cells(g, tri + 9 * t, c0, c1);
-        for (int z = c0[2]; z <= c1[2]; ++z)
-            for (int y = c0[1]; y <= c1[1]; ++y)
-                for (int x = c0[0]; x <= c1[0]; ++x) atomicAdd(&count[(z * g.dims[1] + y) * g.dims[0] + x], 1);
-    }
-}
-
-// count[c] runs down to zero while the cell's records take their places: any order, the minimum has none.  The cells are
-// those entries_count_kernel counted (the same function of the same bits), so every place lies in its cell's range.
-__global__ __launch_bounds__(kThreads) void entries_scatter_kernel(const double *__restrict__ tri, i64 T, const SurfGrid g,
-                                                                   const int *__restrict__ start, int *__restrict__ count,
-                                                                   double *__restrict__ rec)
-{
-    const i64 stride = (i64)gridDim.x * blockDim.x;
-    for (i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x; t < T; t += stride) {
-        const double *s = tri + 9 * t;
-        int c0[3], c1[3];
-        triangle_cells(g, s, c0, c1);
-        double v[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) v[k] = s[k];
-        for (int z = c0[2]; z <= c1[2]; ++z)
-            for (int y = c0[1]; y <= c1[1]; ++y)
-                for (int x = c0[0]; x <= c1[0]; ++x) {
-                    const int c = (z * g.dims[1] + y) * g.dims[0] + x;
-                    double *dst = rec + 9 * ((i64)start[c] + (atomicSub(&count[c], 1) - 1));
-#pragma unroll
-                    for (int k = 0; k < 9; ++k) dst[k] = v[k];
-                }
-    }
-}
-
 // One lane per point.  start == nullptr: no triangles, every distance is the cutoff.
 __global__ __launch_bounds__(kThreads) void surface_query_kernel(const double *__restrict__ pts, i64 n, const double *__restrict__ rec,
-                                                                 const int *__restrict__ start, const SurfGrid g, double cutoff,
+                                                                 const int *__restrict__ start, const Grid g, double cutoff,
                                                                  double *__restrict__ dist, u64 *count)
 {
     unsigned mine = 0;
@@ -236,15 +178,15 @@ __global__ __launch_bounds__(kThreads) void surface_query_kernel(const double *_
         const double p[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
         double d = cutoff;
         // (a point with a coordinate that is not finite keeps the cutoff: its r is inf or a NaN for every triangle)
-        if (start && is_finite(p[0]) && is_finite(p[1]) && is_finite(p[2])) {
+        if (start && mm_is_finite(p[0]) && mm_is_finite(p[1]) && mm_is_finite(p[2])) {
             double e[3], v[3], pmax = 0.0;
             int c[3];
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
                 const double pc = fmin(fmax(p[a], g.lo[a]), g.hi[a]);   // p', the projection onto the box
                 e[a] = p[a] - pc;
-                v[a] = (pc - g.lo[a]) * g.inv_h;                        // >= 0
-                const double fl = floor(v[a]);
+                v[a] = grid_coord(g, a, pc);                            // >= 0
+                const double fl = floor(v[a]);                          // grid_cell(p'), whose lower clamp cannot act
                 c[a] = fl < (double)g.dims[a] ? (int)fl : g.dims[a] - 1;
                 pmax = fmax(pmax, fabs(p[a]));
             }
@@ -267,7 +209,7 @@ __global__ __launch_bounds__(kThreads) void surface_query_kernel(const double *_
                     for (int z = z0; z <= z1; ++z) {
                         const bool zface = z == c[2] - k || z == c[2] + k;
                         for (int y = y0; y <= y1; ++y) {
-                            const int row = (z * dy + y) * dx;
+                            const int row = grid_index(g, 0, y, z);
                             if (zface || y == c[1] - k || y == c[1] + k) {
                                 scan(row + x0, row + x1);
                             } else {
@@ -300,39 +242,8 @@ __global__ __launch_bounds__(kThreads) void surface_query_kernel(const double *_
 extern "C" int64_t mm_boundary_triangles(mm_context *ctx, const double *points_d, int64_t nelem, int order, const int64_t *faces_d,
                                          const int *side_d, int64_t nb, int side_mask, double *tri_d)
 {
-    MM_REQUIRE(ctx != nullptr, "ctx is null");
-    MM_REQUIRE(order == 1 || order == 2 || order == 4, "order must be 1, 2 or 4");
-    MM_REQUIRE(nelem >= 0 && nelem < ((i64)1 << 27), "nelem must lie in [0, 2^27)");
-    MM_REQUIRE(nb >= 0 && nb <= 6 * nelem, "nb must lie in [0, 6 nelem]");
-    MM_REQUIRE(side_mask >= 0 && side_mask <= 7, "side_mask must lie in [0, 7]");
-    MM_REQUIRE(nb == 0 || (points_d != nullptr && faces_d != nullptr && tri_d != nullptr), "null array");
-    MM_HIP_CHECK(hipSetDevice(ctx->device));
-    if (nb == 0) return 0;
-    const int m = order + 1, per = 2 * order * order;
-    int *flag, *rank, *tile_sums;
-    mm_scratch_layout lay;
-    lay.add(&flag, (size_t)nb + 1);
-    lay.add(&rank, (size_t)nb + 1);
-    lay.add(&tile_sums, mm_scan_scratch_ints(nb));
-    int rc = lay.commit(ctx, __func__);
-    if (rc != MM_OK) return rc;
-    u64 *counters = mm_counters_begin(ctx, kSlot, 2);   // [0] bad codes or sides, [1] the selected faces
-    if (!counters) return MM_ERR_HIP;
-    hipLaunchKernelGGL(select_kernel, dim3(stream_grid(nb)), dim3(kThreads), 0, ctx->stream, (const i64 *)faces_d, side_d, (i64)nb,
-                       (i64)nelem, side_mask, flag, counters);
-    MM_HIP_CHECK(hipGetLastError());
-    rc = mm_exclusive_scan_int(ctx, flag, nb, rank, tile_sums);
-    if (rc != MM_OK) return rc;
-    hipLaunchKernelGGL(triangles_emit_kernel, dim3(stream_grid(nb * per)), dim3(kThreads), 0, ctx->stream, points_d, m,
-                       (const i64 *)faces_d, (i64)nb, (const int *)flag, (const int *)rank, tri_d, counters);
-    const i64 *got = mm_counters_end(ctx, kSlot, 2);
-    if (!got) return MM_ERR_HIP;
-    if (got[0] != 0) {
-        mm_set_error(MM_ERR_ARG, "mm_boundary_triangles: %lld faces have a code outside [0, %lld) or a side outside [0, 2]",
-                     (long long)got[0], (long long)(6 * nelem));
-        return MM_ERR_ARG;
-    }
-    return got[1] * per;
+    return selected_face_items<TriangleItems>(ctx, __func__, points_d, nelem, order, (const i64 *)faces_d, side_d, nb, side_mask,
+                                              tri_d);
 }
 
 extern "C" int64_t mm_surface_distance(mm_context *ctx, const double *points_d, int64_t n, const double *tri_d, int64_t T,
@@ -348,7 +259,7 @@ extern "C" int64_t mm_surface_distance(mm_context *ctx, const double *points_d, 
     MM_HIP_CHECK(hipSetDevice(ctx->device));
     u64 *words = mm_counters_begin(ctx, kSlot, kWords);   // [0] points with d < cutoff, [1] bad coordinates, [2..7] the box
     if (!words) return MM_ERR_HIP;
-    SurfGrid g = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, 1.0, 1.0, 0.0, {1, 1, 1}};
+    Grid g = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, 1.0, 1.0, 0.0, {1, 1, 1}};
     double *rec = nullptr;
     int *start = nullptr;
     if (T > 0) {
@@ -385,47 +296,19 @@ extern "C" int64_t mm_surface_distance(mm_context *ctx, const double *points_d, 
         const int e_med = (int)got[1];
         double h = e_med >= 1 && e_med <= 2045 ? ldexp(1.0, e_med - 1023 + 1) : widest;
         if (!(h >= kMinEdge && h < __builtin_inf())) h = 1.0;
-        for (;;) {
+        for (;; h = g.h * 1.5) {
             // enlarged until the grid fits its caps and the entries their cap (a larger edge keeps the search valid); one cell
             // holds T entries, so this ends
-            g.h = h;
-            g.inv_h = 1.0 / h;
-            double cells = 1.0;
-            bool fits = true;
-            for (int a = 0; a < 3; ++a) {
-                const double da = floor(extent[a] * g.inv_h) + 1.0;
-                fits = fits && da <= (double)kMaxDim;
-                g.dims[a] = fits ? (int)da : 1;
-                cells *= da;
-            }
-            if (!(fits && cells <= (double)kMaxCells)) {
-                h *= 1.25;
-                continue;
-            }
+            mm_search_grid_fit(g, extent, h, 1);
             aux = mm_counters_begin(ctx, kAuxSlot, 1);
             if (!aux) return MM_ERR_HIP;
             hipLaunchKernelGGL(entries_total_kernel, grid, block, 0, ctx->stream, tri_d, (i64)T, g, aux);
             got = mm_counters_end(ctx, kAuxSlot, 1);
             if (!got) return MM_ERR_HIP;
             if (got[0] <= kEntryCap * T && got[0] < ((i64)1 << 31) - 1) break;
-            h *= 1.5;
         }
-        const i64 entries = got[0];
-        const i64 ncells = (i64)g.dims[0] * g.dims[1] * g.dims[2];
-        int *count, *tile_sums;
-        mm_scratch_layout lay;
-        lay.add(&rec, (size_t)entries * 9);
-        lay.add(&count, (size_t)ncells + 1);
-        lay.add(&start, (size_t)ncells + 1);
-        lay.add(&tile_sums, mm_scan_scratch_ints(ncells));
-        rc = lay.commit(ctx, __func__);
+        rc = bins_build<TriangleBins>(ctx, __func__, tri_d, T, got[0], g, rec, start);
         if (rc != MM_OK) return rc;
-        if (mm_zero_async(ctx, count, (size_t)(ncells + 1) * sizeof(int)) != MM_OK) return MM_ERR_HIP;
-        hipLaunchKernelGGL(entries_count_kernel, grid, block, 0, ctx->stream, tri_d, (i64)T, g, count);
-        MM_HIP_CHECK(hipGetLastError());
-        rc = mm_exclusive_scan_int(ctx, count, ncells, start, tile_sums);
-        if (rc != MM_OK) return rc;
-        hipLaunchKernelGGL(entries_scatter_kernel, grid, block, 0, ctx->stream, tri_d, (i64)T, g, (const int *)start, count, rec);
     }
     if (n > 0)
         hipLaunchKernelGGL(surface_query_kernel, dim3(stream_grid(n)), dim3(kThreads), 0, ctx->stream, points_d, (i64)n,

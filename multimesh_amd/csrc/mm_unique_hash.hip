@@ -13,6 +13,7 @@
 // -0.0 equals +0.0 as in NumPy (the row kept is the first one); a row with a NaN never merges, not even with a row of
 // the same bits (np.unique(axis=0) keeps every such row apart): it hashes by its own index and claims a slot of its own.
 #include "mm_common.h"
+#include "mm_hash.h"
 
 namespace {
 
@@ -23,16 +24,6 @@ __device__ __forceinline__ u64 canon_bits(double v)
 {
     if (v == 0.0) v = 0.0;   // -0.0 -> +0.0
     return (u64)__double_as_longlong(v);
-}
-
-__device__ __forceinline__ u64 mix64(u64 h)
-{
-    h ^= h >> 33;
-    h *= 0xff51afd7ed558ccdull;
-    h ^= h >> 33;
-    h *= 0xc4ceb9fe1a85ec53ull;
-    h ^= h >> 33;
-    return h;
 }
 
 __device__ __forceinline__ bool nan_bits(u64 b)
@@ -58,8 +49,8 @@ __global__ __launch_bounds__(kBlock) void unique_insert_kernel(const double *__r
     u64 b[3];
     load_row<DIM>(pts, i, b);
     const bool lone = nan_bits(b[0]) || nan_bits(b[1]) || nan_bits(b[2]);
-    u64 h = mix64(b[0] ^ mix64(b[1] ^ mix64(b[2] + 0x9e3779b97f4a7c15ull)));
-    if (lone) h = mix64(h ^ (u64)i);   // equal NaN rows would otherwise probe one chain
+    u64 h = mm_mix64(b[0] ^ mm_mix64(b[1] ^ mm_mix64(b[2] + 0x9e3779b97f4a7c15ull)));
+    if (lone) h = mm_mix64(h ^ (u64)i);   // equal NaN rows would otherwise probe one chain
     unsigned s = (unsigned)h & mask;
     for (;;) {
         int cur = __atomic_load_n(&table[s], __ATOMIC_RELAXED);

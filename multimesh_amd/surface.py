@@ -17,8 +17,8 @@ import numpy as np
 
 from . import boundary as _boundary
 from . import device as _device
-from .api._common import is_mesh, named_fields, points_of
-from .boundary import Boundary, mesh_boundary
+from .api._common import is_mesh, points_of
+from .boundary import mesh_boundary
 from .device import default_context
 from .helpers import f64, i32, i64, load_lib, vp
 
@@ -42,12 +42,6 @@ def bind(lib=None):
             fn.restype, fn.argtypes = restype, list(argtypes)
         lib._surface_bound = True
     return lib
-
-
-def _boundary_of(boundary):
-    if not isinstance(boundary, Boundary):
-        raise ValueError("boundary must come from mesh_boundary")
-    return boundary
 
 
 def _cutoff(cutoff):
@@ -74,7 +68,7 @@ def boundary_triangles(boundary, sides=("side", "bottom")):
     sub-quad of a face's node grid ``q[j][i]`` gives ``(q[j][i], q[j][i+1], q[j+1][i+1])`` and ``(q[j][i], q[j+1][i+1],
     q[j+1][i])``.  The surface is the piecewise-linear one through the nodes (order 1: the corner quad split along a diagonal;
     a curved order-4 face: 32 flat facets).  The default leaves the free surface ("top") out."""
-    return _triangles(_boundary_of(boundary), _boundary._side_mask(sides))
+    return _triangles(_boundary._boundary_of(boundary), _boundary._side_mask(sides))
 
 
 def _distance(ctx, points, triangles, cutoff):
@@ -108,7 +102,7 @@ def distance_to_surface(mesh_or_points, boundary, cutoff=None, sides=("side", "b
     ``sides`` of ``boundary`` -- to the triangles of :func:`boundary_triangles`, not to their nodes --, or ``cutoff`` where
     the surface is farther (``None``: unbounded).  A node of those faces gets exactly 0.0.  The call runs on the boundary's own
     context: ``context`` is that one or ``None`` (``ValueError`` otherwise)."""
-    bnd = _boundary_of(boundary)
+    bnd = _boundary._boundary_of(boundary)
     cutoff, mask = _cutoff(cutoff), _boundary._side_mask(sides)
     pts = points_of(mesh_or_points) if is_mesh(mesh_or_points) else mesh_or_points
     ctx = bnd._context(context)
@@ -130,16 +124,7 @@ def taper_to_surface(mesh, params, inner, outer, sides=("side", "bottom"), bound
     ``params`` times 0 within ``inner`` of the surface of ``sides``, 1 beyond ``outer``, the smoothstep between
     (``mm_distance_taper``).  Every point of a face gets weight 0, not only its nodes; nodes beyond ``outer`` keep their
     bits."""
-    inner, outer = _boundary._radii(inner, outer)
-    mask = _boundary._side_mask(sides)
-    pts = points_of(mesh)
-    _, fields = named_fields(mesh, params)
-    if boundary is None:
-        boundary = mesh_boundary(mesh, context=context)
-    ctx = _boundary_of(boundary)._context(context)
-    dist = _surface_distance(ctx, boundary, pts, mask, outer)
-    out, ntapered = ctx.distance_taper(dist, inner, outer, fields.reshape(fields.shape[0], -1))
-    return out.numpy().reshape(fields.shape), ntapered
+    return _boundary._taper(_surface_distance, mesh, params, inner, outer, sides, boundary, context)
 
 
 def blend_models(regional, host, params, inner, outer, sides=("side", "bottom"), nelem_to_search=20, tolerance=1.05,

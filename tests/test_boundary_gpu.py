@@ -140,7 +140,8 @@ def test_distance_of_a_mesh_to_its_own_boundary(ctx, cube, widths):
     assert ref.min() == 0.0 and (ref.max() == widths * 0.25) == (widths < 2)          # the middle is 2 elements deep
 
 
-def test_distance_of_clouds_and_corner_cases(ctx):
+def _clouds():
+    """3001 sources in the unit box and 5003 targets around it, corner cases among the first 65"""
     rng = np.random.default_rng(11)
     src = rng.uniform(0.0, 1.0, (3001, 3))
     pts = rng.uniform(-0.5, 1.5, (5003, 3))                                          # a cloud larger than the box
@@ -148,7 +149,12 @@ def test_distance_of_clouds_and_corner_cases(ctx):
     pts[50:60] = src[:10]                                                            # ... and on sources
     pts[60, 0], pts[61, 1], pts[62] = np.nan, np.nan, np.nan
     pts[63, 2], pts[64, 0] = np.inf, -np.inf
-    for cutoff in (0.01, 0.06, 0.7, 50.0):                                           # (0.01: the cap on the cells per axis)
+    return src, pts
+
+
+def test_distance_of_clouds_and_corner_cases(ctx):
+    src, pts = _clouds()
+    for cutoff in (0.01, 0.06, 0.7, 50.0):                                           # (0.01: 101 cells per axis, no cap yet)
         ref = _check_distance(ctx, pts, src, cutoff)
         assert (ref[60:65] == cutoff).all() and (ref[50:60] == 0.0).all()
     _check_distance(ctx, pts, src[:1], 0.5)                                          # K = 1
@@ -163,6 +169,21 @@ def test_distance_of_clouds_and_corner_cases(ctx):
     with pytest.raises(ValueError, match="1 sources are not finite"):
         ctx.cutoff_distance(pts, wrong, 0.1)
     _check_distance(ctx, pts[:100], src, 0.1)                                        # the next call is served
+
+
+@pytest.mark.parametrize("sheet, cutoff", [(False, 0.004), (True, 0.0005)])
+def test_distance_on_a_grid_enlarged_to_its_caps(ctx, sheet, cutoff):
+    """cutoffs whose cells would pass a cap of the grid, so that the edge is enlarged: 0.004 on the unit cloud (251^3 cells
+    pass 2^22 in all: two enlargements, 161^3) and 0.0005 on the sheet (2001 cells pass 1024 per axis: four, 821 x 821 x 2)"""
+    src, pts = _clouds()
+    if sheet:
+        src[:, 2] = 0.5
+    # 500 targets within 0.87 cutoff of a source (a random cloud has next to none that close)
+    pts[-500:] = src[:500] + np.random.default_rng(12).uniform(-0.5, 0.5, (500, 3)) * cutoff
+    ref, ref_count = BC.cutoff_distance(pts, src, cutoff)
+    assert ref_count >= 500                                                          # (else the case checks nothing)
+    d, count = ctx.cutoff_distance(pts, src, cutoff)
+    assert count == ref_count and BC.same_bits(d.numpy(), ref)
 
 
 def test_distance_on_an_earth_chunk_far_from_the_origin(ctx):

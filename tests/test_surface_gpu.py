@@ -142,6 +142,21 @@ def test_a_graded_mesh_whose_nearest_triangle_lies_rings_away(ctx):
     assert least.max() > 1.5 and (least > 0.2).sum() > 100
 
 
+@pytest.mark.parametrize("sheet", [False, True])
+def test_small_triangles_whose_grid_is_enlarged_to_its_caps(ctx, sheet):
+    """triangles of size 2^-13 in the unit box: cells of their size would pass the caps of the grid -- 2^22 cells in all in
+    3-D, 1024 per axis on a sheet --, so the edge is enlarged before the entries are counted"""
+    rng = np.random.default_rng(41)
+    tri = _random_triangles(rng, 300, 0.0, 1.0, 2.0 ** -14)
+    if sheet:
+        tri[:, :, 2] = 0.5
+    corners = tri.reshape(-1, 3)
+    near = corners[rng.integers(0, 900, 500)] + rng.uniform(-1e-4, 1e-4, (500, 3))   # within 2e-4 of a vertex
+    pts = np.concatenate([corners, near, rng.uniform(0.0, 1.0, (2000, 3))])
+    least = _check(ctx, pts, tri, [3e-4, 0.2, INF])
+    assert (least < 3e-4).sum() >= 1400                                              # (else the least cutoff checks nothing)
+
+
 def test_one_face_fifty_times_larger_than_the_others(ctx):
     rng = np.random.default_rng(21)
     small = _random_triangles(rng, 400, 0.0, 1.0, 0.02)                              # 200 faces' worth

@@ -4,8 +4,8 @@
 // kernel gll_diffusion_kernel (mm_diffusion.hip) uses the constants and the geometry functions and keeps its own lane
 // set-up, loads and stores (see its header comment); gll_resolution_kernel (mm_resolution.hip) uses the tile, its fetch and
 // the lanes' bookkeeping (Node) but no table and no Jacobian; mm_order.hip uses kThreads, kMaxBlocks, ipow and grid_size;
-// radial_apply_kernel (mm_radial.hip) and point_taper_kernel (mm_precondition.hip) use RunTile, the bookkeeping of the
-// same tile for a P known only at run time.
+// radial_apply_kernel (mm_radial.hip), harmonic_apply_kernel (mm_harmonics.hip) and point_taper_kernel
+// (mm_precondition.hip) use RunTile, the bookkeeping of the same tile for a P known only at run time.
 // Every expression here is under a bit-parity contract with a NumPy statement (tests/mass_cases.py, diffusion_cases.py,
 // gradient_cases.py) and its order of operations is published in include/multimesh_hip.h: every product is rounded on
 // its own (-ffp-contract=off), every sum starts from its first term and adds in ascending a.

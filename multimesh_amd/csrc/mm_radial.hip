@@ -21,6 +21,7 @@
 // The table evaluation works on tiles of 256 / P whole elements (gll::RunTile of mm_gll_tile.h): the
 // coordinates go to LDS coalesced, lane e < tile forms element e's centre and finds its layer, then lane t is node t.
 #include "mm_gll_tile.h"
+#include "mm_radial_table.h"
 
 #include <limits.h>
 
@@ -198,13 +199,6 @@ struct ApplyArgs {
     double *out;
 };
 
-// the first radius of every layer, as an axis to bisect
-struct LayerFloor {
-    const double *R;
-    const int *lstart;
-    __device__ __forceinline__ double operator[](int k) const { return R[lstart[k]]; }
-};
-
 // LDS_TABLE: radii and values are copied to (dynamic) LDS first and read there.
 template <bool LDS_TABLE>
 __global__ __launch_bounds__(kThreads) void radial_apply_kernel(const ApplyArgs args)
@@ -243,13 +237,7 @@ __global__ __launch_bounds__(kThreads) void radial_apply_kernel(const ApplyArgs 
             cx = cx / dp, cy = cy / dp, cz = cz / dp;
             const double rc = mm_norm3(cx, cy, cz);
             int a = -1, b = -1;
-            if (rc == rc) {
-                // the last layer whose first radius is <= rc, clipped: the layer with r_lo <= rc < r_hi
-                int k = mm_upper_bound(LayerFloor{R, args.lstart}, 0, args.nlayers, rc) - 1;
-                k = k < 0 ? 0 : k;
-                a = args.lstart[k];
-                b = args.lstart[k + 1] - 1;
-            }
+            if (rc == rc) mm_radial_table::layer_of(R, args.lstart, args.nlayers, rc, a, b);
             s_a[tid] = a;
             s_b[tid] = b;
         }
@@ -260,15 +248,7 @@ __global__ __launch_bounds__(kThreads) void radial_apply_kernel(const ApplyArgs 
             const i64 node = T.first_node(t) + tid;
             int i = 0;
             double w = __builtin_nan("");
-            if (a >= 0) {
-                double r = mm_norm3(x, y, z);
-                r = r < R[a] ? R[a] : r;
-                r = r > R[b] ? R[b] : r;
-                i = mm_upper_bound(R, a, b + 1, r) - 1;
-                i = i < a ? a : i;
-                i = i > b - 1 ? b - 1 : i;
-                w = (r - R[i]) / (R[i + 1] - R[i]);
-            }
+            if (a >= 0) mm_radial_table::interval_of(R, a, b, mm_norm3(x, y, z), i, w);
             for (int c = 0; c < ncomp; ++c) {
                 const double *Vc = V + (i64)c * m;
                 const double ref = a >= 0 ? mm_lerp(w, Vc[i], Vc[i + 1]) : w;
@@ -404,19 +384,9 @@ extern "C" int mm_radial_model_apply(mm_context *ctx, const double *points_d, in
     MM_HIP_CHECK(hipMemcpyAsync(R.data(), radius_d, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     MM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     std::vector<int> lstart;
-    lstart.push_back(0);
-    for (i64 i = 0; i < m; ++i) {
-        MM_REQUIRE(R[i] - R[i] == 0.0, "a radius of the table is not finite");
-        if (i == 0) continue;
-        MM_REQUIRE(R[i] >= R[i - 1], "the radii of the table descend");
-        if (R[i] == R[i - 1]) {
-            MM_REQUIRE(i - lstart.back() >= 2, "a layer of the table has a single row");
-            lstart.push_back((int)i);
-        }
-    }
-    MM_REQUIRE(m - lstart.back() >= 2, "a layer of the table has a single row");
-    const int nlayers = (int)lstart.size();
-    lstart.push_back((int)m);
+    const int table_rc = mm_radial_table_layers(__func__, R.data(), m, lstart);
+    if (table_rc != MM_OK) return table_rc;
+    const int nlayers = (int)lstart.size() - 1;
     if (!work) return MM_OK;
     int *lstart_d = nullptr;
     mm_scratch_layout lay;

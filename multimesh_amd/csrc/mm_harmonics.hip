@@ -22,42 +22,17 @@
 // Components: NC = 1..4 unrolled; more than four are served four at a time by further launches (the Legendre recurrence,
 // 5 of the 8 NC + 5 operations per term, is repeated per launch; the partial sums of more components would not fit registers).
 #include "mm_gll_tile.h"
-#include "mm_radial_table.h"
-
-#include <math.h>
-
-#include <vector>
+#include "mm_harmonic_node.h"   // what an element and a node are to this kernel and to its transpose
 
 #include "multimesh_harmonics.h"
 
 namespace {
 
 using namespace mm_stream;   // kThreads, kWave, kMaxBlocks
+using namespace mm_harmonic;
 constexpr i64 kMaxExtent = (i64)1 << 48;
 constexpr int kMaxUnrolled = 4;        // components per launch
-constexpr int kDead = -1, kOutside = -2;   // an element's first row when it has none: a NaN centre, a centre outside the table
 typedef unsigned long long u64;
-
-// ---- lstart from the radii, on the device (one workgroup; the host forms the same array for its check, and would have to
-// wait for the stream a second time to hand it over).  lstart[0] = 0, then every row that repeats the radius before it, in
-// ascending order, then m.  Writes at most m + 1 entries whatever the radii hold.
-__global__ __launch_bounds__(kThreads) void layer_starts_kernel(const double *__restrict__ R, int m, int *__restrict__ lstart)
-{
-    __shared__ int s_count[kThreads];
-    const int tid = threadIdx.x;
-    const int len = (m + kThreads - 1) / kThreads;
-    const int lo = tid * len < 1 ? 1 : tid * len, hi = (tid + 1) * len < m ? (tid + 1) * len : m;
-    int count = 0;
-    for (int i = lo; i < hi; ++i) count += R[i] == R[i - 1];
-    s_count[tid] = count;
-    __syncthreads();
-    int at = 1;
-    for (int q = 0; q < tid; ++q) at += s_count[q];
-    for (int i = lo; i < hi; ++i)
-        if (R[i] == R[i - 1]) lstart[at++] = i;
-    if (tid == 0) lstart[0] = 0;
-    if (tid == kThreads - 1) lstart[at] = m;
-}
 
 struct HarmonicArgs {
     i64 ngroups;
@@ -95,12 +70,12 @@ __device__ __forceinline__ void order_sums(int k, int L, int base, i64 knot, i64
     add(base, pkk, true);
     double p1 = pkk, p2 = pkk;
     if (k + 1 <= L) {
-        p1 = (ta[base + 1] * ct) * pkk;
+        p1 = legendre_second(ta[base + 1], ct, pkk);
         add(base + 1, p1, false);
     }
     for (int l = k + 2; l <= L; ++l) {
         const int q = base + (l - k);
-        const double Plk = ta[q] * (ct * p1 - tb[q] * p2);
+        const double Plk = legendre_next(ta[q], tb[q], ct, p1, p2);
         p2 = p1;
         p1 = Plk;
         add(q, Plk, false);
@@ -127,15 +102,8 @@ __device__ __forceinline__ void lateral_sums(const HarmonicArgs &args, const dou
     double pkk = 1.0, C = 1.0, S = 0.0;
     int base = L + 1;   // idx(k, k)
     for (int k = 1; k <= L; ++k) {
-        if (k == 1) {
-            C = cp;
-            S = sp;
-        } else {
-            const double c = C * cp - S * sp;
-            S = S * cp + C * sp;
-            C = c;
-        }
-        pkk = (td[k] * st) * pkk;
+        fourier_step(k, cp, sp, C, S);
+        pkk = sectoral_step(td[k], st, pkk);
         order_sums<NC, true>(k, L, base, knot, comp, nlm, ta, tb, rows, ct, pkk, U0, U1, V0, V1);
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
@@ -176,21 +144,8 @@ __global__ __launch_bounds__(kThreads, 4) void harmonic_apply_kernel(const Harmo
         for (int q = tid; q < 3 * nnodes; q += kThreads) xs[q] = src[q];
         __syncthreads();
         if (tid < nel) {
-            const double *X = xs + 3 * tid * P;
-            double cx = X[0], cy = X[1], cz = X[2];
-            for (int p = 1; p < P; ++p) {
-                cx = cx + X[3 * p];
-                cy = cy + X[3 * p + 1];
-                cz = cz + X[3 * p + 2];
-            }
-            const double dp = (double)P;
-            cx = cx / dp, cy = cy / dp, cz = cz / dp;
-            const double rc = mm_norm3(cx, cy, cz);
-            int a = kDead, b = kDead;
-            if (rc == rc) {
-                if (!args.extend && (rc < R[0] || rc > R[m - 1])) a = kOutside;
-                else mm_radial_table::layer_of(R, lstart, args.nlayers, rc, a, b);
-            }
+            int a, b;
+            element_layer(xs + 3 * tid * P, P, R, m, lstart, args.nlayers, args.extend, a, b);
             s_a[tid] = a;
             s_b[tid] = b;
         }
@@ -210,10 +165,8 @@ __global__ __launch_bounds__(kThreads, 4) void harmonic_apply_kernel(const Harmo
         const u64 livemask = __ballot(live);
         if (livemask != 0) {   // (the same for every lane of the wave)
             // the direction
-            const double rho = sqrt(x * x + y * y);
-            double ct = z / r, st = rho / r, cp = x / rho, sp = y / rho;
-            if (r == 0.0) ct = 0.0, st = 1.0;
-            if (rho == 0.0) cp = 1.0, sp = 0.0;
+            double ct, st, cp, sp;
+            direction(x, y, z, r, ct, st, cp, sp);
             const int iu = __builtin_amdgcn_readlane(i, (int)__builtin_ctzll(livemask));   // the first live lane's interval
             if (!live) i = iu;
             if (__ballot(i != iu) == 0)
@@ -245,24 +198,6 @@ __global__ __launch_bounds__(kThreads, 4) void harmonic_apply_kernel(const Harmo
             for (int wv = 0; wv < kThreads / kWave; ++wv) total += s_count[wv];
             if (total != 0) atomicAdd(args.noutside, (u64)total);
         }
-    }
-}
-
-// d[0 .. L], then a and b at idx(l, k): integer products (exact), one division, one square root.  Entries the recurrence
-// never reads (a_kk, b_kk, b_{k+1,k}) are 0.
-void recurrence_tables(int L, std::vector<double> &tab)
-{
-    const int nlm = (L + 1) * (L + 2) / 2;
-    tab.assign((size_t)(L + 1) + 2 * (size_t)nlm, 0.0);
-    double *d = tab.data(), *a = d + (L + 1), *b = a + nlm;
-    for (int k = 1; k <= L; ++k) d[k] = k == 1 ? sqrt(3.0) : sqrt((double)(2 * k + 1) / (double)(2 * k));
-    int base = 0;
-    for (int k = 0; k <= L; ++k) {
-        for (int l = k + 1; l <= L; ++l) {
-            a[base + l - k] = sqrt((double)((2 * l + 1) * (2 * l - 1)) / (double)((l - k) * (l + k)));
-            if (l >= k + 2) b[base + l - k] = sqrt((double)((l - 1 - k) * (l - 1 + k)) / (double)((2 * l - 1) * (2 * l - 3)));
-        }
-        base += L + 1 - k;
     }
 }
 

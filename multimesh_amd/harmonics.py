@@ -135,6 +135,7 @@ class SphericalHarmonicModel:
 
     def __init__(self, lmax, radii, coefficients, normalization="4pi", csphase=1):
         self.lmax = _check_lmax(lmax)
+        self.normalization, self.csphase = normalization, csphase   # (what the coefficients were given in; kept for the adjoint)
         self.radii = np.ascontiguousarray(radii, dtype=np.float64)
         self.layers = _radial_layers(self.radii)
         shape = (self.radii.size, self.lmax + 1, self.lmax + 1)

@@ -22,7 +22,7 @@
 // and w = (u(tz, a) * u(ty, b)) * u(tx, e), u(t, 0) = 1.0 - t, u(t, 1) = t: rows mm_gather and mm_transpose_* take.
 // Traffic: 24 B read and 128 B written per point; a lane owns one 64-byte row of each array and writes it with four
 // 16-byte stores when both arrays start on 16 bytes, else with eight 8-byte stores (the same bits).
-#include "mm_stream.h"
+#include "mm_latlon.h"   // Cell, find_cell and (lat, lon, depth) of a point: shared with mm_layered.hip
 
 #include <limits.h>
 
@@ -30,9 +30,9 @@ namespace {
 
 using mm_stream::kThreads;
 using mm_stream::kMaxBlocks;
-constexpr int kAxisLds = 2048;      // doubles of LDS for the three axes together (16 KiB: eight workgroups per CU)
-constexpr double kEarthRadius = 6371000.0;
-constexpr double kRadToDeg = 180.0 / 3.14159265358979323846;
+using mm_latlon::kAxisLds;   // doubles of LDS for the three axes together
+using mm_latlon::Cell;
+using mm_latlon::find_cell;
 
 enum { kFill = 0, kClamp = 1, kKeep = 2 };
 
@@ -49,35 +49,6 @@ struct GridArgs {
     unsigned long long *outside;
 };
 
-struct Cell {
-    int i, i1;
-    double t;
-    bool inside;
-};
-
-// np.searchsorted(a, v, side="right") - 1 clipped to [0, n - 2], and the weight in that cell.  NaN is outside (and, in
-// clamp mode, stays NaN: the comparisons are all false for it, so it sorts behind the last node as in NumPy).
-__device__ __forceinline__ Cell find_cell(const double *a, int n, double v, bool clamp)
-{
-    Cell c = {0, 0, 0.0, true};
-    if (n == 1) return c;
-    const double lo = a[0], hi = a[n - 1];
-    if (clamp) {
-        v = v < lo ? lo : v;
-        v = v > hi ? hi : v;
-    } else {
-        c.inside = v >= lo && v <= hi;
-        if (!c.inside) return c;
-    }
-    int i = mm_upper_bound(a, 0, n, v) - 1;
-    i = i < 0 ? 0 : i;
-    i = i > n - 2 ? n - 2 : i;
-    c.i = i;
-    c.i1 = i + 1;
-    c.t = (v - a[i]) / (a[i + 1] - a[i]);
-    return c;
-}
-
 // What mm_sample_grid and mm_grid_operator compute per point before they part, stated once: (lat, lon, depth) of point p,
 // the periodic wrap, the coordinates handed back through lld when it is not null, and the cell on every axis.  Returns
 // whether the point is inside the grid (always, in clamp mode).
@@ -85,16 +56,8 @@ __device__ __forceinline__ bool point_cells(const double *points, i64 p, const d
                                             int nla, const double *lon_a, int nlo, double lon0, int lon_periodic, bool clamp,
                                             double *lld, Cell &cd, Cell &ca, Cell &co)
 {
-    const double x = points[3 * p], y = points[3 * p + 1], z = points[3 * p + 2];
-    const double r = mm_norm3(x, y, z);
-    const double depth = kEarthRadius - r;
-    const double c = r > 0.0 ? z / r : 0.0;
-    const double lat = 90.0 - acos(c) * kRadToDeg;
-    double lon = atan2(y, x) * kRadToDeg;
-    if (lon_periodic) {
-        if (lon < lon0) lon += 360.0;
-        if (lon >= lon0 + 360.0) lon -= 360.0;
-    }
+    double lat, lon, depth;
+    mm_latlon::lat_lon_depth(points[3 * p], points[3 * p + 1], points[3 * p + 2], lon0, lon_periodic, lat, lon, depth);
     if (lld) {
         lld[3 * p] = lat;
         lld[3 * p + 1] = lon;

@@ -67,15 +67,7 @@ inline void recurrence_tables(int L, std::vector<double> &tab)
 __device__ __forceinline__ void element_layer(const double *X, int P, const double *R, int m, const int *lstart, int nlayers,
                                               int extend, int &a, int &b)
 {
-    double cx = X[0], cy = X[1], cz = X[2];
-    for (int p = 1; p < P; ++p) {
-        cx = cx + X[3 * p];
-        cy = cy + X[3 * p + 1];
-        cz = cz + X[3 * p + 2];
-    }
-    const double dp = (double)P;
-    cx = cx / dp, cy = cy / dp, cz = cz / dp;
-    const double rc = mm_norm3(cx, cy, cz);
+    const double rc = mm_radial_table::centre_radius(X, P);
     a = kDead, b = kDead;
     if (rc == rc) {
         if (!extend && (rc < R[0] || rc > R[m - 1])) a = kOutside;

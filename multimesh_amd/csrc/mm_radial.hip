@@ -226,16 +226,7 @@ __global__ __launch_bounds__(kThreads) void radial_apply_kernel(const ApplyArgs 
         for (int q = tid; q < 3 * nnodes; q += kThreads) xs[q] = src[q];
         __syncthreads();
         if (tid < nel) {
-            const double *X = xs + 3 * tid * P;
-            double cx = X[0], cy = X[1], cz = X[2];
-            for (int p = 1; p < P; ++p) {
-                cx = cx + X[3 * p];
-                cy = cy + X[3 * p + 1];
-                cz = cz + X[3 * p + 2];
-            }
-            const double dp = (double)P;
-            cx = cx / dp, cy = cy / dp, cz = cz / dp;
-            const double rc = mm_norm3(cx, cy, cz);
+            const double rc = mm_radial_table::centre_radius(xs + 3 * tid * P, P);
             int a = -1, b = -1;
             if (rc == rc) mm_radial_table::layer_of(R, args.lstart, args.nlayers, rc, a, b);
             s_a[tid] = a;

@@ -38,6 +38,21 @@ struct mm_radial_table {
         __device__ __forceinline__ double operator[](int k) const { return R[lstart[k]]; }
     };
 
+    // rc of the element whose P nodes are X[P][3]: c = (((X[0] + X[1]) + ...) + X[P-1]) / P per coordinate, rc = |c|
+    // (no libm: NumPy's bits).  Also what mm_layered_model_apply (mm_layered.hip) measures an element's depth by.
+    static __device__ __forceinline__ double centre_radius(const double *X, int P)
+    {
+        double cx = X[0], cy = X[1], cz = X[2];
+        for (int p = 1; p < P; ++p) {
+            cx = cx + X[3 * p];
+            cy = cy + X[3 * p + 1];
+            cz = cz + X[3 * p + 2];
+        }
+        const double dp = (double)P;
+        cx = cx / dp, cy = cy / dp, cz = cz / dp;
+        return mm_norm3(cx, cy, cz);
+    }
+
     // the rows [a, b] of the layer of an element whose centre has the radius rc (not a NaN): the last layer whose first
     // radius is <= rc, clipped: the layer with r_lo <= rc < r_hi, below the first layer the first, above the last the last
     static __device__ __forceinline__ void layer_of(const double *R, const int *lstart, int nlayers, double rc, int &a,

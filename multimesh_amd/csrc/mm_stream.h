@@ -1,9 +1,9 @@
 // What a streaming or tile kernel of the model tools needs, each stated once: the launch shape, the integer count of a
 // launch, the chunked sum of mm_weighted_sum, and the three expressions that are under a bit-parity contract with NumPy
 // wherever they appear, the finiteness test and the order-preserving integer key of a double.  Users: mm_sphere, mm_mass,
-// mm_diffusion, mm_transpose, mm_grid_sample, mm_radial, mm_precondition, mm_scattered, mm_parametrisation, mm_resolution;
-// through mm_gll_tile.h, mm_gradient and mm_order; through mm_boundary_parts.h, mm_boundary and mm_surface.  A new unit
-// starts from these.
+// mm_diffusion, mm_transpose, mm_grid_sample, mm_radial, mm_precondition, mm_scattered, mm_parametrisation, mm_resolution,
+// mm_frames; through mm_gll_tile.h, mm_gradient and mm_order; through mm_boundary_parts.h, mm_boundary and mm_surface.  A new
+// unit starts from these.
 // (The library is built with -ffp-contract=off: every product, quotient and sum below is rounded on its own.)
 #pragma once
 

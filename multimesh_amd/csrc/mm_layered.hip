@@ -16,9 +16,10 @@
 // together fit kAxisLds doubles and bisected there, longer axes in global memory: the sampler's rule.
 // The scan.  The tables are column-major (bounds [nlat][nlon][nb], values [nlat][nlon][nlayer][ncomp]): a lane reads its
 // four corner columns (one in cell mode) as contiguous runs from the top and stops at its layer, so trip counts differ from
-// lane to lane and nothing in the loop is wave-wide; neighbouring nodes of a mesh share their columns, which are small beside
+// lane to lane and nothing in the loop is wave-wide (Column: mm_column.h, shared with mm_topography.hip); neighbouring nodes of a mesh share their columns, which are small beside
 // the points (9 x 180 x 360 doubles are 4.7 MB: they live in L2).  Columns are not staged in LDS.
 // Traffic counted per node: 24 B read, 8 B per component written (plus the optional outputs).
+#include "mm_column.h"
 #include "mm_gll_tile.h"
 #include "mm_latlon.h"
 #include "mm_radial_table.h"
@@ -28,6 +29,7 @@
 namespace {
 
 using namespace mm_stream;   // kThreads, kWave, kMaxBlocks
+using mm_column::Column;
 using mm_latlon::Cell;
 using mm_latlon::find_cell;
 using mm_latlon::kAxisLds;
@@ -51,35 +53,6 @@ struct LayeredArgs {
     int *layer;
     double *span, *lld;
     u64 *noutside;
-};
-
-// Entry q of the column(s) of a node in a column-major table whose columns hold `len` doubles: the lerp over longitude, then
-// latitude, of the four corner columns, or (cell mode) the entry of the nearest map node's column.
-template <bool BILINEAR>
-struct Column {
-    const double *c00, *c01, *c10, *c11;   // [ja][io], [ja][io1], [ja1][io], [ja1][io1]
-    double ta, to;
-
-    __device__ __forceinline__ Column(const double *table, i64 len, int nlon, const Cell &ca, const Cell &co)
-    {
-        if (BILINEAR) {
-            const i64 r0 = (i64)ca.i * nlon, r1 = (i64)ca.i1 * nlon;
-            c00 = table + (r0 + co.i) * len;
-            c01 = table + (r0 + co.i1) * len;
-            c10 = table + (r1 + co.i) * len;
-            c11 = table + (r1 + co.i1) * len;
-            ta = ca.t, to = co.t;
-        } else {
-            const int ja = ca.t < 0.5 ? ca.i : ca.i1, io = co.t < 0.5 ? co.i : co.i1;
-            c00 = c01 = c10 = c11 = table + ((i64)ja * nlon + io) * len;
-            ta = to = 0.0;
-        }
-    }
-    __device__ __forceinline__ double at(i64 q) const
-    {
-        if (BILINEAR) return mm_lerp(ta, mm_lerp(to, c00[q], c01[q]), mm_lerp(to, c10[q], c11[q]));
-        return c00[q];
-    }
 };
 
 // The layer of the picking depth dp in the column b (steps 4 and 5 of the statement): -1 when there is none; top and bot are

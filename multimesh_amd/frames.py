@@ -333,7 +333,10 @@ def in_frame(mesh, rotation, context=None):
 
     Preferred to rotating the mesh there and back: ``R^T (R p)`` is not ``p`` bit for bit -- each product and sum rounds,
     so a mesh that made the round trip no longer shares its points with the meshes it was built beside, and exact
-    coincidences (shared faces, points on interfaces) are lost."""
+    coincidences (shared faces, points on interfaces) are lost.
+
+    The view composes with :func:`multimesh_amd.geodesy.as_geographic`, the view of a mesh in geographic (geodetic)
+    coordinates: ``in_frame(as_geographic(mesh, ellipsoid), R)`` is the geographic view seen from the rotated frame."""
     if not isinstance(mesh, (GllMesh, HexMesh)):
         raise ValueError("in_frame takes a GllMesh or a HexMesh")
     pts = _points3d(mesh, "in_frame")

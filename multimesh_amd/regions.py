@@ -150,7 +150,9 @@ class Region:
     ``rings``: one f64[n, 2] or a list of them; a closed ring (first vertex repeated at the end) is accepted.  Consecutive
     vertices are joined by the shorter great-circle arc (:meth:`densify` first for outlines meant as straight lines on a
     lat/lon map, such as parallels).  Several rings combine even-odd: a ring inside another is a hole.  ``geodetic=True``
-    converts geographic to geocentric latitude with the WGS84 flattening first.
+    converts geographic to geocentric latitude with the WGS84 flattening first -- for the nodes of a mesh as it is, whose
+    latitudes are geocentric.  On :func:`multimesh_amd.geodesy.as_geographic`'s view of a mesh the node latitudes ARE geodetic:
+    there the outline keeps its geographic vertices, ``geodetic=False``.
 
     ``interior`` says which side is the region: "left" -- to the left of the FIRST ring walked in order, seen from outside the
     sphere (GeoJSON's counter-clockwise exterior rings and clockwise holes all agree on it); "smaller" -- each ring encloses

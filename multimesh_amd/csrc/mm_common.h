@@ -47,6 +47,7 @@ struct mm_scratch {
     char *base = nullptr;
     size_t capacity = 0;
     size_t used = 0;
+    size_t reserved = 0;          // bytes of the current reservation [base, base + reserved); 0 under MM_GUARD_ALLOC
     void *guard_piece[256] = {};  // MM_GUARD_ALLOC runs: every carve is an allocation of its own (a query over nine density
                                   // levels carves ~8 arrays per level on top of the shared ones)
     int guard_pieces = 0;
@@ -56,6 +57,7 @@ struct mm_scratch {
 // runs: tools/guard_run.sh) every allocation -- and every scratch carve -- is mapped so that it ENDS at the
 // end of its mapping with unmapped address space behind it: a kernel that reads or writes past an array
 // faults at once instead of now and then (there is no GPU AddressSanitizer on this pool).
+// The guard catches reads PAST an array; reads of an array nobody has written are MM_SCRATCH_FILL's (below).
 hipError_t mm_raw_alloc(int device, void **out, size_t bytes);
 hipError_t mm_raw_free(void *ptr);
 bool mm_guard_alloc(void);
@@ -161,7 +163,17 @@ struct mm_context {
     int *abort_flags = nullptr;   // non-null during a call over a guessed grid: d_counters + kMmAbortSlot (mm_aborted)
     hipStream_t copy_stream = nullptr;   // host-array entry points: uploads run beside the kernels (created on first use)
     hipEvent_t ev_copy[3] = {nullptr, nullptr, nullptr};
+    int scratch_fill = -1;         // MM_SCRATCH_FILL, read when the context is created: the fill byte, -1: off
+    long long fills_queued = 0;    // (mm_debug_scratch)
 };
+
+// MM_SCRATCH_FILL=<byte> in the environment (a diagnostic; default off, and then one branch on scratch_fill): contexts
+// created under it fill what they hand out and have not written with that byte, on ctx->stream -- every scratch
+// reservation (each carve, under MM_GUARD_ALLOC), a grow-only buffer when it is allocated (never when it is handed out
+// again), mm_device_alloc and the library's other allocations that are not fully written before use.  A kernel that reads
+// scratch before the call wrote it then computes something that depends on the byte.  DESIGN.md section 7.
+int mm_fill_unwritten(mm_context *ctx, void *dst_d, size_t bytes);   // nothing when the fill is off
+hipError_t mm_ctx_alloc(mm_context *ctx, void **out, size_t bytes);  // mm_raw_alloc on ctx->device, then mm_fill_unwritten
 
 // The scratch of a call: the drivers state their arrays in an mm_scratch_layout and commit it (mm_scratch_layout.h, which
 // also declares mm_round256 and the two primitives under commit(): reserve, then carve piece by piece; mm_context.hip

@@ -1,5 +1,7 @@
 // Context, error reporting, scratch pool, stage timers and resident-array helpers.
+#include <ctype.h>
 #include <stdarg.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <mutex>
@@ -147,6 +149,21 @@ extern "C" int mm_context_create(int device, void *hip_stream, mm_context **out)
         const char *fp = getenv("MM_FP_MODE");
         if (fp && (fp[0] == 't' || fp[0] == 'T' || fp[0] == '1')) ctx->fp_mode = MM_FP_TOL;
     }
+    {
+        // the diagnostic fill (mm_common.h): one byte value, decimal or 0x.., fixed for the life of this context
+        const char *fill = getenv("MM_SCRATCH_FILL");
+        if (fill && fill[0]) {
+            const bool hex = fill[0] == '0' && (fill[1] == 'x' || fill[1] == 'X');
+            char *end = nullptr;
+            const long v = isxdigit((unsigned char)fill[hex ? 2 : 0]) ? strtol(fill + (hex ? 2 : 0), &end, hex ? 16 : 10) : -1;
+            if (!end || *end != '\0' || v < 0 || v > 255) {
+                mm_set_error(MM_ERR_ARG, "mm_context_create: MM_SCRATCH_FILL=\"%s\" is not a byte value (0..255, decimal or 0x..)", fill);
+                delete ctx;
+                return MM_ERR_ARG;
+            }
+            ctx->scratch_fill = (int)v;
+        }
+    }
     hipError_t e = mm_raw_alloc(device, (void **)&ctx->d_counters, 64 * sizeof(i64));
     if (e == hipSuccess) e = hipMemsetAsync(ctx->d_counters, 0, 64 * sizeof(i64), ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -200,7 +217,7 @@ extern "C" int mm_device_alloc(mm_context *ctx, size_t bytes, void **dptr)
     MM_HIP_CHECK(hipSetDevice(ctx->device));
     *dptr = nullptr;
     if (bytes == 0) bytes = 256;
-    hipError_t e = mm_raw_alloc(ctx->device, dptr, bytes);
+    hipError_t e = mm_ctx_alloc(ctx, dptr, bytes);
     if (e != hipSuccess) {
         mm_set_error(MM_ERR_ALLOC, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
         return MM_ERR_ALLOC;
@@ -265,20 +282,51 @@ __global__ __launch_bounds__(256) void zero_fill_kernel(unsigned char *__restric
     if (blockIdx.x == 0 && threadIdx.x < (bytes & 15)) dst[n16 * 16 + threadIdx.x] = 0;
 }
 
-int mm_zero_async(mm_context *ctx, void *dst_d, size_t bytes)
+// the same for any byte: the diagnostic fill of MM_SCRATCH_FILL (the hot path's clears stay on the kernel above)
+__global__ __launch_bounds__(256) void byte_fill_kernel(unsigned char *__restrict__ dst, size_t bytes, unsigned word)
+{
+    const size_t n16 = bytes / 16;
+    uint4 *d4 = reinterpret_cast<uint4 *>(dst);
+    for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < n16; q += (size_t)gridDim.x * blockDim.x)
+        d4[q] = make_uint4(word, word, word, word);
+    if (blockIdx.x == 0 && threadIdx.x < (bytes & 15)) dst[n16 * 16 + threadIdx.x] = (unsigned char)word;
+}
+
+// byte < 0: zero, with the hot path's kernel
+static int fill_async(mm_context *ctx, void *dst_d, size_t bytes, int byte)
 {
     if (bytes == 0) return MM_OK;
     if (bytes >= 16 && (reinterpret_cast<uintptr_t>(dst_d) & 15) != 0) {   // (never on the hot path; a span below 16 bytes
                                                                             // is written byte by byte wherever it starts)
-        MM_HIP_CHECK(hipMemsetAsync(dst_d, 0, bytes, ctx->stream));
+        MM_HIP_CHECK(hipMemsetAsync(dst_d, byte < 0 ? 0 : byte, bytes, ctx->stream));
         return MM_OK;
     }
     const size_t n16 = bytes / 16;
     const size_t want = (n16 + 255) / 256;
     const unsigned grid = (unsigned)(want < 1 ? 1 : (want > 2048 ? 2048 : want));
-    hipLaunchKernelGGL(zero_fill_kernel, dim3(grid), dim3(256), 0, ctx->stream, static_cast<unsigned char *>(dst_d), bytes);
+    if (byte < 0)
+        hipLaunchKernelGGL(zero_fill_kernel, dim3(grid), dim3(256), 0, ctx->stream, static_cast<unsigned char *>(dst_d), bytes);
+    else
+        hipLaunchKernelGGL(byte_fill_kernel, dim3(grid), dim3(256), 0, ctx->stream, static_cast<unsigned char *>(dst_d), bytes,
+                           0x01010101u * (unsigned)byte);
     MM_HIP_CHECK(hipGetLastError());
     return MM_OK;
+}
+
+int mm_zero_async(mm_context *ctx, void *dst_d, size_t bytes) { return fill_async(ctx, dst_d, bytes, -1); }
+
+int mm_fill_unwritten(mm_context *ctx, void *dst_d, size_t bytes)
+{
+    if (ctx->scratch_fill < 0) return MM_OK;
+    ++ctx->fills_queued;
+    return fill_async(ctx, dst_d, bytes, ctx->scratch_fill);
+}
+
+hipError_t mm_ctx_alloc(mm_context *ctx, void **out, size_t bytes)
+{
+    const hipError_t e = mm_raw_alloc(ctx->device, out, bytes);
+    if (e != hipSuccess || ctx->scratch_fill < 0) return e;
+    return mm_fill_unwritten(ctx, *out, bytes) == MM_OK ? hipSuccess : hipErrorLaunchFailure;
 }
 
 // ---- caller arrays off 16 bytes ---------------------------------------------------------
@@ -288,7 +336,8 @@ int mm_aligned16::take(mm_context *ctx, const void *caller, size_t bytes, bool c
     caller_ = caller;
     bytes_ = bytes;
     if (!caller || bytes == 0 || (reinterpret_cast<uintptr_t>(caller) & 15) == 0) return MM_OK;
-    if (mm_raw_alloc(ctx->device, &copy_, bytes) != hipSuccess) {
+    if ((copy_in ? mm_raw_alloc(ctx->device, &copy_, bytes) : mm_ctx_alloc(ctx, &copy_, bytes)) != hipSuccess) {
+        if (copy_) (void)mm_raw_free(copy_);
         copy_ = nullptr;
         mm_set_error(MM_ERR_ALLOC, "device allocation of %zu bytes for an array off 16-byte alignment failed", bytes);
         return MM_ERR_ALLOC;
@@ -362,6 +411,7 @@ int mm_scratch_begin(mm_context *ctx, size_t total)
         scratch_release(ctx);
         ctx->scratch.capacity = total;   // (the carves are still checked against the reservation)
         ctx->scratch.used = 0;
+        ctx->scratch.reserved = 0;       // (no pool: MM_SCRATCH_FILL fills piece by piece, in mm_scratch_take)
         return MM_OK;
     }
     if (total > ctx->scratch.capacity) {
@@ -379,7 +429,8 @@ int mm_scratch_begin(mm_context *ctx, size_t total)
         ctx->scratch.capacity = want;
     }
     ctx->scratch.used = 0;
-    return MM_OK;
+    ctx->scratch.reserved = total;
+    return mm_fill_unwritten(ctx, ctx->scratch.base, total);   // (MM_SCRATCH_FILL: every layout, a call's second one too)
 }
 
 void *mm_scratch_take(mm_context *ctx, size_t bytes)
@@ -393,6 +444,7 @@ void *mm_scratch_take(mm_context *ctx, size_t bytes)
         void *p = nullptr;
         if (mm_raw_alloc(ctx->device, &p, bytes > 0 ? bytes : 16) != hipSuccess) return nullptr;
         ctx->scratch.guard_piece[ctx->scratch.guard_pieces++] = p;
+        if (mm_fill_unwritten(ctx, p, bytes > 0 ? bytes : 16) != MM_OK) return nullptr;
         ctx->scratch.used += mm_round256(bytes);
         return p;
     }
@@ -413,7 +465,8 @@ int mm_buffer_get(mm_context *ctx, int slot, size_t bytes, void **out)
         ctx->buf_ptr[slot] = nullptr;
         ctx->buf_cap[slot] = 0;
         const size_t want = mm_guard_alloc() ? bytes : mm_round256(bytes + bytes / 16);
-        hipError_t e = mm_raw_alloc(ctx->device, &ctx->buf_ptr[slot], want);
+        // (MM_SCRATCH_FILL: filled here, when it is new, and never when it is handed out again -- it may hold kept state)
+        hipError_t e = mm_ctx_alloc(ctx, &ctx->buf_ptr[slot], want);
         if (e != hipSuccess) {
             mm_set_error(MM_ERR_ALLOC, "hipMalloc(%zu) for pipeline buffer %d failed: %s", want, slot,
                          hipGetErrorString(e));
@@ -482,6 +535,19 @@ extern "C" int mm_last_knn_kernels(mm_context *ctx, int *mask)
 {
     MM_REQUIRE(ctx != nullptr && mask != nullptr, "null argument");
     *mask = ctx->knn_kernels;
+    return MM_OK;
+}
+
+// Debugging aid (not part of the drop-in surface, like mm_debug_grid_guess): out4 = {the byte of MM_SCRATCH_FILL or -1, the
+// address of the scratch pool, the bytes of the current reservation with its trailing 4096 (0 under MM_GUARD_ALLOC: no
+// pool), fills this context has queued so far}.
+extern "C" int mm_debug_scratch(mm_context *ctx, long long *out4)
+{
+    MM_REQUIRE(ctx != nullptr && out4 != nullptr, "null argument");
+    out4[0] = ctx->scratch_fill;
+    out4[1] = (long long)reinterpret_cast<uintptr_t>(ctx->scratch.base);
+    out4[2] = (long long)ctx->scratch.reserved;
+    out4[3] = ctx->fills_queued;
     return MM_OK;
 }
 

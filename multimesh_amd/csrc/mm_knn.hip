@@ -451,9 +451,9 @@ static int build_level(mm_context *ctx, const double *src_d, i64 nsrc, int ndim,
             brc = mm_buffer_get(ctx, slot_xyz, (size_t)(nsrc + 1) * kRec * sizeof(double), (void **)&ix->sorted_xyz);
         if (brc != MM_OK) return brc;
     } else {
-        e = mm_raw_alloc(ctx->device, (void **)&ix->cell_start, (size_t)(ncells + 1) * sizeof(int));
+        e = mm_ctx_alloc(ctx, (void **)&ix->cell_start, (size_t)(ncells + 1) * sizeof(int));
         if (e == hipSuccess)
-            e = mm_raw_alloc(ctx->device, (void **)&ix->sorted_xyz, (size_t)(nsrc + 1) * kRec * sizeof(double));
+            e = mm_ctx_alloc(ctx, (void **)&ix->sorted_xyz, (size_t)(nsrc + 1) * kRec * sizeof(double));
         if (e != hipSuccess) {
             mm_set_error(MM_ERR_ALLOC, "kNN index allocation failed: %s", hipGetErrorString(e));
             return MM_ERR_ALLOC;
@@ -783,10 +783,10 @@ static int tree_build(mm_context *ctx, mm_knn_index *ix, const double *src_d, i6
         if (rc == MM_OK) rc = mm_buffer_get(ctx, MM_BUF_TREE_LEVEL, n_sz, (void **)&tr->level);
         if (rc == MM_OK) rc = mm_buffer_get(ctx, MM_BUF_TREE_COARSE, (size_t)(kTreeCoarse + 2) * sizeof(int), (void **)&tr->coarse);
     } else {
-        hipError_t e = mm_raw_alloc(ctx->device, (void **)&tr->keys, n_sz * sizeof(u64));
-        if (e == hipSuccess) e = mm_raw_alloc(ctx->device, (void **)&tr->xyz, (n_sz + 1) * kRec * sizeof(double));
-        if (e == hipSuccess) e = mm_raw_alloc(ctx->device, (void **)&tr->level, n_sz);
-        if (e == hipSuccess) e = mm_raw_alloc(ctx->device, (void **)&tr->coarse, (size_t)(kTreeCoarse + 2) * sizeof(int));
+        hipError_t e = mm_ctx_alloc(ctx, (void **)&tr->keys, n_sz * sizeof(u64));
+        if (e == hipSuccess) e = mm_ctx_alloc(ctx, (void **)&tr->xyz, (n_sz + 1) * kRec * sizeof(double));
+        if (e == hipSuccess) e = mm_ctx_alloc(ctx, (void **)&tr->level, n_sz);
+        if (e == hipSuccess) e = mm_ctx_alloc(ctx, (void **)&tr->coarse, (size_t)(kTreeCoarse + 2) * sizeof(int));
         if (e != hipSuccess) {
             mm_set_error(MM_ERR_ALLOC, "kNN tree allocation failed: %s", hipGetErrorString(e));
             rc = MM_ERR_ALLOC;

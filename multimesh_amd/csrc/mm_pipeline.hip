@@ -425,7 +425,7 @@ extern "C" int mm_source_create(mm_context *ctx, const double *nodes_d, int64_t 
     int rc = conn.take(ctx, conn_d, (size_t)nelem * 8 * sizeof(i64));
     s->conn = conn.as<const i64>();
     s->conn_copy = static_cast<i64 *>(conn.release());   // (the wait before this function returns covers the copy)
-    if (rc == MM_OK && mm_raw_alloc(ctx->device, (void **)&s->centroids, (size_t)nelem * 3 * sizeof(double)) != hipSuccess) {
+    if (rc == MM_OK && mm_ctx_alloc(ctx, (void **)&s->centroids, (size_t)nelem * 3 * sizeof(double)) != hipSuccess) {
         mm_set_error(MM_ERR_ALLOC, "mm_source_create: device allocation failed");
         rc = MM_ERR_ALLOC;
     }

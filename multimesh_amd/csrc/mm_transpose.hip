@@ -287,18 +287,18 @@ int build_handle(mm_context *ctx, mm_transpose *t, const i64 *ids, const double 
     unsigned *va = nullptr, *vb = nullptr;
     void *sort_scratch = nullptr;
     u64 *counters = nullptr;   // [0] ids out of range, [1] long rows
-    bool ok = mm_raw_alloc(ctx->device, (void **)&t->offsets, (size_t)(ndst + 1) * sizeof(unsigned)) == hipSuccess;
+    bool ok = mm_ctx_alloc(ctx, (void **)&t->offsets, (size_t)(ndst + 1) * sizeof(unsigned)) == hipSuccess;
     if (n > 0) {
-        ok = ok && mm_raw_alloc(ctx->device, (void **)&t->target, n_sz * sizeof(unsigned)) == hipSuccess;
+        ok = ok && mm_ctx_alloc(ctx, (void **)&t->target, n_sz * sizeof(unsigned)) == hipSuccess;
         if (w) {
-            ok = ok && mm_raw_alloc(ctx->device, (void **)&t->weights, n_sz * sizeof(double)) == hipSuccess;
-            ok = ok && mm_raw_alloc(ctx->device, (void **)&t->long_rows, (n_sz / (kLongRow + 1) + 1) * sizeof(int)) == hipSuccess;
+            ok = ok && mm_ctx_alloc(ctx, (void **)&t->weights, n_sz * sizeof(double)) == hipSuccess;
+            ok = ok && mm_ctx_alloc(ctx, (void **)&t->long_rows, (n_sz / (kLongRow + 1) + 1) * sizeof(int)) == hipSuccess;
         }
-        ok = ok && mm_raw_alloc(ctx->device, (void **)&ka, n_sz * sizeof(u64)) == hipSuccess;
-        ok = ok && mm_raw_alloc(ctx->device, (void **)&kb, n_sz * sizeof(u64)) == hipSuccess;
-        ok = ok && mm_raw_alloc(ctx->device, (void **)&va, n_sz * sizeof(unsigned)) == hipSuccess;
-        ok = ok && mm_raw_alloc(ctx->device, (void **)&vb, n_sz * sizeof(unsigned)) == hipSuccess;
-        ok = ok && mm_raw_alloc(ctx->device, &sort_scratch, mm_radix_sort_scratch(n)) == hipSuccess;
+        ok = ok && mm_ctx_alloc(ctx, (void **)&ka, n_sz * sizeof(u64)) == hipSuccess;
+        ok = ok && mm_ctx_alloc(ctx, (void **)&kb, n_sz * sizeof(u64)) == hipSuccess;
+        ok = ok && mm_ctx_alloc(ctx, (void **)&va, n_sz * sizeof(unsigned)) == hipSuccess;
+        ok = ok && mm_ctx_alloc(ctx, (void **)&vb, n_sz * sizeof(unsigned)) == hipSuccess;
+        ok = ok && mm_ctx_alloc(ctx, &sort_scratch, mm_radix_sort_scratch(n)) == hipSuccess;
     }
     if (!ok) {
         mm_set_error(MM_ERR_ALLOC, "%s: device allocation failed", what);

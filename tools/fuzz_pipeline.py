@@ -1,110 +1,36 @@
 """Randomised end-to-end check of mm_interpolate_hex8 against the oracle (cKDTree + C restatement +
 NumPy-order gather): random mesh sizes, shears, anisotropy, k, component counts, target clouds that
-lie inside, on and outside the hull, lazy and eager candidate lists.  Not part of the test suite (it
-takes minutes); prints one line per case and exits non-zero on the first mismatch.
+lie inside, on and outside the hull, lazy and eager candidate lists.  The long run of tests/fuzz_cases.py
+(draw_pipeline / check_pipeline at the "tool" sizes; tests/test_fuzz_gpu.py runs a seeded slice at the suite's sizes);
+prints one line per case and exits non-zero on the first mismatch.
+    python tools/fuzz_pipeline.py [ncases [seed [only [big]]]]
 FP_MODE=tol in the environment runs the context in MM_FP_TOL: node ids, failed counts and zero rows are still compared
 exactly, weights and values to max(1e-12, 64 eps max|x| / shortest element edge) (the mode's stated tolerance)."""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, ".")
-from multimesh_amd import synth
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+import fuzz_cases as F
 from multimesh_amd.device import Context
-from oracle import oracle as O
 
 ncases = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 only = int(sys.argv[3]) if len(sys.argv) > 3 else -1      # replay one case of a seed's sequence
 big = len(sys.argv) > 4 and sys.argv[4] == "big"         # meshes up to 120^3 nodes, up to 2 M targets
-rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 12345)
+seed = int(sys.argv[2]) if len(sys.argv) > 2 else 12345
 ctx = Context(0)
 TOL = os.environ.get("FP_MODE", "exact") == "tol"
 ctx.set_fp_mode("tol" if TOL else "exact")
 redone = solves_guess = 0
-EDGES = [(0, 1), (1, 2), (2, 3), (3, 0), (4, 5), (5, 6), (6, 7), (7, 4), (0, 4), (1, 5), (2, 6), (3, 7)]   # exodus order
-
-
-def tolerance(pa, ca):
-    v = pa[ca]
-    hmin = min(np.linalg.norm(v[:, a] - v[:, b], axis=1).min() for a, b in EDGES)
-    return max(1e-12, 64 * 2.220446049250313e-16 * np.abs(pa).max() / hmin)
-
-
 t_start = time.time()
-for case in range(ncases):
-    n = int(rng.integers(60, 121)) if big else int(rng.integers(4, 42))
-    pa, ca = synth.hex_mesh(n, seed=int(rng.integers(1, 1 << 30)), jitter=float(rng.uniform(0.0, 0.3)) + 1e-3)
-    pa = pa.copy()
-    if rng.random() < 0.5:                                   # anisotropy / shear / offset
-        pa *= rng.uniform(0.2, 5.0, size=3)
-        pa[:, 0] += rng.uniform(-0.6, 0.6) * pa[:, 1]
-        pa += rng.uniform(-1e3, 1e3, size=3)
-    # general position (no exact kNN ties): a tiny random perturbation of every node
-    pa += rng.normal(scale=1e-9 * np.ptp(pa, axis=0).max(), size=pa.shape)
-    lo, hi = pa.min(axis=0), pa.max(axis=0)
-    npts = int(rng.integers(200_000, 2_000_000)) if big else int(rng.integers(1, 60_000))
-    margin = rng.choice([0.0, 0.02, 0.3])
-    pb = rng.uniform(lo - margin * (hi - lo), hi + margin * (hi - lo), size=(npts, 3))
-    if rng.random() < 0.3:                                   # some targets exactly on mesh nodes
-        take = rng.integers(0, len(pa), size=min(npts, 500))
-        pb[: len(take)] = pa[take]
-    k = int(rng.choice([1, 2, 3, 4, 5, 8, 9, 13, 16, 20, 24, 25, 32, 33, 40, 64]))
-    k = min(k, len(ca))
-    ncomp = int(rng.choice([1, 1, 2, 3, 5]))
-    fields = rng.normal(size=(ncomp, len(pa)))
-    lazy = bool(rng.random() < 0.7)
-    if only >= 0 and case != only:
+for c in F.cases("pipeline", seed, ncases, "big" if big else "tool"):
+    if only >= 0 and c["case"] != only:
         continue
-    ctx.set_lazy_lists(lazy)
-    vals, enc, w, nf = ctx.interpolate_hex8(pa, ca, pb, fields, nelem_to_search=k, want_operator=True)
-    vals2, nf2 = ctx.interpolate_hex8(pa, ca, pb, fields, nelem_to_search=k)
-    nn, _ = O.knn_ckdtree(O.centroid(ca, pa), pb, k, workers=-1)
-    nn = nn.reshape(npts, k)
-    enc_o, w_o, nf_o, status = O.locate_hex8(nn, synth.reorder_hex8(ca), pa, pb, want_status=True)
-    ok = status >= 0
-    tol = tolerance(pa, ca) if TOL else 0.0
-    if TOL:
-        redone += ctx.last_locate_stats()["redone_exact"]
-        solves_guess += npts
-    same_w = (np.abs(w.numpy()[ok] - w_o[ok]).max(initial=0.0) <= tol) if TOL else np.array_equal(w.numpy()[ok], w_o[ok])
-    good = (nf == nf_o == nf2 and np.array_equal(enc.numpy()[ok], enc_o[ok]) and same_w
-            and not enc.numpy()[~ok].any() and not w.numpy()[~ok].any())
-    enc_z, w_z = enc_o.copy(), w_o.copy()
-    enc_z[~ok] = 0
-    w_z[~ok] = 0
-    ref_vals = O.gather(fields, enc_z, w_z)
-    if TOL:
-        vtol = tol * 8 * np.abs(fields).max()
-        good = good and np.abs(vals.numpy() - ref_vals).max(initial=0.0) <= vtol and np.abs(vals2.numpy() - ref_vals).max(initial=0.0) <= vtol
-        # rows of failed points are produced by the exact kernel: bit-equal, sign of zero included
-        good = good and vals.numpy()[~ok].tobytes() == ref_vals[~ok].tobytes() and vals2.numpy()[~ok].tobytes() == ref_vals[~ok].tobytes()
-    else:
-        good = good and vals.numpy().tobytes() == ref_vals.tobytes() and vals2.numpy().tobytes() == ref_vals.tobytes()
-    print(f"case {case:3d} n={n:2d} N={npts:6d} k={k:2d} C={ncomp} lazy={int(lazy)} margin={margin} "
-          f"nfailed={nf:6d} fallback={(status >= k).sum():5d} -> {'ok' if good else 'MISMATCH'}", flush=True)
-    if not good:
-        e, ww, v1, v2 = enc.numpy(), w.numpy(), vals.numpy(), vals2.numpy()
-        print("  nfailed gpu/oracle/values-only:", nf, nf_o, nf2)
-        bad_e = np.nonzero((e[ok] != enc_o[ok]).any(axis=1))[0]
-        bad_w = np.nonzero((ww[ok] != w_o[ok]).any(axis=1))[0]
-        print("  rows with different ids:", len(bad_e), "weights:", len(bad_w), "failed rows non-zero:",
-              int(e[~ok].any(axis=1).sum()), int(ww[~ok].any(axis=1).sum()))
-        bv1 = np.nonzero((v1.view(np.int64) != ref_vals.view(np.int64)).any(axis=1))[0]
-        bv2 = np.nonzero((v2.view(np.int64) != ref_vals.view(np.int64)).any(axis=1))[0]
-        print("  value rows differing (operator call / values-only call):", len(bv1), len(bv2))
-        for r in list(bv1[:5]) + list(bv2[:5]):
-            print("   row", r, "status", status[r], "gpu", v1[r], v2[r], "ref", ref_vals[r])
-        # is it the kNN stage?  (public int64 lists against cKDTree, three runs: a race shows as varying counts)
-        cen = O.centroid(ca, pa)
-        tree = ctx.knn_build(cen)
-        for rep in range(3):
-            got = tree.query(pb, k).numpy().reshape(npts, k)
-            badr = np.nonzero((got != nn).any(axis=1))[0]
-            print("   kNN run", rep, "rows differing from cKDTree:", len(badr))
-            for r in badr[:3]:
-                pos = np.nonzero(got[r] != nn[r])[0]
-                print("     row", r, "differs at", pos, "ours", got[r][pos], "ref", nn[r][pos], "same set", set(got[r]) == set(nn[r]))
-        idx_ok = np.nonzero(ok)[0]
-        for r in bad_e[:5]:
-            t = idx_ok[r]
-            print("   target", t, "status", status[t], "gpu ids", e[t], "ref ids", enc_o[t])
+    try:
+        info = F.check_pipeline(ctx, c)
+    except AssertionError as e:
+        print(e, flush=True)
         sys.exit(1)
+    print(info["line"], flush=True)
+    redone += info["redone"]
+    solves_guess += c["npts"] if TOL else 0
 print(f"{ncases} cases ok in {time.time() - t_start:.0f} s" + (f" (MM_FP_TOL: {redone} solves repeated exactly for {solves_guess} targets)" if TOL else ""))
